@@ -228,6 +228,8 @@ class DiffusionModel:
         if latents is None and images is None:
             raise ValueError("train_step needs images (inputs[0]) or pre-encoded latents=")
         _lib.require_device()
+        if torch.device(dev).type != "cuda":            # buffers of a CPU-built model would reach the kernels as host pointers
+            raise _lib.Dm3dError(f"train_step: the model was built on {dev}; the dm3d kernels have no CPU path")
         if latents is None:
             latents = self.encode_latents(torch.as_tensor(images, dtype=torch.float32).to(dev))
         latents = torch.as_tensor(latents, dtype=torch.float32).to(dev).contiguous()

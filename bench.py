@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — latent volumes/sec of the conditional 3D U-Net DDPM sampler at 32^3 x 8ch, T=1000 on MI355X.
 
-Contract (one JSON line from rank 0):  python bench.py --gpus N --steps K --warmup W
+Contract (one JSON line from rank 0):  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   * workload: BASELINE.json configs[2] per GPU — conditional_dm3d U-Net (widths 64/128/256), 32^3 x 8ch latents,
     B=32 volumes per GPU, T=1000 DDPM.  A "step" is one denoising step of the whole per-GPU batch: U-Net eps
     prediction + posterior update (+ Philox noise) — every one of the T steps of a chain does exactly this work, so
@@ -11,7 +11,12 @@ Contract (one JSON line from rank 0):  python bench.py --gpus N --steps K --warm
     scaling: B per GPU fixed).  Under torchrun (RANK/LOCAL_RANK/WORLD_SIZE set) this process is one rank; started plainly as
     `python bench.py --gpus N` it launches the N ranks itself as fresh child processes — before this process has touched the
     GPU — relays rank 0's JSON line and exits non-zero if any rank fails.
-  * roofline: the dominant kernel is the k3/stride-1 Conv3d with the norm+SiLU prologue in its Winograd F(2,3)-along-x form,
+  * a plain run sets up, warms up, times the K steps and prints the line (ms_per_step, value); everything else it can measure — roofline,
+    per_kernel_kind, fp32_mode, full_chain, cpu_baseline — takes runs of its own and is done only with --full (null / empty otherwise).
+  * --dump-outputs DIR: after the timed steps, the latents x the last timed step left (what generate() hands its caller) as DIR/x.npy,
+    float32; at N>1 each rank writes x_rank<r>.npy, a fixed seeded sample where the shards would exceed 64 MB together.  Weights
+    (seed 0), x_T and every step's noise (Philox, rank seed) are fixed, so the same arguments give the same inputs on every run.
+  * roofline (--full): the dominant kernel is the k3/stride-1 Conv3d with the norm+SiLU prologue in its Winograd F(2,3)-along-x form,
     conv3d_igemm_h3w<1> (23 launches/step at B = 32: every Cin >= 32 conv of the 32^3 / 16^3 levels that reads a float32 tensor, and the
     Cin >= 256 convs of the 8^3 level with their two-way Cin split (the halves meet inside the launch), with or without a fused 1x1 skip tail; ~52 % of the step; persistent
     workgroups, one per CU); its MODE-2 twin behind a DM3D_FMT_H2 hand-off (10 launches, ~28 %), the direct kernel conv3d_igemm_h3v3
@@ -23,7 +28,7 @@ Contract (one JSON line from rank 0):  python bench.py --gpus N --steps K --warm
     passes per product: executed_mfma_tflops counts what is issued — 40/54 of the direct form's k-steps in the Winograd-x form, a tenth of
     them against a zero pad tap; useful_mfma_tflops leaves the pad steps out), float32 157.3 TFLOP/s with
     --precision fp32 (v_mfma_f32_32x32x2_f32).  traffic = HBM bytes per launch from the committed rocprofv3 --pmc summary.
-  * cpu_baseline: the CPU oracle (PyTorch-CPU restatement of the reference path; TensorFlow is not installed) on the
+  * cpu_baseline (--full): the CPU oracle (PyTorch-CPU restatement of the reference path; TensorFlow is not installed) on the
     host cores, a bounded sample of the same workload (rank 0, N=1 only).
 """
 import argparse
@@ -131,6 +136,23 @@ def csrc_digest() -> str:
     return h.hexdigest()[:16]
 
 
+DUMP_LIMIT_BYTES = 64_000_000         # --dump-outputs: at most 64 MB in all (every rank's file together)
+
+
+def dump_outputs(d, name, t, budget):
+    """Write tensor ``t`` as ``d/name.npy`` (float32): whole if it fits ``budget`` bytes, else a fixed seeded sample of its
+    flattened entries (the same indices on every run)."""
+    import numpy as np
+    a = t.detach().float().cpu().numpy()
+    if a.nbytes + 4096 > budget:                        # (4096: room for the .npy header)
+        k = (budget - 4096) // a.itemsize
+        idx = np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))
+        a = a.reshape(-1)[idx]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, name + ".npy"), a)
+    log(f"wrote {name}.npy {list(a.shape)} to {d}")
+
+
 def _restarting(smp):
     """step() of a sampler whose finished chain (t = 0 done) restarts from x_T, as the headline loop does: --steps may exceed T."""
     left = [T_FULL]
@@ -152,7 +174,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="volumes per GPU (BASELINE configs[2]: 32)")
     ap.add_argument("--channels", type=int, default=8)
     ap.add_argument("--size", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--norm", choices=["batch", "group"], default="batch",
                     help="batch = the reference's inference BatchNormalization (folded); group = its commented-out "
@@ -160,15 +182,22 @@ def main():
     ap.add_argument("--precision", choices=["h3", "fp32"], default="h3",
                     help="Conv3d arithmetic: h3 = float16 hi+lo split, 3 MFMA passes, fp32 accumulate (default); "
                          "fp32 = exact float32 MFMA")
-    ap.add_argument("--no-fp32-mode", action="store_true", help="skip the extra exact-float32 timing (N=1, h3 runs only)")
-    ap.add_argument("--no-full-chain", action="store_true", help="skip the wall-clock timing of one whole T=1000 generate() (N=1 only)")
+    ap.add_argument("--no-fp32-mode", action="store_true", help="with --full: skip the extra exact-float32 timing (N=1, h3 runs only)")
+    ap.add_argument("--no-full-chain", action="store_true", help="with --full: skip the wall-clock timing of one whole T=1000 generate() (N=1 only)")
     ap.add_argument("--print-csrc-digest", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and per-kernel times, the exact-float32 mode, one "
+                         "whole T=1000 chain and the CPU baseline (the --no-* switches above still leave single legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the latents of the last timed step as DIR/x.npy (float32)")
     args = ap.parse_args()
     if args.print_csrc_digest:
         print(csrc_digest())
         return
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus))              # nothing above has imported torch or touched the GPU
 
@@ -304,11 +333,13 @@ def main():
         ranks_info["per_rank"][r]["ms_per_step"] = float(ms_r)
     log(f"timed {K} steps: {s_per_step * 1e3:.2f} ms/step")
     value = world * B / (T_FULL * s_per_step)
+    if args.dump_outputs:                 # before any --full leg: those run the plan again and generate() restarts its chain
+        dump_outputs(args.dump_outputs, "x" if world == 1 else f"x_rank{rank}", smp.plan.x, DUMP_LIMIT_BYTES // world)
 
-    # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream (rank 0) --------------
+    # ---- --full: roofline of the dominant kernel, measured live with HIP events on the launch stream (rank 0) -------
     roofline = None
     per_kind = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         plan = smp.plan
         plan.run_timed()                                                   # warm
         reps = 2
@@ -470,7 +501,7 @@ def main():
 
     # ---- the same K steps in exact-float32 arithmetic (v_mfma_f32_32x32x2_f32), so that number is timed in this run too ------
     fp32_mode = None
-    if rank == 0 and world == 1 and args.precision == "h3" and not args.no_fp32_mode:
+    if rank == 0 and world == 1 and args.full and args.precision == "h3" and not args.no_fp32_mode:
         log("fp32 mode: building the exact-float32 model")
         m32 = cdm.DiffusionModel(S, 1024, Cc, None, margs, device=dev, weights=W, precision="fp32", norm=args.norm)
         s32 = m32.sampler((B, S, S, S, Cc), context_value=1, seed=parallel.rank_seed(1234, rank), use_graph=not args.no_graph)
@@ -504,7 +535,7 @@ def main():
 
     # ---- one whole chain, wall clock: generate() of B volumes through all T steps (the K-step figure extrapolates to this) ------
     full_chain = None
-    if rank == 0 and world == 1 and not args.no_full_chain:
+    if rank == 0 and world == 1 and args.full and not args.no_full_chain:
         torch.cuda.synchronize()
         f0 = time.perf_counter()
         out = model.generate((B, S, S, S, Cc), context_value=1, seed=parallel.rank_seed(1234, rank), use_graph=not args.no_graph)
@@ -518,7 +549,7 @@ def main():
 
     # ---- CPU baseline: the oracle on the host cores, bounded sample (rank 0, N=1 only) ----------------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import ref_torch as rt
         cores = host_cores()
         log(f"cpu baseline on {cores} threads (os.cpu_count()={os.cpu_count()})")
@@ -572,7 +603,7 @@ def main():
             "conv_algorithmic_pct_of_peak": None if roofline is None else {"dominant": round(100 * roofline["frac"], 2),
                                                                            "all": round(100 * roofline["all_convs"]["algorithmic_frac_of_peak"], 2)},
             "conv_algorithmic_frac_of_peak": None if roofline is None else roofline["all_convs"]["algorithmic_frac_of_peak"],
-            "precision": args.precision, "norm": args.norm,
+            "precision": args.precision, "norm": args.norm, "full": args.full,
         }
         print(json.dumps(line), flush=True)
     if world > 1:

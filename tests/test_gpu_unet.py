@@ -597,7 +597,7 @@ def test_bench_two_rank_rehearsal(dev):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--size", "8", "--channels", "4", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--size", "8", "--channels", "4", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 4 and line["scaling"] == "weak"
@@ -611,6 +611,34 @@ def test_bench_two_rank_rehearsal(dev):
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=dict(env, WORLD_SIZE="3", RANK="0", LOCAL_RANK="0"),
                          capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0 and "WORLD_SIZE" in (bad.stderr + bad.stdout)
+
+
+def test_bench_plain_full_and_dumped_outputs(dev, tmp_path):
+    """A plain `python bench.py` times exactly --steps steps and measures nothing else (roofline, per-kernel times, fp32 mode, whole chain and
+    CPU baseline only with --full); --dump-outputs writes the latents of the last timed step, and they are the same in both runs: the inputs
+    are seeded and the --full legs run after the dump."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    shape, lines = (2, 8, 8, 8, 4), []
+    for extra in ([], ["--full"]):
+        d = tmp_path / ("full" if extra else "plain")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2", "--size", "8",
+                            "--channels", "4", "--dump-outputs", str(d), *extra], env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    plain, full = lines
+    for line in lines:
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "volumes/s"
+        assert line["value"] == pytest.approx(2 / (1000 * line["ms_per_step"] * 1e-3))
+    assert not plain["full"] and plain["roofline"] is None and plain["per_kernel_kind"] == {}
+    assert plain["cpu_baseline"] is None and plain["fp32_mode"] is None and plain["full_chain"] is None
+    assert full["full"] and full["roofline"]["achieved"] > 0 and full["per_kernel_kind"] and full["full_chain"]["finite"]
+    assert full["cpu_baseline"]["value"] > 0 and full["fp32_mode"]["ms_per_step"] > 0
+    a, b = np.load(tmp_path / "plain" / "x.npy"), np.load(tmp_path / "full" / "x.npy")
+    assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all() and a.std() > 0.1
+    assert np.array_equal(a, b)
 
 
 def test_generate_sharded_single_process(dev):

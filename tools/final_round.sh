@@ -10,10 +10,10 @@ tail -2 $out/${tag}_gpu_tests.log
 bash tools/profile_round.sh ${tag}_h3 h3
 for f in pmc_hbm sq clock clockv3; do [ -f $out/${tag}_h3_$f.csv ] && cp $out/${tag}_h3_$f.csv profiles/; done      # so that the bench below attaches them
 [ -f $out/${tag}_h3_clock.csv ] || echo "WARNING: no in-kernel clock summary (csrc/variants/cck.so missing: python tools/mk_stamp_variants.py first)"
-python3 bench.py --steps 30 --warmup 5 2> $out/${tag}_h3_bench.log | tail -1 > $out/${tag}_h3_bench.json
-python3 bench.py --batch 4 --channels 4 --steps 50 --warmup 5 --no-fp32-mode 2> /dev/null | tail -1 > $out/${tag}_h3_config2_bench.json
-python3 bench.py --batch 1 --steps 50 --warmup 5 --no-cpu-baseline --no-fp32-mode --no-full-chain 2> /dev/null | tail -1 > $out/${tag}_h3_b1_bench.json
-python3 bench.py --norm group --steps 20 --warmup 3 --no-cpu-baseline --no-fp32-mode --no-full-chain 2> /dev/null | tail -1 > $out/${tag}_h3_groupnorm_bench.json
+python3 bench.py --steps 30 --warmup 5 --full 2> $out/${tag}_h3_bench.log | tail -1 > $out/${tag}_h3_bench.json
+python3 bench.py --batch 4 --channels 4 --steps 50 --warmup 5 --full --no-fp32-mode 2> /dev/null | tail -1 > $out/${tag}_h3_config2_bench.json
+python3 bench.py --batch 1 --steps 50 --warmup 5 --full --no-cpu-baseline --no-fp32-mode --no-full-chain 2> /dev/null | tail -1 > $out/${tag}_h3_b1_bench.json
+python3 bench.py --norm group --steps 20 --warmup 3 --full --no-cpu-baseline --no-fp32-mode --no-full-chain 2> /dev/null | tail -1 > $out/${tag}_h3_groupnorm_bench.json
 python3 tools/e2e_config5.py > $out/${tag}_e2e_config5.log 2>&1 || tail -5 $out/${tag}_e2e_config5.log
 python3 tools/chain_repeatability.py > $out/${tag}_chain_repeatability.log 2>&1 || tail -5 $out/${tag}_chain_repeatability.log
 python3 tools/small_batch_floor.py > $out/${tag}_small_batch_floor.log 2>&1 || tail -5 $out/${tag}_small_batch_floor.log
