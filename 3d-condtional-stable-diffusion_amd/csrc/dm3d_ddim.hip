@@ -1,0 +1,69 @@
+// dm3d_ddim.hip — the DDIM update (Song et al., "Denoising Diffusion Implicit Models", eq. 12) over a schedule of timesteps:
+// strided sampling (eta = 0 deterministic, eta > 0 stochastic, eta = 1 strided DDPM) and inversion share one kernel, because
+// every per-step constant comes from a coefficient table the host writes once per chain (include/dm3d.h, dm3d_ddim_desc).
+// A pure HBM stream like ddpm_kernel: 16 B per lane, read x and eps, write x (or out).
+#include "dm3d_common.h"
+#include "dm3d_philox.h"
+
+namespace {
+
+struct DdimArgs {
+    float* x; const float* eps; const float* noise; float* out;
+    long per4;                                     // float4 per sample
+    const float* coef; const int* tau; const int* t_next; int rows;
+    const int* pos; int* t_idx;
+    uint64_t seed; const uint64_t* seed_dev; int mode;
+};
+
+__global__ __launch_bounds__(256) void ddim_kernel(const DdimArgs p) {
+    const int b = blockIdx.y;
+    const int r = min(max(p.pos[b], 0), p.rows - 1);
+    const f32x4 c0 = reinterpret_cast<const f32x4*>(p.coef)[2 * r];          // sqrt(ab), sqrt(1-ab), a_x0, a_eps
+    const f32x4 c1 = reinterpret_cast<const f32x4*>(p.coef)[2 * r + 1];      // sigma, clip, -, -
+    const float sqab = c0[0], sq1ab = c0[1], a_x0 = c0[2], a_eps = c0[3], sigma = c1[0];
+    const bool clip = c1[1] != 0.f, draw = sigma != 0.f;
+    const int tau = p.tau[r];
+    const uint64_t seed = p.seed_dev ? *p.seed_dev : p.seed;
+    // the next step's U-Net row; the kernel never reads t_idx, so this one lane per sample races with nobody
+    if (p.t_idx && blockIdx.x == 0 && threadIdx.x == 0) p.t_idx[b] = p.t_next[r];
+    float* dst = p.mode == 0 ? p.out : p.x;
+    const long base = (long)b * p.per4;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < p.per4; i += (long)gridDim.x * 256) {
+        const f32x4 x = reinterpret_cast<const f32x4*>(p.x)[base + i];
+        const f32x4 e = reinterpret_cast<const f32x4*>(p.eps)[base + i];
+        f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        if (draw) z = p.noise ? reinterpret_cast<const f32x4*>(p.noise)[base + i]
+                              : philox_normal4((uint64_t)(base + i), (uint32_t)tau, 0xdd1au, seed);
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float x0 = __fdiv_rn(__fsub_rn(x[k], __fmul_rn(sq1ab, e[k])), sqab);     // ddpm_kernel's order
+            if (clip) x0 = x0 != x0 ? x0 : fminf(fmaxf(x0, -1.0f), 1.0f);           // a NaN passes, as in ddpm_kernel's clip
+            o[k] = __fadd_rn(__fadd_rn(__fmul_rn(a_x0, x0), __fmul_rn(a_eps, e[k])), __fmul_rn(sigma, z[k]));
+        }
+        reinterpret_cast<f32x4*>(dst)[base + i] = o;
+    }
+}
+
+}  // namespace
+
+extern "C" int dm3d_ddim_update(const dm3d_ddim_desc* d, void* stream) {
+    DM3D_REQUIRE(d != nullptr, "ddim: null descriptor");
+    DM3D_REQUIRE(d->x && d->eps && d->coef && d->tau && d->pos, "ddim: x/eps/coef/tau/pos must be non-null");
+    DM3D_REQUIRE(d->batch > 0 && d->batch <= 65535 && d->per_sample > 0 && d->per_sample % 4 == 0,
+                 "ddim: batch=%d per_sample=%lld (must be a positive multiple of 4)", d->batch, (long long)d->per_sample);
+    DM3D_REQUIRE(d->rows > 0, "ddim: rows=%d", d->rows);
+    DM3D_REQUIRE(d->mode == 0 || d->mode == 1, "ddim: mode %d not in {0,1}", d->mode);
+    DM3D_REQUIRE(d->mode == 1 || d->out, "ddim: mode 0 needs out");
+    DM3D_REQUIRE(!d->t_idx || d->t_next, "ddim: t_idx needs t_next");
+    DM3D_REQUIRE(dm3d_aligned16(d->x) && dm3d_aligned16(d->eps) && dm3d_aligned16(d->noise) && dm3d_aligned16(d->out) &&
+                 dm3d_aligned16(d->coef), "ddim: pointers must be 16-byte aligned");
+    DdimArgs a{};
+    a.x = d->x; a.eps = d->eps; a.noise = d->noise; a.out = d->out; a.per4 = d->per_sample / 4;
+    a.coef = d->coef; a.tau = d->tau; a.t_next = d->t_next; a.rows = d->rows; a.pos = d->pos; a.t_idx = d->t_idx;
+    a.seed = d->seed; a.seed_dev = d->seed_dev; a.mode = d->mode;
+    const long blocks = (a.per4 + 255) / 256;
+    dim3 grid((unsigned)(blocks > 256 ? 256 : blocks), (unsigned)d->batch);                 // ddpm_kernel's grid
+    hipLaunchKernelGGL(ddim_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return dm3d_launch_check("ddim_kernel");
+}

@@ -17,10 +17,46 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DdpmDesc, check, lib
+from ._lib import DdimDesc, DdpmDesc, check, lib
 from .betas import BETAS_FIELDS, Betas
 from .unet import UNet
 from .weights import UNetConfig
+
+
+def ddim_timesteps(T: int, num_steps=None, timesteps=None) -> np.ndarray:
+    """The DDIM schedule tau_0 < ... < tau_{S-1} in [0, T): ``timesteps`` as given (strictly increasing), or for ``num_steps`` = S
+    tau_i = round(i (T-1) / (S-1)) (halves rounded up, in integers) for i = 0..S-1, and [T-1] for S = 1: always holds 0 and T-1.
+    Neither given: every timestep (S = T)."""
+    T = int(T)
+    if num_steps is not None and timesteps is not None:
+        raise ValueError("give num_steps or timesteps, not both")
+    if timesteps is not None:
+        ts = np.asarray(timesteps).reshape(-1)
+        if ts.size == 0 or not np.all(ts == np.round(ts)) or ts.min() < 0 or ts.max() >= T or np.any(np.diff(ts) <= 0):
+            raise ValueError(f"timesteps must be strictly increasing integers in [0, {T})")
+        return ts.astype(np.int64)
+    S = T if num_steps is None else int(num_steps)
+    if not 1 <= S <= T:
+        raise ValueError(f"num_steps must lie in [1, {T}], got {num_steps}")
+    if S == 1:
+        return np.array([T - 1], dtype=np.int64)
+    i = np.arange(S, dtype=np.int64)
+    return (2 * i * (T - 1) + (S - 1)) // (2 * (S - 1))
+
+
+def ddim_coefficients(alpha_bar, src, dst, eta=0.0) -> np.ndarray:
+    """float64 [n, 5] rows (sqrt(a), sqrt(1-a), a_x0, a_eps, sigma) of the DDIM steps src[r] -> dst[r] (include/dm3d.h,
+    dm3d_ddim_desc): a = alpha_bar[src], a' = alpha_bar[dst] (1 where dst < 0), sigma = eta sqrt((1-a')/(1-a)) sqrt(1 - a/a'),
+    a_x0 = sqrt(a'), a_eps = sqrt(max(1 - a' - sigma^2, 0)).  eta = 0 gives sigma = 0 for either direction (inversion: a' < a)."""
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    a = ab[src]
+    ap = np.where(dst < 0, 1.0, ab[np.maximum(dst, 0)])
+    sigma = np.zeros_like(a)
+    if eta != 0:
+        sigma = float(eta) * np.sqrt((1 - ap) / (1 - a)) * np.sqrt(1 - a / ap)
+    a_eps = np.sqrt(np.maximum(1 - ap - sigma ** 2, 0.0))
+    return np.stack([np.sqrt(a), np.sqrt(1 - a), np.sqrt(ap), a_eps, sigma], axis=1)
 
 
 class _LossTracker:
@@ -299,6 +335,52 @@ class DiffusionModel:
         check(lib().dm3d_ddpm_update(C.byref(d), torch.cuda.current_stream().cuda_stream), "ddpm_update")
         return mean, var.reshape(B, 1, 1, 1, 1)
 
+    def ddim_step(self, x_t, pred_noise, t, t_prev, eta=0.0, noise=None, *, clip_x0=True, seed=None):
+        """One DDIM update (include/dm3d.h, dm3d_ddim_desc, mode 0): x_t at timestep ``t`` -> x at ``t_prev`` (-1: the x0
+        estimate), the DDIM counterpart of sample().  ``t`` / ``t_prev``: one index or one per sample, -1 <= t_prev < t.
+        ``noise`` (optional): z of the step (eta > 0); None draws it from Philox under ``seed`` (None: a fresh key)."""
+        x_t = torch.as_tensor(x_t, dtype=torch.float32).to(self.device).contiguous()
+        eps = torch.as_tensor(pred_noise, dtype=torch.float32).to(self.device).contiguous()
+        B = x_t.shape[0]
+        if eps.shape != x_t.shape or x_t[0].numel() % 4:
+            raise ValueError("x_t / pred_noise disagree")
+        t = np.broadcast_to(np.asarray(torch.as_tensor(t).reshape(-1).cpu(), dtype=np.int64), (B,))
+        tp = np.broadcast_to(np.asarray(torch.as_tensor(t_prev).reshape(-1).cpu(), dtype=np.int64), (B,))
+        if t.min() < 0 or t.max() >= self.timesteps or tp.min() < -1 or np.any(tp >= t):
+            raise ValueError("t must lie in [0, timesteps) and t_prev in [-1, t)")
+        if not eta >= 0:
+            raise ValueError("eta must be >= 0")
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32).to(self.device).contiguous()
+            if noise.shape != x_t.shape:
+                raise ValueError("noise must have x_t's shape")
+        coef = self._ddim_table(t, tp, eta, clip_x0).to(self.device)
+        tau = torch.from_numpy(t.astype(np.int32)).to(self.device)
+        pos = torch.arange(B, dtype=torch.int32, device=self.device)
+        out = torch.empty_like(x_t)
+        d = self._ddim_desc(x_t, eps, coef, tau, pos, 0, noise=noise, out=out, seed=self.fresh_seed() if seed is None else seed)
+        check(lib().dm3d_ddim_update(C.byref(d), torch.cuda.current_stream().cuda_stream), "ddim_update")
+        return out
+
+    def _ddim_table(self, src, dst, eta, clip_x0) -> torch.Tensor:
+        """The [n, 8] float32 coefficient rows of dm3d_ddim_desc, from the float32 alpha_bar table the kernels use, in float64."""
+        tab = np.zeros((len(src), 8), dtype=np.float64)
+        tab[:, :5] = ddim_coefficients(self.b.alpha_bar, src, dst, eta)
+        tab[:, 5] = 1.0 if clip_x0 else 0.0
+        return torch.from_numpy(tab.astype(np.float32))
+
+    def _ddim_desc(self, x, eps, coef, tau, pos, mode, noise=None, out=None, t_next=None, t_idx=None, seed=0) -> DdimDesc:
+        d = DdimDesc()
+        d.x, d.eps, d.noise = x.data_ptr(), eps.data_ptr(), (noise.data_ptr() if noise is not None else None)
+        d.out = out.data_ptr() if out is not None else None
+        d.batch, d.per_sample = x.shape[0], x[0].numel()
+        d.coef, d.tau, d.rows, d.pos = coef.data_ptr(), tau.data_ptr(), coef.shape[0], pos.data_ptr()
+        d.t_next = t_next.data_ptr() if t_next is not None else None
+        d.t_idx = t_idx.data_ptr() if t_idx is not None else None
+        d.seed, d.mode = int(seed) & (2 ** 64 - 1), mode
+        d._keep = (x, eps, noise, out, coef, tau, pos, t_next, t_idx)
+        return d
+
     # -- a14: generate ----------------------------------------------------------------------------------------------
     def _context_ids(self, context_value, batch=None):
         """The reference takes one scalar id and broadcasts it (conditional_dm3d.py:552); an array of shape [B], [B,1] or [B,1,1]
@@ -319,27 +401,52 @@ class DiffusionModel:
         import secrets
         return secrets.randbits(64)
 
-    def sampler(self, shape, context_value=None, *, seed=None, use_graph=True) -> "Sampler":
+    def sampler(self, shape, context_value=None, *, seed=None, use_graph=True, kind="ddpm", num_steps=None, timesteps=None,
+                eta=0.0, clip_x0=True) -> "Sampler":
         """The state of one generate() call: plan, tables, context rows and the captured step graph.  There is one live
-        Sampler per (batch, context mode): creating another one for the same plan retires the older (its step() raises)."""
-        net = self.network
-        cfg = net.cfg
+        Sampler per (batch, context mode): creating another one for the same plan retires the older (its step() raises).
+        ``kind="ddim"``: a DDIM chain over ``ddim_timesteps(T, num_steps, timesteps)`` (S steps) with ``eta`` / ``clip_x0``."""
+        shape = self._sampler_shape(shape)
+        if kind not in ("ddpm", "ddim"):
+            raise ValueError(f"sampler kind must be 'ddpm' or 'ddim', got {kind!r}")
+        if kind == "ddpm" and (num_steps is not None or timesteps is not None or eta != 0.0 or clip_x0 is not True):
+            raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim'")
+        if kind == "ddim":
+            taus = ddim_timesteps(self.timesteps, num_steps, timesteps)        # validated before the plan is touched
+            if not eta >= 0:
+                raise ValueError("eta must be >= 0")
+        ctx = self._context_ids(context_value, shape[0]) if self.conditional else None
+        if kind == "ddpm":
+            return Sampler(self, shape, ctx, seed, use_graph)
+        return DdimSampler(self, shape, ctx, seed, use_graph, taus, eta=eta, clip_x0=clip_x0)
+
+    def _sampler_shape(self, shape):
+        cfg = self.network.cfg
         shape = tuple(int(s) for s in shape)
         if len(shape) != 5 or shape[1:] != (cfg.img_size,) * 3 + (cfg.img_channels,):
             raise ValueError(f"shape must be (B,{cfg.img_size},{cfg.img_size},{cfg.img_size},{cfg.img_channels})")
-        return Sampler(self, shape, self._context_ids(context_value, shape[0]) if self.conditional else None, seed, use_graph)
+        return shape
 
     def generate(self, shape=(1, 16, 16, 16, 16), last_step=0, context_value=None, *, x_T=None, noise=None, seed=None,
-                 use_graph=True, steps=None):
+                 use_graph=True, steps=None, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0, clip_x0=True):
         """conditional_dm3d.py:550-575.  For shape[0] > 1 the single context row is broadcast to every sample.
         ``seed`` (optional): Philox key of x_T and of every step's noise; None (default) draws a fresh key per call, as the
         reference draws fresh tf.random.normal noise, an integer makes the call reproducible.
         ``noise`` (optional): tensor [timesteps, *shape]; row i is the draw of step i.  ``steps`` (optional) stops
-        after that many steps (benchmarks time a prefix of the chain)."""
+        after that many steps (benchmarks time a prefix of the chain).
+        ``sampler="ddim"``: the DDIM chain over ``ddim_timesteps(T, num_steps, timesteps)`` = tau_0 < ... < tau_{S-1}, S U-Net
+        evaluations, ``eta`` (0: deterministic), ``clip_x0`` (clamp the x0 estimate to [-1, 1], as the reference's DDPM loop
+        clips); ``noise`` is then [S, *shape] with row k the z of the step from tau_k; last_step must be 0."""
         if not 0 <= last_step <= self.timesteps:
             raise ValueError("last_step out of range")
+        if sampler == "ddim":
+            if last_step != 0:
+                raise ValueError("sampler='ddim' runs whole chains: last_step must be 0")
+            return self._generate_ddim(shape, context_value, x_T=x_T, noise=noise, seed=seed, use_graph=use_graph, steps=steps,
+                                       num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0)
         self._sync_from_trainer()
-        smp = self.sampler(shape, context_value, seed=seed, use_graph=use_graph and noise is None)
+        smp = self.sampler(shape, context_value, seed=seed, use_graph=use_graph and noise is None, kind=sampler,
+                           num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0)
         smp.reset(x_T)
         T = self.timesteps
         n_steps = T - last_step if steps is None else min(int(steps), T - last_step)
@@ -356,12 +463,48 @@ class DiffusionModel:
         self.network.check_range(smp.plan)
         return out
 
+    def _generate_ddim(self, shape, context_value, *, x_T, noise, seed, use_graph, steps, num_steps, timesteps, eta, clip_x0):
+        self._sync_from_trainer()
+        smp = self.sampler(shape, context_value, seed=seed, use_graph=use_graph and noise is None, kind="ddim",
+                           num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0)
+        S = smp.n_steps
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32).to(self.device)
+            if tuple(noise.shape) != (S,) + smp.shape:
+                raise ValueError(f"noise must be [S={S}, *shape] for sampler='ddim'")
+        smp.reset(x_T)
+        n_steps = S if steps is None else min(int(steps), S)
+        for k in range(n_steps):
+            smp.step(noise=None if noise is None else noise[S - 1 - k].contiguous())
+        out = smp.plan.x.clone()
+        self.network.check_range(smp.plan)
+        return out
+
+    def invert(self, x0, context_value=None, *, num_steps=None, timesteps=None, use_graph=True, seed=None):
+        """DDIM inversion: ``x0`` taken as the state at tau_0 of ``ddim_timesteps(T, num_steps, timesteps)``, then for
+        i = 0..S-2 eps = U-Net(x, tau_i) and the deterministic update (sigma = 0, no clip) to tau_{i+1}: S-1 U-Net evaluations.
+        Returns x at tau_{S-1}, which sampler='ddim' with eta=0 (clip_x0=False) maps back near ``x0``.  ``seed`` only keys the
+        (unused) Philox stream."""
+        x0 = torch.as_tensor(x0, dtype=torch.float32)
+        shape = self._sampler_shape(x0.shape)
+        taus = ddim_timesteps(self.timesteps, num_steps, timesteps)
+        ctx = self._context_ids(context_value, shape[0]) if self.conditional else None
+        self._sync_from_trainer()
+        smp = DdimSampler(self, shape, ctx, seed, use_graph, taus, clip_x0=False, invert=True)
+        smp.reset(x0)
+        for _ in range(smp.n_steps):
+            smp.step()
+        out = smp.plan.x.clone()
+        self.network.check_range(smp.plan)
+        return out
+
     MAX_GRAPHS = 8      # captured step graphs kept per model (one per plan); the least recently used one is destroyed
 
     def _capture(self, smp: "Sampler"):
-        """Capture one step of ``smp`` into a HIP graph, cached per plan: the Philox key lives in a device scalar of the plan
-        (dm3d_ddpm_desc.seed_dev), so one graph serves every seed."""
-        key = id(smp.plan)
+        """Capture one step of ``smp`` into a HIP graph, cached per (plan, sampler kind): the Philox key lives in a device scalar of
+        the plan (dm3d_ddpm_desc.seed_dev), and a DDIM chain's schedule, eta and clip in the plan's tables, so one graph serves
+        every seed and every DDIM schedule."""
+        key = (id(smp.plan), smp.KIND)
         if key in self._graphs:
             self._graphs[key] = self._graphs.pop(key)                  # most recently used last
             return self._graphs[key][0]
@@ -436,9 +579,14 @@ class Sampler:
             plan.seed_buf = torch.zeros(1, dtype=torch.int64, device=model.device)
         plan._owner_gen = getattr(plan, "_owner_gen", 0) + 1
         self._gen = plan._owner_gen
-        self.desc = model._ddpm_desc(plan.x, plan.eps, plan.t_idx, 1, seed=self.seed)
+        self.desc = self._desc()
         self.desc.seed_dev = plan.seed_buf.data_ptr()
         self._t = -1                          # host mirror of the device step index; -1: no chain in progress
+
+    KIND = "ddpm"
+
+    def _desc(self, noise=None):
+        return self.model._ddpm_desc(self.plan.x, self.plan.eps, self.plan.t_idx, 1, noise=noise, seed=self.seed)
 
     def _own(self):
         if self._gen != self.plan._owner_gen:
@@ -446,7 +594,16 @@ class Sampler:
 
     def reset(self, x_T=None):
         self._own()
-        plan, T = self.plan, self.model.timesteps
+        T = self.model.timesteps
+        self._start(x_T)
+        self.plan.t_idx.fill_(T - 1)
+        if self.plan.range_flag is not None:
+            self.plan.range_flag.zero_()
+        self._t = T - 1
+
+    def _start(self, x_T):
+        """Philox key and x_T (given, or drawn under the key) of a new chain."""
+        plan = self.plan
         st = torch.cuda.current_stream().cuda_stream
         seed_i64 = self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed
         plan.seed_buf.fill_(seed_i64)
@@ -454,10 +611,6 @@ class Sampler:
             plan.x.copy_(torch.as_tensor(x_T, dtype=torch.float32).reshape(self.shape))
         else:
             check(lib().dm3d_randn(plan.x.data_ptr(), plan.x.numel(), self.seed, 0x7fffffff, st), "randn")
-        plan.t_idx.fill_(T - 1)
-        if plan.range_flag is not None:
-            plan.range_flag.zero_()
-        self._t = T - 1
 
     def _enqueue(self, st, desc):
         self.plan.run(st)
@@ -479,8 +632,7 @@ class Sampler:
             raise RuntimeError("the chain is finished (or was never started): call reset() before step()")
         st = torch.cuda.current_stream().cuda_stream
         if noise is not None:
-            d = self.model._ddpm_desc(self.plan.x, self.plan.eps, self.plan.t_idx, 1, noise=noise)
-            self._enqueue(st, d)
+            self._enqueue(st, self._desc(noise))
         elif self.use_graph:
             # resolved through the model's cache on every step: load_weights / LRU eviction destroy graphs, never under a live handle
             check(lib().dm3d_graph_launch(self.model._capture(self), st), "graph_launch")
@@ -496,3 +648,63 @@ class Sampler:
         caller that stops a chain early calls it itself."""
         self._own()
         self.model.network.check_range(self.plan)
+
+
+class DdimSampler(Sampler):
+    """One DDIM chain over a fixed batch: S steps tau_{S-1} -> ... -> tau_0 -> x0 (``invert``: S-1 steps tau_0 -> ... -> tau_{S-1}).
+
+    It drives the DDPM Sampler's plan (its full T-row time table serves any schedule) and keeps the chain in tables of that
+    plan, rewritten by reset(): coefficient rows, the timestep of each row, the next step's timestep and the device row counter.
+    Row n-1 is the first step and row 0 the last, so one step is U-Net + dm3d_ddim_update (which also moves t_idx to the next
+    step's timestep) + counter decrement in either direction, and one captured graph serves every schedule, eta and clip."""
+
+    KIND = "ddim"
+
+    def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=True, invert=False):
+        self.taus, self.eta, self.clip_x0, self.invert = np.asarray(taus, dtype=np.int64), float(eta), bool(clip_x0), bool(invert)
+        self.n_steps = len(self.taus) - 1 if self.invert else len(self.taus)
+        super().__init__(model, shape, ctx_ids, seed, use_graph)
+
+    def _desc(self, noise=None):
+        plan, T, dev = self.plan, self.model.timesteps, self.model.device
+        if getattr(plan, "ddim_coef", None) is None:          # sized for the longest chain (S = T): one graph serves every S
+            plan.ddim_coef = torch.zeros(T, 8, dtype=torch.float32, device=dev)
+            plan.ddim_tau = torch.zeros(T, dtype=torch.int32, device=dev)
+            plan.ddim_next = torch.zeros(T, dtype=torch.int32, device=dev)
+            plan.ddim_pos = torch.zeros(plan.B, dtype=torch.int32, device=dev)
+        d = self.model._ddim_desc(plan.x, plan.eps, plan.ddim_coef, plan.ddim_tau, plan.ddim_pos, 1, noise=noise,
+                                  t_next=plan.ddim_next, t_idx=plan.t_idx, seed=self.seed)
+        d.seed_dev = plan.seed_buf.data_ptr()
+        return d
+
+    def _rows(self):
+        """(src, dst) timesteps of rows 0..n-1 (row n-1 runs first); dst -1: the x0 target of a sampling chain's last step."""
+        t = self.taus
+        if self.invert:
+            return t[:-1][::-1], t[1:][::-1]
+        return t, np.concatenate([[-1], t[:-1]])
+
+    def reset(self, x_T=None):
+        self._own()
+        if self.invert and x_T is None:
+            raise ValueError("an inversion chain starts from a given x0")
+        plan, n = self.plan, self.n_steps
+        self._start(x_T)
+        if n > 0:
+            src, dst = self._rows()
+            plan.ddim_coef[:n].copy_(self.model._ddim_table(src, dst, self.eta, self.clip_x0 and not self.invert))
+            plan.ddim_tau[:n].copy_(torch.from_numpy(src.astype(np.int32)))
+            plan.ddim_next[:n].copy_(torch.from_numpy(np.maximum(dst, 0).astype(np.int32)))
+            plan.ddim_pos.fill_(n - 1)
+            plan.t_idx.fill_(int(src[n - 1]))
+        if plan.range_flag is not None:
+            plan.range_flag.zero_()
+        self._t = n - 1
+
+    def _enqueue(self, st, desc):
+        self.plan.run(st)
+        push, pop = _lib.roctx()
+        push("ddim")
+        check(lib().dm3d_ddim_update(C.byref(desc), st), "ddim_update")
+        check(lib().dm3d_add_i32(self.plan.ddim_pos.data_ptr(), self.plan.B, -1, st), "add_i32")
+        pop()

@@ -25,7 +25,8 @@ extern "C" {
                                      104 (dm3d_attention), 105 (x1_fmt / out_fmt / post_*), 106 (ddpm seed_dev; conv/gemm range_flag; the
                                      training entries), 107 (conv wpk_f8: a float8 cross-term form, removed again in 109), 108 (conv wpk_wino: the Winograd-x form), 109 (wpk_f8 and
                                      dm3d_pack_weights_h3f8 are gone; the Winograd-x image pairs its taps differently; dm3d_mlp_fused; conv skip_wpk_frag, gn_stats; dm3d_groupnorm_finalize2), 110 (dm3d_attn_front), 111 (conv split_counters: the Cin split
-                                     meets inside the launch; dm3d_conv_split_counter_words): a host built against an older header must be rebuilt */
+                                     meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc were added within 111 (no existing struct or
+                                     entry changed): a host built against an older header must be rebuilt */
 
 #define DM3D_OK            0
 #define DM3D_EINVAL       -1      /* bad argument (shape, alignment, null pointer) */
@@ -411,6 +412,38 @@ typedef struct dm3d_ddpm_desc {
 } dm3d_ddpm_desc;
 
 int dm3d_ddpm_update(const dm3d_ddpm_desc* d, void* stream);
+
+/* ---- DDIM step over a timestep schedule: the strided generalisation of generate's loop body (:517-548, 571-575) ---------
+ * Row r = pos[b] of the coefficient table describes one step from timestep tau[r] (alpha_bar a) to a target a' (1 for the
+ * last step of a chain):  x0 = (x - sqrt(1-a)*eps) / sqrt(a)          (ddpm_update's float32 order)
+ *                         x0 = clip ? clamp(x0, -1, 1) : x0             (a NaN passes)
+ *                         res = a_x0*x0 + a_eps*eps + sigma*z           (float32, in that order)
+ * with a_x0 = sqrt(a'), a_eps = sqrt(max(1 - a' - sigma^2, 0)), sigma = eta*sqrt((1-a')/(1-a))*sqrt(1 - a/a'), computed by the host
+ * in float64 once per chain and rounded once to float32.  One table serves sampling (eta = 0 deterministic, eta > 0 stochastic,
+ * eta = 1 strided DDPM) and inversion (a' the next larger timestep's, sigma = 0, no clip).  z = noise (if given) or Philox N(0,1)
+ * keyed by (seed, tau[r], element) under a stream constant of its own (never ddpm_update's draws); z = 0 where sigma == 0.
+ *   mode 0 (DiffusionModel.ddim_step): out = res, x untouched.
+ *   mode 1 (generate / invert):        x <- res.
+ * Graph-capturable without host reads: the row comes from device memory (advanced with dm3d_add_i32 after each step), and with t_idx
+ * set the kernel writes t_idx[b] = t_next[pos[b]] (the U-Net row of the next step; the kernel does not read t_idx). */
+typedef struct dm3d_ddim_desc {
+    float* x;                   /* [batch, per_sample] x at tau[pos[b]] (updated in place in mode 1) */
+    const float* eps;           /* predicted noise */
+    const float* noise;         /* optional injected z, same shape */
+    float* out;                 /* mode 0: the result, same shape */
+    int32_t batch; int64_t per_sample;     /* per_sample % 4 == 0 */
+    const float* coef;          /* [rows][8] device: sqrt(a), sqrt(1-a), a_x0, a_eps, sigma, clip (nonzero: clamp x0), 0, 0 */
+    const int32_t* tau;         /* [rows] device: the timestep each row steps from (the Philox counter) */
+    const int32_t* t_next;      /* [rows] device, optional: the timestep the step after row r evaluates */
+    int32_t rows;               /* pos[b] is clamped to [0, rows) before any table is indexed */
+    const int32_t* pos;         /* [batch] device: the row of each sample */
+    int32_t* t_idx;             /* [batch] device, optional: receives t_next[pos[b]] */
+    uint64_t seed;
+    const uint64_t* seed_dev;   /* optional: the Philox key is read from device memory instead of `seed` (as dm3d_ddpm_desc) */
+    int32_t mode;
+} dm3d_ddim_desc;
+
+int dm3d_ddim_update(const dm3d_ddim_desc* d, void* stream);
 
 /* p[i] = max(p[i] + delta, 0) (the loop counter of generate kept on the device so a captured step replays unchanged; it
  * saturates at 0, so a step issued past the end of a chain never indexes row -1 of a table). */
