@@ -121,6 +121,14 @@ class DdimDesc(C.Structure):
     ]
 
 
+class EditDesc(C.Structure):
+    _fields_ = [
+        ("x", _f32p), ("x0", _f32p), ("w", _f32p), ("noise", _f32p), ("out", _f32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
+        ("channels", C.c_int32), ("levels", _f32p), ("rows", C.c_int32), ("pos", _i32p),
+        ("seed", C.c_uint64), ("seed_dev", C.c_void_p), ("mode", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes): every symbol include/dm3d.h declares
 SIGNATURES = {
     "dm3d_version": (C.c_int, []),
@@ -173,6 +181,7 @@ SIGNATURES = {
     "dm3d_affine_act": (C.c_int, [_f32p, _f32p, C.c_int64, C.c_int32, _f32p, _f32p, C.c_int32, C.c_void_p]),
     "dm3d_ddpm_update": (C.c_int, [C.POINTER(DdpmDesc), C.c_void_p]),
     "dm3d_ddim_update": (C.c_int, [C.POINTER(DdimDesc), C.c_void_p]),
+    "dm3d_edit_update": (C.c_int, [C.POINTER(EditDesc), C.c_void_p]),
     "dm3d_range_check": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "dm3d_add_i32": (C.c_int, [_i32p, C.c_int32, C.c_int32, C.c_void_p]),
     "dm3d_randn": (C.c_int, [_f32p, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p]),

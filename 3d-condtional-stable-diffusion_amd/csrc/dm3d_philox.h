@@ -1,5 +1,5 @@
 // dm3d_philox.h — the counter-based N(0,1) generator of the sampling kernels (dm3d_elem.hip: randn, ddpm_update;
-// dm3d_ddim.hip: ddim_update).  Each caller keys its draws with a stream constant of its own in the counter.
+// dm3d_ddim.hip: ddim_update; dm3d_edit.hip: edit_update).  Each caller keys its draws with a stream constant of its own in the counter.
 #pragma once
 #include "dm3d_common.h"
 

@@ -11,13 +11,14 @@ The sampling loop (:559-573) runs with no host synchronisation: the step index l
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DdimDesc, DdpmDesc, check, lib
+from ._lib import DdimDesc, DdpmDesc, EditDesc, check, lib
 from .betas import BETAS_FIELDS, Betas
 from .unet import UNet
 from .weights import UNetConfig
@@ -57,6 +58,49 @@ def ddim_coefficients(alpha_bar, src, dst, eta=0.0) -> np.ndarray:
         sigma = float(eta) * np.sqrt((1 - ap) / (1 - a)) * np.sqrt(1 - a / ap)
     a_eps = np.sqrt(np.maximum(1 - ap - sigma ** 2, 0.0))
     return np.stack([np.sqrt(a), np.sqrt(1 - a), np.sqrt(ap), a_eps, sigma], axis=1)
+
+
+def edit_steps(strength, n: int) -> int:
+    """The steps an edit keeps of an n-step schedule: floor(strength n + 1/2) for strength in (0, 1]; 0 steps is an error."""
+    s = float(strength)
+    if not 0 < s <= 1:                                    # a NaN fails the comparison too
+        raise ValueError(f"strength must lie in (0, 1], got {strength}")
+    k = int(math.floor(s * int(n) + 0.5))
+    if k == 0:
+        raise ValueError(f"strength {strength} keeps no step of a {n}-step schedule")
+    return k
+
+
+def edit_levels(alpha_bar, levels) -> np.ndarray:
+    """float64 [n, 2] rows (sqrt(a'), sqrt(1-a')) of the known-latent levels (include/dm3d.h, dm3d_edit_desc): a' = alpha_bar[level],
+    1 where level < 0 (clean)."""
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    lv = np.asarray(levels, dtype=np.int64)
+    ap = np.where(lv < 0, 1.0, ab[np.maximum(lv, 0)])
+    return np.stack([np.sqrt(ap), np.sqrt(1 - ap)], axis=1)
+
+
+def latent_mask(mask, latent_shape) -> torch.Tensor:
+    """An edit mask (1 = regenerate, 0 = keep, values in [0, 1]) at latent resolution: ``mask`` is [B|1, D', H', W'] or
+    [B|1, D', H', W', 1] with (D', H', W') = k (D, H, W) for an integer k >= 1 (k = 4: a 128^3 image mask over a 32^3 latent),
+    ``latent_shape`` = (B, D, H, W, C).  Each k^3 block is pooled by its max (a voxel any part of which is regenerated is
+    regenerated) and a batch of one is broadcast: float32 [B, D, H, W] on the mask's device."""
+    B, D, H, W = (int(v) for v in latent_shape[:4])
+    m = (mask if torch.is_tensor(mask) else torch.as_tensor(np.asarray(mask))).to(torch.float32)
+    if m.dim() == 5:
+        if m.shape[-1] != 1:
+            raise ValueError(f"a 5-D mask has one trailing channel, got {tuple(m.shape)}")
+        m = m[..., 0]
+    if m.dim() != 4 or m.shape[0] not in (1, B):
+        raise ValueError(f"mask must be [B|1, D', H', W'(, 1)] with B = {B}, got {tuple(m.shape)}")
+    k = m.shape[1] // D
+    if k < 1 or tuple(m.shape[1:]) != (k * D, k * H, k * W):
+        raise ValueError(f"mask extent {tuple(m.shape[1:])} is no integer multiple of the latent's {(D, H, W)}")
+    if not bool(((m >= 0) & (m <= 1)).all()):
+        raise ValueError("mask values must lie in [0, 1]")
+    if k > 1:
+        m = m.reshape(m.shape[0], D, k, H, k, W, k).amax(dim=(2, 4, 6))
+    return m.expand(B, D, H, W).contiguous()
 
 
 class _LossTracker:
@@ -381,6 +425,61 @@ class DiffusionModel:
         d._keep = (x, eps, noise, out, coef, tau, pos, t_next, t_idx)
         return d
 
+    def q_sample(self, x0, t, noise=None, *, seed=None):
+        """Forward noising (include/dm3d.h, dm3d_edit_desc, mode 0): sqrt(a) x0 + sqrt(1-a) z with a = alpha_bar[t], in the
+        reference's order (conditional_dm3d.py:484-491); the single-call counterpart of edit()'s known latent, as ddim_step is of a
+        DDIM chain.  ``t``: one index or one per sample in [-1, timesteps); -1 (clean) returns x0 bitwise.  ``noise`` (optional): z;
+        None draws it from Philox under ``seed`` (None: a fresh key)."""
+        return self._edit_call(x0, t, 0, noise=noise, seed=seed)
+
+    def _edit_call(self, x0, t, mode, x=None, keep=None, noise=None, seed=None):
+        """One dm3d_edit_update outside a chain, one level per sample; mode 1 blends into a copy of ``x`` with keep weights
+        ``keep`` [B, per_sample / C]."""
+        x0 = torch.as_tensor(x0, dtype=torch.float32).to(self.device).contiguous()
+        B = x0.shape[0]
+        if x0.dim() < 2 or x0[0].numel() % 4:
+            raise ValueError("x0 must be [B, ...] with a multiple of 4 elements per sample")
+        t = np.broadcast_to(np.asarray(torch.as_tensor(t).reshape(-1).cpu(), dtype=np.int64), (B,))
+        if t.min() < -1 or t.max() >= self.timesteps:
+            raise ValueError("t must lie in [-1, timesteps)")
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32).to(self.device).contiguous()
+            if noise.shape != x0.shape:
+                raise ValueError("noise must have x0's shape")
+        out = None
+        if mode == 1:
+            x = torch.as_tensor(x, dtype=torch.float32).to(self.device).contiguous().clone()
+            keep = torch.as_tensor(keep, dtype=torch.float32).to(self.device).contiguous()
+            if x.shape != x0.shape or keep.numel() * x0.shape[-1] != x0.numel():
+                raise ValueError("x / keep disagree with x0")
+        else:
+            out = torch.empty_like(x0)
+        levels = self._edit_table(t).to(self.device)
+        pos = torch.arange(B, dtype=torch.int32, device=self.device)
+        d = self._edit_desc(x0, levels, pos, mode, x=x, w=keep, noise=noise, out=out, seed=self.fresh_seed() if seed is None else seed)
+        check(lib().dm3d_edit_update(C.byref(d), torch.cuda.current_stream().cuda_stream), "edit_update")
+        return out if mode == 0 else x
+
+    def _edit_table(self, levels) -> torch.Tensor:
+        """The [n, 4] float32 level rows of dm3d_edit_desc (sqrt(a'), sqrt(1-a'), level, 0), from the float32 alpha_bar table the
+        kernels use, in float64, rounded once."""
+        tab = np.zeros((len(levels), 4), dtype=np.float64)
+        tab[:, :2] = edit_levels(self.b.alpha_bar, levels)
+        tab[:, 2] = np.maximum(np.asarray(levels, dtype=np.int64), -1)
+        return torch.from_numpy(tab.astype(np.float32))
+
+    def _edit_desc(self, x0, levels, pos, mode, x=None, w=None, noise=None, out=None, seed=0) -> EditDesc:
+        d = EditDesc()
+        d.x0, d.levels, d.rows, d.pos = x0.data_ptr(), levels.data_ptr(), levels.shape[0], pos.data_ptr()
+        d.x = x.data_ptr() if x is not None else None
+        d.w = w.data_ptr() if w is not None else None
+        d.noise = noise.data_ptr() if noise is not None else None
+        d.out = out.data_ptr() if out is not None else None
+        d.batch, d.per_sample, d.channels = x0.shape[0], x0[0].numel(), x0.shape[-1]
+        d.seed, d.mode = int(seed) & (2 ** 64 - 1), mode
+        d._keep = (x0, levels, pos, x, w, noise, out)
+        return d
+
     # -- a14: generate ----------------------------------------------------------------------------------------------
     def _context_ids(self, context_value, batch=None):
         """The reference takes one scalar id and broadcasts it (conditional_dm3d.py:552); an array of shape [B], [B,1] or [B,1,1]
@@ -498,6 +597,65 @@ class DiffusionModel:
         self.network.check_range(smp.plan)
         return out
 
+    def edit(self, x0, context_value=None, *, mask=None, strength=1.0, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0,
+             clip_x0=True, seed=None, use_graph=True, noise=None, known_noise=None, steps=None):
+        """Inpainting and image-to-image editing (SDEdit) of latents ``x0`` [B, S, S, S, C]; returns latents of x0's shape.
+
+        ``mask`` (1 = regenerate, 0 = keep, in [0, 1]; None: regenerate everything) is pooled to the latent by latent_mask() and
+        kept with weight w = 1 - mask: after every step of the chain the known latent, noised to the level the step reached, is put
+        back, x <- w known_t + (1-w) x (RePaint's replacement step), so the last step leaves x0 bitwise where w = 1.
+        ``strength`` in (0, 1]: the chain keeps the first n = edit_steps(strength, N) entries sched_0 < ... < sched_{n-1} of its
+        schedule (DDPM: 0..T-1, N = T; DDIM: ddim_timesteps(T, num_steps, timesteps), N = S).  At n = N it starts from the x_T that
+        generate() draws under the same seed (x0 unused); otherwise from q_sample(x0, sched_{n-1}) over the whole volume.
+        ``sampler`` / ``num_steps`` / ``timesteps`` / ``eta`` / ``clip_x0`` / ``seed`` / ``use_graph`` / ``steps``: as generate();
+        context_value: one id or one per volume, as generate().
+        ``noise`` (optional): [n, *x0.shape], row i the sampler's z of the step from sched_i (generate's rows at n = N).
+        ``known_noise`` (optional): [n+1, *x0.shape], row j the z of the known latent at level L_j of L = (clean, sched_0, ...,
+        sched_{n-1}): row i is the blend after the step from sched_i (row 0, clean, draws none) and row n the start (unused at n = N)."""
+        x0 = torch.as_tensor(x0, dtype=torch.float32)
+        shape = self._sampler_shape(x0.shape)
+        if sampler not in ("ddpm", "ddim"):
+            raise ValueError(f"sampler must be 'ddpm' or 'ddim', got {sampler!r}")
+        if sampler == "ddpm":
+            if num_steps is not None or timesteps is not None or eta != 0.0 or clip_x0 is not True:
+                raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim'")
+            sched = np.arange(self.timesteps, dtype=np.int64)
+        else:
+            sched = ddim_timesteps(self.timesteps, num_steps, timesteps)
+            if not eta >= 0:
+                raise ValueError("eta must be >= 0")
+        n = edit_steps(strength, len(sched))
+        full, sched = n == len(sched), sched[:n]
+        mask = None if mask is None else latent_mask(mask, shape)
+        ctx = self._context_ids(context_value, shape[0]) if self.conditional else None
+        for name, arr, rows in (("noise", noise, n), ("known_noise", known_noise, n + 1)):
+            if arr is not None and tuple(arr.shape) != (rows,) + shape:
+                raise ValueError(f"{name} must be [{rows}, *x0.shape] for this chain")
+        if steps is not None and int(steps) < 0:
+            raise ValueError("steps must be >= 0")
+        # device work from here on
+        self._sync_from_trainer()
+        dev = self.device
+        keep = torch.zeros(shape[:4], dtype=torch.float32, device=dev) if mask is None else 1 - mask.to(dev)
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32).to(dev)
+        if known_noise is not None:
+            known_noise = torch.as_tensor(known_noise, dtype=torch.float32).to(dev)
+        eager = noise is not None or known_noise is not None
+        if sampler == "ddpm":
+            smp = EditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full)
+        else:
+            smp = DdimEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, eta=eta, clip_x0=clip_x0)
+        smp.reset(x0.to(dev), keep, None if known_noise is None else known_noise[n].contiguous())
+        n_steps = n if steps is None else min(int(steps), n)
+        for k in range(n_steps):
+            i = n - 1 - k
+            smp.step(noise=None if noise is None else noise[i].contiguous(),
+                     known_noise=None if known_noise is None else known_noise[i].contiguous())
+        out = smp.plan.x.clone()
+        self.network.check_range(smp.plan)
+        return out
+
     MAX_GRAPHS = 8      # captured step graphs kept per model (one per plan); the least recently used one is destroyed
 
     def _capture(self, smp: "Sampler"):
@@ -551,6 +709,10 @@ class UnconditionalDiffusionModel(DiffusionModel):
     def generate(self, shape=(1, 16, 16, 16, 16), last_step=0, **kw):
         kw.pop("context_value", None)
         return super().generate(shape, last_step, None, **kw)
+
+    def edit(self, x0, **kw):
+        kw.pop("context_value", None)
+        return super().edit(x0, None, **kw)
 
     def test(self, test_prefix):
         return super().test(test_prefix, None)
@@ -708,3 +870,110 @@ class DdimSampler(Sampler):
         check(lib().dm3d_ddim_update(C.byref(desc), st), "ddim_update")
         check(lib().dm3d_add_i32(self.plan.ddim_pos.data_ptr(), self.plan.B, -1, st), "add_i32")
         pop()
+
+
+class _EditChain:
+    """The known-latent half of an edit chain (DiffusionModel.edit): after every update of the chain's kind, dm3d_edit_update
+    (mode 1) blends the known latent, noised to the level the step reached, into the kept region, before the row counter's
+    decrement.  The known latent, the keep weights and the level table are buffers of the plan, rewritten by reset(), so one captured
+    graph per (plan, kind) serves every x0, mask, strength and seed.  Level row j holds L_j of L = (clean, sched_0, ..., sched_{n-1}):
+    the blend after the step from sched_i reads row i through the chain's own row counter, the start (q_sample) row n."""
+
+    def _edit_init(self, sched, full):
+        self.sched, self.full = np.asarray(sched, dtype=np.int64), bool(full)
+        plan, dev = self.plan, self.model.device
+        if getattr(plan, "edit_known", None) is None:
+            plan.edit_known = torch.zeros_like(plan.x)
+            plan.edit_keep = torch.zeros(plan.B, plan.x[0].numel() // plan.x.shape[-1], dtype=torch.float32, device=dev)
+            plan.edit_levels = torch.zeros(self.model.timesteps + 1, 4, dtype=torch.float32, device=dev)
+            plan.edit_start = torch.zeros(plan.B, dtype=torch.int32, device=dev)
+        self.edit = self._edit_d()
+
+    def _edit_d(self, noise=None, start=False):
+        plan = self.plan
+        if start:
+            d = self.model._edit_desc(plan.edit_known, plan.edit_levels, plan.edit_start, 0, noise=noise, out=plan.x, seed=self.seed)
+        else:
+            d = self.model._edit_desc(plan.edit_known, plan.edit_levels, self._edit_pos(), 1, x=plan.x, w=plan.edit_keep, noise=noise,
+                                      seed=self.seed)
+        d.seed_dev = plan.seed_buf.data_ptr()
+        return d
+
+    def reset(self, x0, keep, start_noise=None):
+        """A new chain from known latent ``x0`` (device, the plan's shape) with keep weights ``keep`` [B, D, H, W]."""
+        self._own()
+        plan, n = self.plan, len(self.sched)
+        plan.edit_known.copy_(x0.reshape(plan.x.shape))
+        plan.edit_keep.copy_(keep.reshape(plan.edit_keep.shape))
+        plan.edit_levels[:n + 1].copy_(self.model._edit_table(np.concatenate([[-1], self.sched])))
+        plan.edit_start.fill_(n)
+        self._chain_reset(None if self.full else plan.edit_known)
+        if not self.full:                                        # SDEdit's start: the whole volume noised to sched_{n-1}
+            st = torch.cuda.current_stream().cuda_stream
+            check(lib().dm3d_edit_update(C.byref(self._edit_d(start_noise, start=True)), st), "edit_update")
+
+    def step(self, noise=None, known_noise=None):
+        self._own()
+        if self._t < 0:
+            raise RuntimeError("the chain is finished (or was never started): call reset() before step()")
+        st = torch.cuda.current_stream().cuda_stream
+        if noise is not None or known_noise is not None:
+            self._enqueue(st, self.desc if noise is None else self._desc(noise), None if known_noise is None else self._edit_d(known_noise))
+        elif self.use_graph:
+            check(lib().dm3d_graph_launch(self.model._capture(self), st), "graph_launch")
+        else:
+            self._enqueue(st, self.desc)
+        self._t -= 1
+        if self._t < 0:
+            self.finish()
+
+    def _enqueue(self, st, desc, edit=None):
+        self.plan.run(st)
+        push, pop = _lib.roctx()
+        push(self.KIND)
+        self._update(desc, st)
+        check(lib().dm3d_edit_update(C.byref(self.edit if edit is None else edit), st), "edit_update")
+        check(lib().dm3d_add_i32(self._edit_pos().data_ptr(), self.plan.B, -1, st), "add_i32")
+        pop()
+
+
+class EditSampler(_EditChain, Sampler):
+    """A DDPM edit chain of n steps from t = n-1 (DiffusionModel.edit): its blend reads the still-undecremented t_idx."""
+
+    KIND = "ddpm-edit"
+
+    def __init__(self, model, shape, ctx_ids, seed, use_graph, sched, full):
+        Sampler.__init__(self, model, shape, ctx_ids, seed, use_graph)
+        self._edit_init(sched, full)
+
+    def _edit_pos(self):
+        return self.plan.t_idx
+
+    def _chain_reset(self, x_T):
+        Sampler.reset(self, x_T)
+        n = len(self.sched)
+        self.plan.t_idx.fill_(n - 1)
+        self._t = n - 1
+
+    def _update(self, desc, st):
+        check(lib().dm3d_ddpm_update(C.byref(desc), st), "ddpm_update")
+
+
+class DdimEditSampler(_EditChain, DdimSampler):
+    """A DDIM edit chain over the first n entries of a schedule (DiffusionModel.edit): its blend reads the row counter ddim_pos
+    before the decrement (row r steps to dst[r], row 0 to x0)."""
+
+    KIND = "ddim-edit"
+
+    def __init__(self, model, shape, ctx_ids, seed, use_graph, sched, full, eta=0.0, clip_x0=True):
+        DdimSampler.__init__(self, model, shape, ctx_ids, seed, use_graph, sched, eta=eta, clip_x0=clip_x0)
+        self._edit_init(sched, full)
+
+    def _edit_pos(self):
+        return self.plan.ddim_pos
+
+    def _chain_reset(self, x_T):
+        DdimSampler.reset(self, x_T)
+
+    def _update(self, desc, st):
+        check(lib().dm3d_ddim_update(C.byref(desc), st), "ddim_update")

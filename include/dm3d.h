@@ -25,8 +25,8 @@ extern "C" {
                                      104 (dm3d_attention), 105 (x1_fmt / out_fmt / post_*), 106 (ddpm seed_dev; conv/gemm range_flag; the
                                      training entries), 107 (conv wpk_f8: a float8 cross-term form, removed again in 109), 108 (conv wpk_wino: the Winograd-x form), 109 (wpk_f8 and
                                      dm3d_pack_weights_h3f8 are gone; the Winograd-x image pairs its taps differently; dm3d_mlp_fused; conv skip_wpk_frag, gn_stats; dm3d_groupnorm_finalize2), 110 (dm3d_attn_front), 111 (conv split_counters: the Cin split
-                                     meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc were added within 111 (no existing struct or
-                                     entry changed): a host built against an older header must be rebuilt */
+                                     meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc and dm3d_edit_update / dm3d_edit_desc were added
+                                     within 111 (no existing struct or entry changed): a host built against an older header must be rebuilt */
 
 #define DM3D_OK            0
 #define DM3D_EINVAL       -1      /* bad argument (shape, alignment, null pointer) */
@@ -444,6 +444,37 @@ typedef struct dm3d_ddim_desc {
 } dm3d_ddim_desc;
 
 int dm3d_ddim_update(const dm3d_ddim_desc* d, void* stream);
+
+/* ---- Known-latent step of inpainting / image-to-image editing (RePaint's replacement step, SDEdit's start) -------------
+ * Row r = clamp(pos[b], 0, rows-1) of the level table gives a target level a' (alpha_bar of a timestep, 1 for "clean"):
+ *   known_t = sqrt(a')*x0 + sqrt(1-a')*z            (float32, in that order: conditional_dm3d.py:484-491's q_sample)
+ *   known_t = x0 (bitwise) where sqrt(1-a') == 0    (clean: z is not drawn)
+ *   mode 0 (q_sample):  out = known_t; x and w are not read.
+ *   mode 1 (blend):     x <- w*known_t + (1-w)*x    (float32, in that order) for 0 < w < 1, with w = w[b][e / channels] the keep
+ *                        weight of element e's voxel; w == 0 leaves x bitwise untouched (x0, z are not read), w == 1 writes
+ *                        known_t bitwise.
+ * z = noise (if given) or Philox N(0,1) keyed by (seed, the row's level timestep, element) under a stream constant of its own
+ * (never randn's, ddpm_update's or ddim_update's draws).  The host computes a' in float64 from the float32 alpha_bar table and
+ * rounds sqrt(a') and sqrt(1-a') once to float32.  Graph-capturable without host reads, as dm3d_ddim_desc: in a DDPM chain the
+ * blend runs after dm3d_ddpm_update and before the dm3d_add_i32 decrement with pos = t_idx (row t holds level t-1, row 0 clean);
+ * in a DDIM chain after dm3d_ddim_update with pos = its row counter (row r holds that step's target, row 0 clean). */
+typedef struct dm3d_edit_desc {
+    float* x;                   /* mode 1: [batch, per_sample] the chain's state, updated in place */
+    const float* x0;            /* [batch, per_sample] the known latent */
+    const float* w;             /* mode 1: [batch, per_sample / channels] keep weight per voxel in [0, 1] */
+    const float* noise;         /* optional injected z, x0's shape */
+    float* out;                 /* mode 0: the result, x0's shape */
+    int32_t batch; int64_t per_sample;     /* batch <= 65535, per_sample % 4 == 0 */
+    int32_t channels;           /* innermost extent the weight is broadcast over; divides per_sample */
+    const float* levels;        /* [rows][4] device: sqrt(a'), sqrt(1-a'), the level's timestep (the Philox counter, -1 clean), 0 */
+    int32_t rows;
+    const int32_t* pos;         /* [batch] device: the row of each sample */
+    uint64_t seed;
+    const uint64_t* seed_dev;   /* optional: the Philox key is read from device memory instead of `seed` (as dm3d_ddpm_desc) */
+    int32_t mode;
+} dm3d_edit_desc;
+
+int dm3d_edit_update(const dm3d_edit_desc* d, void* stream);
 
 /* p[i] = max(p[i] + delta, 0) (the loop counter of generate kept on the device so a captured step replays unchanged; it
  * saturates at 0, so a step issued past the end of a chain never indexes row -1 of a table). */
