@@ -129,6 +129,15 @@ class EditDesc(C.Structure):
     ]
 
 
+class GuideDesc(C.Structure):
+    _fields_ = [
+        ("eps_pos", _f32p), ("eps_neg", _f32p), ("out", _f32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
+        ("scale", _f32p), ("rescale", _f32p), ("partials", C.c_void_p), ("x", _f32p), ("t_idx", _i32p), ("mode", C.c_int32),
+    ]
+
+
+GUIDE_PARTIAL_BLOCKS = 256          # DM3D_GUIDE_PARTIAL_BLOCKS: GuideDesc.partials holds [batch][256][4] doubles
+
 # name -> (restype, argtypes): every symbol include/dm3d.h declares
 SIGNATURES = {
     "dm3d_version": (C.c_int, []),
@@ -182,6 +191,7 @@ SIGNATURES = {
     "dm3d_ddpm_update": (C.c_int, [C.POINTER(DdpmDesc), C.c_void_p]),
     "dm3d_ddim_update": (C.c_int, [C.POINTER(DdimDesc), C.c_void_p]),
     "dm3d_edit_update": (C.c_int, [C.POINTER(EditDesc), C.c_void_p]),
+    "dm3d_guide_update": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p]),
     "dm3d_range_check": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "dm3d_add_i32": (C.c_int, [_i32p, C.c_int32, C.c_int32, C.c_void_p]),
     "dm3d_randn": (C.c_int, [_f32p, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p]),

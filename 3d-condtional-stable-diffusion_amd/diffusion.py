@@ -3,7 +3,8 @@
 reference: networks/conditional_dm3d.py:418-594 (conditional) and networks/dm3d.py:379-545 (unconditional).  Same
 constructor, attributes and method signatures; tensors are PyTorch device tensors (NDHWC float32) instead of tf.Tensor.
 Keyword-only extensions: ``x_T=`` / ``noise=`` inject the random draws (parity tests), ``seed=``
-selects the in-kernel Philox stream, ``use_graph=`` toggles HIP-graph replay of the step.
+selects the in-kernel Philox stream, ``use_graph=`` toggles HIP-graph replay of the step; ``guidance_scale=`` /
+``negative_context=`` / ``guidance_rescale=`` turn on classifier-free guidance (include/dm3d.h, dm3d_guide_desc).
 
 The sampling loop (:559-573) runs with no host synchronisation: the step index lives in device memory, one step
 (U-Net forward + posterior update + index decrement) is captured once into a HIP graph and replayed T times.
@@ -18,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DdimDesc, DdpmDesc, EditDesc, check, lib
+from ._lib import DdimDesc, DdpmDesc, EditDesc, GuideDesc, check, lib
 from .betas import BETAS_FIELDS, Betas
 from .unet import UNet
 from .weights import UNetConfig
@@ -480,6 +481,75 @@ class DiffusionModel:
         d._keep = (x0, levels, pos, x, w, noise, out)
         return d
 
+    def _guide_desc(self, mode, batch, per_sample, eps_pos=None, eps_neg=None, out=None, scale=None, rescale=None, partials=None,
+                    x=None, t_idx=None) -> GuideDesc:
+        d = GuideDesc()
+        for name, t in (("eps_pos", eps_pos), ("eps_neg", eps_neg), ("out", out), ("scale", scale), ("rescale", rescale),
+                        ("partials", partials), ("x", x), ("t_idx", t_idx)):
+            setattr(d, name, t.data_ptr() if t is not None else None)
+        d.batch, d.per_sample, d.mode = int(batch), int(per_sample), mode
+        d._keep = (eps_pos, eps_neg, out, scale, rescale, partials, x, t_idx)
+        return d
+
+    @staticmethod
+    def _guide_tables(B, guidance_scale, guidance_rescale):
+        """(w, phi): float32 [B] host arrays of the guidance scale and rescale, one value broadcast or one per volume, validated."""
+        out = []
+        for name, v in (("guidance_scale", guidance_scale), ("guidance_rescale", guidance_rescale)):
+            a = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)
+            if a.size not in (1, B):
+                raise ValueError(f"{name} must hold one value or one per volume ({B}), got {a.size}")
+            if not np.all(np.isfinite(a)):
+                raise ValueError(f"{name} must be finite")
+            out.append(np.ascontiguousarray(np.broadcast_to(a, (B,)).astype(np.float32)))
+        if out[1].min() < 0 or out[1].max() > 1:
+            raise ValueError("guidance_rescale must lie in [0, 1]")
+        return out[0], out[1]
+
+    def _guidance(self, B, guidance_scale, negative_context, guidance_rescale):
+        """The argument rules of classifier-free guidance, checked before any plan or device buffer is made: None for an unguided
+        call, else (w [B] float32, phi [B] float32, negative ids [B] int32)."""
+        rescaled = guidance_rescale is not None and bool(np.any(np.asarray(
+            guidance_rescale.detach().cpu() if torch.is_tensor(guidance_rescale) else guidance_rescale) != 0))
+        if guidance_scale is None:
+            if negative_context is not None or rescaled:
+                raise ValueError("negative_context / guidance_rescale need guidance_scale")
+            return None
+        if not self.conditional:
+            raise ValueError("classifier-free guidance needs the conditional model: there is no context to guide with")
+        if negative_context is None:
+            raise ValueError("guidance_scale needs negative_context (the model has no reserved null context)")
+        w, phi = self._guide_tables(B, guidance_scale, 0.0 if guidance_rescale is None else guidance_rescale)
+        neg = self._context_ids(negative_context, B)
+        return w, phi, np.ascontiguousarray(np.broadcast_to(neg, (B,)))
+
+    def guide_eps(self, eps_pos, eps_neg, guidance_scale, guidance_rescale=0.0):
+        """Classifier-free guidance of one noise prediction (include/dm3d.h, dm3d_guide_desc): eps_neg + w (eps_pos - eps_neg) in
+        float32 (sub, mul, add), then with guidance_rescale = phi != 0 scaled by phi std(eps_pos) / std(eps_g) + (1 - phi) per
+        volume (population standard deviations over the whole volume); the single-call counterpart of a guided chain's step, as
+        ddim_step is of a DDIM chain.  ``guidance_scale`` / ``guidance_rescale``: one value or one per volume.  Returns a new
+        tensor; the inputs are left untouched."""
+        eps_pos = torch.as_tensor(eps_pos, dtype=torch.float32)
+        eps_neg = torch.as_tensor(eps_neg, dtype=torch.float32)
+        if eps_pos.dim() < 2 or eps_neg.shape != eps_pos.shape or eps_pos[0].numel() % 4:
+            raise ValueError("eps_pos / eps_neg must share one shape [B, ...] with a multiple of 4 elements per volume")
+        B, per = eps_pos.shape[0], eps_pos[0].numel()
+        w, phi = self._guide_tables(B, guidance_scale, guidance_rescale)
+        dev = self.device
+        eps_pos, eps_neg = eps_pos.to(dev).contiguous(), eps_neg.to(dev).contiguous()
+        out = torch.empty_like(eps_pos)
+        w_d, phi_d = torch.from_numpy(w).to(dev), torch.from_numpy(phi).to(dev)
+        st = torch.cuda.current_stream().cuda_stream
+        partials = None
+        if phi.any():
+            partials = torch.empty(B * _lib.GUIDE_PARTIAL_BLOCKS * 4, dtype=torch.float64, device=dev)
+        d = self._guide_desc(0, B, per, eps_pos=eps_pos, eps_neg=eps_neg, out=out, scale=w_d, rescale=phi_d, partials=partials)
+        check(lib().dm3d_guide_update(C.byref(d), st), "guide_update")
+        if partials is not None:
+            d = self._guide_desc(1, B, per, out=out, rescale=phi_d, partials=partials)
+            check(lib().dm3d_guide_update(C.byref(d), st), "guide_update")
+        return out
+
     # -- a14: generate ----------------------------------------------------------------------------------------------
     def _context_ids(self, context_value, batch=None):
         """The reference takes one scalar id and broadcasts it (conditional_dm3d.py:552); an array of shape [B], [B,1] or [B,1,1]
@@ -501,10 +571,11 @@ class DiffusionModel:
         return secrets.randbits(64)
 
     def sampler(self, shape, context_value=None, *, seed=None, use_graph=True, kind="ddpm", num_steps=None, timesteps=None,
-                eta=0.0, clip_x0=True) -> "Sampler":
+                eta=0.0, clip_x0=True, guidance_scale=None, negative_context=None, guidance_rescale=0.0) -> "Sampler":
         """The state of one generate() call: plan, tables, context rows and the captured step graph.  There is one live
         Sampler per (batch, context mode): creating another one for the same plan retires the older (its step() raises).
-        ``kind="ddim"``: a DDIM chain over ``ddim_timesteps(T, num_steps, timesteps)`` (S steps) with ``eta`` / ``clip_x0``."""
+        ``kind="ddim"``: a DDIM chain over ``ddim_timesteps(T, num_steps, timesteps)`` (S steps) with ``eta`` / ``clip_x0``.
+        ``guidance_scale`` / ``negative_context`` / ``guidance_rescale``: a guided chain, as generate()."""
         shape = self._sampler_shape(shape)
         if kind not in ("ddpm", "ddim"):
             raise ValueError(f"sampler kind must be 'ddpm' or 'ddim', got {kind!r}")
@@ -514,7 +585,13 @@ class DiffusionModel:
             taus = ddim_timesteps(self.timesteps, num_steps, timesteps)        # validated before the plan is touched
             if not eta >= 0:
                 raise ValueError("eta must be >= 0")
+        guide = self._guidance(shape[0], guidance_scale, negative_context, guidance_rescale)
         ctx = self._context_ids(context_value, shape[0]) if self.conditional else None
+        if guide is not None:
+            ctx = _guided_ids(ctx, guide[2])
+            if kind == "ddpm":
+                return GuidedSampler(self, shape, ctx, seed, use_graph, guide=guide[:2])
+            return GuidedDdimSampler(self, shape, ctx, seed, use_graph, taus, eta=eta, clip_x0=clip_x0, guide=guide[:2])
         if kind == "ddpm":
             return Sampler(self, shape, ctx, seed, use_graph)
         return DdimSampler(self, shape, ctx, seed, use_graph, taus, eta=eta, clip_x0=clip_x0)
@@ -527,7 +604,8 @@ class DiffusionModel:
         return shape
 
     def generate(self, shape=(1, 16, 16, 16, 16), last_step=0, context_value=None, *, x_T=None, noise=None, seed=None,
-                 use_graph=True, steps=None, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0, clip_x0=True):
+                 use_graph=True, steps=None, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0, clip_x0=True,
+                 guidance_scale=None, negative_context=None, guidance_rescale=0.0):
         """conditional_dm3d.py:550-575.  For shape[0] > 1 the single context row is broadcast to every sample.
         ``seed`` (optional): Philox key of x_T and of every step's noise; None (default) draws a fresh key per call, as the
         reference draws fresh tf.random.normal noise, an integer makes the call reproducible.
@@ -535,17 +613,25 @@ class DiffusionModel:
         after that many steps (benchmarks time a prefix of the chain).
         ``sampler="ddim"``: the DDIM chain over ``ddim_timesteps(T, num_steps, timesteps)`` = tau_0 < ... < tau_{S-1}, S U-Net
         evaluations, ``eta`` (0: deterministic), ``clip_x0`` (clamp the x0 estimate to [-1, 1], as the reference's DDPM loop
-        clips); ``noise`` is then [S, *shape] with row k the z of the step from tau_k; last_step must be 0."""
+        clips); ``noise`` is then [S, *shape] with row k the z of the step from tau_k; last_step must be 0.
+        ``guidance_scale`` = w (None, the default: no guidance, today's path): classifier-free guidance, for either sampler.  Every
+        step evaluates the U-Net under ``context_value`` and under ``negative_context`` (one id or one per volume, always given: the
+        model has no reserved null context) in one pass over a plan of 2 B rows and continues from eps_neg + w (eps_pos - eps_neg);
+        ``guidance_rescale`` = phi in [0, 1] then scales it by phi std(eps_pos) / std(eps_g) + (1 - phi) per volume (Lin et al. 2023).
+        w and phi take one value or one per volume; w < 0 and w > 1 are legal, w = 1 is the plain chain under context_value.  The
+        chain draws the x_T and the per-step z of the unguided call of the same B volumes and seed."""
         if not 0 <= last_step <= self.timesteps:
             raise ValueError("last_step out of range")
         if sampler == "ddim":
             if last_step != 0:
                 raise ValueError("sampler='ddim' runs whole chains: last_step must be 0")
             return self._generate_ddim(shape, context_value, x_T=x_T, noise=noise, seed=seed, use_graph=use_graph, steps=steps,
-                                       num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0)
+                                       num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0, guidance_scale=guidance_scale,
+                                       negative_context=negative_context, guidance_rescale=guidance_rescale)
         self._sync_from_trainer()
         smp = self.sampler(shape, context_value, seed=seed, use_graph=use_graph and noise is None, kind=sampler,
-                           num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0)
+                           num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0, guidance_scale=guidance_scale,
+                           negative_context=negative_context, guidance_rescale=guidance_rescale)
         smp.reset(x_T)
         T = self.timesteps
         n_steps = T - last_step if steps is None else min(int(steps), T - last_step)
@@ -558,14 +644,16 @@ class DiffusionModel:
         else:
             for _ in range(n_steps):
                 smp.step()
-        out = smp.plan.x.clone()
+        out = smp.x.clone()
         self.network.check_range(smp.plan)
         return out
 
-    def _generate_ddim(self, shape, context_value, *, x_T, noise, seed, use_graph, steps, num_steps, timesteps, eta, clip_x0):
+    def _generate_ddim(self, shape, context_value, *, x_T, noise, seed, use_graph, steps, num_steps, timesteps, eta, clip_x0,
+                       guidance_scale=None, negative_context=None, guidance_rescale=0.0):
         self._sync_from_trainer()
         smp = self.sampler(shape, context_value, seed=seed, use_graph=use_graph and noise is None, kind="ddim",
-                           num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0)
+                           num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0, guidance_scale=guidance_scale,
+                           negative_context=negative_context, guidance_rescale=guidance_rescale)
         S = smp.n_steps
         if noise is not None:
             noise = torch.as_tensor(noise, dtype=torch.float32).to(self.device)
@@ -575,7 +663,7 @@ class DiffusionModel:
         n_steps = S if steps is None else min(int(steps), S)
         for k in range(n_steps):
             smp.step(noise=None if noise is None else noise[S - 1 - k].contiguous())
-        out = smp.plan.x.clone()
+        out = smp.x.clone()
         self.network.check_range(smp.plan)
         return out
 
@@ -593,12 +681,13 @@ class DiffusionModel:
         smp.reset(x0)
         for _ in range(smp.n_steps):
             smp.step()
-        out = smp.plan.x.clone()
+        out = smp.x.clone()
         self.network.check_range(smp.plan)
         return out
 
     def edit(self, x0, context_value=None, *, mask=None, strength=1.0, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0,
-             clip_x0=True, seed=None, use_graph=True, noise=None, known_noise=None, steps=None):
+             clip_x0=True, seed=None, use_graph=True, noise=None, known_noise=None, steps=None, guidance_scale=None,
+             negative_context=None, guidance_rescale=0.0):
         """Inpainting and image-to-image editing (SDEdit) of latents ``x0`` [B, S, S, S, C]; returns latents of x0's shape.
 
         ``mask`` (1 = regenerate, 0 = keep, in [0, 1]; None: regenerate everything) is pooled to the latent by latent_mask() and
@@ -611,7 +700,9 @@ class DiffusionModel:
         context_value: one id or one per volume, as generate().
         ``noise`` (optional): [n, *x0.shape], row i the sampler's z of the step from sched_i (generate's rows at n = N).
         ``known_noise`` (optional): [n+1, *x0.shape], row j the z of the known latent at level L_j of L = (clean, sched_0, ...,
-        sched_{n-1}): row i is the blend after the step from sched_i (row 0, clean, draws none) and row n the start (unused at n = N)."""
+        sched_{n-1}): row i is the blend after the step from sched_i (row 0, clean, draws none) and row n the start (unused at n = N).
+        ``guidance_scale`` / ``negative_context`` / ``guidance_rescale``: classifier-free guidance of the chain's eps, as generate();
+        the known latent, the blend and every draw are those of the unguided edit."""
         x0 = torch.as_tensor(x0, dtype=torch.float32)
         shape = self._sampler_shape(x0.shape)
         if sampler not in ("ddpm", "ddim"):
@@ -627,6 +718,7 @@ class DiffusionModel:
         n = edit_steps(strength, len(sched))
         full, sched = n == len(sched), sched[:n]
         mask = None if mask is None else latent_mask(mask, shape)
+        guide = self._guidance(shape[0], guidance_scale, negative_context, guidance_rescale)
         ctx = self._context_ids(context_value, shape[0]) if self.conditional else None
         for name, arr, rows in (("noise", noise, n), ("known_noise", known_noise, n + 1)):
             if arr is not None and tuple(arr.shape) != (rows,) + shape:
@@ -642,7 +734,13 @@ class DiffusionModel:
         if known_noise is not None:
             known_noise = torch.as_tensor(known_noise, dtype=torch.float32).to(dev)
         eager = noise is not None or known_noise is not None
-        if sampler == "ddpm":
+        if guide is not None:
+            ctx, gkw = _guided_ids(ctx, guide[2]), dict(guide=guide[:2])
+            if sampler == "ddpm":
+                smp = GuidedEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, **gkw)
+            else:
+                smp = GuidedDdimEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, eta=eta, clip_x0=clip_x0, **gkw)
+        elif sampler == "ddpm":
             smp = EditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full)
         else:
             smp = DdimEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, eta=eta, clip_x0=clip_x0)
@@ -652,7 +750,7 @@ class DiffusionModel:
             i = n - 1 - k
             smp.step(noise=None if noise is None else noise[i].contiguous(),
                      known_noise=None if known_noise is None else known_noise[i].contiguous())
-        out = smp.plan.x.clone()
+        out = smp.x.clone()
         self.network.check_range(smp.plan)
         return out
 
@@ -660,8 +758,8 @@ class DiffusionModel:
 
     def _capture(self, smp: "Sampler"):
         """Capture one step of ``smp`` into a HIP graph, cached per (plan, sampler kind): the Philox key lives in a device scalar of
-        the plan (dm3d_ddpm_desc.seed_dev), and a DDIM chain's schedule, eta and clip in the plan's tables, so one graph serves
-        every seed and every DDIM schedule."""
+        the plan (dm3d_ddpm_desc.seed_dev), a DDIM chain's schedule, eta and clip and a guided chain's scale and rescale in the
+        plan's tables, so one graph serves every seed, every DDIM schedule and every guidance scale."""
         key = (id(smp.plan), smp.KIND)
         if key in self._graphs:
             self._graphs[key] = self._graphs.pop(key)                  # most recently used last
@@ -730,7 +828,7 @@ class Sampler:
         self.seed = (model.fresh_seed() if seed is None else int(seed)) & (2 ** 64 - 1)
         net, T = model.network, model.timesteps
         # one context row per volume, or one broadcast; "sampler": never the plan UNet.__call__ fills with its own time rows
-        self.plan = net.plan(shape[0], T, ctx_ids is not None and len(ctx_ids) > 1, purpose="sampler")
+        self.plan = net.plan(shape[0] * self.COPIES, T, ctx_ids is not None and len(ctx_ids) > 1, purpose="sampler")
         plan = self.plan
         if getattr(plan, "_time_filled", None) is not net.P:
             net.fill_time_table(np.arange(T), plan.vec)
@@ -746,9 +844,25 @@ class Sampler:
         self._t = -1                          # host mirror of the device step index; -1: no chain in progress
 
     KIND = "ddpm"
+    COPIES = 1                                # rows of the plan per volume of the chain (a guided chain: 2)
+
+    def _head(self, t):
+        """The rows of a plan buffer this chain updates and returns: all of them (a guided chain: the first half)."""
+        return t
+
+    @property
+    def x(self):
+        """The chain's latents [B, ...]: a view of the plan's state."""
+        return self._head(self.plan.x)
+
+    def _guide(self, st):
+        """Between the U-Net and the update: nothing (a guided chain: eps <- the guided eps)."""
+
+    def _mirror(self, st):
+        """After the update and the blend, before the counter's decrement: nothing (a guided chain: the second half follows)."""
 
     def _desc(self, noise=None):
-        return self.model._ddpm_desc(self.plan.x, self.plan.eps, self.plan.t_idx, 1, noise=noise, seed=self.seed)
+        return self.model._ddpm_desc(self.x, self._head(self.plan.eps), self.plan.t_idx, 1, noise=noise, seed=self.seed)
 
     def _own(self):
         if self._gen != self.plan._owner_gen:
@@ -770,15 +884,17 @@ class Sampler:
         seed_i64 = self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed
         plan.seed_buf.fill_(seed_i64)
         if x_T is not None:
-            plan.x.copy_(torch.as_tensor(x_T, dtype=torch.float32).reshape(self.shape))
+            self.x.copy_(torch.as_tensor(x_T, dtype=torch.float32).reshape(self.shape))
         else:
-            check(lib().dm3d_randn(plan.x.data_ptr(), plan.x.numel(), self.seed, 0x7fffffff, st), "randn")
+            check(lib().dm3d_randn(self.x.data_ptr(), self.x.numel(), self.seed, 0x7fffffff, st), "randn")
 
     def _enqueue(self, st, desc):
         self.plan.run(st)
         push, pop = _lib.roctx()
         push("ddpm")
+        self._guide(st)
         check(lib().dm3d_ddpm_update(C.byref(desc), st), "ddpm_update")
+        self._mirror(st)
         check(lib().dm3d_add_i32(self.plan.t_idx.data_ptr(), self.plan.B, -1, st), "add_i32")
         pop()
 
@@ -834,7 +950,7 @@ class DdimSampler(Sampler):
             plan.ddim_tau = torch.zeros(T, dtype=torch.int32, device=dev)
             plan.ddim_next = torch.zeros(T, dtype=torch.int32, device=dev)
             plan.ddim_pos = torch.zeros(plan.B, dtype=torch.int32, device=dev)
-        d = self.model._ddim_desc(plan.x, plan.eps, plan.ddim_coef, plan.ddim_tau, plan.ddim_pos, 1, noise=noise,
+        d = self.model._ddim_desc(self.x, self._head(plan.eps), plan.ddim_coef, plan.ddim_tau, plan.ddim_pos, 1, noise=noise,
                                   t_next=plan.ddim_next, t_idx=plan.t_idx, seed=self.seed)
         d.seed_dev = plan.seed_buf.data_ptr()
         return d
@@ -867,7 +983,9 @@ class DdimSampler(Sampler):
         self.plan.run(st)
         push, pop = _lib.roctx()
         push("ddim")
+        self._guide(st)
         check(lib().dm3d_ddim_update(C.byref(desc), st), "ddim_update")
+        self._mirror(st)
         check(lib().dm3d_add_i32(self.plan.ddim_pos.data_ptr(), self.plan.B, -1, st), "add_i32")
         pop()
 
@@ -891,10 +1009,11 @@ class _EditChain:
 
     def _edit_d(self, noise=None, start=False):
         plan = self.plan
+        known = self._head(plan.edit_known)                      # (a guided chain: the first half of every buffer)
         if start:
-            d = self.model._edit_desc(plan.edit_known, plan.edit_levels, plan.edit_start, 0, noise=noise, out=plan.x, seed=self.seed)
+            d = self.model._edit_desc(known, plan.edit_levels, plan.edit_start, 0, noise=noise, out=plan.x, seed=self.seed)
         else:
-            d = self.model._edit_desc(plan.edit_known, plan.edit_levels, self._edit_pos(), 1, x=plan.x, w=plan.edit_keep, noise=noise,
+            d = self.model._edit_desc(known, plan.edit_levels, self._edit_pos(), 1, x=plan.x, w=plan.edit_keep, noise=noise,
                                       seed=self.seed)
         d.seed_dev = plan.seed_buf.data_ptr()
         return d
@@ -903,11 +1022,12 @@ class _EditChain:
         """A new chain from known latent ``x0`` (device, the plan's shape) with keep weights ``keep`` [B, D, H, W]."""
         self._own()
         plan, n = self.plan, len(self.sched)
-        plan.edit_known.copy_(x0.reshape(plan.x.shape))
-        plan.edit_keep.copy_(keep.reshape(plan.edit_keep.shape))
+        known, kept = self._head(plan.edit_known), self._head(plan.edit_keep)
+        known.copy_(x0.reshape(known.shape))
+        kept.copy_(keep.reshape(kept.shape))
         plan.edit_levels[:n + 1].copy_(self.model._edit_table(np.concatenate([[-1], self.sched])))
         plan.edit_start.fill_(n)
-        self._chain_reset(None if self.full else plan.edit_known)
+        self._chain_reset(None if self.full else known)
         if not self.full:                                        # SDEdit's start: the whole volume noised to sched_{n-1}
             st = torch.cuda.current_stream().cuda_stream
             check(lib().dm3d_edit_update(C.byref(self._edit_d(start_noise, start=True)), st), "edit_update")
@@ -931,8 +1051,10 @@ class _EditChain:
         self.plan.run(st)
         push, pop = _lib.roctx()
         push(self.KIND)
+        self._guide(st)
         self._update(desc, st)
         check(lib().dm3d_edit_update(C.byref(self.edit if edit is None else edit), st), "edit_update")
+        self._mirror(st)
         check(lib().dm3d_add_i32(self._edit_pos().data_ptr(), self.plan.B, -1, st), "add_i32")
         pop()
 
@@ -977,3 +1099,69 @@ class DdimEditSampler(_EditChain, DdimSampler):
 
     def _update(self, desc, st):
         check(lib().dm3d_ddim_update(C.byref(desc), st), "ddim_update")
+
+
+def _guided_ids(ctx, neg) -> np.ndarray:
+    """The context rows of a guided chain's plan: B rows of the wanted ids, then B rows of the negative ones."""
+    B = len(neg)
+    return np.concatenate([np.broadcast_to(ctx, (B,)), neg]).astype(np.int32)
+
+
+class _GuidedChain:
+    """Classifier-free guidance of a chain (include/dm3d.h, dm3d_guide_desc).  The chain of B volumes drives a plan of 2 B rows with
+    one context row per volume: rows :B run under context_value, rows B: under negative_context on the same x, so one U-Net pass
+    gives both predictions.  A step is U-Net, guide (eps[:B] <- eps_out in place), the chain's own update and blend on rows :B
+    (their descriptors carry batch = B, so the Philox counters are those of the unguided B-row chain), mirror (x and t_idx of rows
+    :B to rows B:), counter decrement.  The scales and rescales are tables of the plan, rewritten by reset(): one captured graph per
+    (plan, kind) serves every scale, and its kind keeps it apart from the plain step of the same 2 B-row plan.  The graph always
+    holds the rescale launch (rows with phi = 0 return at once); an eager chain launches it only if some phi != 0."""
+
+    COPIES = 2
+
+    def __init__(self, *args, guide, **kw):
+        self.w, self.phi = guide
+        super().__init__(*args, **kw)
+        plan, dev, B = self.plan, self.model.device, self.shape[0]
+        if getattr(plan, "guide_w", None) is None:
+            plan.guide_w = torch.zeros(B, dtype=torch.float32, device=dev)
+            plan.guide_phi = torch.zeros(B, dtype=torch.float32, device=dev)
+            plan.guide_partials = torch.zeros(B * _lib.GUIDE_PARTIAL_BLOCKS * 4, dtype=torch.float64, device=dev)
+        per, mk = plan.x[0].numel(), self.model._guide_desc
+        self._rescales = bool(self.use_graph or self.phi.any())
+        self._guide_descs = [mk(0, B, per, eps_pos=plan.eps, eps_neg=plan.eps[B:], out=plan.eps, scale=plan.guide_w,
+                                rescale=plan.guide_phi, partials=plan.guide_partials)]
+        if self._rescales:
+            self._guide_descs.append(mk(1, B, per, out=plan.eps, rescale=plan.guide_phi, partials=plan.guide_partials))
+        self._mirror_desc = mk(2, B, per, x=plan.x, t_idx=plan.t_idx)
+
+    def _head(self, t):
+        return t[:self.shape[0]]
+
+    def reset(self, *args, **kw):
+        super().reset(*args, **kw)
+        self.plan.guide_w.copy_(torch.from_numpy(self.w))
+        self.plan.guide_phi.copy_(torch.from_numpy(self.phi))
+        self._mirror(torch.cuda.current_stream().cuda_stream)      # x_T (or the q_sample start) and t_idx, first half to second
+
+    def _guide(self, st):
+        for d in self._guide_descs:
+            check(lib().dm3d_guide_update(C.byref(d), st), "guide_update")
+
+    def _mirror(self, st):
+        check(lib().dm3d_guide_update(C.byref(self._mirror_desc), st), "guide_update")
+
+
+class GuidedSampler(_GuidedChain, Sampler):
+    KIND = "ddpm-cfg"
+
+
+class GuidedDdimSampler(_GuidedChain, DdimSampler):
+    KIND = "ddim-cfg"
+
+
+class GuidedEditSampler(_GuidedChain, EditSampler):
+    KIND = "ddpm-edit-cfg"
+
+
+class GuidedDdimEditSampler(_GuidedChain, DdimEditSampler):
+    KIND = "ddim-edit-cfg"

@@ -67,18 +67,29 @@ def generate_sharded(model, global_shape, last_step: int = 0, context_value=None
     single-process MirroredStrategy scope of main_conditional_dm.py:197).  Rank r denoises volumes ``shard_range(B, r, R)`` with
     Philox key ``rank_seed(seed, r)``; there is no per-step collective.  ``context_value``: one id (broadcast) or one per volume
     of the GLOBAL batch (each rank takes its slice).  ``gather=True``: one all_gather at the end, every rank returns the whole
-    ``global_shape`` tensor in rank order; otherwise the local shard ([hi-lo, ...]; may be empty)."""
+    ``global_shape`` tensor in rank order; otherwise the local shard ([hi-lo, ...]; may be empty).  The classifier-free guidance
+    keywords of generate() are forwarded; ``guidance_scale`` / ``guidance_rescale`` / ``negative_context`` given per volume of the
+    global batch are sliced per rank as ``context_value`` is."""
     shape = tuple(int(s) for s in global_shape)
     dist_on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
     lo, hi = shard_range(shape[0], rank, world)
-    ctx = context_value
-    if ctx is not None:
-        ids = np.asarray(ctx.detach().cpu() if torch.is_tensor(ctx) else ctx).reshape(-1)
-        if ids.size == shape[0] and ids.size > 1:
-            ctx = ids[lo:hi]
-        elif ids.size != 1:
-            raise ValueError(f"context_value must hold one id or one per volume of the global batch ({shape[0]}), got {ids.size}")
+
+    def shard(name, v):
+        """One value stays as given; one per volume of the global batch becomes this rank's slice."""
+        if v is None:
+            return v
+        arr = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v).reshape(-1)
+        if arr.size == shape[0] and arr.size > 1:
+            return arr[lo:hi]
+        if arr.size != 1:
+            raise ValueError(f"{name} must hold one value or one per volume of the global batch ({shape[0]}), got {arr.size}")
+        return v
+
+    ctx = shard("context_value", context_value)
+    for name in ("guidance_scale", "negative_context", "guidance_rescale"):
+        if name in generate_kw:
+            generate_kw[name] = shard(name, generate_kw[name])
     dev = getattr(model, "device", torch.device("cpu"))
     if hi > lo:
         local = model.generate((hi - lo,) + shape[1:], last_step, ctx, seed=rank_seed(seed, rank), **generate_kw)

@@ -25,8 +25,8 @@ extern "C" {
                                      104 (dm3d_attention), 105 (x1_fmt / out_fmt / post_*), 106 (ddpm seed_dev; conv/gemm range_flag; the
                                      training entries), 107 (conv wpk_f8: a float8 cross-term form, removed again in 109), 108 (conv wpk_wino: the Winograd-x form), 109 (wpk_f8 and
                                      dm3d_pack_weights_h3f8 are gone; the Winograd-x image pairs its taps differently; dm3d_mlp_fused; conv skip_wpk_frag, gn_stats; dm3d_groupnorm_finalize2), 110 (dm3d_attn_front), 111 (conv split_counters: the Cin split
-                                     meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc and dm3d_edit_update / dm3d_edit_desc were added
-                                     within 111 (no existing struct or entry changed): a host built against an older header must be rebuilt */
+                                     meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc, dm3d_edit_update / dm3d_edit_desc and
+                                     dm3d_guide_update / dm3d_guide_desc were added within 111 (no existing struct or entry changed): a host built against an older header must be rebuilt */
 
 #define DM3D_OK            0
 #define DM3D_EINVAL       -1      /* bad argument (shape, alignment, null pointer) */
@@ -475,6 +475,41 @@ typedef struct dm3d_edit_desc {
 } dm3d_edit_desc;
 
 int dm3d_edit_update(const dm3d_edit_desc* d, void* stream);
+
+/* ---- Classifier-free guidance (Ho and Salimans 2022) with the guidance rescale of Lin et al. 2023, section 3.4 ---------------
+ * Between the U-Net and the update of a guided chain, whose plan holds batch "positive" rows followed by batch "negative" rows:
+ *   eps_g   = eps_neg + w*(eps_pos - eps_neg)          float32, in that order: sub, mul, add, each rounded
+ *   eps_g   = eps_pos bitwise where w == 1, eps_neg bitwise where w == 0 (the other operand is not read, unless the row's statistics
+ *             below need eps_pos)
+ *   f       = phi*std(eps_pos)/std(eps_g) + (1 - phi)  per sample; std is the population standard deviation (divide by per_sample; the
+ *             ratio is the unbiased estimator's too) over all per_sample elements, from float64 sums of the values and of their
+ *             squares; f is computed in float64 and rounded once to float32; std(eps_g) == 0 gives f = 1
+ *   eps_out = f*eps_g                                   only where phi != 0; phi == 0 leaves eps_g bitwise
+ * w = scale[b] and phi = rescale[b] are read from device memory, so one captured step graph serves every scale and rescale.
+ *   mode 0 (combine): out = eps_g.  out may be eps_pos (in place: a row with w == 1 is then not touched at all), never eps_neg.
+ *                     With partials set, each block of a row with phi != 0 also leaves its float64 partial sums (sum and sum of
+ *                     squares of eps_pos and of eps_g) there; rows with phi == 0 leave theirs unwritten.
+ *   mode 1 (rescale): out <- f*out for the rows with phi != 0, f from the partials mode 0 left (same batch and per_sample); rows with
+ *                     phi == 0 are not touched.  A host that knows every phi to be 0 need not launch it.
+ *   mode 2 (mirror):  x[batch + b] <- x[b] and, with t_idx set, t_idx[batch + b] <- t_idx[b] for b < batch: the second half of the
+ *                     plan takes over the state the update left in the first.
+ * The sums are reduced in a fixed order (lanes by shuffles, waves and blocks in index order, no atomics): runs repeat bitwise.
+ * A NaN in eps_pos or eps_neg reaches that element of eps_g, and with phi != 0 every element of that sample. */
+#define DM3D_GUIDE_PARTIAL_BLOCKS 256      /* partials holds [batch][DM3D_GUIDE_PARTIAL_BLOCKS][4] doubles */
+typedef struct dm3d_guide_desc {
+    const float* eps_pos;       /* mode 0: [batch, per_sample] prediction under the wanted context */
+    const float* eps_neg;       /* mode 0: the same under the negative context */
+    float* out;                 /* modes 0, 1: [batch, per_sample] */
+    int32_t batch; int64_t per_sample;     /* batch <= 65535, per_sample % 4 == 0 */
+    const float* scale;         /* mode 0: [batch] device, w */
+    const float* rescale;       /* mode 0: optional (NULL: every phi is 0); mode 1: required.  [batch] device, phi in [0, 1] */
+    double* partials;           /* mode 0: optional; mode 1: required.  [batch][256][4] device scratch */
+    float* x;                   /* mode 2: [2*batch, per_sample] */
+    int32_t* t_idx;             /* mode 2: optional [2*batch] device */
+    int32_t mode;
+} dm3d_guide_desc;
+
+int dm3d_guide_update(const dm3d_guide_desc* d, void* stream);
 
 /* p[i] = max(p[i] + delta, 0) (the loop counter of generate kept on the device so a captured step replays unchanged; it
  * saturates at 0, so a step issued past the end of a chain never indexes row -1 of a table). */
