@@ -121,6 +121,13 @@ class DdimDesc(C.Structure):
     ]
 
 
+class DpmDesc(C.Structure):
+    _fields_ = [
+        ("x", _f32p), ("eps", _f32p), ("hist", _f32p), ("out", _f32p), ("x0_out", _f32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
+        ("coef", _f32p), ("rows", C.c_int32), ("pos", _i32p), ("t_next", _i32p), ("t_idx", _i32p), ("mode", C.c_int32),
+    ]
+
+
 class EditDesc(C.Structure):
     _fields_ = [
         ("x", _f32p), ("x0", _f32p), ("w", _f32p), ("noise", _f32p), ("out", _f32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
@@ -190,6 +197,7 @@ SIGNATURES = {
     "dm3d_affine_act": (C.c_int, [_f32p, _f32p, C.c_int64, C.c_int32, _f32p, _f32p, C.c_int32, C.c_void_p]),
     "dm3d_ddpm_update": (C.c_int, [C.POINTER(DdpmDesc), C.c_void_p]),
     "dm3d_ddim_update": (C.c_int, [C.POINTER(DdimDesc), C.c_void_p]),
+    "dm3d_dpm_update": (C.c_int, [C.POINTER(DpmDesc), C.c_void_p]),
     "dm3d_edit_update": (C.c_int, [C.POINTER(EditDesc), C.c_void_p]),
     "dm3d_guide_update": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p]),
     "dm3d_range_check": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),

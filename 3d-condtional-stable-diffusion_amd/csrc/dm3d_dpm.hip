@@ -1,0 +1,71 @@
+// dm3d_dpm.hip — the DPM-Solver++(2M) update (Lu et al. 2022, "DPM-Solver++", Algorithm 2): a second-order multistep solver of the
+// sampling ODE in the data-prediction form.  Every per-step constant comes from a coefficient table the host writes once per chain
+// (include/dm3d.h, dm3d_dpm_desc), so first-order rows (the DDIM eta = 0 step), second-order rows and the step to the clean sample
+// share one kernel.  A pure HBM stream like ddim_kernel: 16 B per lane, read x, eps and (second-order rows only) the previous x0
+// estimate, write x and this step's x0 estimate.  No noise term: no Philox.
+#include "dm3d_common.h"
+
+namespace {
+
+struct DpmArgs {
+    float* x; const float* eps; float* hist; float* out; float* x0_out;
+    long per4;                                     // float4 per sample
+    const float* coef; const int* t_next; int rows;
+    const int* pos; int* t_idx;
+    int mode;
+};
+
+__global__ __launch_bounds__(256) void dpm_kernel(const DpmArgs p) {
+    const int b = blockIdx.y;
+    const int r = min(max(p.pos[b], 0), p.rows - 1);
+    const f32x4 c0 = reinterpret_cast<const f32x4*>(p.coef)[2 * r];          // sqrt(ab), sqrt(1-ab), c_x, c_0
+    const f32x4 c1 = reinterpret_cast<const f32x4*>(p.coef)[2 * r + 1];      // c_1, clip, -, -
+    const float sqab = c0[0], sq1ab = c0[1], c_x = c0[2], c_0 = c0[3], c_1 = c1[0];
+    const bool clip = c1[1] != 0.f;
+    const bool second = c_1 != 0.f && p.hist != nullptr;                     // a first-order row never reads the history
+    // the next step's U-Net row; the kernel never reads t_idx, so this one lane per sample races with nobody
+    if (p.t_idx && blockIdx.x == 0 && threadIdx.x == 0) p.t_idx[b] = p.t_next[r];
+    float* dst = p.mode == 0 ? p.out : p.x;
+    float* x0_dst = p.mode == 0 ? p.x0_out : p.hist;
+    const long base = (long)b * p.per4;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < p.per4; i += (long)gridDim.x * 256) {
+        const f32x4 x = reinterpret_cast<const f32x4*>(p.x)[base + i];
+        const f32x4 e = reinterpret_cast<const f32x4*>(p.eps)[base + i];
+        f32x4 h = {0.f, 0.f, 0.f, 0.f};
+        if (second) h = reinterpret_cast<const f32x4*>(p.hist)[base + i];
+        f32x4 o, x0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float v = __fdiv_rn(__fsub_rn(x[k], __fmul_rn(sq1ab, e[k])), sqab);      // ddim_kernel's order
+            if (clip) v = v != v ? v : fminf(fmaxf(v, -1.0f), 1.0f);                 // a NaN passes, as in ddim_kernel's clip
+            x0[k] = v;
+            const float first = __fadd_rn(__fmul_rn(c_x, x[k]), __fmul_rn(c_0, v));
+            o[k] = second ? __fadd_rn(first, __fmul_rn(c_1, h[k])) : first;
+        }
+        reinterpret_cast<f32x4*>(dst)[base + i] = o;
+        if (x0_dst) reinterpret_cast<f32x4*>(x0_dst)[base + i] = x0;
+    }
+}
+
+}  // namespace
+
+extern "C" int dm3d_dpm_update(const dm3d_dpm_desc* d, void* stream) {
+    DM3D_REQUIRE(d != nullptr, "dpm: null descriptor");
+    DM3D_REQUIRE(d->x && d->eps && d->coef && d->pos, "dpm: x/eps/coef/pos must be non-null");
+    DM3D_REQUIRE(d->batch > 0 && d->batch <= 65535 && d->per_sample > 0 && d->per_sample % 4 == 0,
+                 "dpm: batch=%d per_sample=%lld (must be a positive multiple of 4)", d->batch, (long long)d->per_sample);
+    DM3D_REQUIRE(d->rows > 0, "dpm: rows=%d", d->rows);
+    DM3D_REQUIRE(d->mode == 0 || d->mode == 1, "dpm: mode %d not in {0,1}", d->mode);
+    DM3D_REQUIRE(d->mode == 1 || d->out, "dpm: mode 0 needs out");
+    DM3D_REQUIRE(d->mode == 0 || d->hist, "dpm: mode 1 needs hist");
+    DM3D_REQUIRE(!d->t_idx || d->t_next, "dpm: t_idx needs t_next");
+    DM3D_REQUIRE(dm3d_aligned16(d->x) && dm3d_aligned16(d->eps) && dm3d_aligned16(d->hist) && dm3d_aligned16(d->out) &&
+                 dm3d_aligned16(d->x0_out) && dm3d_aligned16(d->coef), "dpm: pointers must be 16-byte aligned");
+    DpmArgs a{};
+    a.x = d->x; a.eps = d->eps; a.hist = d->hist; a.out = d->out; a.x0_out = d->x0_out; a.per4 = d->per_sample / 4;
+    a.coef = d->coef; a.t_next = d->t_next; a.rows = d->rows; a.pos = d->pos; a.t_idx = d->t_idx; a.mode = d->mode;
+    const long blocks = (a.per4 + 255) / 256;
+    dim3 grid((unsigned)(blocks > 256 ? 256 : blocks), (unsigned)d->batch);                 // ddpm_kernel's grid
+    hipLaunchKernelGGL(dpm_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return dm3d_launch_check("dpm_kernel");
+}

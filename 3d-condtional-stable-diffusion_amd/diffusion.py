@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DdimDesc, DdpmDesc, EditDesc, GuideDesc, check, lib
+from ._lib import DdimDesc, DdpmDesc, DpmDesc, EditDesc, GuideDesc, check, lib
 from .betas import BETAS_FIELDS, Betas
 from .unet import UNet
 from .weights import UNetConfig
@@ -59,6 +59,29 @@ def ddim_coefficients(alpha_bar, src, dst, eta=0.0) -> np.ndarray:
         sigma = float(eta) * np.sqrt((1 - ap) / (1 - a)) * np.sqrt(1 - a / ap)
     a_eps = np.sqrt(np.maximum(1 - ap - sigma ** 2, 0.0))
     return np.stack([np.sqrt(a), np.sqrt(1 - a), np.sqrt(ap), a_eps, sigma], axis=1)
+
+
+def dpm_coefficients(alpha_bar, src, dst, prev, order=2) -> np.ndarray:
+    """float64 [n, 3] rows (c_x, c_0, c_1) of the DPM-Solver++(2M) steps src[r] -> dst[r] (include/dm3d.h, dm3d_dpm_desc):
+    x' = c_x x + c_0 x0 + c_1 x0_prev.  With alpha = sqrt(a), sigma = sqrt(1-a), lambda = log(alpha/sigma) and h = lambda_dst -
+    lambda_src: c_x = sigma_dst / sigma_src and A = alpha_dst (1 - e^-h); a first-order row is (c_x, A, 0), a second-order row with
+    r = (lambda_src - lambda_prev) / h is (c_x, A (1 + 1/(2r)), -A / (2r)), ``prev[r]`` being the level the step before started from.
+    ``prev[r] < 0`` or ``order`` = 1 makes row r first order; ``dst[r] < 0`` (clean, a' = 1) is (0, 1, 0) exactly."""
+    if order not in (1, 2):
+        raise ValueError(f"solver_order must be 1 or 2, got {order!r}")
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    src, dst, prev = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (src, dst, prev))
+    lam = lambda a: 0.5 * (np.log(a) - np.log1p(-a))            # log(sqrt(a) / sqrt(1-a))
+    a_s, a_t, a_p = ab[src], ab[np.maximum(dst, 0)], ab[np.maximum(prev, 0)]
+    h = lam(a_t) - lam(a_s)
+    c_x = np.sqrt((1 - a_t) / (1 - a_s))
+    A = -np.sqrt(a_t) * np.expm1(-h)
+    second = (prev >= 0) & (dst >= 0) & (order == 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = np.where(second, h / (2 * (lam(a_s) - lam(a_p))), 0.0)          # 1 / (2r)
+    out = np.stack([c_x, A * (1 + g), -A * g], axis=1)
+    out[dst < 0] = (0.0, 1.0, 0.0)
+    return out
 
 
 def edit_steps(strength, n: int) -> int:
@@ -426,6 +449,57 @@ class DiffusionModel:
         d._keep = (x, eps, noise, out, coef, tau, pos, t_next, t_idx)
         return d
 
+    def dpm_step(self, x_t, pred_noise, t, t_prev, x0_prev=None, t_before=None, *, clip_x0=True):
+        """One DPM-Solver++(2M) update (include/dm3d.h, dm3d_dpm_desc, mode 0): x_t at timestep ``t`` -> x at ``t_prev`` (-1: the x0
+        estimate), the single-call counterpart of a sampler="dpmpp" chain's step, as ddim_step is of a DDIM chain.  Returns
+        (x_next, x0), x0 being this step's (clipped) estimate: the ``x0_prev`` of the next call.  With ``x0_prev`` and ``t_before``
+        (the estimate and the timestep of the step before; given together or not at all) the step is second order, else first order
+        (= ddim_step at eta = 0 where the x0 estimate is not clipped).  ``t`` / ``t_prev`` / ``t_before``: one index or one per sample, -1 <= t_prev < t < t_before."""
+        if (x0_prev is None) != (t_before is None):
+            raise ValueError("x0_prev and t_before are given together or not at all")
+        x_t = torch.as_tensor(x_t, dtype=torch.float32)
+        eps = torch.as_tensor(pred_noise, dtype=torch.float32)
+        B = x_t.shape[0]
+        if eps.shape != x_t.shape or x_t[0].numel() % 4:
+            raise ValueError("x_t / pred_noise disagree")
+        idx = lambda v: np.broadcast_to(np.asarray(torch.as_tensor(v).reshape(-1).cpu(), dtype=np.int64), (B,))
+        t, tp = idx(t), idx(t_prev)
+        tb = np.full(B, -1, dtype=np.int64) if t_before is None else idx(t_before)
+        if t.min() < 0 or t.max() >= self.timesteps or tp.min() < -1 or np.any(tp >= t):
+            raise ValueError("t must lie in [0, timesteps) and t_prev in [-1, t)")
+        if t_before is not None:
+            if np.any(tb <= t) or tb.max() >= self.timesteps:
+                raise ValueError("t_before must lie in (t, timesteps)")
+            x0_prev = torch.as_tensor(x0_prev, dtype=torch.float32)
+            if x0_prev.shape != x_t.shape:
+                raise ValueError("x0_prev must have x_t's shape")
+        dev = self.device
+        x_t, eps = x_t.to(dev).contiguous(), eps.to(dev).contiguous()
+        hist = None if x0_prev is None else x0_prev.to(dev).contiguous()
+        coef = self._dpm_table(t, tp, tb, 2, clip_x0).to(dev)
+        pos = torch.arange(B, dtype=torch.int32, device=dev)
+        out, x0 = torch.empty_like(x_t), torch.empty_like(x_t)
+        d = self._dpm_desc(x_t, eps, hist, coef, pos, 0, out=out, x0_out=x0)
+        check(lib().dm3d_dpm_update(C.byref(d), torch.cuda.current_stream().cuda_stream), "dpm_update")
+        return out, x0
+
+    def _dpm_table(self, src, dst, prev, order, clip_x0) -> torch.Tensor:
+        """The [n, 8] float32 coefficient rows of dm3d_dpm_desc, from the float32 alpha_bar table the kernels use, in float64."""
+        tab = np.zeros((len(src), 8), dtype=np.float64)
+        tab[:, :2] = ddim_coefficients(self.b.alpha_bar, src, dst)[:, :2]
+        tab[:, 2:5] = dpm_coefficients(self.b.alpha_bar, src, dst, prev, order)
+        tab[:, 5] = 1.0 if clip_x0 else 0.0
+        return torch.from_numpy(tab.astype(np.float32))
+
+    def _dpm_desc(self, x, eps, hist, coef, pos, mode, out=None, x0_out=None, t_next=None, t_idx=None) -> DpmDesc:
+        d = DpmDesc()
+        for name, t in (("x", x), ("eps", eps), ("hist", hist), ("out", out), ("x0_out", x0_out), ("coef", coef), ("pos", pos),
+                        ("t_next", t_next), ("t_idx", t_idx)):
+            setattr(d, name, t.data_ptr() if t is not None else None)
+        d.batch, d.per_sample, d.rows, d.mode = x.shape[0], x[0].numel(), coef.shape[0], mode
+        d._keep = (x, eps, hist, out, x0_out, coef, pos, t_next, t_idx)
+        return d
+
     def q_sample(self, x0, t, noise=None, *, seed=None):
         """Forward noising (include/dm3d.h, dm3d_edit_desc, mode 0): sqrt(a) x0 + sqrt(1-a) z with a = alpha_bar[t], in the
         reference's order (conditional_dm3d.py:484-491); the single-call counterpart of edit()'s known latent, as ddim_step is of a
@@ -571,30 +645,52 @@ class DiffusionModel:
         return secrets.randbits(64)
 
     def sampler(self, shape, context_value=None, *, seed=None, use_graph=True, kind="ddpm", num_steps=None, timesteps=None,
-                eta=0.0, clip_x0=True, guidance_scale=None, negative_context=None, guidance_rescale=0.0) -> "Sampler":
+                eta=0.0, clip_x0=True, guidance_scale=None, negative_context=None, guidance_rescale=0.0, solver_order=2,
+                lower_order_final=True) -> "Sampler":
         """The state of one generate() call: plan, tables, context rows and the captured step graph.  There is one live
         Sampler per (batch, context mode): creating another one for the same plan retires the older (its step() raises).
         ``kind="ddim"``: a DDIM chain over ``ddim_timesteps(T, num_steps, timesteps)`` (S steps) with ``eta`` / ``clip_x0``.
+        ``kind="dpmpp"``: a DPM-Solver++(2M) chain over the same schedule with ``clip_x0`` / ``solver_order`` / ``lower_order_final``.
         ``guidance_scale`` / ``negative_context`` / ``guidance_rescale``: a guided chain, as generate()."""
         shape = self._sampler_shape(shape)
-        if kind not in ("ddpm", "ddim"):
-            raise ValueError(f"sampler kind must be 'ddpm' or 'ddim', got {kind!r}")
+        if kind not in ("ddpm", "ddim", "dpmpp"):
+            raise ValueError(f"sampler kind must be 'ddpm', 'ddim' or 'dpmpp', got {kind!r}")
         if kind == "ddpm" and (num_steps is not None or timesteps is not None or eta != 0.0 or clip_x0 is not True):
-            raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim'")
-        if kind == "ddim":
+            raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim' and 'dpmpp'")
+        self._dpm_rules(kind, eta, solver_order, lower_order_final)
+        if kind != "ddpm":
             taus = ddim_timesteps(self.timesteps, num_steps, timesteps)        # validated before the plan is touched
             if not eta >= 0:
                 raise ValueError("eta must be >= 0")
+        dpm = dict(clip_x0=clip_x0, solver_order=solver_order, lower_order_final=lower_order_final)
         guide = self._guidance(shape[0], guidance_scale, negative_context, guidance_rescale)
         ctx = self._context_ids(context_value, shape[0]) if self.conditional else None
         if guide is not None:
             ctx = _guided_ids(ctx, guide[2])
             if kind == "ddpm":
                 return GuidedSampler(self, shape, ctx, seed, use_graph, guide=guide[:2])
+            if kind == "dpmpp":
+                return GuidedDpmSampler(self, shape, ctx, seed, use_graph, taus, guide=guide[:2], **dpm)
             return GuidedDdimSampler(self, shape, ctx, seed, use_graph, taus, eta=eta, clip_x0=clip_x0, guide=guide[:2])
         if kind == "ddpm":
             return Sampler(self, shape, ctx, seed, use_graph)
+        if kind == "dpmpp":
+            return DpmSampler(self, shape, ctx, seed, use_graph, taus, **dpm)
         return DdimSampler(self, shape, ctx, seed, use_graph, taus, eta=eta, clip_x0=clip_x0)
+
+    @staticmethod
+    def _dpm_rules(kind, eta, solver_order, lower_order_final, noise=None):
+        """The argument rules of sampler='dpmpp', checked before any plan or device buffer is made."""
+        if kind != "dpmpp":
+            if solver_order != 2 or lower_order_final is not True:
+                raise ValueError("solver_order / lower_order_final belong to sampler='dpmpp'")
+            return
+        if eta != 0:
+            raise ValueError("sampler='dpmpp' is the deterministic solver: eta must be 0 (the SDE variant is not implemented)")
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
+        if noise is not None:
+            raise ValueError("sampler='dpmpp' draws no noise: noise= does not apply (x_T= sets the start)")
 
     def _sampler_shape(self, shape):
         cfg = self.network.cfg
@@ -605,7 +701,7 @@ class DiffusionModel:
 
     def generate(self, shape=(1, 16, 16, 16, 16), last_step=0, context_value=None, *, x_T=None, noise=None, seed=None,
                  use_graph=True, steps=None, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0, clip_x0=True,
-                 guidance_scale=None, negative_context=None, guidance_rescale=0.0):
+                 guidance_scale=None, negative_context=None, guidance_rescale=0.0, solver_order=2, lower_order_final=True):
         """conditional_dm3d.py:550-575.  For shape[0] > 1 the single context row is broadcast to every sample.
         ``seed`` (optional): Philox key of x_T and of every step's noise; None (default) draws a fresh key per call, as the
         reference draws fresh tf.random.normal noise, an integer makes the call reproducible.
@@ -614,6 +710,13 @@ class DiffusionModel:
         ``sampler="ddim"``: the DDIM chain over ``ddim_timesteps(T, num_steps, timesteps)`` = tau_0 < ... < tau_{S-1}, S U-Net
         evaluations, ``eta`` (0: deterministic), ``clip_x0`` (clamp the x0 estimate to [-1, 1], as the reference's DDPM loop
         clips); ``noise`` is then [S, *shape] with row k the z of the step from tau_k; last_step must be 0.
+        ``sampler="dpmpp"``: DPM-Solver++(2M) (Lu et al. 2022) over the same schedule, S U-Net evaluations like DDIM at eta = 0 but
+        second order: it reuses the x0 estimate of the step before (include/dm3d.h, dm3d_dpm_desc).  The first step of a chain and
+        the step to the clean sample are first order; with ``lower_order_final`` (default) the step tau_1 -> tau_0 before it too:
+        these schedules end in timestep 0, which that step reaches over a log-SNR gap several times the previous step's, and
+        extrapolating over it costs more than the second order gains.  ``solver_order=1`` makes every step first order: DDIM at
+        eta = 0 wherever the x0 estimate is not clipped (where it is, DDIM carries the model's eps on, this solver the eps the
+        clipped estimate implies).  eta must be 0, last_step 0, and ``noise`` does not apply (the chain draws none; ``x_T`` / ``seed`` set the start).
         ``guidance_scale`` = w (None, the default: no guidance, today's path): classifier-free guidance, for either sampler.  Every
         step evaluates the U-Net under ``context_value`` and under ``negative_context`` (one id or one per volume, always given: the
         model has no reserved null context) in one pass over a plan of 2 B rows and continues from eps_neg + w (eps_pos - eps_neg);
@@ -622,12 +725,14 @@ class DiffusionModel:
         chain draws the x_T and the per-step z of the unguided call of the same B volumes and seed."""
         if not 0 <= last_step <= self.timesteps:
             raise ValueError("last_step out of range")
-        if sampler == "ddim":
+        self._dpm_rules(sampler, eta, solver_order, lower_order_final, noise)
+        if sampler in ("ddim", "dpmpp"):
             if last_step != 0:
-                raise ValueError("sampler='ddim' runs whole chains: last_step must be 0")
+                raise ValueError(f"sampler={sampler!r} runs whole chains: last_step must be 0")
+            dpm = dict(kind=sampler, solver_order=solver_order, lower_order_final=lower_order_final) if sampler == "dpmpp" else {}
             return self._generate_ddim(shape, context_value, x_T=x_T, noise=noise, seed=seed, use_graph=use_graph, steps=steps,
                                        num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0, guidance_scale=guidance_scale,
-                                       negative_context=negative_context, guidance_rescale=guidance_rescale)
+                                       negative_context=negative_context, guidance_rescale=guidance_rescale, **dpm)
         self._sync_from_trainer()
         smp = self.sampler(shape, context_value, seed=seed, use_graph=use_graph and noise is None, kind=sampler,
                            num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0, guidance_scale=guidance_scale,
@@ -649,11 +754,11 @@ class DiffusionModel:
         return out
 
     def _generate_ddim(self, shape, context_value, *, x_T, noise, seed, use_graph, steps, num_steps, timesteps, eta, clip_x0,
-                       guidance_scale=None, negative_context=None, guidance_rescale=0.0):
+                       guidance_scale=None, negative_context=None, guidance_rescale=0.0, kind="ddim", **dpm):
         self._sync_from_trainer()
-        smp = self.sampler(shape, context_value, seed=seed, use_graph=use_graph and noise is None, kind="ddim",
+        smp = self.sampler(shape, context_value, seed=seed, use_graph=use_graph and noise is None, kind=kind,
                            num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0, guidance_scale=guidance_scale,
-                           negative_context=negative_context, guidance_rescale=guidance_rescale)
+                           negative_context=negative_context, guidance_rescale=guidance_rescale, **dpm)
         S = smp.n_steps
         if noise is not None:
             noise = torch.as_tensor(noise, dtype=torch.float32).to(self.device)
@@ -687,7 +792,7 @@ class DiffusionModel:
 
     def edit(self, x0, context_value=None, *, mask=None, strength=1.0, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0,
              clip_x0=True, seed=None, use_graph=True, noise=None, known_noise=None, steps=None, guidance_scale=None,
-             negative_context=None, guidance_rescale=0.0):
+             negative_context=None, guidance_rescale=0.0, solver_order=2, lower_order_final=True):
         """Inpainting and image-to-image editing (SDEdit) of latents ``x0`` [B, S, S, S, C]; returns latents of x0's shape.
 
         ``mask`` (1 = regenerate, 0 = keep, in [0, 1]; None: regenerate everything) is pooled to the latent by latent_mask() and
@@ -702,14 +807,18 @@ class DiffusionModel:
         ``known_noise`` (optional): [n+1, *x0.shape], row j the z of the known latent at level L_j of L = (clean, sched_0, ...,
         sched_{n-1}): row i is the blend after the step from sched_i (row 0, clean, draws none) and row n the start (unused at n = N).
         ``guidance_scale`` / ``negative_context`` / ``guidance_rescale``: classifier-free guidance of the chain's eps, as generate();
-        the known latent, the blend and every draw are those of the unguided edit."""
+        the known latent, the blend and every draw are those of the unguided edit.
+        ``sampler="dpmpp"`` / ``solver_order`` / ``lower_order_final``: the DPM-Solver++(2M) chain of generate() over the kept
+        schedule; its first step (from x_T or from the q_sample start) is first order, the blend runs after every update as for the
+        other samplers, and the solver's history keeps the model's own x0 estimate, unblended.  ``noise`` does not apply."""
         x0 = torch.as_tensor(x0, dtype=torch.float32)
         shape = self._sampler_shape(x0.shape)
-        if sampler not in ("ddpm", "ddim"):
-            raise ValueError(f"sampler must be 'ddpm' or 'ddim', got {sampler!r}")
+        if sampler not in ("ddpm", "ddim", "dpmpp"):
+            raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpmpp', got {sampler!r}")
+        self._dpm_rules(sampler, eta, solver_order, lower_order_final, noise)
         if sampler == "ddpm":
             if num_steps is not None or timesteps is not None or eta != 0.0 or clip_x0 is not True:
-                raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim'")
+                raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim' and 'dpmpp'")
             sched = np.arange(self.timesteps, dtype=np.int64)
         else:
             sched = ddim_timesteps(self.timesteps, num_steps, timesteps)
@@ -734,14 +843,19 @@ class DiffusionModel:
         if known_noise is not None:
             known_noise = torch.as_tensor(known_noise, dtype=torch.float32).to(dev)
         eager = noise is not None or known_noise is not None
+        dpm = dict(clip_x0=clip_x0, solver_order=solver_order, lower_order_final=lower_order_final)
         if guide is not None:
             ctx, gkw = _guided_ids(ctx, guide[2]), dict(guide=guide[:2])
             if sampler == "ddpm":
                 smp = GuidedEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, **gkw)
+            elif sampler == "dpmpp":
+                smp = GuidedDpmEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, **dpm, **gkw)
             else:
                 smp = GuidedDdimEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, eta=eta, clip_x0=clip_x0, **gkw)
         elif sampler == "ddpm":
             smp = EditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full)
+        elif sampler == "dpmpp":
+            smp = DpmEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, **dpm)
         else:
             smp = DdimEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, eta=eta, clip_x0=clip_x0)
         smp.reset(x0.to(dev), keep, None if known_noise is None else known_noise[n].contiguous())
@@ -943,13 +1057,17 @@ class DdimSampler(Sampler):
         self.n_steps = len(self.taus) - 1 if self.invert else len(self.taus)
         super().__init__(model, shape, ctx_ids, seed, use_graph)
 
-    def _desc(self, noise=None):
+    def _tables(self):
         plan, T, dev = self.plan, self.model.timesteps, self.model.device
         if getattr(plan, "ddim_coef", None) is None:          # sized for the longest chain (S = T): one graph serves every S
             plan.ddim_coef = torch.zeros(T, 8, dtype=torch.float32, device=dev)
             plan.ddim_tau = torch.zeros(T, dtype=torch.int32, device=dev)
             plan.ddim_next = torch.zeros(T, dtype=torch.int32, device=dev)
             plan.ddim_pos = torch.zeros(plan.B, dtype=torch.int32, device=dev)
+
+    def _desc(self, noise=None):
+        plan = self.plan
+        self._tables()
         d = self.model._ddim_desc(self.x, self._head(plan.eps), plan.ddim_coef, plan.ddim_tau, plan.ddim_pos, 1, noise=noise,
                                   t_next=plan.ddim_next, t_idx=plan.t_idx, seed=self.seed)
         d.seed_dev = plan.seed_buf.data_ptr()
@@ -985,6 +1103,72 @@ class DdimSampler(Sampler):
         push("ddim")
         self._guide(st)
         check(lib().dm3d_ddim_update(C.byref(desc), st), "ddim_update")
+        self._mirror(st)
+        check(lib().dm3d_add_i32(self.plan.ddim_pos.data_ptr(), self.plan.B, -1, st), "add_i32")
+        pop()
+
+
+class DpmSampler(DdimSampler):
+    """One DPM-Solver++(2M) chain over a fixed batch: S steps tau_{S-1} -> ... -> tau_0 -> x0, one U-Net pass each, as a DDIM chain.
+
+    It shares the DDIM chain's frame: the plan's schedule tables (ddim_tau / ddim_next / ddim_pos) and row counter, with a
+    coefficient table of its own (plan.dpm_coef, rows (sqrt(a), sqrt(1-a), c_x, c_0, c_1, clip, 0, 0)) and the history buffer
+    plan.dpm_hist, the x0 estimate of the step before.  reset() rewrites the tables, so one captured graph serves every schedule,
+    order and lower_order_final.  The history is never cleared: the first row of every chain has c_1 = 0 and does not read it."""
+
+    KIND = "dpmpp"
+
+    def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, clip_x0=True, solver_order=2, lower_order_final=True):
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
+        self.solver_order, self.lower_order_final = int(solver_order), bool(lower_order_final)
+        super().__init__(model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=clip_x0)
+
+    def _desc(self, noise=None):
+        plan = self.plan
+        self._tables()
+        if getattr(plan, "dpm_coef", None) is None:
+            plan.dpm_coef = torch.zeros(self.model.timesteps, 8, dtype=torch.float32, device=self.model.device)
+            plan.dpm_hist = torch.zeros_like(plan.x)
+        return self.model._dpm_desc(self.x, self._head(plan.eps), self._head(plan.dpm_hist), plan.dpm_coef, plan.ddim_pos, 1,
+                                    t_next=plan.ddim_next, t_idx=plan.t_idx)
+
+    def _prev(self):
+        """The level the step before row r started from (row n-1 runs first), -1 where the row is first order: the chain's first
+        step, with lower_order_final the step into the schedule's lowest level (row 1), and every row at solver_order 1.  (Row 0,
+        the step to clean, is first order by its target.)"""
+        prev = np.concatenate([self.taus[1:], [-1]])
+        if self.solver_order == 1:
+            prev[:] = -1
+        if self.lower_order_final and len(prev) > 1:
+            prev[1] = -1
+        return prev
+
+    def reset(self, x_T=None):
+        self._own()
+        plan, n = self.plan, self.n_steps
+        self._start(x_T)
+        src, dst = self._rows()
+        plan.dpm_coef[:n].copy_(self.model._dpm_table(src, dst, self._prev(), self.solver_order, self.clip_x0))
+        plan.ddim_tau[:n].copy_(torch.from_numpy(src.astype(np.int32)))
+        plan.ddim_next[:n].copy_(torch.from_numpy(np.maximum(dst, 0).astype(np.int32)))
+        plan.ddim_pos.fill_(n - 1)
+        plan.t_idx.fill_(int(src[n - 1]))
+        if plan.range_flag is not None:
+            plan.range_flag.zero_()
+        self._t = n - 1
+
+    def step(self, noise=None):
+        if noise is not None:
+            raise ValueError("a 'dpmpp' chain draws no noise")
+        super().step()
+
+    def _enqueue(self, st, desc):
+        self.plan.run(st)
+        push, pop = _lib.roctx()
+        push("dpmpp")
+        self._guide(st)
+        check(lib().dm3d_dpm_update(C.byref(desc), st), "dpm_update")
         self._mirror(st)
         check(lib().dm3d_add_i32(self.plan.ddim_pos.data_ptr(), self.plan.B, -1, st), "add_i32")
         pop()
@@ -1101,6 +1285,32 @@ class DdimEditSampler(_EditChain, DdimSampler):
         check(lib().dm3d_ddim_update(C.byref(desc), st), "ddim_update")
 
 
+class DpmEditSampler(_EditChain, DpmSampler):
+    """A DPM-Solver++(2M) edit chain over the first n entries of a schedule (DiffusionModel.edit): the blend after each update reads
+    the row counter ddim_pos before the decrement, as DdimEditSampler's; the history holds the model's x0 estimates, unblended."""
+
+    KIND = "dpmpp-edit"
+
+    def __init__(self, model, shape, ctx_ids, seed, use_graph, sched, full, clip_x0=True, solver_order=2, lower_order_final=True):
+        DpmSampler.__init__(self, model, shape, ctx_ids, seed, use_graph, sched, clip_x0=clip_x0, solver_order=solver_order,
+                            lower_order_final=lower_order_final)
+        self._edit_init(sched, full)
+
+    def _edit_pos(self):
+        return self.plan.ddim_pos
+
+    def _chain_reset(self, x_T):
+        DpmSampler.reset(self, x_T)
+
+    def step(self, noise=None, known_noise=None):
+        if noise is not None:
+            raise ValueError("a 'dpmpp' chain draws no noise")
+        _EditChain.step(self, known_noise=known_noise)
+
+    def _update(self, desc, st):
+        check(lib().dm3d_dpm_update(C.byref(desc), st), "dpm_update")
+
+
 def _guided_ids(ctx, neg) -> np.ndarray:
     """The context rows of a guided chain's plan: B rows of the wanted ids, then B rows of the negative ones."""
     B = len(neg)
@@ -1165,3 +1375,11 @@ class GuidedEditSampler(_GuidedChain, EditSampler):
 
 class GuidedDdimEditSampler(_GuidedChain, DdimEditSampler):
     KIND = "ddim-edit-cfg"
+
+
+class GuidedDpmSampler(_GuidedChain, DpmSampler):
+    KIND = "dpmpp-cfg"
+
+
+class GuidedDpmEditSampler(_GuidedChain, DpmEditSampler):
+    KIND = "dpmpp-edit-cfg"

@@ -25,8 +25,8 @@ extern "C" {
                                      104 (dm3d_attention), 105 (x1_fmt / out_fmt / post_*), 106 (ddpm seed_dev; conv/gemm range_flag; the
                                      training entries), 107 (conv wpk_f8: a float8 cross-term form, removed again in 109), 108 (conv wpk_wino: the Winograd-x form), 109 (wpk_f8 and
                                      dm3d_pack_weights_h3f8 are gone; the Winograd-x image pairs its taps differently; dm3d_mlp_fused; conv skip_wpk_frag, gn_stats; dm3d_groupnorm_finalize2), 110 (dm3d_attn_front), 111 (conv split_counters: the Cin split
-                                     meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc, dm3d_edit_update / dm3d_edit_desc and
-                                     dm3d_guide_update / dm3d_guide_desc were added within 111 (no existing struct or entry changed): a host built against an older header must be rebuilt */
+                                     meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc, dm3d_edit_update / dm3d_edit_desc,
+                                     dm3d_guide_update / dm3d_guide_desc and dm3d_dpm_update / dm3d_dpm_desc were added within 111 (no existing struct or entry changed): a host built against an older header must be rebuilt */
 
 #define DM3D_OK            0
 #define DM3D_EINVAL       -1      /* bad argument (shape, alignment, null pointer) */
@@ -444,6 +444,41 @@ typedef struct dm3d_ddim_desc {
 } dm3d_ddim_desc;
 
 int dm3d_ddim_update(const dm3d_ddim_desc* d, void* stream);
+
+/* ---- DPM-Solver++(2M) step over a timestep schedule (Lu et al. 2022, "DPM-Solver++", Algorithm 2) -------------------------------
+ * A second-order multistep solver of the sampling ODE in the data-prediction form: one U-Net evaluation per step, as DDIM, plus the
+ * x0 estimate of the step before.  With alpha = sqrt(a), sigma = sqrt(1-a), lambda = log(alpha/sigma), a step from level s to level t
+ * has h = lambda_t - lambda_s; for a second-order step p is the level the step before started from and r = (lambda_s - lambda_p) / h:
+ *   x0  = (x - sigma_s*eps) / alpha_s                   (ddim_update's float32 order)
+ *   x0  = clip ? clamp(x0, -1, 1) : x0                  (a NaN passes)
+ *   first order:   res = (sigma_t/sigma_s)*x + alpha_t*(1 - exp(-h))*x0                          (DDIM's eta = 0 step where x0 is unclipped)
+ *   second order:  res = (sigma_t/sigma_s)*x + alpha_t*(1 - exp(-h))*((1 + 1/(2r))*x0 - (1/(2r))*hist)
+ *   to "clean" (a' = 1): res = x0, always first order (r would be 0)
+ * The host folds this into one row (c_x, c_0, c_1) per step, in float64 from the float32 alpha_bar table, rounded once to float32:
+ *   res = (c_x*x + c_0*x0) + c_1*hist                   (float32, in that order, each operation rounded)
+ *   res = c_x*x + c_0*x0                                where c_1 == 0: hist is not read (a first step never sees a stale buffer)
+ * and then hist <- x0 (the clipped estimate).  There is no noise term: no Philox stream, no seed.
+ *   mode 0 (DiffusionModel.dpm_step): out = res and, with x0_out set, x0_out = x0; x and hist are left untouched (hist may be NULL:
+ *                                     every row is then computed as a first-order row).
+ *   mode 1 (generate / edit):         x <- res, hist <- x0.
+ * Graph-capturable without host reads, as dm3d_ddim_desc: the row comes from device memory and, with t_idx set, the kernel writes
+ * t_idx[b] = t_next[pos[b]] (the kernel does not read t_idx). */
+typedef struct dm3d_dpm_desc {
+    float* x;                   /* [batch, per_sample] x at the row's level (updated in place in mode 1) */
+    const float* eps;           /* predicted noise */
+    float* hist;                /* the x0 estimate of the step before, same shape (mode 1: required, replaced by this step's) */
+    float* out;                 /* mode 0: the result, same shape */
+    float* x0_out;              /* mode 0, optional: this step's x0 estimate, same shape */
+    int32_t batch; int64_t per_sample;     /* batch <= 65535, per_sample % 4 == 0 */
+    const float* coef;          /* [rows][8] device: sqrt(a), sqrt(1-a), c_x, c_0, c_1, clip (nonzero: clamp x0), 0, 0 */
+    int32_t rows;               /* pos[b] is clamped to [0, rows) before any table is indexed */
+    const int32_t* pos;         /* [batch] device: the row of each sample */
+    const int32_t* t_next;      /* [rows] device, optional: the timestep the step after row r evaluates */
+    int32_t* t_idx;             /* [batch] device, optional: receives t_next[pos[b]] */
+    int32_t mode;
+} dm3d_dpm_desc;
+
+int dm3d_dpm_update(const dm3d_dpm_desc* d, void* stream);
 
 /* ---- Known-latent step of inpainting / image-to-image editing (RePaint's replacement step, SDEdit's start) -------------
  * Row r = clamp(pos[b], 0, rows-1) of the level table gives a target level a' (alpha_bar of a timestep, 1 for "clean"):
