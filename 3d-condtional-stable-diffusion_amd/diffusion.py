@@ -8,6 +8,11 @@ selects the in-kernel Philox stream, ``use_graph=`` toggles HIP-graph replay of 
 
 The sampling loop (:559-573) runs with no host synchronisation: the step index lives in device memory, one step
 (U-Net forward + posterior update + index decrement) is captured once into a HIP graph and replayed T times.
+
+Every chain (DDPM, DDIM, DPM-Solver++; plain, edit, guided) is a ``Sampler``: reset(), step() and the launch sequence of a step
+exist once, in that class; a solver subclass names its update entry point and row counter and writes its tables, ``_EditChain``
+and ``_GuidedChain`` mix the blend and the guidance in, and the table ``_CHAINS`` picks the class.  generate(), edit() and invert()
+check their arguments through one rule function (``_solver_rules``) and drive the chain through one loop (``_run``).
 """
 from __future__ import annotations
 
@@ -125,6 +130,27 @@ def latent_mask(mask, latent_shape) -> torch.Tensor:
     if k > 1:
         m = m.reshape(m.shape[0], D, k, H, k, W, k).amax(dim=(2, 4, 6))
     return m.expand(B, D, H, W).contiguous()
+
+
+def _indices(v, B: int) -> np.ndarray:
+    """One timestep index, or one per sample, as int64 [B] on the host."""
+    return np.broadcast_to(np.asarray(torch.as_tensor(v).reshape(-1).cpu(), dtype=np.int64), (B,))
+
+
+def _fill(d, **tensors):
+    """Points each named field of descriptor ``d`` at its tensor (None: a null pointer); the tensors live as long as ``d`` does."""
+    for name, t in tensors.items():
+        setattr(d, name, None if t is None else t.data_ptr())
+    d._keep = tuple(tensors.values())
+    return d
+
+
+def _plan_buffer(plan, name, make):
+    """The buffer ``name`` of a plan, made by ``make()`` on first use.  A chain's tables and state live with its plan and are
+    rewritten by reset(), so the graph captured for (plan, kind) serves every later chain of that kind."""
+    if getattr(plan, name, None) is None:
+        setattr(plan, name, make())
+    return getattr(plan, name)
 
 
 class _LossTracker:
@@ -373,17 +399,10 @@ class DiffusionModel:
     # -- a13: sample ------------------------------------------------------------------------------------------------
     def _ddpm_desc(self, x, eps, t_idx, mode, noise=None, seed=0, mean_out=None, var_out=None) -> DdpmDesc:
         tab = self.b.device_tables(self.device)
-        d = DdpmDesc()
-        d.x, d.eps, d.noise = x.data_ptr(), eps.data_ptr(), (noise.data_ptr() if noise is not None else None)
-        d.batch, d.per_sample = x.shape[0], x[0].numel()
-        d.t, d.timesteps = t_idx.data_ptr(), self.timesteps
-        for i, f in enumerate(BETAS_FIELDS):
-            if f != "alpha":
-                setattr(d, f, tab[i].data_ptr())
+        d = _fill(DdpmDesc(), x=x, eps=eps, noise=noise, t=t_idx, mean_out=mean_out, var_out=var_out,
+                  **{f: tab[i] for i, f in enumerate(BETAS_FIELDS) if f != "alpha"})
+        d.batch, d.per_sample, d.timesteps = x.shape[0], x[0].numel(), self.timesteps
         d.seed, d.mode = int(seed) & (2 ** 64 - 1), mode
-        d.mean_out = mean_out.data_ptr() if mean_out is not None else None
-        d.var_out = var_out.data_ptr() if var_out is not None else None
-        d._keep = (x, eps, noise, t_idx, tab, mean_out, var_out)
         return d
 
     def sample(self, x_t, pred_noise, curr_time_step, shape):
@@ -412,8 +431,7 @@ class DiffusionModel:
         B = x_t.shape[0]
         if eps.shape != x_t.shape or x_t[0].numel() % 4:
             raise ValueError("x_t / pred_noise disagree")
-        t = np.broadcast_to(np.asarray(torch.as_tensor(t).reshape(-1).cpu(), dtype=np.int64), (B,))
-        tp = np.broadcast_to(np.asarray(torch.as_tensor(t_prev).reshape(-1).cpu(), dtype=np.int64), (B,))
+        t, tp = _indices(t, B), _indices(t_prev, B)
         if t.min() < 0 or t.max() >= self.timesteps or tp.min() < -1 or np.any(tp >= t):
             raise ValueError("t must lie in [0, timesteps) and t_prev in [-1, t)")
         if not eta >= 0:
@@ -438,15 +456,9 @@ class DiffusionModel:
         return torch.from_numpy(tab.astype(np.float32))
 
     def _ddim_desc(self, x, eps, coef, tau, pos, mode, noise=None, out=None, t_next=None, t_idx=None, seed=0) -> DdimDesc:
-        d = DdimDesc()
-        d.x, d.eps, d.noise = x.data_ptr(), eps.data_ptr(), (noise.data_ptr() if noise is not None else None)
-        d.out = out.data_ptr() if out is not None else None
-        d.batch, d.per_sample = x.shape[0], x[0].numel()
-        d.coef, d.tau, d.rows, d.pos = coef.data_ptr(), tau.data_ptr(), coef.shape[0], pos.data_ptr()
-        d.t_next = t_next.data_ptr() if t_next is not None else None
-        d.t_idx = t_idx.data_ptr() if t_idx is not None else None
+        d = _fill(DdimDesc(), x=x, eps=eps, noise=noise, out=out, coef=coef, tau=tau, pos=pos, t_next=t_next, t_idx=t_idx)
+        d.batch, d.per_sample, d.rows = x.shape[0], x[0].numel(), coef.shape[0]
         d.seed, d.mode = int(seed) & (2 ** 64 - 1), mode
-        d._keep = (x, eps, noise, out, coef, tau, pos, t_next, t_idx)
         return d
 
     def dpm_step(self, x_t, pred_noise, t, t_prev, x0_prev=None, t_before=None, *, clip_x0=True):
@@ -462,9 +474,8 @@ class DiffusionModel:
         B = x_t.shape[0]
         if eps.shape != x_t.shape or x_t[0].numel() % 4:
             raise ValueError("x_t / pred_noise disagree")
-        idx = lambda v: np.broadcast_to(np.asarray(torch.as_tensor(v).reshape(-1).cpu(), dtype=np.int64), (B,))
-        t, tp = idx(t), idx(t_prev)
-        tb = np.full(B, -1, dtype=np.int64) if t_before is None else idx(t_before)
+        t, tp = _indices(t, B), _indices(t_prev, B)
+        tb = np.full(B, -1, dtype=np.int64) if t_before is None else _indices(t_before, B)
         if t.min() < 0 or t.max() >= self.timesteps or tp.min() < -1 or np.any(tp >= t):
             raise ValueError("t must lie in [0, timesteps) and t_prev in [-1, t)")
         if t_before is not None:
@@ -492,12 +503,8 @@ class DiffusionModel:
         return torch.from_numpy(tab.astype(np.float32))
 
     def _dpm_desc(self, x, eps, hist, coef, pos, mode, out=None, x0_out=None, t_next=None, t_idx=None) -> DpmDesc:
-        d = DpmDesc()
-        for name, t in (("x", x), ("eps", eps), ("hist", hist), ("out", out), ("x0_out", x0_out), ("coef", coef), ("pos", pos),
-                        ("t_next", t_next), ("t_idx", t_idx)):
-            setattr(d, name, t.data_ptr() if t is not None else None)
+        d = _fill(DpmDesc(), x=x, eps=eps, hist=hist, out=out, x0_out=x0_out, coef=coef, pos=pos, t_next=t_next, t_idx=t_idx)
         d.batch, d.per_sample, d.rows, d.mode = x.shape[0], x[0].numel(), coef.shape[0], mode
-        d._keep = (x, eps, hist, out, x0_out, coef, pos, t_next, t_idx)
         return d
 
     def q_sample(self, x0, t, noise=None, *, seed=None):
@@ -514,7 +521,7 @@ class DiffusionModel:
         B = x0.shape[0]
         if x0.dim() < 2 or x0[0].numel() % 4:
             raise ValueError("x0 must be [B, ...] with a multiple of 4 elements per sample")
-        t = np.broadcast_to(np.asarray(torch.as_tensor(t).reshape(-1).cpu(), dtype=np.int64), (B,))
+        t = _indices(t, B)
         if t.min() < -1 or t.max() >= self.timesteps:
             raise ValueError("t must lie in [-1, timesteps)")
         if noise is not None:
@@ -544,25 +551,15 @@ class DiffusionModel:
         return torch.from_numpy(tab.astype(np.float32))
 
     def _edit_desc(self, x0, levels, pos, mode, x=None, w=None, noise=None, out=None, seed=0) -> EditDesc:
-        d = EditDesc()
-        d.x0, d.levels, d.rows, d.pos = x0.data_ptr(), levels.data_ptr(), levels.shape[0], pos.data_ptr()
-        d.x = x.data_ptr() if x is not None else None
-        d.w = w.data_ptr() if w is not None else None
-        d.noise = noise.data_ptr() if noise is not None else None
-        d.out = out.data_ptr() if out is not None else None
-        d.batch, d.per_sample, d.channels = x0.shape[0], x0[0].numel(), x0.shape[-1]
+        d = _fill(EditDesc(), x0=x0, levels=levels, pos=pos, x=x, w=w, noise=noise, out=out)
+        d.batch, d.per_sample, d.channels, d.rows = x0.shape[0], x0[0].numel(), x0.shape[-1], levels.shape[0]
         d.seed, d.mode = int(seed) & (2 ** 64 - 1), mode
-        d._keep = (x0, levels, pos, x, w, noise, out)
         return d
 
     def _guide_desc(self, mode, batch, per_sample, eps_pos=None, eps_neg=None, out=None, scale=None, rescale=None, partials=None,
                     x=None, t_idx=None) -> GuideDesc:
-        d = GuideDesc()
-        for name, t in (("eps_pos", eps_pos), ("eps_neg", eps_neg), ("out", out), ("scale", scale), ("rescale", rescale),
-                        ("partials", partials), ("x", x), ("t_idx", t_idx)):
-            setattr(d, name, t.data_ptr() if t is not None else None)
+        d = _fill(GuideDesc(), eps_pos=eps_pos, eps_neg=eps_neg, out=out, scale=scale, rescale=rescale, partials=partials, x=x, t_idx=t_idx)
         d.batch, d.per_sample, d.mode = int(batch), int(per_sample), mode
-        d._keep = (eps_pos, eps_neg, out, scale, rescale, partials, x, t_idx)
         return d
 
     @staticmethod
@@ -653,44 +650,43 @@ class DiffusionModel:
         ``kind="dpmpp"``: a DPM-Solver++(2M) chain over the same schedule with ``clip_x0`` / ``solver_order`` / ``lower_order_final``.
         ``guidance_scale`` / ``negative_context`` / ``guidance_rescale``: a guided chain, as generate()."""
         shape = self._sampler_shape(shape)
-        if kind not in ("ddpm", "ddim", "dpmpp"):
-            raise ValueError(f"sampler kind must be 'ddpm', 'ddim' or 'dpmpp', got {kind!r}")
-        if kind == "ddpm" and (num_steps is not None or timesteps is not None or eta != 0.0 or clip_x0 is not True):
-            raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim' and 'dpmpp'")
-        self._dpm_rules(kind, eta, solver_order, lower_order_final)
-        if kind != "ddpm":
-            taus = ddim_timesteps(self.timesteps, num_steps, timesteps)        # validated before the plan is touched
-            if not eta >= 0:
-                raise ValueError("eta must be >= 0")
-        dpm = dict(clip_x0=clip_x0, solver_order=solver_order, lower_order_final=lower_order_final)
-        guide = self._guidance(shape[0], guidance_scale, negative_context, guidance_rescale)
-        ctx = self._context_ids(context_value, shape[0]) if self.conditional else None
-        if guide is not None:
-            ctx = _guided_ids(ctx, guide[2])
-            if kind == "ddpm":
-                return GuidedSampler(self, shape, ctx, seed, use_graph, guide=guide[:2])
-            if kind == "dpmpp":
-                return GuidedDpmSampler(self, shape, ctx, seed, use_graph, taus, guide=guide[:2], **dpm)
-            return GuidedDdimSampler(self, shape, ctx, seed, use_graph, taus, eta=eta, clip_x0=clip_x0, guide=guide[:2])
-        if kind == "ddpm":
-            return Sampler(self, shape, ctx, seed, use_graph)
-        if kind == "dpmpp":
-            return DpmSampler(self, shape, ctx, seed, use_graph, taus, **dpm)
-        return DdimSampler(self, shape, ctx, seed, use_graph, taus, eta=eta, clip_x0=clip_x0)
+        taus, opts = self._solver_rules(kind, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final)
+        ctx, guide = self._contexts(shape[0], context_value, guidance_scale, negative_context, guidance_rescale)
+        return _CHAINS[kind, False, bool(guide)](self, shape, ctx, seed, use_graph, taus, **opts, **guide)
 
-    @staticmethod
-    def _dpm_rules(kind, eta, solver_order, lower_order_final, noise=None):
-        """The argument rules of sampler='dpmpp', checked before any plan or device buffer is made."""
-        if kind != "dpmpp":
-            if solver_order != 2 or lower_order_final is not True:
-                raise ValueError("solver_order / lower_order_final belong to sampler='dpmpp'")
-            return
-        if eta != 0:
-            raise ValueError("sampler='dpmpp' is the deterministic solver: eta must be 0 (the SDE variant is not implemented)")
-        if solver_order not in (1, 2):
-            raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
-        if noise is not None:
-            raise ValueError("sampler='dpmpp' draws no noise: noise= does not apply (x_T= sets the start)")
+    def _solver_rules(self, kind, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise=None, what="sampler kind"):
+        """The argument rules of the three solvers, checked before any plan or device buffer is made.  Returns the chain's schedule
+        (``kind="ddpm"``: every timestep) and the keywords its sampler class takes besides.  ``noise``: the caller's injected z."""
+        if kind not in ("ddpm", "ddim", "dpmpp"):
+            raise ValueError(f"{what} must be 'ddpm', 'ddim' or 'dpmpp', got {kind!r}")
+        if kind != "dpmpp" and (solver_order != 2 or lower_order_final is not True):
+            raise ValueError("solver_order / lower_order_final belong to sampler='dpmpp'")
+        if kind == "ddpm":
+            if num_steps is not None or timesteps is not None or eta != 0.0 or clip_x0 is not True:
+                raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim' and 'dpmpp'")
+            return np.arange(self.timesteps, dtype=np.int64), {}
+        if kind == "dpmpp":
+            if eta != 0:
+                raise ValueError("sampler='dpmpp' is the deterministic solver: eta must be 0 (the SDE variant is not implemented)")
+            if solver_order not in (1, 2):
+                raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
+            if noise is not None:
+                raise ValueError("sampler='dpmpp' draws no noise: noise= does not apply (x_T= sets the start)")
+        taus = ddim_timesteps(self.timesteps, num_steps, timesteps)
+        if not eta >= 0:
+            raise ValueError("eta must be >= 0")
+        if kind == "dpmpp":
+            return taus, dict(clip_x0=clip_x0, solver_order=solver_order, lower_order_final=lower_order_final)
+        return taus, dict(eta=eta, clip_x0=clip_x0)
+
+    def _contexts(self, B, context_value, guidance_scale, negative_context, guidance_rescale):
+        """The context and guidance rules, checked before any plan or device buffer is made: (context rows of the chain's plan, the
+        ``guide=`` keyword of a guided sampler class or nothing)."""
+        guide = self._guidance(B, guidance_scale, negative_context, guidance_rescale)
+        ctx = self._context_ids(context_value, B) if self.conditional else None
+        if guide is None:
+            return ctx, {}
+        return _guided_ids(ctx, guide[2]), dict(guide=guide[:2])
 
     def _sampler_shape(self, shape):
         cfg = self.network.cfg
@@ -725,49 +721,29 @@ class DiffusionModel:
         chain draws the x_T and the per-step z of the unguided call of the same B volumes and seed."""
         if not 0 <= last_step <= self.timesteps:
             raise ValueError("last_step out of range")
-        self._dpm_rules(sampler, eta, solver_order, lower_order_final, noise)
-        if sampler in ("ddim", "dpmpp"):
-            if last_step != 0:
-                raise ValueError(f"sampler={sampler!r} runs whole chains: last_step must be 0")
-            dpm = dict(kind=sampler, solver_order=solver_order, lower_order_final=lower_order_final) if sampler == "dpmpp" else {}
-            return self._generate_ddim(shape, context_value, x_T=x_T, noise=noise, seed=seed, use_graph=use_graph, steps=steps,
-                                       num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0, guidance_scale=guidance_scale,
-                                       negative_context=negative_context, guidance_rescale=guidance_rescale, **dpm)
+        shape = self._sampler_shape(shape)
+        taus, opts = self._solver_rules(sampler, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise)
+        if sampler != "ddpm" and last_step != 0:
+            raise ValueError(f"sampler={sampler!r} runs whole chains: last_step must be 0")
+        ctx, guide = self._contexts(shape[0], context_value, guidance_scale, negative_context, guidance_rescale)
         self._sync_from_trainer()
-        smp = self.sampler(shape, context_value, seed=seed, use_graph=use_graph and noise is None, kind=sampler,
-                           num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0, guidance_scale=guidance_scale,
-                           negative_context=negative_context, guidance_rescale=guidance_rescale)
-        smp.reset(x_T)
-        T = self.timesteps
-        n_steps = T - last_step if steps is None else min(int(steps), T - last_step)
-        if noise is not None:
-            noise = torch.as_tensor(noise, dtype=torch.float32).to(self.device)
-            if tuple(noise.shape) != (T,) + smp.shape:
-                raise ValueError("noise must be [timesteps, *shape]")
-            for k in range(n_steps):
-                smp.step(noise=noise[T - 1 - k])
-        else:
-            for _ in range(n_steps):
-                smp.step()
-        out = smp.x.clone()
-        self.network.check_range(smp.plan)
-        return out
+        smp = _CHAINS[sampler, False, bool(guide)](self, shape, ctx, seed, use_graph and noise is None, taus, **opts, **guide)
+        return self._run(smp, (x_T,), noise, steps=steps, last_step=last_step)
 
-    def _generate_ddim(self, shape, context_value, *, x_T, noise, seed, use_graph, steps, num_steps, timesteps, eta, clip_x0,
-                       guidance_scale=None, negative_context=None, guidance_rescale=0.0, kind="ddim", **dpm):
-        self._sync_from_trainer()
-        smp = self.sampler(shape, context_value, seed=seed, use_graph=use_graph and noise is None, kind=kind,
-                           num_steps=num_steps, timesteps=timesteps, eta=eta, clip_x0=clip_x0, guidance_scale=guidance_scale,
-                           negative_context=negative_context, guidance_rescale=guidance_rescale, **dpm)
-        S = smp.n_steps
+    def _run(self, smp, start, noise=None, known_noise=None, steps=None, last_step=0):
+        """Drives one chain of ``smp`` from reset(*start): all its steps but the last ``last_step``, at most ``steps`` of them.  Row i
+        of ``noise`` [n_steps, *shape] and of ``known_noise`` goes to the step from the schedule's entry i (the first step takes the
+        last row).  Returns a copy of the chain's latents, after the range check of the steps taken."""
+        n = smp.n_steps
         if noise is not None:
             noise = torch.as_tensor(noise, dtype=torch.float32).to(self.device)
-            if tuple(noise.shape) != (S,) + smp.shape:
-                raise ValueError(f"noise must be [S={S}, *shape] for sampler='ddim'")
-        smp.reset(x_T)
-        n_steps = S if steps is None else min(int(steps), S)
-        for k in range(n_steps):
-            smp.step(noise=None if noise is None else noise[S - 1 - k].contiguous())
+            if tuple(noise.shape) != (n,) + smp.shape:
+                raise ValueError("noise must be [timesteps, *shape]" if smp.SOLVER == "ddpm" else f"noise must be [S={n}, *shape] for sampler='ddim'")
+        smp.reset(*start)
+        row = lambda rows, i: None if rows is None else rows[i].contiguous()
+        count = n - last_step if steps is None else min(int(steps), n - last_step)
+        for i in range(n - 1, n - 1 - count, -1):
+            smp.step(row(noise, i), row(known_noise, i))
         out = smp.x.clone()
         self.network.check_range(smp.plan)
         return out
@@ -783,12 +759,7 @@ class DiffusionModel:
         ctx = self._context_ids(context_value, shape[0]) if self.conditional else None
         self._sync_from_trainer()
         smp = DdimSampler(self, shape, ctx, seed, use_graph, taus, clip_x0=False, invert=True)
-        smp.reset(x0)
-        for _ in range(smp.n_steps):
-            smp.step()
-        out = smp.x.clone()
-        self.network.check_range(smp.plan)
-        return out
+        return self._run(smp, (x0,))
 
     def edit(self, x0, context_value=None, *, mask=None, strength=1.0, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0,
              clip_x0=True, seed=None, use_graph=True, noise=None, known_noise=None, steps=None, guidance_scale=None,
@@ -813,22 +784,11 @@ class DiffusionModel:
         other samplers, and the solver's history keeps the model's own x0 estimate, unblended.  ``noise`` does not apply."""
         x0 = torch.as_tensor(x0, dtype=torch.float32)
         shape = self._sampler_shape(x0.shape)
-        if sampler not in ("ddpm", "ddim", "dpmpp"):
-            raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpmpp', got {sampler!r}")
-        self._dpm_rules(sampler, eta, solver_order, lower_order_final, noise)
-        if sampler == "ddpm":
-            if num_steps is not None or timesteps is not None or eta != 0.0 or clip_x0 is not True:
-                raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim' and 'dpmpp'")
-            sched = np.arange(self.timesteps, dtype=np.int64)
-        else:
-            sched = ddim_timesteps(self.timesteps, num_steps, timesteps)
-            if not eta >= 0:
-                raise ValueError("eta must be >= 0")
+        sched, opts = self._solver_rules(sampler, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise, what="sampler")
         n = edit_steps(strength, len(sched))
         full, sched = n == len(sched), sched[:n]
         mask = None if mask is None else latent_mask(mask, shape)
-        guide = self._guidance(shape[0], guidance_scale, negative_context, guidance_rescale)
-        ctx = self._context_ids(context_value, shape[0]) if self.conditional else None
+        ctx, guide = self._contexts(shape[0], context_value, guidance_scale, negative_context, guidance_rescale)
         for name, arr, rows in (("noise", noise, n), ("known_noise", known_noise, n + 1)):
             if arr is not None and tuple(arr.shape) != (rows,) + shape:
                 raise ValueError(f"{name} must be [{rows}, *x0.shape] for this chain")
@@ -838,35 +798,12 @@ class DiffusionModel:
         self._sync_from_trainer()
         dev = self.device
         keep = torch.zeros(shape[:4], dtype=torch.float32, device=dev) if mask is None else 1 - mask.to(dev)
-        if noise is not None:
-            noise = torch.as_tensor(noise, dtype=torch.float32).to(dev)
         if known_noise is not None:
             known_noise = torch.as_tensor(known_noise, dtype=torch.float32).to(dev)
         eager = noise is not None or known_noise is not None
-        dpm = dict(clip_x0=clip_x0, solver_order=solver_order, lower_order_final=lower_order_final)
-        if guide is not None:
-            ctx, gkw = _guided_ids(ctx, guide[2]), dict(guide=guide[:2])
-            if sampler == "ddpm":
-                smp = GuidedEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, **gkw)
-            elif sampler == "dpmpp":
-                smp = GuidedDpmEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, **dpm, **gkw)
-            else:
-                smp = GuidedDdimEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, eta=eta, clip_x0=clip_x0, **gkw)
-        elif sampler == "ddpm":
-            smp = EditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full)
-        elif sampler == "dpmpp":
-            smp = DpmEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, **dpm)
-        else:
-            smp = DdimEditSampler(self, shape, ctx, seed, use_graph and not eager, sched, full, eta=eta, clip_x0=clip_x0)
-        smp.reset(x0.to(dev), keep, None if known_noise is None else known_noise[n].contiguous())
-        n_steps = n if steps is None else min(int(steps), n)
-        for k in range(n_steps):
-            i = n - 1 - k
-            smp.step(noise=None if noise is None else noise[i].contiguous(),
-                     known_noise=None if known_noise is None else known_noise[i].contiguous())
-        out = smp.x.clone()
-        self.network.check_range(smp.plan)
-        return out
+        smp = _CHAINS[sampler, True, bool(guide)](self, shape, ctx, seed, use_graph and not eager, sched, full, **opts, **guide)
+        start = (x0.to(dev), keep, None if known_noise is None else known_noise[n].contiguous())
+        return self._run(smp, start, noise, known_noise, steps)
 
     MAX_GRAPHS = 8      # captured step graphs kept per model (one per plan); the least recently used one is destroyed
 
@@ -915,7 +852,7 @@ class UnconditionalDiffusionModel(DiffusionModel):
 
     conditional = False
 
-    def _context_ids(self, context_value):
+    def _context_ids(self, context_value, batch=None):
         return None
 
     def generate(self, shape=(1, 16, 16, 16, 16), last_step=0, **kw):
@@ -931,16 +868,30 @@ class UnconditionalDiffusionModel(DiffusionModel):
 
 
 class Sampler:
-    """One DDPM chain over a fixed batch (the loop body of generate, conditional_dm3d.py:559-573).
+    """One DDPM chain over a fixed batch (the loop body of generate, conditional_dm3d.py:559-573), and the frame of every chain.
 
     ``step()`` enqueues U-Net forward + posterior update + index decrement on the current stream and never synchronises;
-    with ``use_graph`` the three are one HIP-graph replay.  A chain has T steps: step() past its end raises until reset().
-    The plan (buffers, step index, Philox key) belongs to the newest Sampler made for it; an older one raises on use."""
+    with ``use_graph`` the three are one HIP-graph replay.  A chain has ``n_steps`` steps (T): step() past its end raises until reset().
+    The plan (buffers, step index, Philox key) belongs to the newest Sampler made for it; an older one raises on use.
 
-    def __init__(self, model: DiffusionModel, shape, ctx_ids, seed, use_graph):
+    reset(), step() and _enqueue() exist once, here.  A solver subclass names its update entry point (UPDATE) and its device row counter
+    (_pos), builds its descriptor (_desc) and writes its tables (_schedule, _coefficients); _EditChain adds the blend after the update and
+    _GuidedChain fills the hooks around it (_guide, _mirror, _head).  _CHAINS lists the combinations."""
+
+    KIND = "ddpm"                             # the step graph's cache key beside the plan: one per class
+    SOLVER = "ddpm"                           # generate()'s ``sampler=``; the roctx label of a step (an edit chain's: KIND)
+    UPDATE = "ddpm_update"                    # the dm3d_* entry point of the solver's update
+    COPIES = 1                                # rows of the plan per volume of the chain (a guided chain: 2)
+    DRAWS = True                              # whether the update takes a z: step(noise=) applies
+    edit = None                               # an edit chain: the blend's descriptor
+
+    def __init__(self, model: DiffusionModel, shape, ctx_ids, seed, use_graph, taus=None):
         self.model, self.shape, self.use_graph = model, shape, use_graph
         self.seed = (model.fresh_seed() if seed is None else int(seed)) & (2 ** 64 - 1)
         net, T = model.network, model.timesteps
+        # the schedule, lowest timestep first; a DDPM chain walks t = n-1 .. 0 (an edit chain keeps the prefix its strength asks for)
+        self.taus = np.arange(T, dtype=np.int64) if taus is None else np.asarray(taus, dtype=np.int64)
+        self.n_steps = len(self.taus)
         # one context row per volume, or one broadcast; "sampler": never the plan UNet.__call__ fills with its own time rows
         self.plan = net.plan(shape[0] * self.COPIES, T, ctx_ids is not None and len(ctx_ids) > 1, purpose="sampler")
         plan = self.plan
@@ -949,16 +900,13 @@ class Sampler:
             plan._time_filled = net.P
         if ctx_ids is not None:
             plan.set_context(ctx_ids)
-        if getattr(plan, "seed_buf", None) is None:
-            plan.seed_buf = torch.zeros(1, dtype=torch.int64, device=model.device)
+        _plan_buffer(plan, "seed_buf", lambda: torch.zeros(1, dtype=torch.int64, device=model.device))
         plan._owner_gen = getattr(plan, "_owner_gen", 0) + 1
         self._gen = plan._owner_gen
+        self._launch = getattr(lib(), "dm3d_" + self.UPDATE)
         self.desc = self._desc()
         self.desc.seed_dev = plan.seed_buf.data_ptr()
         self._t = -1                          # host mirror of the device step index; -1: no chain in progress
-
-    KIND = "ddpm"
-    COPIES = 1                                # rows of the plan per volume of the chain (a guided chain: 2)
 
     def _head(self, t):
         """The rows of a plan buffer this chain updates and returns: all of them (a guided chain: the first half)."""
@@ -978,18 +926,21 @@ class Sampler:
     def _desc(self, noise=None):
         return self.model._ddpm_desc(self.x, self._head(self.plan.eps), self.plan.t_idx, 1, noise=noise, seed=self.seed)
 
+    def _pos(self):
+        """The device counter a step decrements (and an edit chain's blend reads first): here the timestep itself."""
+        return self.plan.t_idx
+
     def _own(self):
         if self._gen != self.plan._owner_gen:
             raise RuntimeError("this Sampler was retired: a newer Sampler (generate() call) took over its plan")
 
     def reset(self, x_T=None):
         self._own()
-        T = self.model.timesteps
         self._start(x_T)
-        self.plan.t_idx.fill_(T - 1)
+        self._schedule()
         if self.plan.range_flag is not None:
             self.plan.range_flag.zero_()
-        self._t = T - 1
+        self._t = self.n_steps - 1
 
     def _start(self, x_T):
         """Philox key and x_T (given, or drawn under the key) of a new chain."""
@@ -1002,14 +953,20 @@ class Sampler:
         else:
             check(lib().dm3d_randn(self.x.data_ptr(), self.x.numel(), self.seed, 0x7fffffff, st), "randn")
 
-    def _enqueue(self, st, desc):
+    def _schedule(self):
+        """The device tables and counters of a new chain: here the first timestep."""
+        self.plan.t_idx.fill_(self.n_steps - 1)
+
+    def _enqueue(self, st, desc, edit=None):
         self.plan.run(st)
         push, pop = _lib.roctx()
-        push("ddpm")
+        push(self.SOLVER if self.edit is None else self.KIND)
         self._guide(st)
-        check(lib().dm3d_ddpm_update(C.byref(desc), st), "ddpm_update")
+        check(self._launch(C.byref(desc), st), self.UPDATE)
+        if self.edit is not None:
+            check(lib().dm3d_edit_update(C.byref(self.edit if edit is None else edit), st), "edit_update")
         self._mirror(st)
-        check(lib().dm3d_add_i32(self.plan.t_idx.data_ptr(), self.plan.B, -1, st), "add_i32")
+        check(lib().dm3d_add_i32(self._pos().data_ptr(), self.plan.B, -1, st), "add_i32")
         pop()
 
     def prepare(self):
@@ -1018,13 +975,19 @@ class Sampler:
             self.model._capture(self)
         return self
 
-    def step(self, noise=None):
+    def step(self, noise=None, known_noise=None):
+        """One step; ``noise`` injects the update's z and ``known_noise`` (edit chains) the z of the blend's known latent: such a step
+        is enqueued eagerly with descriptors of its own."""
+        if noise is not None and not self.DRAWS:
+            raise ValueError(f"a {self.SOLVER!r} chain draws no noise")
+        if known_noise is not None and self.edit is None:
+            raise TypeError("known_noise belongs to an edit chain")
         self._own()
         if self._t < 0:
             raise RuntimeError("the chain is finished (or was never started): call reset() before step()")
         st = torch.cuda.current_stream().cuda_stream
-        if noise is not None:
-            self._enqueue(st, self._desc(noise))
+        if noise is not None or known_noise is not None:
+            self._enqueue(st, self.desc if noise is None else self._desc(noise), None if known_noise is None else self._edit_d(known_noise))
         elif self.use_graph:
             # resolved through the model's cache on every step: load_weights / LRU eviction destroy graphs, never under a live handle
             check(lib().dm3d_graph_launch(self.model._capture(self), st), "graph_launch")
@@ -1050,28 +1013,32 @@ class DdimSampler(Sampler):
     Row n-1 is the first step and row 0 the last, so one step is U-Net + dm3d_ddim_update (which also moves t_idx to the next
     step's timestep) + counter decrement in either direction, and one captured graph serves every schedule, eta and clip."""
 
-    KIND = "ddim"
+    KIND = SOLVER = "ddim"
+    UPDATE = "ddim_update"
 
     def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=True, invert=False):
-        self.taus, self.eta, self.clip_x0, self.invert = np.asarray(taus, dtype=np.int64), float(eta), bool(clip_x0), bool(invert)
-        self.n_steps = len(self.taus) - 1 if self.invert else len(self.taus)
-        super().__init__(model, shape, ctx_ids, seed, use_graph)
+        self.eta, self.clip_x0, self.invert = float(eta), bool(clip_x0), bool(invert)
+        super().__init__(model, shape, ctx_ids, seed, use_graph, taus)
+        self.n_steps = len(self.taus) - int(self.invert)
 
-    def _tables(self):
+    def _tables(self, coef):
+        """The plan's schedule tables, sized for the longest chain (S = T) so that one graph serves every S; ``coef``: the solver's own."""
         plan, T, dev = self.plan, self.model.timesteps, self.model.device
-        if getattr(plan, "ddim_coef", None) is None:          # sized for the longest chain (S = T): one graph serves every S
-            plan.ddim_coef = torch.zeros(T, 8, dtype=torch.float32, device=dev)
-            plan.ddim_tau = torch.zeros(T, dtype=torch.int32, device=dev)
-            plan.ddim_next = torch.zeros(T, dtype=torch.int32, device=dev)
-            plan.ddim_pos = torch.zeros(plan.B, dtype=torch.int32, device=dev)
+        _plan_buffer(plan, coef, lambda: torch.zeros(T, 8, dtype=torch.float32, device=dev))
+        for name in ("ddim_tau", "ddim_next"):
+            _plan_buffer(plan, name, lambda: torch.zeros(T, dtype=torch.int32, device=dev))
+        _plan_buffer(plan, "ddim_pos", lambda: torch.zeros(plan.B, dtype=torch.int32, device=dev))
+        return plan
 
     def _desc(self, noise=None):
-        plan = self.plan
-        self._tables()
+        plan = self._tables("ddim_coef")
         d = self.model._ddim_desc(self.x, self._head(plan.eps), plan.ddim_coef, plan.ddim_tau, plan.ddim_pos, 1, noise=noise,
                                   t_next=plan.ddim_next, t_idx=plan.t_idx, seed=self.seed)
         d.seed_dev = plan.seed_buf.data_ptr()
         return d
+
+    def _pos(self):
+        return self.plan.ddim_pos
 
     def _rows(self):
         """(src, dst) timesteps of rows 0..n-1 (row n-1 runs first); dst -1: the x0 target of a sampling chain's last step."""
@@ -1080,32 +1047,27 @@ class DdimSampler(Sampler):
             return t[:-1][::-1], t[1:][::-1]
         return t, np.concatenate([[-1], t[:-1]])
 
-    def reset(self, x_T=None):
-        self._own()
+    def _start(self, x_T):
         if self.invert and x_T is None:
             raise ValueError("an inversion chain starts from a given x0")
+        super()._start(x_T)
+
+    def _coefficients(self, src, dst):
+        """(the solver's coefficient buffer of the plan, its float32 rows for the steps src[r] -> dst[r])."""
+        return self.plan.ddim_coef, self.model._ddim_table(src, dst, self.eta, self.clip_x0 and not self.invert)
+
+    def _schedule(self):
+        """Rows 0..n-1 of the chain: the solver's coefficients, each row's timestep, the timestep the step after it evaluates, the
+        row counter at the first step (row n-1) and that step's timestep."""
         plan, n = self.plan, self.n_steps
-        self._start(x_T)
         if n > 0:
             src, dst = self._rows()
-            plan.ddim_coef[:n].copy_(self.model._ddim_table(src, dst, self.eta, self.clip_x0 and not self.invert))
+            coef, table = self._coefficients(src, dst)
+            coef[:n].copy_(table)
             plan.ddim_tau[:n].copy_(torch.from_numpy(src.astype(np.int32)))
             plan.ddim_next[:n].copy_(torch.from_numpy(np.maximum(dst, 0).astype(np.int32)))
             plan.ddim_pos.fill_(n - 1)
             plan.t_idx.fill_(int(src[n - 1]))
-        if plan.range_flag is not None:
-            plan.range_flag.zero_()
-        self._t = n - 1
-
-    def _enqueue(self, st, desc):
-        self.plan.run(st)
-        push, pop = _lib.roctx()
-        push("ddim")
-        self._guide(st)
-        check(lib().dm3d_ddim_update(C.byref(desc), st), "ddim_update")
-        self._mirror(st)
-        check(lib().dm3d_add_i32(self.plan.ddim_pos.data_ptr(), self.plan.B, -1, st), "add_i32")
-        pop()
 
 
 class DpmSampler(DdimSampler):
@@ -1116,7 +1078,9 @@ class DpmSampler(DdimSampler):
     plan.dpm_hist, the x0 estimate of the step before.  reset() rewrites the tables, so one captured graph serves every schedule,
     order and lower_order_final.  The history is never cleared: the first row of every chain has c_1 = 0 and does not read it."""
 
-    KIND = "dpmpp"
+    KIND = SOLVER = "dpmpp"
+    UPDATE = "dpm_update"
+    DRAWS = False
 
     def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, clip_x0=True, solver_order=2, lower_order_final=True):
         if solver_order not in (1, 2):
@@ -1125,11 +1089,8 @@ class DpmSampler(DdimSampler):
         super().__init__(model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=clip_x0)
 
     def _desc(self, noise=None):
-        plan = self.plan
-        self._tables()
-        if getattr(plan, "dpm_coef", None) is None:
-            plan.dpm_coef = torch.zeros(self.model.timesteps, 8, dtype=torch.float32, device=self.model.device)
-            plan.dpm_hist = torch.zeros_like(plan.x)
+        plan = self._tables("dpm_coef")
+        _plan_buffer(plan, "dpm_hist", lambda: torch.zeros_like(plan.x))
         return self.model._dpm_desc(self.x, self._head(plan.eps), self._head(plan.dpm_hist), plan.dpm_coef, plan.ddim_pos, 1,
                                     t_next=plan.ddim_next, t_idx=plan.t_idx)
 
@@ -1144,51 +1105,27 @@ class DpmSampler(DdimSampler):
             prev[1] = -1
         return prev
 
-    def reset(self, x_T=None):
-        self._own()
-        plan, n = self.plan, self.n_steps
-        self._start(x_T)
-        src, dst = self._rows()
-        plan.dpm_coef[:n].copy_(self.model._dpm_table(src, dst, self._prev(), self.solver_order, self.clip_x0))
-        plan.ddim_tau[:n].copy_(torch.from_numpy(src.astype(np.int32)))
-        plan.ddim_next[:n].copy_(torch.from_numpy(np.maximum(dst, 0).astype(np.int32)))
-        plan.ddim_pos.fill_(n - 1)
-        plan.t_idx.fill_(int(src[n - 1]))
-        if plan.range_flag is not None:
-            plan.range_flag.zero_()
-        self._t = n - 1
-
-    def step(self, noise=None):
-        if noise is not None:
-            raise ValueError("a 'dpmpp' chain draws no noise")
-        super().step()
-
-    def _enqueue(self, st, desc):
-        self.plan.run(st)
-        push, pop = _lib.roctx()
-        push("dpmpp")
-        self._guide(st)
-        check(lib().dm3d_dpm_update(C.byref(desc), st), "dpm_update")
-        self._mirror(st)
-        check(lib().dm3d_add_i32(self.plan.ddim_pos.data_ptr(), self.plan.B, -1, st), "add_i32")
-        pop()
+    def _coefficients(self, src, dst):
+        return self.plan.dpm_coef, self.model._dpm_table(src, dst, self._prev(), self.solver_order, self.clip_x0)
 
 
 class _EditChain:
-    """The known-latent half of an edit chain (DiffusionModel.edit): after every update of the chain's kind, dm3d_edit_update
+    """The known-latent half of an edit chain (DiffusionModel.edit), mixed in before a solver's class: ``sched`` is the kept prefix of
+    its schedule and ``full`` whether that is all of it.  After every update of the chain's kind, dm3d_edit_update
     (mode 1) blends the known latent, noised to the level the step reached, into the kept region, before the row counter's
     decrement.  The known latent, the keep weights and the level table are buffers of the plan, rewritten by reset(), so one captured
     graph per (plan, kind) serves every x0, mask, strength and seed.  Level row j holds L_j of L = (clean, sched_0, ..., sched_{n-1}):
-    the blend after the step from sched_i reads row i through the chain's own row counter, the start (q_sample) row n."""
+    the blend after the step from sched_i reads row i through the chain's own row counter (_pos, still undecremented: t_idx in a
+    DDPM chain, where row t is level t-1; ddim_pos otherwise, where row r is its target dst[r]), the start (q_sample) row n."""
 
-    def _edit_init(self, sched, full):
-        self.sched, self.full = np.asarray(sched, dtype=np.int64), bool(full)
-        plan, dev = self.plan, self.model.device
-        if getattr(plan, "edit_known", None) is None:
-            plan.edit_known = torch.zeros_like(plan.x)
-            plan.edit_keep = torch.zeros(plan.B, plan.x[0].numel() // plan.x.shape[-1], dtype=torch.float32, device=dev)
-            plan.edit_levels = torch.zeros(self.model.timesteps + 1, 4, dtype=torch.float32, device=dev)
-            plan.edit_start = torch.zeros(plan.B, dtype=torch.int32, device=dev)
+    def __init__(self, model, shape, ctx_ids, seed, use_graph, sched, full, **kw):
+        self.full = bool(full)
+        super().__init__(model, shape, ctx_ids, seed, use_graph, sched, **kw)
+        plan, dev = self.plan, model.device
+        _plan_buffer(plan, "edit_known", lambda: torch.zeros_like(plan.x))
+        _plan_buffer(plan, "edit_keep", lambda: torch.zeros(plan.B, plan.x[0].numel() // plan.x.shape[-1], dtype=torch.float32, device=dev))
+        _plan_buffer(plan, "edit_levels", lambda: torch.zeros(model.timesteps + 1, 4, dtype=torch.float32, device=dev))
+        _plan_buffer(plan, "edit_start", lambda: torch.zeros(plan.B, dtype=torch.int32, device=dev))
         self.edit = self._edit_d()
 
     def _edit_d(self, noise=None, start=False):
@@ -1197,118 +1134,39 @@ class _EditChain:
         if start:
             d = self.model._edit_desc(known, plan.edit_levels, plan.edit_start, 0, noise=noise, out=plan.x, seed=self.seed)
         else:
-            d = self.model._edit_desc(known, plan.edit_levels, self._edit_pos(), 1, x=plan.x, w=plan.edit_keep, noise=noise,
-                                      seed=self.seed)
+            d = self.model._edit_desc(known, plan.edit_levels, self._pos(), 1, x=plan.x, w=plan.edit_keep, noise=noise, seed=self.seed)
         d.seed_dev = plan.seed_buf.data_ptr()
         return d
 
     def reset(self, x0, keep, start_noise=None):
         """A new chain from known latent ``x0`` (device, the plan's shape) with keep weights ``keep`` [B, D, H, W]."""
         self._own()
-        plan, n = self.plan, len(self.sched)
+        plan, n = self.plan, self.n_steps
         known, kept = self._head(plan.edit_known), self._head(plan.edit_keep)
         known.copy_(x0.reshape(known.shape))
         kept.copy_(keep.reshape(kept.shape))
-        plan.edit_levels[:n + 1].copy_(self.model._edit_table(np.concatenate([[-1], self.sched])))
+        plan.edit_levels[:n + 1].copy_(self.model._edit_table(np.concatenate([[-1], self.taus])))
         plan.edit_start.fill_(n)
-        self._chain_reset(None if self.full else known)
+        super().reset(None if self.full else known)
         if not self.full:                                        # SDEdit's start: the whole volume noised to sched_{n-1}
             st = torch.cuda.current_stream().cuda_stream
             check(lib().dm3d_edit_update(C.byref(self._edit_d(start_noise, start=True)), st), "edit_update")
 
-    def step(self, noise=None, known_noise=None):
-        self._own()
-        if self._t < 0:
-            raise RuntimeError("the chain is finished (or was never started): call reset() before step()")
-        st = torch.cuda.current_stream().cuda_stream
-        if noise is not None or known_noise is not None:
-            self._enqueue(st, self.desc if noise is None else self._desc(noise), None if known_noise is None else self._edit_d(known_noise))
-        elif self.use_graph:
-            check(lib().dm3d_graph_launch(self.model._capture(self), st), "graph_launch")
-        else:
-            self._enqueue(st, self.desc)
-        self._t -= 1
-        if self._t < 0:
-            self.finish()
-
-    def _enqueue(self, st, desc, edit=None):
-        self.plan.run(st)
-        push, pop = _lib.roctx()
-        push(self.KIND)
-        self._guide(st)
-        self._update(desc, st)
-        check(lib().dm3d_edit_update(C.byref(self.edit if edit is None else edit), st), "edit_update")
-        self._mirror(st)
-        check(lib().dm3d_add_i32(self._edit_pos().data_ptr(), self.plan.B, -1, st), "add_i32")
-        pop()
-
 
 class EditSampler(_EditChain, Sampler):
-    """A DDPM edit chain of n steps from t = n-1 (DiffusionModel.edit): its blend reads the still-undecremented t_idx."""
-
+    """A DDPM edit chain of n steps from t = n-1 (DiffusionModel.edit)."""
     KIND = "ddpm-edit"
-
-    def __init__(self, model, shape, ctx_ids, seed, use_graph, sched, full):
-        Sampler.__init__(self, model, shape, ctx_ids, seed, use_graph)
-        self._edit_init(sched, full)
-
-    def _edit_pos(self):
-        return self.plan.t_idx
-
-    def _chain_reset(self, x_T):
-        Sampler.reset(self, x_T)
-        n = len(self.sched)
-        self.plan.t_idx.fill_(n - 1)
-        self._t = n - 1
-
-    def _update(self, desc, st):
-        check(lib().dm3d_ddpm_update(C.byref(desc), st), "ddpm_update")
 
 
 class DdimEditSampler(_EditChain, DdimSampler):
-    """A DDIM edit chain over the first n entries of a schedule (DiffusionModel.edit): its blend reads the row counter ddim_pos
-    before the decrement (row r steps to dst[r], row 0 to x0)."""
-
+    """A DDIM edit chain over the first n entries of a schedule (DiffusionModel.edit)."""
     KIND = "ddim-edit"
-
-    def __init__(self, model, shape, ctx_ids, seed, use_graph, sched, full, eta=0.0, clip_x0=True):
-        DdimSampler.__init__(self, model, shape, ctx_ids, seed, use_graph, sched, eta=eta, clip_x0=clip_x0)
-        self._edit_init(sched, full)
-
-    def _edit_pos(self):
-        return self.plan.ddim_pos
-
-    def _chain_reset(self, x_T):
-        DdimSampler.reset(self, x_T)
-
-    def _update(self, desc, st):
-        check(lib().dm3d_ddim_update(C.byref(desc), st), "ddim_update")
 
 
 class DpmEditSampler(_EditChain, DpmSampler):
-    """A DPM-Solver++(2M) edit chain over the first n entries of a schedule (DiffusionModel.edit): the blend after each update reads
-    the row counter ddim_pos before the decrement, as DdimEditSampler's; the history holds the model's x0 estimates, unblended."""
-
+    """A DPM-Solver++(2M) edit chain over the first n entries of a schedule (DiffusionModel.edit): the blend follows each update as
+    in DdimEditSampler; the history holds the model's x0 estimates, unblended."""
     KIND = "dpmpp-edit"
-
-    def __init__(self, model, shape, ctx_ids, seed, use_graph, sched, full, clip_x0=True, solver_order=2, lower_order_final=True):
-        DpmSampler.__init__(self, model, shape, ctx_ids, seed, use_graph, sched, clip_x0=clip_x0, solver_order=solver_order,
-                            lower_order_final=lower_order_final)
-        self._edit_init(sched, full)
-
-    def _edit_pos(self):
-        return self.plan.ddim_pos
-
-    def _chain_reset(self, x_T):
-        DpmSampler.reset(self, x_T)
-
-    def step(self, noise=None, known_noise=None):
-        if noise is not None:
-            raise ValueError("a 'dpmpp' chain draws no noise")
-        _EditChain.step(self, known_noise=known_noise)
-
-    def _update(self, desc, st):
-        check(lib().dm3d_dpm_update(C.byref(desc), st), "dpm_update")
 
 
 def _guided_ids(ctx, neg) -> np.ndarray:
@@ -1332,10 +1190,9 @@ class _GuidedChain:
         self.w, self.phi = guide
         super().__init__(*args, **kw)
         plan, dev, B = self.plan, self.model.device, self.shape[0]
-        if getattr(plan, "guide_w", None) is None:
-            plan.guide_w = torch.zeros(B, dtype=torch.float32, device=dev)
-            plan.guide_phi = torch.zeros(B, dtype=torch.float32, device=dev)
-            plan.guide_partials = torch.zeros(B * _lib.GUIDE_PARTIAL_BLOCKS * 4, dtype=torch.float64, device=dev)
+        for name in ("guide_w", "guide_phi"):
+            _plan_buffer(plan, name, lambda: torch.zeros(B, dtype=torch.float32, device=dev))
+        _plan_buffer(plan, "guide_partials", lambda: torch.zeros(B * _lib.GUIDE_PARTIAL_BLOCKS * 4, dtype=torch.float64, device=dev))
         per, mk = plan.x[0].numel(), self.model._guide_desc
         self._rescales = bool(self.use_graph or self.phi.any())
         self._guide_descs = [mk(0, B, per, eps_pos=plan.eps, eps_neg=plan.eps[B:], out=plan.eps, scale=plan.guide_w,
@@ -1383,3 +1240,9 @@ class GuidedDpmSampler(_GuidedChain, DpmSampler):
 
 class GuidedDpmEditSampler(_GuidedChain, DpmEditSampler):
     KIND = "dpmpp-edit-cfg"
+
+
+# (generate()'s ``sampler=``, edit chain?, guided?) -> the chain's class: the one place that picks it
+_CHAINS = {(c.SOLVER, issubclass(c, _EditChain), issubclass(c, _GuidedChain)): c
+           for c in (Sampler, DdimSampler, DpmSampler, EditSampler, DdimEditSampler, DpmEditSampler, GuidedSampler, GuidedDdimSampler,
+                     GuidedDpmSampler, GuidedEditSampler, GuidedDdimEditSampler, GuidedDpmEditSampler)}
