@@ -756,6 +756,7 @@ extern "C" int dm3d_groupnorm_stats(const float* x, int32_t batch, int64_t voxel
 extern "C" int dm3d_groupnorm_finalize(double* acc, int32_t batch, int64_t voxels, int32_t c_total, int32_t groups, float eps,
                                        const float* gamma, const float* beta, float* scale, float* shift, void* stream) {
     DM3D_REQUIRE(acc && gamma && beta && scale && shift && batch > 0 && voxels > 0, "groupnorm_finalize: bad arguments");
+    DM3D_REQUIRE(c_total > 0, "groupnorm_finalize: c_total=%d", c_total);
     DM3D_REQUIRE(groups > 0 && groups <= 64 && c_total % groups == 0, "groupnorm_finalize: groups=%d must divide c=%d (<= 64)", groups, c_total);
     hipLaunchKernelGGL(groupnorm_finalize_kernel, dim3((unsigned)batch), dim3(256), 0, static_cast<hipStream_t>(stream), acc,
                        (long)voxels, c_total, groups, eps, gamma, beta, scale, shift);

@@ -634,6 +634,7 @@ extern "C" int dm3d_affine_act_cat(const float* x1, int32_t c1, const float* x2,
     if (int rc = check_cat("affine_act_cat", x1, c1, x2, c2)) return rc;
     DM3D_REQUIRE(y && rows > 0 && dm3d_aligned16(y) && (scale == nullptr) == (shift == nullptr), "affine_act_cat: bad arguments");
     DM3D_REQUIRE(act >= DM3D_ACT_NONE && act <= DM3D_ACT_SILU, "affine_act_cat: unknown act %d", act);
+    DM3D_REQUIRE(dm3d_aligned16(scale) && dm3d_aligned16(shift), "affine_act_cat: scale / shift must be 16-byte aligned");
     const Cat x{x1, x2, c1, c2};
     hipLaunchKernelGGL(affine_act_cat_kernel, dim3(tgrid(rows * ((c1 + c2) / 4))), dim3(256), 0, TR_ST, x, (long)rows, scale, shift, act, y);
     return dm3d_launch_check("affine_act_cat_kernel");
@@ -645,6 +646,9 @@ extern "C" int dm3d_bn_act_bwd(const float* g, const float* x1, int32_t c1, cons
     if (int rc = check_cat("bn_act_bwd", x1, c1, x2, c2)) return rc;
     DM3D_REQUIRE(g && scale && shift && mean && rstd && red && rows > 0, "bn_act_bwd: null argument");
     DM3D_REQUIRE(act >= DM3D_ACT_NONE && act <= DM3D_ACT_SILU, "bn_act_bwd: unknown act %d", act);
+    DM3D_REQUIRE(dm3d_aligned16(g) && dm3d_aligned16(scale) && dm3d_aligned16(shift) && dm3d_aligned16(mean) && dm3d_aligned16(rstd) &&
+                 dm3d_aligned16(dx1) && dm3d_aligned16(dx2), "bn_act_bwd: pointers must be 16-byte aligned");
+    DM3D_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "bn_act_bwd: dgamma and dbeta go together");      // before anything is launched
     const Cat x{x1, x2, c1, c2};
     const int ct = c1 + c2, c4 = ct / 4, lanes = c4 < 256 ? c4 : 256;
     long slabs = rows / (256 / lanes * 8);
@@ -658,7 +662,6 @@ extern "C" int dm3d_bn_act_bwd(const float* g, const float* x1, int32_t c1, cons
         if (int rc = dm3d_launch_check("bn_act_bwd_apply_kernel")) return rc;
     }
     if (dgamma) {
-        DM3D_REQUIRE(dbeta != nullptr, "bn_act_bwd: dgamma and dbeta go together");
         hipLaunchKernelGGL(bn_param_grad_kernel, dim3((unsigned)((ct + 255) / 256)), dim3(256), 0, TR_ST, red, ct, dgamma, dbeta);
         return dm3d_launch_check("bn_param_grad_kernel");
     }
@@ -672,6 +675,8 @@ extern "C" int dm3d_wgrad(const dm3d_wgrad_desc* d, void* stream) {
     DM3D_REQUIRE(d->batch > 0 && d->in_d > 0 && d->in_h > 0 && d->in_w > 0, "wgrad: non-positive extent");
     DM3D_REQUIRE(dm3d_aligned16(d->a) && dm3d_aligned16(d->g), "wgrad: a / g must be 16-byte aligned");
     DM3D_REQUIRE(d->ksize == 1 || d->per_item_output == 0, "wgrad: per-item outputs exist for ksize 1 only");
+    DM3D_REQUIRE(!d->per_item_output || (d->stride_a % 4 == 0 && d->stride_g % 4 == 0 && d->stride_a >= 0 && d->stride_g >= 0 && d->stride_dw >= 0),
+                 "wgrad: per-item strides of a / g must be non-negative multiples of 4 (16-byte aligned items)");
     WgradArgs p{};
     p.a = d->a; p.g = d->g; p.dw = d->dw; p.cin = d->cin; p.cout = d->cout; p.ksize = d->ksize;
     p.d = d->in_d; p.h = d->in_h; p.w = d->in_w;
@@ -787,6 +792,7 @@ extern "C" int dm3d_sumpool2_add(const float* src, float* dst, int32_t batch, in
 extern "C" int dm3d_dilate2(const float* src, float* dst, int32_t batch, int32_t od, int32_t oh, int32_t ow, int32_t id, int32_t ih, int32_t iw,
                             int32_t offz, int32_t offy, int32_t offx, int32_t c, void* stream) {
     DM3D_REQUIRE(src && dst && batch > 0 && od > 0 && oh > 0 && ow > 0 && c > 0 && c % 4 == 0 && dm3d_aligned16(src) && dm3d_aligned16(dst), "dilate2: bad arguments");
+    DM3D_REQUIRE(id > 0 && ih > 0 && iw > 0, "dilate2: non-positive destination extent");
     DM3D_REQUIRE(offz >= 0 && offz <= 1 && offy >= 0 && offy <= 1 && offx >= 0 && offx <= 1, "dilate2: offsets must be 0 or 1");
     const long n = (long)batch * id * ih * iw * c;
     hipLaunchKernelGGL(fill_kernel, dim3(tgrid(n / 4 + 1)), dim3(256), 0, TR_ST, dst, n / 4, n, 0.0f);

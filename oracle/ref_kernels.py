@@ -1,0 +1,289 @@
+"""ORACLE (kernel by kernel) — plain float64 restatements of the training and normalisation entries of the C ABI, one function per
+entry, written from the comments of ``include/dm3d.h``.
+
+TEST INFRASTRUCTURE ONLY: the product never imports it.  Every backward formula exists twice: the closed form the header states
+(``*_bwd``) and ``torch.autograd`` applied to the float64 forward (``*_bwd_autograd``); ``tests/test_ref_kernels.py`` holds the two
+against each other, ``tests/test_gpu_train_kernels.py`` holds the HIP kernels against the closed forms.
+
+Tensors are torch float64 unless a function says otherwise; the data-movement entries are numpy and keep the dtype they are given
+(they are compared bitwise).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
+
+
+def f64(a) -> torch.Tensor:
+    return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).double()
+
+
+# ---- activations -----------------------------------------------------------------------------------------------------------------
+def act(u, kind):
+    if kind == ACT_RELU:
+        return torch.relu(u)
+    if kind == ACT_SILU:
+        return u * torch.sigmoid(u)
+    return u
+
+
+def act_grad(u, kind):
+    """d act(u) / du; ReLU'(0) = 0."""
+    if kind == ACT_RELU:
+        return (u > 0).to(u.dtype)
+    if kind == ACT_SILU:
+        s = torch.sigmoid(u)
+        return s * (1 + u * (1 - s))
+    return torch.ones_like(u)
+
+
+def act_bwd(ref, dy, kind):
+    return dy * act_grad(ref, kind)
+
+
+def act_bwd_autograd(ref, dy, kind):
+    u = ref.clone().requires_grad_(True)
+    act(u, kind).backward(dy)
+    return u.grad
+
+
+# ---- BatchNormalization(training=True) ---------------------------------------------------------------------------------------------
+def moments_acc(x):
+    """acc[b][c][0..1] = (sum, sum of squares) of x[b, :, c]: what dm3d_groupnorm_stats leaves.  x [batch, voxels, c]."""
+    return torch.stack([x.sum(1), (x * x).sum(1)], -1)
+
+
+def batchnorm_finalize(acc, voxels, eps, gamma, beta, moving_mean=None, moving_var=None, momentum=0.99, unbiased_moving=1):
+    """acc [batch][c][2] -> scale, shift, mean, rstd (and the moving averages when given)."""
+    n = acc.shape[0] * voxels
+    mean = acc[..., 0].sum(0) / n
+    var = (acc[..., 1].sum(0) / n - mean * mean).clamp_min(0)
+    rstd = 1 / torch.sqrt(var + eps)
+    scale = gamma * rstd
+    shift = beta - mean * scale
+    out = [scale, shift, mean, rstd]
+    if moving_mean is not None:
+        vmov = var * (n / (n - 1.0)) if (unbiased_moving and n > 1) else var
+        out += [moving_mean * momentum + mean * (1 - momentum), moving_var * momentum + vmov * (1 - momentum)]
+    return out
+
+
+def affine_act_cat(x1, x2, scale, shift, kind):
+    x = x1 if x2 is None else torch.cat([x1, x2], -1)
+    if scale is not None:
+        x = x * scale + shift
+    return act(x, kind)
+
+
+def bn_act_bwd(g, x, scale, shift, mean, rstd, kind):
+    """Backward of y = act(BatchNorm_train(x)) from the vectors the forward kept.  x, g [rows][c].
+    Returns dx, dgamma, dbeta, red [c][2] = (sum du, sum du*xhat)."""
+    du = g * act_grad(x * scale + shift, kind)
+    xhat = (x - mean) * rstd
+    s, sx = du.sum(0), (du * xhat).sum(0)
+    n = x.shape[0]
+    dx = scale * (du - s / n - xhat * (sx / n))
+    return dx, sx, s, torch.stack([s, sx], -1)
+
+
+def bn_act_fwd(x, gamma, beta, eps, kind):
+    mean = x.mean(0)
+    var = x.var(0, unbiased=False)
+    return act((x - mean) / torch.sqrt(var + eps) * gamma + beta, kind)
+
+
+def bn_act_bwd_autograd(g, x, gamma, beta, eps, kind):
+    xr, gr, br = (t.clone().requires_grad_(True) for t in (x, gamma, beta))
+    bn_act_fwd(xr, gr, br, eps, kind).backward(g)
+    return xr.grad, gr.grad, br.grad
+
+
+# ---- GroupNormalization --------------------------------------------------------------------------------------------------------------
+def groupnorm_scale_shift(x, groups, eps, gamma, beta):
+    """x [batch, voxels, c] -> per-sample scale[b][c] = gamma*rstd, shift[b][c] = beta - mean*scale (biased group variance)."""
+    B, V, Cn = x.shape
+    xg = x.reshape(B, V, groups, Cn // groups)
+    mean = xg.mean((1, 3))
+    var = ((xg * xg).mean((1, 3)) - mean * mean).clamp_min(0)
+    rstd = 1 / torch.sqrt(var + eps)
+    gc = Cn // groups
+    scale = gamma[None, :] * rstd.repeat_interleave(gc, 1)
+    shift = beta[None, :] - mean.repeat_interleave(gc, 1) * scale
+    return scale, shift
+
+
+def groupnorm_partials(x):
+    """part[b][slot][c][2] = (sum, sum of squares) over the 64 voxels of a slot, slots = ceil(voxels / 64)."""
+    B, V, Cn = x.shape
+    slots = -(-V // 64)
+    xp = torch.zeros(B, slots * 64, Cn, dtype=x.dtype)
+    xp[:, :V] = x
+    xp = xp.reshape(B, slots, 64, Cn)
+    return torch.stack([xp.sum(2), (xp * xp).sum(2)], -1)
+
+
+def affine_act_batched(x, scale, shift, kind):
+    """x [batch, rows, c], scale / shift [batch, c]."""
+    return act(x * scale[:, None, :] + shift[:, None, :], kind)
+
+
+# ---- Conv3D / Dense weight gradient, column sums, flipped kernel ---------------------------------------------------------------------
+def wgrad(a, g, ksize):
+    """dw[tap][ci][co] = sum over samples and voxels of a[voxel + tap - 1][ci] * g[voxel][co] with zero padding.
+    a [B, D, H, W, cin], g [B, D, H, W, cout] -> [ksize^3, cin, cout] (tap = (dz*3 + dy)*3 + dx)."""
+    if ksize == 1:
+        return (a.reshape(-1, a.shape[-1]).T @ g.reshape(-1, g.shape[-1]))[None]
+    B, D, H, W, _ = a.shape
+    ap = F.pad(a, (0, 0, 1, 1, 1, 1, 1, 1))
+    taps = []
+    for dz in range(3):
+        for dy in range(3):
+            for dx in range(3):
+                taps.append(torch.einsum("bzyxi,bzyxo->io", ap[:, dz:dz + D, dy:dy + H, dx:dx + W], g))
+    return torch.stack(taps)
+
+
+def _conv_same(x, kernel):
+    """Conv3D(padding="same", stride 1) as cross-correlation, kernel [k, k, k, cin, cout]."""
+    k = kernel.shape[0]
+    y = F.conv3d(x.permute(0, 4, 1, 2, 3), kernel.permute(4, 3, 0, 1, 2), None, padding=k // 2)
+    return y.permute(0, 2, 3, 4, 1)
+
+
+def wgrad_autograd(a, g, ksize):
+    w = torch.zeros(ksize, ksize, ksize, a.shape[-1], g.shape[-1], dtype=a.dtype, requires_grad=True)
+    _conv_same(a, w).backward(g)
+    return w.grad.reshape(ksize ** 3, a.shape[-1], g.shape[-1])
+
+
+def colsum(x, groups):
+    """x [groups*rows][c] -> [groups][c]."""
+    return x.reshape(groups, -1, x.shape[-1]).sum(1)
+
+
+def colsum_autograd(x, groups):
+    """The gradient of a per-group vector added to every row of its group."""
+    v = torch.zeros(groups, x.shape[-1], dtype=x.dtype, requires_grad=True)
+    (x.reshape(groups, -1, x.shape[-1]) + v[:, None, :]).backward(x.reshape(groups, -1, x.shape[-1]))
+    return v.grad
+
+
+def flip_transpose(w):
+    """numpy [taps][cin][cout] -> [taps][cout][cin] with the taps reversed."""
+    return np.ascontiguousarray(w[::-1].transpose(0, 2, 1))
+
+
+def conv_dgrad_autograd(x, kernel, g):
+    xr = x.clone().requires_grad_(True)
+    _conv_same(xr, kernel).backward(g)
+    return xr.grad
+
+
+# ---- LayerNormalization / softmax backward ------------------------------------------------------------------------------------------
+def layernorm_bwd(x, gamma, dy, eps):
+    mean = x.mean(-1, keepdim=True)
+    var = x.var(-1, unbiased=False, keepdim=True)
+    rstd = 1 / torch.sqrt(var + eps)
+    xhat = (x - mean) * rstd
+    dg = dy * gamma
+    dx = rstd * (dg - dg.mean(-1, keepdim=True) - xhat * (dg * xhat).mean(-1, keepdim=True))
+    return dx, (dy * xhat).sum(0), dy.sum(0)
+
+
+def layernorm_bwd_autograd(x, gamma, dy, eps):
+    xr, gr = x.clone().requires_grad_(True), gamma.clone().requires_grad_(True)
+    br = torch.zeros_like(gamma, requires_grad=True)
+    mean = xr.mean(-1, keepdim=True)
+    var = xr.var(-1, unbiased=False, keepdim=True)
+    ((xr - mean) / torch.sqrt(var + eps) * gr + br).backward(dy)
+    return xr.grad, gr.grad, br.grad
+
+
+def softmax_bwd(p, dp, scale):
+    return scale * p * (dp - (p * dp).sum(-1, keepdim=True))
+
+
+def softmax_bwd_autograd(logits, dp, scale):
+    """p = softmax(scale * logits); returns (p, dL/dlogits)."""
+    s = logits.clone().requires_grad_(True)
+    p = torch.softmax(scale * s, -1)
+    p.backward(dp)
+    return p.detach(), s.grad
+
+
+# ---- data movement (numpy, dtype preserved) --------------------------------------------------------------------------------------------
+def upsample2(x):
+    """[B, D, H, W, C] -> [B, 2D, 2H, 2W, C], nearest (numpy or torch)."""
+    if isinstance(x, np.ndarray):
+        return x.repeat(2, 1).repeat(2, 2).repeat(2, 3)
+    return x.repeat_interleave(2, 1).repeat_interleave(2, 2).repeat_interleave(2, 3)
+
+
+def sumpool2_add(dst, y):
+    """dst [B, D, H, W, C] + the 8 children of y [B, 2D, 2H, 2W, C], added one at a time in the order (dz, dy, dx) = 000, 001, ... 111
+    in the dtype given (numpy or torch)."""
+    out = dst
+    for k in range(8):
+        out = out + y[:, (k >> 2)::2, ((k >> 1) & 1)::2, (k & 1)::2]
+    return out
+
+
+def sumpool2_autograd(y):
+    B, D2, H2, W2, Cn = y.shape
+    x = torch.zeros(B, D2 // 2, H2 // 2, W2 // 2, Cn, dtype=y.dtype, requires_grad=True)
+    upsample2(x).backward(y)
+    return x.grad
+
+
+def dilate2(src, in_extent, off):
+    """src [B, od, oh, ow, C] -> zeros [B, id, ih, iw, C] with src[o] at 2*o + off per axis (positions outside are dropped)."""
+    B, od, oh, ow, Cn = src.shape
+    dst = np.zeros((B,) + tuple(in_extent) + (Cn,), src.dtype)
+    nz = min(od, (in_extent[0] - off[0] + 1) // 2)
+    ny = min(oh, (in_extent[1] - off[1] + 1) // 2)
+    nx = min(ow, (in_extent[2] - off[2] + 1) // 2)
+    dst[:, off[0]:off[0] + 2 * nz:2, off[1]:off[1] + 2 * ny:2, off[2]:off[2] + 2 * nx:2] = src[:, :nz, :ny, :nx]
+    return dst
+
+
+def scatter_add_rows(table, idx, src):
+    """float64 table[idx[r]] += src[r]; rows with an index outside the table are ignored."""
+    out = table.clone()
+    for r, t in enumerate(idx.tolist()):
+        if 0 <= t < out.shape[0]:
+            out[t] += src[r]
+    return out
+
+
+def gather_rows(table, idx):
+    return table[np.clip(idx, 0, table.shape[0] - 1)]
+
+
+def q_sample_f32(lat, noise, t, sqab, sq1ab):
+    """float32 numpy, each operation rounded: sqab[t[b]]*lat + sq1ab[t[b]]*noise with t clamped to the table."""
+    tt = np.clip(t, 0, len(sqab) - 1)
+    shape = (-1,) + (1,) * (lat.ndim - 1)
+    a, s = sqab[tt].astype(np.float32).reshape(shape), sq1ab[tt].astype(np.float32).reshape(shape)
+    return (a * lat.astype(np.float32)).astype(np.float32) + (s * noise.astype(np.float32)).astype(np.float32)
+
+
+# ---- loss and optimizer ---------------------------------------------------------------------------------------------------------------
+def mse_loss_grad(pred, noise, inv):
+    d = pred - noise
+    return (d * d).sum() * inv, 2 * d * inv
+
+
+def mse_loss_grad_autograd(pred, noise, inv):
+    p = pred.clone().requires_grad_(True)
+    loss = ((noise - p) ** 2).sum() * inv
+    loss.backward()
+    return loss.detach(), p.grad
+
+
+def adam(w, g, m, v, lr_t, b1, b2, eps):
+    m = b1 * m + (1 - b1) * g
+    v = b2 * v + (1 - b2) * g * g
+    return w - lr_t * m / (torch.sqrt(v) + eps), m, v
