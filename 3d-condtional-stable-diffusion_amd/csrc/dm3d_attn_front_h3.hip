@@ -435,15 +435,8 @@ extern "C" int dm3d_attn_front(const dm3d_attn_front_desc* d, void* stream) {
     a.y = d->y; a.ldy = d->ldy; a.qk = d->qk; a.ldqk = d->ldqk; a.vt = d->vt; a.ldvt = d->ldvt; a.q2 = d->q2; a.ldq2 = d->ldq2; a.n3 = d->n3; a.ldn3 = d->ldn3;
     a.m = d->m; a.range_flag = d->range_flag; a.range_limit = d->range_limit > 0.0f ? d->range_limit : 65504.0f;
     const size_t lds = (size_t)2 * 16 * (32 * mr * 64 + 32) + (size_t)2 * 4 * 32 * mr * sizeof(float);       // two operand images + the statistics exchange
-    static std::atomic<bool> attr_set[64][2] = {};     // (atomic: two host threads may meet in a first launch; the attribute call itself is idempotent)
-    int dev = 0;
-    DM3D_HIP(hipGetDevice(&dev));
-    DM3D_REQUIRE(dev >= 0 && dev < 64, "attn_front: device ordinal %d", dev);
-    if (!attr_set[dev][mr - 1]) {
-        if (mr == 2) DM3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_front_h3<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        else DM3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_front_h3<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev][mr - 1] = true;
-    }
+    static std::atomic<bool> attr_set[2][64] = {};
+    if (int dev = dm3d_dyn_lds(lds, attr_set[mr - 1], "attn_front", mr == 2 ? &attn_front_h3<2> : &attn_front_h3<1>); dev < 0) return dev;
     if (mr == 2) hipLaunchKernelGGL(attn_front_h3<2>, dim3((unsigned)(d->m / 64)), dim3(256), lds, static_cast<hipStream_t>(stream), a);
     else hipLaunchKernelGGL(attn_front_h3<1>, dim3((unsigned)(d->m / 32)), dim3(256), lds, static_cast<hipStream_t>(stream), a);
     return dm3d_launch_check("attn_front_h3");

@@ -335,14 +335,8 @@ int dm3d_attention_fused_launch(const dm3d_attention_desc* descs, int count, hip
     constexpr size_t lds_stage = (size_t)2 * (K_TILE + V_TILE) * sizeof(_Float16), lds_out = (size_t)4 * 32 * O_LD * sizeof(float);
     constexpr size_t lds = lds_stage > lds_out ? lds_stage : lds_out;
     static_assert(lds <= 160 * 1024, "LDS");
-    static std::atomic<bool> attr_set[64] = {};            // per device: the attribute belongs to the device the launch goes to
-    int dev_ = 0;
-    DM3D_HIP(hipGetDevice(&dev_));
-    DM3D_REQUIRE(dev_ >= 0 && dev_ < 64, "attention: device ordinal %d", dev_);
-    if (!attr_set[dev_]) {
-        DM3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fused_h3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev_] = true;
-    }
+    static std::atomic<bool> attr_set[64] = {};
+    if (int dev = dm3d_dyn_lds(lds, attr_set, "attention", &attn_fused_h3); dev < 0) return dev;
     dim3 grid((unsigned)(a.lq / QT), (unsigned)descs[0].batch, (unsigned)count);
     hipLaunchKernelGGL(attn_fused_h3, grid, dim3(256), lds, st, a);
     return dm3d_launch_check("attn_fused_h3");

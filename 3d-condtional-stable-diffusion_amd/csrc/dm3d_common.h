@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <atomic>
+#include <initializer_list>
 #include "dm3d.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -29,6 +30,22 @@ static inline int dm3d_launch_check(const char* what) {
 }
 static inline bool dm3d_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int64_t dm3d_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+
+// Raises the dynamic-LDS limit of `kernels` to `lds` bytes on the device the launch goes to (the attribute belongs to the device), once per
+// device: `set` is the caller's static array of 64 flags, one array per kernel instantiation (atomic: two host threads may meet in a first
+// launch; the attribute call itself is idempotent).  Returns the device ordinal, or a negative DM3D_E* code; `who` names the caller in the text.
+template <class... K>
+static inline int dm3d_dyn_lds(size_t lds, std::atomic<bool>* set, const char* who, K*... kernels) {
+    int dev = 0;
+    DM3D_HIP(hipGetDevice(&dev));
+    DM3D_REQUIRE(dev >= 0 && dev < 64, "%s: device ordinal %d", who, dev);
+    if (!set[dev]) {
+        for (const void* f : {reinterpret_cast<const void*>(kernels)...})
+            DM3D_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        set[dev] = true;
+    }
+    return dev;
+}
 
 // H3 range guard (include/dm3d.h, range_flag): running max |value| of what an epilogue stores.  -DDM3D_NO_RANGE_GUARD builds the
 // A/B variant without it (tools/mk_variant.sh).

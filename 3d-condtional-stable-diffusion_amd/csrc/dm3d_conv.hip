@@ -13,6 +13,7 @@
 // Every input element is fetched from HBM/L2 once per workgroup and chunk (halo overhead 2.3x for a 4x8x8 brick) instead
 // of k^3 times, and activation tensors are read in their raw form, so norm/activation/concat/upsample never round-trip
 // through HBM.  LDS: 600*20*4 + 2*64*20*4 = 58 KB -> two workgroups per CU, whose staging and MFMA phases overlap.
+#include <algorithm>
 #include <cstdlib>
 #include "dm3d_conv_args.h"
 #include <math.h>
@@ -215,15 +216,8 @@ int launch_conv(ConvArgs& a, hipStream_t st) {
     a.bd = (a.od + TD - 1) / TD;
     a.bh = (a.oh + TH - 1) / TH;
     a.bw = (a.ow + TW - 1) / TW;
-    static std::atomic<bool> attr_set[64] = {};            // per device: the attribute belongs to the device the launch goes to
-    int dev_ = 0;
-    DM3D_HIP(hipGetDevice(&dev_));
-    DM3D_REQUIRE(dev_ >= 0 && dev_ < 64, "conv: device ordinal %d", dev_);
-    if (!attr_set[dev_]) {
-        DM3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_igemm_f32<TD, TH, TW, S, KS, WM, WN>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev_] = true;
-    }
+    static std::atomic<bool> attr_set[64] = {};
+    if (int dev = dm3d_dyn_lds(lds, attr_set, "conv", &conv3d_igemm_f32<TD, TH, TW, S, KS, WM, WN>); dev < 0) return dev;
     dim3 grid((unsigned)(a.batch * a.bd * a.bh * a.bw), (unsigned)(a.coutpad / 64), a.parity ? 8u : 1u);
     hipLaunchKernelGGL((conv3d_igemm_f32<TD, TH, TW, S, KS, WM, WN>), grid, dim3(256), lds, st, a);
     return dm3d_launch_check("conv3d_igemm_f32");
@@ -231,7 +225,186 @@ int launch_conv(ConvArgs& a, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int dm3d_conv3d_ndhwc(const dm3d_conv_desc* d, void* stream) {
+// ---- the launch decision: dm3d_conv_resolve turns a descriptor into a ConvLaunch; the launch entry and the three queries all read it -----
+
+// The policy's environment knobs with their defaults (README.md lists them).  The first seven are read once per process — the weight layout
+// and the Cin split must not change between packing / sizing the workspace and the launch —, the last four on every call (tests and A/B
+// tools switch them inside one process).
+struct ConvKnobs {
+    bool pair_off; int ksplit_mode; long split_wgs, split_target; int split_minchunks, split_maxparts; bool wino_split_off;
+    int v3_td; long wide_wgs; bool wino_off; int wino_minchunks;
+};
+static ConvKnobs conv_knobs() {
+    auto num = [](const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; };
+    auto zero = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+    static const ConvKnobs once = {
+        zero("DM3D_CONV_PAIR"),                         // =0: every H3 conv on the DM3D_WL_TAP kernel (A/B switch)
+        (int)num("DM3D_CONV_KSPLIT", -1),               // 0: the direct kernel never splits Cin (A/B, debugging)
+        num("DM3D_CONV_SPLIT_WGS", 256),                // largest grid (tiles) that still splits
+        num("DM3D_CONV_SPLIT_TARGET", 512),             // workgroups to aim for
+        (int)num("DM3D_CONV_SPLIT_MINCHUNKS", 2),       // least 16-channel chunks per part
+        (int)num("DM3D_CONV_SPLIT_MAXPARTS", 16),       // most parts
+        zero("DM3D_CONV_WINO_SPLIT"),                   // =0: the Winograd-x form never splits Cin
+        0, 0, false, 0};
+    ConvKnobs k = once;
+    k.v3_td = (int)num("DM3D_CONV_V3_TD", 0);           // 4 = always 4-slice bricks; 8 = 8 wherever the grid allows; else auto
+    k.wide_wgs = num("DM3D_CONV_WIDE_WGS", 512);        // workgroups from which the one-workgroup-per-CU forms (8-slice bricks, Winograd-x) serve
+    k.wino_off = zero("DM3D_CONV_WINO");                // =0: never the Winograd-x form
+    k.wino_minchunks = (int)num("DM3D_CONV_WINO_MINCHUNKS", 2);     // smallest Cin in chunks that takes the Winograd-x form
+    return k;
+}
+
+// tiles of a launch of the 16x16x32 kernels in td-slice bricks: bricks x 64-column tiles x parities
+static long split_tiles(const ConvArgs& a, int td) {
+    return (long)a.batch * ((a.od + td - 1) / td) * ((a.oh + 7) / 8) * ((a.ow + 7) / 8) * (a.coutpad / 64) * (a.parity ? 8 : 1);
+}
+
+// Workgroups per tile along Cin of the direct kernel's 4-slice form, given split_counters (the host's statement that it provides the
+// hand-over workspace).  Small grids (the 8^3 level at B = 32 has 64 bricks x 4 channel tiles = one workgroup per CU, i.e. one wave per
+// SIMD with nothing to hide its barriers and LDS latency behind; at B = 1 that level has 8 workgroups for 256 CUs) split the Cin chunks
+// over several workgroups per tile.  Goal: at least ~2 workgroups per CU (512) while every part keeps >= 2 chunks.
+static int direct_ksplit(const ConvArgs& a, const ConvKnobs& K) {
+    const long wgs = split_tiles(a, 4);
+    if (K.ksplit_mode == 0 || wgs > K.split_wgs || a.nchunks < 4) return 1;
+    int best = 1;                                             // smallest divisor that fills the chip, else the largest allowed
+    for (int d = 2; d <= K.split_maxparts; ++d) {
+        if (a.nchunks % d != 0 || a.nchunks / d < K.split_minchunks) continue;
+        best = d;
+        if (wgs * d >= K.split_target) break;
+    }
+    return best;
+}
+
+// Cin split of the Winograd form, given split_counters: two workgroups per brick and column tile where one would leave at least half of
+// the CUs without work (the 8^3 level at B = 32: 32 bricks x 4 column tiles), each contracting half of the chunks (at least eight) and
+// half of a fused skip conv's pairs; the halves meet inside the launch (the hand-over form, dm3d_conv_h3v2_parts.h: any epilogue, fused
+// statistics and output formats included).
+static int winograd_ksplit(const ConvArgs& a, const ConvKnobs& K) {
+    if (K.wino_split_off || a.nchunks % 2 != 0 || a.nchunks < 16) return 1;
+    const long wgs = (long)a.batch * (a.od / 8) * (a.oh / 8) * (a.ow / 8) * (a.coutpad / 64);
+    return wgs <= 128 ? 2 : 1;
+}
+
+// The Winograd form serves a k3 / stride-1 launch when the caller supplied the transformed image (wpk_wino), the volume is whole 8 x 8 x 8
+// bricks, a fused skip conv comes with its fragment image, the grid gives every CU two workgroups in turn or exactly one (the same
+// threshold as the 8-slice bricks of the direct kernel: DM3D_CONV_WIDE_WGS) and Cin is at least 32 (two 16-channel chunks,
+// DM3D_CONV_WINO_MINCHUNKS: its unoverlapped prologue and epilogue cost as much as two chunks; at 32 input channels it is still 9 %
+// ahead of the direct kernel, at 64 10-13 %, profiles/r03_wino_ab.log).  The input tensors must be below 4 GB (32-bit lane offsets).
+// ksplit: the Cin split this launch would run with.
+static bool winograd_serves(const ConvArgs& a, int which, int ksplit, const ConvKnobs& K) {
+    if (!a.wpk_wino || which != DM3D_CONV_K3S1 || a.parity || a.cout <= 32) return false;
+    // (a fused skip conv needs its weights as operand fragments: dm3d_conv_desc.skip_wpk_frag; raw skip inputs below 4 GB: 32-bit lane offsets)
+    if (a.s_npairs > 0) {
+        if (!a.swpk_f) return false;
+        const long long svox = (long long)a.batch * a.ind * a.inh * a.inw;
+        if (svox * (a.sc1 > a.sc2 ? a.sc1 : a.sc2) * 4 >= (1ll << 32)) return false;
+    }
+    if (a.od % 8 != 0 || a.oh % 8 != 0 || a.ow % 8 != 0 || a.padz != 1 || a.pady != 1 || a.padx != 1) return false;
+    if (K.wino_off || a.nchunks < K.wino_minchunks) return false;
+    const long long vox = (long long)a.batch * a.ind * a.inh * a.inw;
+    if (vox * (a.c1 > a.c2 ? a.c1 : a.c2) * 4 >= (1ll << 32)) return false;
+    const long wgs = (long)a.batch * (a.od / 8) * (a.oh / 8) * (a.ow / 8) * (a.coutpad / 64) * ksplit;
+    const long need = K.wide_wgs;
+    // (one workgroup per CU: exactly 256 workgroups are one full round — B = 4 at 32^3, config 2: 3.21 -> 3.09 ms per step —; between 256
+    // and 512 the second round would be part empty, which two small workgroups per CU of the direct kernel handle better)
+    return wgs >= need || wgs == 256 || (ksplit > 1 && wgs >= (need < 256 ? need : 256L));
+}
+
+// Brick depth of a launch of the direct kernel's wide (64-column) form.  8 slices (512 threads, one workgroup per CU: half the weight bytes
+// per FLOP, halo factor 1.95 instead of 2.34) where the grid still gives every CU at least two such workgroups in turn; 4 slices (256
+// threads, two independent workgroups per CU, Cin splitting for tiny grids) for small grids, the parity convs (4 pairs per chunk: nothing
+// for a wider barrier to amortise) and the launches with a fused skip phase.
+static int direct_td(const ConvArgs& a, const ConvKnobs& K) {
+    if (K.v3_td == 4) return 4;
+    if (K.v3_td != 8 && (a.parity || a.s_npairs > 0)) return 4;
+    if ((a.out_h2 || a.post_scale) && a.od % 8 != 0) return 4;      // the fused output forms live in the full-brick epilogue: whole bricks
+    return split_tiles(a, 8) >= K.wide_wgs ? 8 : 4;
+}
+
+ConvLaunch dm3d_conv_resolve(const dm3d_conv_desc* d) {
+    ConvLaunch r{};
+    if (!d) return r;
+    const ConvKnobs K = conv_knobs();
+    ConvArgs a{};
+    a.x1 = d->x1; a.x2 = d->x2; a.c1 = d->c1; a.c2 = d->c2;
+    a.ind = d->in_d; a.inh = d->in_h; a.inw = d->in_w;
+    // Logical output domain the bricks tile.  upsample: the k3 conv on the nearest-2x upsampled tensor is evaluated as 8
+    // 2x2x2 convs (one per output parity) on the low-resolution input, so the domain is the input extent and results are
+    // scattered with stride 2 into the full output.
+    const bool par_mode = d->upsample || d->transpose;      // both run as 8 parity 2x2x2 convs on the input grid
+    const int cstride = (par_mode || d->stride != 2) ? 1 : 2;
+    a.lgd = d->in_d; a.lgh = d->in_h; a.lgw = d->in_w;
+    a.od = (d->in_d + cstride - 1) / cstride;
+    a.oh = (d->in_h + cstride - 1) / cstride;
+    a.ow = (d->in_w + cstride - 1) / cstride;
+    a.parity = par_mode ? 1 : 0;
+    a.os = par_mode ? 2 : 1;
+    a.fd = a.od * a.os; a.fh = a.oh * a.os; a.fw = a.ow * a.os;
+    // TF SAME: total = max((out-1)*stride + k - in, 0), zeros in front = total/2 (k=3: stride 1 -> 1; stride 2 -> 0 on even
+    // sizes, 1 on odd sizes).  In parity mode the kernel derives the pads from the parity bits.
+    auto pad_front = [&](int in, int out) { int t = (out - 1) * cstride + d->ksize - in; return t > 0 ? t / 2 : 0; };
+    a.padz = pad_front(a.lgd, a.od); a.pady = pad_front(a.lgh, a.oh); a.padx = pad_front(a.lgw, a.ow);
+    const int cin = d->c1 + d->c2;
+    a.cinpad = (int)dm3d_round_up(cin, DM3D_CIN_PAD);
+    a.coutpad = (int)dm3d_round_up(d->cout, DM3D_COUT_PAD);
+    a.nchunks = a.cinpad / 16;
+    a.wpk = d->wpk; a.bias = d->bias; a.pscale = d->pro_scale; a.pshift = d->pro_shift; a.pro_bstride = d->pro_batch_stride;
+    a.vec = d->vec; a.vec_idx = d->vec_idx; a.vec_ld = d->vec_ld;
+    a.relu = d->relu; a.res = d->res; a.out = d->out; a.cout = d->cout;
+    a.prelu = d->prelu_alpha; a.relu_out = d->relu_out;
+    a.scratch = d->scratch; a.scratch_bytes = d->scratch_bytes;
+    a.split_counters = d->split_counters; a.split_counter_words = d->split_counter_words;
+    a.range_flag = d->range_flag; a.range_limit = d->range_limit > 0.0f ? d->range_limit : 65504.0f;
+    a.wpk_wino = d->wpk_wino;
+    a.x_h2 = d->x1_fmt == DM3D_FMT_H2; a.out_h2 = d->out_fmt == DM3D_FMT_H2;
+    a.post_scale = d->post_scale; a.post_shift = d->post_shift;
+    if (d->skip_wpk) {
+        a.sx1 = d->skip_x1; a.sx2 = d->skip_x2; a.sc1 = d->skip_c1; a.sc2 = d->skip_c2; a.swpk = d->skip_wpk;
+        a.s_npairs = (int)(dm3d_round_up(d->skip_c1 + d->skip_c2, 32) / 32);
+        a.swpk_f = d->skip_wpk_frag;
+    }
+    a.batch = d->batch;
+    a.out_scale = d->precision == DM3D_PREC_H3 ? ldexpf(1.0f, -d->w_exp) : 1.0f;
+    if (par_mode) a.w_parity_stride = d->precision == DM3D_PREC_H3
+        ? dm3d_packed_weight_h3_bytes(8, cin, d->cout) / 2 : dm3d_packed_weight_elems(8, cin, d->cout);
+    a.gn_stats = d->gn_stats;
+    r.a = a;
+    r.which = par_mode ? DM3D_CONV_UP
+                       : (d->ksize == 1 ? DM3D_CONV_K1 : (d->ksize == 4 ? DM3D_CONV_K4S2 : (d->stride == 2 ? DM3D_CONV_K3S2 : DM3D_CONV_K3S1)));
+
+    if (d->precision != DM3D_PREC_H3) { r.family = DM3D_CONV_FAM_F32; return r; }
+    if (dm3d_conv_weight_layout(d->ksize, d->stride, d->upsample, d->transpose, d->cout) != DM3D_WL_PAIR) { r.family = DM3D_CONV_FAM_TAP; return r; }
+    // the two 16x16x32 kernels: same arguments and epilogue.  The Winograd-x form (its own weight image) where it is eligible, else the
+    // free-running direct form; no Cin split without the host's ticket words.
+    const bool wino_geometry = r.which == DM3D_CONV_K3S1 && a.cout > 32 && a.od % 8 == 0 && a.oh % 8 == 0 && a.ow % 8 == 0;
+    const int ks_direct = direct_ksplit(a, K), ks_wino = wino_geometry ? winograd_ksplit(a, K) : 1;
+    auto bytes = [&](int td, int ks) { return split_tiles(a, td) * ks * (int64_t)(td * 8 * 8 * 64) * (int64_t)sizeof(float); };
+    if (winograd_serves(a, r.which, a.split_counters ? ks_wino : 1, K)) {
+        r.family = DM3D_CONV_FAM_WINO; r.td = 8; r.nct = 4;
+        r.ksplit = a.split_counters ? ks_wino : 1;
+    } else {
+        r.family = DM3D_CONV_FAM_V3;
+        // the narrow column forms (k3 convs with few output channels) take 4-slice bricks: with 8-slice bricks conv_out / conv_in were
+        // 4 % / 11 % slower — these launches are bound by staging the input, 12 or 24 MFMAs per pair against the same halo, not by the
+        // matrix pipe: profiles/r03_layers_h3.log
+        r.nct = (r.which == DM3D_CONV_K3S1 && a.cout <= 32) ? (a.cout <= 16 ? 1 : 2) : 4;
+        r.td = r.nct != 4 ? 4 : direct_td(a, K);
+        r.ksplit = (r.td == 4 && a.split_counters) ? ks_direct : 1;
+    }
+    r.tiles = split_tiles(a, r.td);
+    r.tile_floats = (long)r.td * 8 * 8 * 64;                  // a whole brick x 64 columns, whatever part of it is inside the volume
+    if (r.ksplit > 1) { r.need_words = r.tiles; r.need_bytes = bytes(r.td, r.ksplit); }
+    // What the sizing queries answer is the maximum over the forms this geometry could take — the direct kernel's 4-slice split and the
+    // Winograd split, given ticket words —, not this launch's own need: callers size one workspace before they attach split_counters or
+    // wpk_wino (include/dm3d.h: "how much a descriptor can use").
+    if (d->batch <= 0 || d->cout <= 0 || d->in_d <= 0 || d->in_h <= 0 || d->in_w <= 0) return r;
+    if (ks_direct > 1) { r.can_words = split_tiles(a, 4); r.can_bytes = bytes(4, ks_direct); }
+    if (ks_wino > 1) { r.can_words = std::max(r.can_words, split_tiles(a, 8)); r.can_bytes = std::max(r.can_bytes, bytes(8, ks_wino)); }
+    return r;
+}
+
+// Everything a launch requires of its descriptor (the queries require nothing: they answer for descriptors a launch would refuse).
+static int conv_validate(const dm3d_conv_desc* d) {
     DM3D_REQUIRE(d != nullptr, "conv: null descriptor");
     DM3D_REQUIRE(d->x1 && d->wpk && d->out, "conv: x1/wpk/out must be non-null");
     DM3D_REQUIRE(d->ksize == 1 || d->ksize == 3 || (d->ksize == 4 && d->stride == 2), "conv: ksize %d not in {1,3} (4 needs stride 2)", d->ksize);
@@ -249,44 +422,11 @@ extern "C" int dm3d_conv3d_ndhwc(const dm3d_conv_desc* d, void* stream) {
     for (const void* q : ptrs) DM3D_REQUIRE(dm3d_aligned16(q), "conv: pointer %p is not 16-byte aligned", q);
     const int64_t vox = (int64_t)d->batch * d->in_d * d->in_h * d->in_w;
     DM3D_REQUIRE(vox < (1ll << 31) / 4, "conv: %lld voxels overflow the 32-bit voxel index", (long long)vox);
-
-    ConvArgs a{};
-    a.x1 = d->x1; a.x2 = d->x2; a.c1 = d->c1; a.c2 = d->c2;
-    a.ind = d->in_d; a.inh = d->in_h; a.inw = d->in_w;
-    // Logical output domain the bricks tile.  upsample: the k3 conv on the nearest-2x upsampled tensor is evaluated as 8
-    // 2x2x2 convs (one per output parity) on the low-resolution input, so the domain is the input extent and results are
-    // scattered with stride 2 into the full output.
-    const bool par_mode = d->upsample || d->transpose;      // both run as 8 parity 2x2x2 convs on the input grid
-    const int cstride = par_mode ? 1 : d->stride;
-    a.lgd = d->in_d; a.lgh = d->in_h; a.lgw = d->in_w;
-    a.od = (d->in_d + cstride - 1) / cstride;
-    a.oh = (d->in_h + cstride - 1) / cstride;
-    a.ow = (d->in_w + cstride - 1) / cstride;
-    a.parity = par_mode ? 1 : 0;
-    a.os = par_mode ? 2 : 1;
-    a.fd = a.od * a.os; a.fh = a.oh * a.os; a.fw = a.ow * a.os;
-    // TF SAME: total = max((out-1)*stride + k - in, 0), zeros in front = total/2 (k=3: stride 1 -> 1; stride 2 -> 0 on even
-    // sizes, 1 on odd sizes).  In parity mode the kernel derives the pads from the parity bits.
-    auto pad_front = [&](int in, int out) { int t = (out - 1) * cstride + d->ksize - in; return t > 0 ? t / 2 : 0; };
-    a.padz = pad_front(a.lgd, a.od); a.pady = pad_front(a.lgh, a.oh); a.padx = pad_front(a.lgw, a.ow);
-    const int cin = d->c1 + d->c2;
-    a.cinpad = (int)dm3d_round_up(cin, DM3D_CIN_PAD);
-    a.coutpad = (int)dm3d_round_up(d->cout, DM3D_COUT_PAD);
-    a.nchunks = a.cinpad / 16;
-    a.wpk = d->wpk; a.bias = d->bias; a.pscale = d->pro_scale; a.pshift = d->pro_shift; a.pro_bstride = d->pro_batch_stride;
     DM3D_REQUIRE(d->pro_batch_stride == 0 || (d->pro_batch_stride >= d->c1 + d->c2 && d->pro_batch_stride % 4 == 0),
                  "conv: pro_batch_stride must be 0 or a multiple of 4 >= c1+c2");
-    a.vec = d->vec; a.vec_idx = d->vec_idx; a.vec_ld = d->vec_ld;
-    a.relu = d->relu; a.res = d->res; a.out = d->out; a.cout = d->cout;
-    a.prelu = d->prelu_alpha; a.relu_out = d->relu_out;
-    a.scratch = d->scratch; a.scratch_bytes = d->scratch_bytes;
     DM3D_REQUIRE((d->split_counters == nullptr) == (d->split_counter_words == 0) && d->split_counter_words >= 0, "conv: split_counters and split_counter_words go together");
-    a.split_counters = d->split_counters; a.split_counter_words = d->split_counter_words;
-    a.range_flag = d->range_flag; a.range_limit = d->range_limit > 0.0f ? d->range_limit : 65504.0f;
-    if (d->wpk_wino) {
+    if (d->wpk_wino)
         DM3D_REQUIRE(d->precision == DM3D_PREC_H3 && dm3d_aligned16(d->wpk_wino), "conv: wpk_wino needs precision H3 and 16-byte alignment");
-        a.wpk_wino = d->wpk_wino;
-    }
     DM3D_REQUIRE((d->x1_fmt == DM3D_FMT_F32 || d->x1_fmt == DM3D_FMT_H2) && (d->out_fmt == DM3D_FMT_F32 || d->out_fmt == DM3D_FMT_H2),
                  "conv: unknown x1_fmt / out_fmt");
     DM3D_REQUIRE((d->post_scale == nullptr) == (d->post_shift == nullptr), "conv: post_scale and post_shift go together");
@@ -302,8 +442,6 @@ extern "C" int dm3d_conv3d_ndhwc(const dm3d_conv_desc* d, void* stream) {
         DM3D_REQUIRE(!d->post_scale || (d->in_d % 4 == 0 && d->in_h % 8 == 0 && d->in_w % 8 == 0 && d->cout % 64 == 0),
                      "conv: post_scale needs extents of whole 4x8x8 bricks and cout %% 64 == 0");
         DM3D_REQUIRE(dm3d_aligned16(d->post_scale) && dm3d_aligned16(d->post_shift), "conv: post_* must be 16-byte aligned");
-        a.x_h2 = d->x1_fmt == DM3D_FMT_H2; a.out_h2 = d->out_fmt == DM3D_FMT_H2;
-        a.post_scale = d->post_scale; a.post_shift = d->post_shift;
     }
     if (d->skip_wpk) {
         DM3D_REQUIRE(d->precision == DM3D_PREC_H3 && d->ksize == 3 && d->stride == 1 && !d->upsample && !d->transpose && d->cout > 32,
@@ -311,40 +449,32 @@ extern "C" int dm3d_conv3d_ndhwc(const dm3d_conv_desc* d, void* stream) {
         DM3D_REQUIRE(d->skip_x1 && d->skip_c1 > 0 && d->skip_c1 % 4 == 0 && d->skip_c2 >= 0 && d->skip_c2 % 4 == 0, "conv: skip_c1=%d skip_c2=%d must be multiples of 4", d->skip_c1, d->skip_c2);
         DM3D_REQUIRE((d->skip_c2 == 0) == (d->skip_x2 == nullptr) && (d->skip_c2 == 0 || d->skip_c1 % 16 == 0), "conv: skip_x2 / skip_c2 go together and need skip_c1 %% 16 == 0");
         DM3D_REQUIRE(dm3d_aligned16(d->skip_x1) && dm3d_aligned16(d->skip_x2) && dm3d_aligned16(d->skip_wpk), "conv: skip pointers must be 16-byte aligned");
-        a.sx1 = d->skip_x1; a.sx2 = d->skip_x2; a.sc1 = d->skip_c1; a.sc2 = d->skip_c2; a.swpk = d->skip_wpk;
-        a.s_npairs = (int)(dm3d_round_up(d->skip_c1 + d->skip_c2, 32) / 32);
         DM3D_REQUIRE(dm3d_aligned16(d->skip_wpk_frag), "conv: skip_wpk_frag must be 16-byte aligned");
-        a.swpk_f = d->skip_wpk_frag;
     }
     DM3D_REQUIRE(dm3d_aligned16(d->scratch) && d->scratch_bytes >= 0, "conv: scratch must be 16-byte aligned");
-    a.batch = d->batch;
     DM3D_REQUIRE(d->precision == DM3D_PREC_F32 || d->precision == DM3D_PREC_H3, "conv: unknown precision %d", d->precision);
     DM3D_REQUIRE(d->w_exp >= -100 && d->w_exp <= 100, "conv: w_exp %d out of range", d->w_exp);
-    a.out_scale = d->precision == DM3D_PREC_H3 ? ldexpf(1.0f, -d->w_exp) : 1.0f;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int which = par_mode ? DM3D_CONV_UP
-                               : (d->ksize == 1 ? DM3D_CONV_K1 : (d->ksize == 4 ? DM3D_CONV_K4S2 : (d->stride == 2 ? DM3D_CONV_K3S2 : DM3D_CONV_K3S1)));
-    if (par_mode) a.w_parity_stride = d->precision == DM3D_PREC_H3
-        ? dm3d_packed_weight_h3_bytes(8, cin, d->cout) / 2 : dm3d_packed_weight_elems(8, cin, d->cout);
     // Fused GroupNormalization statistics of the output (gn_stats): the 16x16x32 kernels' full-brick epilogue accumulates them; behind every
     // other kernel or form the stand-alone statistics kernel reads the finished output once (same buffer, same result up to summation order).
-    if (d->gn_stats) {
+    if (d->gn_stats)
         DM3D_REQUIRE(d->out_fmt == DM3D_FMT_F32 && d->cout % 4 == 0 && dm3d_aligned16(d->gn_stats),
                      "conv: gn_stats needs a float32 output, cout %% 4 == 0 and a 16-byte aligned buffer");
-        a.gn_stats = d->gn_stats;
+    if (d->precision == DM3D_PREC_H3) {
+        const int layout = dm3d_conv_weight_layout(d->ksize, d->stride, d->upsample, d->transpose, d->cout);
+        DM3D_REQUIRE(d->w_layout == layout, "conv: w_layout %d but this geometry reads layout %d (dm3d_conv_weight_layout)", d->w_layout, layout);
     }
-    auto stats_behind = [&](int rc) {
-        if (rc != DM3D_OK || !a.gn_stats) return rc;
-        return dm3d_groupnorm_partials(a.out, a.batch, (int64_t)a.fd * a.fh * a.fw, a.cout, a.gn_stats, stream);
-    };
-    if (d->precision != DM3D_PREC_H3) return stats_behind(dm3d_conv_launch_f32(a, which, st));
-    const int layout = dm3d_conv_weight_layout(d->ksize, d->stride, d->upsample, d->transpose, d->cout);
-    DM3D_REQUIRE(d->w_layout == layout, "conv: w_layout %d but this geometry reads layout %d (dm3d_conv_weight_layout)", d->w_layout, layout);
-    if (layout != DM3D_WL_PAIR) return stats_behind(dm3d_conv_launch_h3(a, which, st));
-    // same arguments and epilogue: the Winograd-x form (dm3d_conv_h3w.hip, its own weight image) where it is eligible, else the
-    // free-running direct form (dm3d_conv_h3v3.hip)
-    if (dm3d_conv_h3w_serves(a, which)) return dm3d_conv_launch_h3w(a, which, st);
-    return dm3d_conv_launch_h3v3(a, which, st);
+    return DM3D_OK;
+}
+
+extern "C" int dm3d_conv3d_ndhwc(const dm3d_conv_desc* d, void* stream) {
+    if (int rc = conv_validate(d)) return rc;
+    ConvLaunch r = dm3d_conv_resolve(d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (r.family == DM3D_CONV_FAM_WINO) return dm3d_conv_launch_h3w(r, st);
+    if (r.family == DM3D_CONV_FAM_V3) return dm3d_conv_launch_h3v3(r, st);
+    const int rc = r.family == DM3D_CONV_FAM_TAP ? dm3d_conv_launch_h3(r.a, r.which, st) : dm3d_conv_launch_f32(r.a, r.which, st);
+    if (rc != DM3D_OK || !r.a.gn_stats) return rc;           // (these kernels do not accumulate the statistics: the stand-alone pass)
+    return dm3d_groupnorm_partials(r.a.out, r.a.batch, (int64_t)r.a.fd * r.a.fh * r.a.fw, r.a.cout, r.a.gn_stats, stream);
 }
 
 extern "C" int64_t dm3d_packed_weight_skip_h3p_bytes(int32_t cin, int32_t cout) {
@@ -364,65 +494,17 @@ extern "C" int dm3d_pack_weights_skip_h3f(const float* keras_kernel, int32_t cin
 }
 
 extern "C" int32_t dm3d_conv_tile_form(const dm3d_conv_desc* d) {
-    if (!d || d->precision != DM3D_PREC_H3) return 0;
-    if (dm3d_conv_weight_layout(d->ksize, d->stride, d->upsample, d->transpose, d->cout) != DM3D_WL_PAIR) return 0;
-    ConvArgs a{};
-    const bool par_mode = d->upsample || d->transpose;
-    a.batch = d->batch; a.od = d->in_d; a.oh = d->in_h; a.ow = d->in_w;      // (WL_PAIR convs are stride 1 / parity convs on the input grid)
-    a.coutpad = (int)dm3d_round_up(d->cout, DM3D_COUT_PAD);
-    a.parity = par_mode ? 1 : 0;
-    a.s_npairs = d->skip_wpk ? (int)(dm3d_round_up(d->skip_c1 + d->skip_c2, 32) / 32) : 0;
-    a.swpk_f = d->skip_wpk ? d->skip_wpk_frag : nullptr; a.sc1 = d->skip_c1; a.sc2 = d->skip_c2;
-    a.wpk_wino = d->wpk_wino; a.cout = d->cout; a.c1 = d->c1; a.c2 = d->c2; a.ind = d->in_d; a.inh = d->in_h; a.inw = d->in_w;
-    a.nchunks = (int)(dm3d_round_up(d->c1 + d->c2, DM3D_CIN_PAD) / 16);
-    a.x1 = d->x1; a.x2 = d->x2; a.out = d->out; a.res = d->res; a.relu = d->relu; a.relu_out = d->relu_out; a.prelu = d->prelu_alpha;
-    a.out_h2 = d->out_fmt == DM3D_FMT_H2; a.post_scale = d->post_scale;
-    a.split_counters = d->split_counters; a.split_counter_words = d->split_counter_words;      // (no Cin split without them)
-    a.padz = a.pady = a.padx = (d->ksize == 3 && d->stride == 1 && !par_mode) ? 1 : 0;
-    if (dm3d_conv_h3w_serves(a, (d->ksize == 3 && d->stride == 1 && !par_mode) ? DM3D_CONV_K3S1 : DM3D_CONV_UP)) return 10;
-    return dm3d_conv_h3v3_td(a);
+    const ConvLaunch r = dm3d_conv_resolve(d);
+    return r.family == DM3D_CONV_FAM_WINO ? 10 : (r.family == DM3D_CONV_FAM_V3 ? r.td : 0);
 }
 
-// What a Cin-split launch of this descriptor needs (the hand-over form, dm3d_conv_h3v2_parts.h): tiles x parts x a tile's image.  Both
-// 16x16x32 kernels are asked (which one serves the launch depends on the weight images the caller passes at launch time): the larger need.
-static void split_needs(const dm3d_conv_desc* d, int64_t& bytes, int64_t& words) {
-    bytes = words = 0;
-    if (!d || d->precision != DM3D_PREC_H3 || d->batch <= 0 || d->cout <= 0 || d->in_d <= 0 || d->in_h <= 0 || d->in_w <= 0) return;
-    if (dm3d_conv_weight_layout(d->ksize, d->stride, d->upsample, d->transpose, d->cout) != DM3D_WL_PAIR) return;
-    const bool par = d->upsample || d->transpose;
-    ConvArgs a{};
-    int dummy = 0;
-    a.split_counters = &dummy;                               // "the host will provide them": what the split would be
-    a.batch = d->batch; a.od = d->in_d; a.oh = d->in_h; a.ow = d->in_w; a.parity = par ? 1 : 0;
-    a.coutpad = (int)dm3d_round_up(d->cout, DM3D_COUT_PAD);
-    a.nchunks = (int)(dm3d_round_up(d->c1 + d->c2, DM3D_CIN_PAD) / 16);
-    const int ks = dm3d_conv_h3v2_ksplit(a);
-    if (ks > 1) {
-        words = dm3d_conv_split_tiles(a, 4);
-        bytes = words * ks * (int64_t)(4 * 8 * 8 * 64) * (int64_t)sizeof(float);
-    }
-    if (d->ksize == 3 && d->stride == 1 && !par && d->cout > 32 && d->in_d % 8 == 0 && d->in_h % 8 == 0 && d->in_w % 8 == 0 && dm3d_conv_h3w_ksplit(a) > 1) {
-        const int64_t tw = dm3d_conv_split_tiles(a, 8), bw = tw * 2 * (int64_t)(8 * 8 * 8 * 64) * (int64_t)sizeof(float);
-        if (tw > words) words = tw;
-        if (bw > bytes) bytes = bw;
-    }
-}
+extern "C" int64_t dm3d_conv_scratch_bytes(const dm3d_conv_desc* d) { return dm3d_conv_resolve(d).can_bytes; }
 
-extern "C" int64_t dm3d_conv_scratch_bytes(const dm3d_conv_desc* d) {
-    int64_t bytes, words;
-    split_needs(d, bytes, words);
-    return bytes;
-}
-
-extern "C" int32_t dm3d_conv_split_counter_words(const dm3d_conv_desc* d) {
-    int64_t bytes, words;
-    split_needs(d, bytes, words);
-    return (int32_t)words;
-}
+extern "C" int32_t dm3d_conv_split_counter_words(const dm3d_conv_desc* d) { return (int32_t)dm3d_conv_resolve(d).can_words; }
 
 extern "C" int32_t dm3d_conv_weight_layout(int32_t ksize, int32_t stride, int32_t upsample, int32_t transpose, int32_t cout) {
-    static const bool pair_off = [] { const char* e = getenv("DM3D_CONV_PAIR"); return e && e[0] == '0'; }();   // A/B switch
-    if (pair_off) return DM3D_WL_TAP;
+    (void)cout;
+    if (conv_knobs().pair_off) return DM3D_WL_TAP;
     if (upsample || transpose) return DM3D_WL_PAIR;
     return (ksize == 3 && stride == 1) ? DM3D_WL_PAIR : DM3D_WL_TAP;     // (round 3: also Cout <= 32, the narrow column forms of the 16x16x32 kernel)
 }

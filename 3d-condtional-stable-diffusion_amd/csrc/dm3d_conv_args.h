@@ -1,4 +1,8 @@
-// dm3d_conv_args.h — launch arguments shared by the fp32 and the split-fp16 ("H3") implicit-GEMM Conv3d kernels.
+// dm3d_conv_args.h — what the Conv3d host code and kernels share.  ConvArgs: the launch arguments every conv kernel (fp32 and split-fp16
+// "H3") takes by value.  ConvLaunch: the host's resolved description of one launch — the arguments the descriptor determines plus the
+// decision which kernel, brick depth, column form and Cin split serve it and what workspace that needs.  dm3d_conv_resolve
+// (dm3d_conv.hip) is the one place that fills it; dm3d_conv3d_ndhwc and the three queries (dm3d_conv_tile_form, dm3d_conv_scratch_bytes,
+// dm3d_conv_split_counter_words) consume it, and the launchers dispatch on it without deriving anything again.
 #pragma once
 #include "dm3d_common.h"
 
@@ -45,21 +49,39 @@ struct ConvArgs {
 // which tile configuration a (ksize, stride) pair uses
 enum { DM3D_CONV_K3S1 = 0, DM3D_CONV_K3S2 = 1, DM3D_CONV_K1 = 2, DM3D_CONV_UP = 3, DM3D_CONV_K4S2 = 4 };
 
+// Kernel family that serves a launch
+enum { DM3D_CONV_FAM_F32 = 0,      // conv3d_igemm_f32 (dm3d_conv.hip)
+       DM3D_CONV_FAM_TAP = 1,      // H3, DM3D_WL_TAP weights: conv3d_igemm_h3 (dm3d_conv_h3.hip)
+       DM3D_CONV_FAM_V3 = 2,       // H3, DM3D_WL_PAIR weights: the free-running direct form conv3d_igemm_h3v3 (dm3d_conv_h3v3.hip)
+       DM3D_CONV_FAM_WINO = 3 };   // H3, DM3D_WL_PAIR weights + wpk_wino: the Winograd-x form conv3d_igemm_h3w (dm3d_conv_h3w.hip)
+
+// Host only: one conv launch, resolved from its descriptor by dm3d_conv_resolve.  `a` holds everything the descriptor determines (the
+// launchers add what belongs to their kernel: bricks per volume, epi_vec4, the split fields); the rest is the decision.
+struct ConvLaunch {
+    ConvArgs a;
+    int which;                  // DM3D_CONV_K3S1 ...
+    int family;                 // DM3D_CONV_FAM_*
+    // the two 16x16x32 kernels (FAM_V3, FAM_WINO) only; 0 elsewhere
+    int td;                     // z-slices per brick: 4 or 8 (the Winograd-x form: 8)
+    int nct;                    // 16-column tiles per workgroup: 4, or the narrow forms 2 (cout <= 32) and 1 (cout <= 16) of the k3 direct kernel
+    int ksplit;                 // workgroups per tile along Cin (1: no split)
+    long tiles, tile_floats;    // tiles of the launch (bricks x 64-column tiles x parities); floats of one part's image of one tile in scratch
+    int64_t need_bytes; long need_words;        // scratch bytes and ticket words this launch needs (0 unless ksplit > 1)
+    // what dm3d_conv_scratch_bytes / dm3d_conv_split_counter_words answer: the most a descriptor of this geometry can use
+    int64_t can_bytes; long can_words;
+};
+ConvLaunch dm3d_conv_resolve(const dm3d_conv_desc* d);     // validates nothing (the queries ask about descriptors a launch refuses)
+
 int dm3d_conv_launch_f32(ConvArgs& a, int which, hipStream_t st);
 int dm3d_conv_launch_h3(ConvArgs& a, int which, hipStream_t st);
-int dm3d_conv_launch_h3v3(ConvArgs& a, int which, hipStream_t st);     // DM3D_WL_PAIR weights; which in {K3S1, UP}: the free-running form (dm3d_conv_h3v3.hip)
-struct H3v2Launch { ConvArgs k; bool stats_after; };       // what pre_launch decided: the kernel's own arguments; the stand-alone statistics pass behind it
-int dm3d_h3v2_pre_launch(ConvArgs& a, int td, H3v2Launch& L, hipStream_t st, int force_ksplit = 0);    // force_ksplit > 0: the caller's Cin split
+int dm3d_conv_launch_h3v3(const ConvLaunch& r, hipStream_t st);      // which in {K3S1, UP}
+int dm3d_conv_launch_h3w(const ConvLaunch& r, hipStream_t st);
+struct H3v2Launch { ConvArgs k; bool stats_after; };       // what pre_launch made of a ConvLaunch: the kernel's own arguments; the stand-alone statistics pass behind it
+int dm3d_h3v2_pre_launch(const ConvLaunch& r, H3v2Launch& L);
 int dm3d_h3v2_post_launch(const ConvArgs& a, const H3v2Launch& L, hipStream_t st);
-int dm3d_conv_h3v2_ksplit(const ConvArgs& a);            // parts along Cin the direct kernel's 4-slice form would use (1: no split_counters, or the grid is large)
-long dm3d_conv_split_tiles(const ConvArgs& a, int td);   // tiles of a launch in td-slice bricks: bricks x column tiles x parities
-int dm3d_conv_h3v3_td(const ConvArgs& a);              // z-slices per brick (4 or 8) the free-running kernel takes for this launch
 int64_t dm3d_h3v2_skip_image_bytes(int cin, int cout);
 int dm3d_pack_skip_h3v2(const float* keras_kernel, int cin, int cout, int w_exp, void* packed, hipStream_t st);
-int dm3d_pack_skip_h3f(const float* keras_kernel, int cin, int cout, int w_exp, void* packed, hipStream_t st);      // operand-fragment order       // split factor the launch would choose
+int dm3d_pack_skip_h3f(const float* keras_kernel, int cin, int cout, int w_exp, void* packed, hipStream_t st);      // operand-fragment order
 int64_t dm3d_h3v2_image_bytes(int taps, int cin, int cout);
 int dm3d_pack_h3v2(const float* keras_kernel, int taps, int cin, int cout, int w_exp, const float* in_scale, void* packed, int mode,
                    hipStream_t st);
-bool dm3d_conv_h3w_serves(const ConvArgs& a, int which);    // true: the Winograd-x form (wpk_wino, dm3d_conv_h3w.hip) serves this launch
-int dm3d_conv_launch_h3w(ConvArgs& a, int which, hipStream_t st);
-int dm3d_conv_h3w_ksplit(const ConvArgs& a);             // workgroups per brick along Cin the Winograd form would use (1 or 2)

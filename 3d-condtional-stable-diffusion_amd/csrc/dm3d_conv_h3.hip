@@ -370,15 +370,8 @@ int launch_h3(ConvArgs& a, hipStream_t st) {
     a.bd = (a.od + TD - 1) / TD;
     a.bh = (a.oh + TH - 1) / TH;
     a.bw = (a.ow + TW - 1) / TW;
-    static std::atomic<bool> attr_set[64] = {};            // per device: the attribute belongs to the device the launch goes to
-    int dev_ = 0;
-    DM3D_HIP(hipGetDevice(&dev_));
-    DM3D_REQUIRE(dev_ >= 0 && dev_ < 64, "conv: device ordinal %d", dev_);
-    if (!attr_set[dev_]) {
-        DM3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_igemm_h3<TD, TH, TW, S, KS, WM, WN, MINW, NRA>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev_] = true;
-    }
+    static std::atomic<bool> attr_set[64] = {};
+    if (int dev = dm3d_dyn_lds(lds, attr_set, "conv", &conv3d_igemm_h3<TD, TH, TW, S, KS, WM, WN, MINW, NRA>); dev < 0) return dev;
     dim3 grid((unsigned)(a.batch * a.bd * a.bh * a.bw), (unsigned)(a.coutpad / 64), a.parity ? 8u : 1u);
     hipLaunchKernelGGL((conv3d_igemm_h3<TD, TH, TW, S, KS, WM, WN, MINW, NRA>), grid, dim3(256), lds, st, a);
     return dm3d_launch_check("conv3d_igemm_h3");

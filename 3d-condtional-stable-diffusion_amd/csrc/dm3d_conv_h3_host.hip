@@ -1,58 +1,45 @@
-// dm3d_conv_h3_host.hip — what the 16x16x32 split-float16 Conv3d kernels (dm3d_conv_h3v3.hip: the free-running three-pass kernel;
-// dm3d_conv_h3w.hip: its Winograd-x form) share on the host side: brick counts and the Cin split of small grids (the hand-over form: raw
-// partial tiles into caller scratch, the last part of a tile to arrive sums them and runs the epilogue — one launch, no zero fill, no
-// atomics on the output, no reduce launch), the weight packers of the DM3D_WL_PAIR
-// geometry (plain / UpSample parity sums / Conv3DTranspose / the Winograd-x transform) and of the fused skip conv's image.
+// dm3d_conv_h3_host.hip — what the two 16x16x32 split-float16 Conv3d kernels (dm3d_conv_h3v3.hip: the free-running direct kernel;
+// dm3d_conv_h3w.hip: its Winograd-x form) share on the host side around the launch itself, and the weight packers.
+//   * pre_launch / post_launch turn a resolved ConvLaunch (dm3d_conv_args.h; the decision — brick depth, Cin split, tile sizes, workspace
+//     needs — is made in dm3d_conv_resolve, dm3d_conv.hip, not here) into the kernel's own arguments: bricks per volume, the split fields
+//     of the hand-over form (raw partial tiles into caller scratch, the last part of a tile to arrive sums them and runs the epilogue —
+//     one launch, no zero fill, no atomics on the output, no reduce launch), 16-byte epilogue eligibility, and where the
+//     GroupNormalization statistics come from.
+//   * the weight packers of the DM3D_WL_PAIR geometry (plain / UpSample parity sums / Conv3DTranspose / the Winograd-x transform) and of
+//     the fused skip conv's two images.
 // reference ops: Conv3D / UpSampling3D + Conv3D / Conv3DTranspose weights in Keras layouts (networks/conditional_dm3d.py:238-296,
 // networks/vqvae3d_monai.py:373-377).
-#include <cstdlib>
 #include "dm3d_conv_h3v2_parts.h"
 
 using namespace h3v2;
 
-// Everything around the conv launch itself that the two kernels share: brick counts, the Cin split of small grids, 16-byte epilogue
-// eligibility, where the GroupNormalization statistics come from.
-long dm3d_conv_split_tiles(const ConvArgs& a, int td) {
-    return (long)a.batch * ((a.od + td - 1) / td) * ((a.oh + 7) / 8) * ((a.ow + 7) / 8) * (a.coutpad / 64) * (a.parity ? 8 : 1);
-}
-
-int dm3d_h3v2_pre_launch(ConvArgs& a, int td, H3v2Launch& L, hipStream_t st, int force_ksplit) {
-    (void)st;
-    a.bd = (a.od + td - 1) / td;
-    a.bh = (a.oh + 7) / 8;
-    a.bw = (a.ow + 7) / 8;
-    // Small grids (the 8^3 level at B = 32 has 64 bricks x 4 channel tiles = one workgroup per CU, i.e. one wave per SIMD with
-    // nothing to hide its barriers and LDS latency behind; at B = 1 that level has 8 workgroups for 256 CUs) split the Cin chunks over
-    // several workgroups per tile.  Round 5: the parts meet INSIDE the launch (split_* in dm3d_conv_h3v2_parts.h) — every epilogue form,
-    // the fused output formats and the fused statistics included, since one workgroup sees the finished sums.
-    a.ksplit = force_ksplit > 0 ? force_ksplit : (td != 4 ? 1 : dm3d_conv_h3v2_ksplit(a));
-    {
-        auto al16 = [](const void* q) { return (reinterpret_cast<size_t>(q) & 15) == 0; };
-        a.epi_vec4 = a.cout % 4 == 0 && al16(a.out) && al16(a.bias) && al16(a.res) && al16(a.prelu) && al16(a.post_scale) && al16(a.post_shift)
-                     && al16(a.vec) && (a.vec == nullptr || a.vec_ld % 4 == 0);
-    }
-    a.split_tile_floats = 0;
-    if (a.ksplit > 1) {
-        const long tiles = dm3d_conv_split_tiles(a, td);
-        a.split_tile_floats = (long)td * 8 * 8 * 64;                      // a whole brick x 64 columns, whatever part of it is inside the volume
-        DM3D_REQUIRE(a.split_counters && a.split_counter_words >= tiles, "conv: a Cin-split launch of %ld tiles needs split_counters of as many zeroed words (have %d)",
-                     tiles, a.split_counter_words);
-        DM3D_REQUIRE(a.scratch && (size_t)a.scratch_bytes >= (size_t)tiles * a.ksplit * a.split_tile_floats * sizeof(float),
-                     "conv: scratch of %ld bytes is too small for %d parts x %ld tiles (dm3d_conv_scratch_bytes)", a.scratch_bytes, a.ksplit, tiles);
-        DM3D_REQUIRE((size_t)a.ksplit * a.split_tile_floats * sizeof(float) < (1ull << 31), "conv: %d parts overflow a tile's buffer descriptor", a.ksplit);
-    }
+int dm3d_h3v2_pre_launch(const ConvLaunch& r, H3v2Launch& L) {
     ConvArgs& k = L.k;
-    k = a;
+    k = r.a;
+    k.bd = (k.od + r.td - 1) / r.td; k.bh = (k.oh + 7) / 8; k.bw = (k.ow + 7) / 8;
+    k.ksplit = r.ksplit;
+    auto al16 = [](const void* q) { return (reinterpret_cast<size_t>(q) & 15) == 0; };
+    k.epi_vec4 = k.cout % 4 == 0 && al16(k.out) && al16(k.bias) && al16(k.res) && al16(k.prelu) && al16(k.post_scale) && al16(k.post_shift)
+                 && al16(k.vec) && (k.vec == nullptr || k.vec_ld % 4 == 0);
+    k.split_tile_floats = 0;
+    if (r.ksplit > 1) {                 // the hand-over form (split_* in dm3d_conv_h3v2_parts.h): the parts meet inside the launch
+        k.split_tile_floats = r.tile_floats;
+        DM3D_REQUIRE(k.split_counters && k.split_counter_words >= r.need_words, "conv: a Cin-split launch of %ld tiles needs split_counters of as many zeroed words (have %d)",
+                     r.tiles, k.split_counter_words);
+        DM3D_REQUIRE(k.scratch && (size_t)k.scratch_bytes >= (size_t)r.need_bytes,
+                     "conv: scratch of %ld bytes is too small for %d parts x %ld tiles (dm3d_conv_scratch_bytes)", k.scratch_bytes, r.ksplit, r.tiles);
+        DM3D_REQUIRE((size_t)r.ksplit * r.tile_floats * sizeof(float) < (1ull << 31), "conv: %d parts overflow a tile's buffer descriptor", r.ksplit);
+    }
     // Fused GroupNormalization statistics: the kernel's 16-byte full-brick epilogue accumulates them (whole bricks, cout % 64 == 0, plain
     // float32 output without PReLU; a split launch's last part runs that epilogue like any other); every other form leaves them to the
     // stand-alone kernel behind the launch (post_launch).
     L.stats_after = false;
-    if (a.gn_stats) {
+    if (k.gn_stats) {
 #ifdef DM3D_EPILOGUE_SCALAR
         const bool fused = false;            // (that A/B build compiles the 16-byte epilogue — the only form that accumulates — out)
 #else
-        const bool fused = a.od % td == 0 && a.oh % 8 == 0 && a.ow % 8 == 0 && a.cout % 64 == 0 && a.epi_vec4 && !a.prelu
-                           && !a.out_h2 && !a.post_scale;
+        const bool fused = k.od % r.td == 0 && k.oh % 8 == 0 && k.ow % 8 == 0 && k.cout % 64 == 0 && k.epi_vec4 && !k.prelu
+                           && !k.out_h2 && !k.post_scale;
 #endif
         if (!fused) { k.gn_stats = nullptr; L.stats_after = true; }
     }
@@ -182,27 +169,6 @@ int dm3d_pack_skip_h3v2(const float* keras_kernel, int cin, int cout, int w_exp,
     hipLaunchKernelGGL(pack_skip_h3v2_kernel, dim3(1024), dim3(256), 0, st, keras_kernel, cin, cout, npairs, ntiles, ldexpf(1.0f, w_exp),
                        static_cast<_Float16*>(packed));
     return dm3d_launch_check("pack_skip_h3v2_kernel");
-}
-
-// Workgroups per tile along Cin (the direct kernel's 4-slice form).  Goal: at least ~2 workgroups per CU (512) while every part keeps >= 2
-// chunks.  Only with split_counters (the host's statement that it provides the hand-over workspace: dm3d_conv_scratch_bytes).
-int dm3d_conv_h3v2_ksplit(const ConvArgs& a) {
-    static const int mode = [] { const char* e = getenv("DM3D_CONV_KSPLIT"); return e ? atoi(e) : -1; }();   // 0: never split (A/B, debugging)
-    if (mode == 0 || !a.split_counters) return 1;
-    const long wgs = dm3d_conv_split_tiles(a, 4);
-    static const long wg_limit = [] { const char* e = getenv("DM3D_CONV_SPLIT_WGS"); return e ? atol(e) : 256L; }();   // A/B knob
-    if (wgs > wg_limit || a.nchunks < 4) return 1;
-    // A/B knobs (read once: dm3d_conv_scratch_bytes and the launch must agree): least chunks per part, workgroups to aim for, most parts
-    static const int min_chunks = [] { const char* e = getenv("DM3D_CONV_SPLIT_MINCHUNKS"); return e ? atoi(e) : 2; }();
-    static const long target = [] { const char* e = getenv("DM3D_CONV_SPLIT_TARGET"); return e ? atol(e) : 512L; }();
-    static const int max_parts = [] { const char* e = getenv("DM3D_CONV_SPLIT_MAXPARTS"); return e ? atoi(e) : 16; }();
-    int best = 1;                                             // smallest divisor that fills the chip, else the largest allowed
-    for (int d = 2; d <= max_parts; ++d) {
-        if (a.nchunks % d != 0 || a.nchunks / d < min_chunks) continue;
-        best = d;
-        if (wgs * d >= target) break;
-    }
-    return best;
 }
 
 int64_t dm3d_h3v2_image_bytes(int taps, int cin, int cout) {

@@ -525,7 +525,7 @@ __device__ __forceinline__ void gn_flush(const ConvArgs& p, float (&gn)[NCT * 8]
 // instructions per tile), and the sixteen lanes of a row group write 256 contiguous bytes of a voxel: a store instruction covers 8 whole
 // cache lines instead of 16 half lines (timing-only bound of fully coalesced stores: profiles/r05_ab_store_coalescing.log).
 // e[2 g + parity][ni][r]: voxel (y = 4 g + r, x = 2 * x-pair + parity) of z-slice zs, channel 64 ntile + 4 j + ni; lane = 16 * g + j with x-pair = g ^ (g >> 1).
-// Whole 8 x 8 x 8 bricks only (dm3d_conv_h3w_serves), stride-1 outputs.  gn: this lane's partial (sum, sum of squares) of its four
+// Whole 8 x 8 x 8 bricks only (winograd_serves, dm3d_conv.hip), stride-1 outputs.  gn: this lane's partial (sum, sum of squares) of its four
 // channels, [ni][2] (gn_flush_cq below).
 // The per-channel operands of epilogue_cq's 16-byte form — bias + vector row, post-norm scale / shift of this lane's four channels — are
 // the same for every z-slice of a work item: loaded ONCE per item (epilogue_cq_vecs, in front of the first slice).  Loaded per slice, the

@@ -30,7 +30,6 @@
 // 1.85 instead of 1.95 GHz, i.e. the same wall time; on all-zero operands the same stream runs at 2.39 GHz, 30 % faster.  The split-float16
 // conv is bound by what the MFMA array draws on random data, not by its schedule; this kernel is kept because it is one loop for every
 // form (k3, parity, 4 / 8 slices, 16 / 32 / 64 columns) and because its work assignment halves the HBM traffic.
-#include <cstdlib>
 #include "dm3d_conv_h3v2_parts.h"
 
 using namespace h3v2;
@@ -466,59 +465,39 @@ __global__ __launch_bounds__(TD * 64, 2) void conv3d_igemm_h3v3(const ConvArgs p
 }
 
 template <int KS, int MODE, int TD, int NCT = 4>
-int launch_v3(ConvArgs& a, hipStream_t st) {
+int launch_v3(const ConvLaunch& r, hipStream_t st) {
     constexpr int HREC = (TD - 1 + KS) * (7 + KS) * 12;
     constexpr int main_halfs = HREC * REC + 4 * 2 * 64 * REC, skip_halfs = (KS == 3 && NCT == 4) ? skip_lds_halfs<TD>() : 0;
     constexpr size_t lds = (size_t)(main_halfs > skip_halfs ? main_halfs : skip_halfs) * sizeof(_Float16);
     static_assert((TD == 4 ? 2 : 1) * lds <= 160 * 1024, "workgroups per CU x LDS");
-    static std::atomic<bool> attr_set[64] = {};            // per device: the attribute belongs to the device the launch goes to
-    int dev = 0;
-    DM3D_HIP(hipGetDevice(&dev));
-    DM3D_REQUIRE(dev >= 0 && dev < 64, "conv: device ordinal %d", dev);
-    if (!attr_set[dev]) {
-        DM3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_igemm_h3v3<KS, MODE, TD, NCT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev] = true;
-    }
+    static std::atomic<bool> attr_set[64] = {};
+    if (int dev = dm3d_dyn_lds(lds, attr_set, "conv", &conv3d_igemm_h3v3<KS, MODE, TD, NCT>); dev < 0) return dev;
     H3v2Launch L;
-    if (int rc = dm3d_h3v2_pre_launch(a, TD, L, st)) return rc;
-    dim3 grid((unsigned)(a.batch * a.bd * a.bh * a.bw), (unsigned)(a.coutpad / 64 * a.ksplit), a.parity ? 8u : 1u);
-    hipLaunchKernelGGL((conv3d_igemm_h3v3<KS, MODE, TD, NCT>), grid, dim3(TD * 64), lds, st, L.k);
+    if (int rc = dm3d_h3v2_pre_launch(r, L)) return rc;
+    const ConvArgs& k = L.k;
+    dim3 grid((unsigned)(k.batch * k.bd * k.bh * k.bw), (unsigned)(k.coutpad / 64 * k.ksplit), k.parity ? 8u : 1u);
+    hipLaunchKernelGGL((conv3d_igemm_h3v3<KS, MODE, TD, NCT>), grid, dim3(TD * 64), lds, st, k);
     if (int rc = dm3d_launch_check("conv3d_igemm_h3v3")) return rc;
-    return dm3d_h3v2_post_launch(a, L, st);
+    return dm3d_h3v2_post_launch(r.a, L, st);
 }
 
+// the resolved brick depth and column form (dm3d_conv_resolve) -> the instantiation
 template <int KS, int MODE>
-int launch_td(ConvArgs& a, hipStream_t st) {
+int launch_td(const ConvLaunch& r, hipStream_t st) {
     if constexpr (KS == 3) {                        // the narrow column forms: k3 convs with few output channels
-        if (a.cout <= 32) {
-            DM3D_REQUIRE(a.s_npairs == 0 && !a.out_h2, "conv: the fused skip conv / hand-off output need cout > 32");
-            // (4-slice bricks: with 8-slice bricks conv_out / conv_in were 4 % / 11 % slower — these launches are bound by staging the input,
-            // 12 or 24 MFMAs per pair against the same halo, not by the matrix pipe: profiles/r03_layers_h3.log)
-            return a.cout <= 16 ? launch_v3<KS, MODE, 4, 1>(a, st) : launch_v3<KS, MODE, 4, 2>(a, st);
+        if (r.nct != 4) {
+            DM3D_REQUIRE(r.a.s_npairs == 0 && !r.a.out_h2, "conv: the fused skip conv / hand-off output need cout > 32");
+            return r.nct == 1 ? launch_v3<KS, MODE, 4, 1>(r, st) : launch_v3<KS, MODE, 4, 2>(r, st);
         }
     }
-    return dm3d_conv_h3v3_td(a) == 8 ? launch_v3<KS, MODE, 8>(a, st) : launch_v3<KS, MODE, 4>(a, st);
+    return r.td == 8 ? launch_v3<KS, MODE, 8>(r, st) : launch_v3<KS, MODE, 4>(r, st);
 }
 
 }  // namespace
 
-// Brick depth of a launch.  8 slices (512 threads, one workgroup per CU: half the weight bytes per FLOP, halo factor 1.95 instead of 2.34)
-// where the grid still gives every CU at least two such workgroups in turn; 4 slices (256 threads, two independent workgroups per CU,
-// Cin splitting for tiny grids) for small grids, the parity convs (4 pairs per chunk: nothing for a wider barrier to amortise) and the
-// launches with a fused skip phase.  DM3D_CONV_V3_TD (A/B knob, read per call): 4 = always 4; 8 = 8 wherever the grid allows; else auto.
-int dm3d_conv_h3v3_td(const ConvArgs& a) {
-    const char* e = getenv("DM3D_CONV_V3_TD");
-    const int mode = e ? atoi(e) : 0;
-    if (mode == 4) return 4;
-    if (mode != 8 && (a.parity || a.s_npairs > 0)) return 4;
-    if ((a.out_h2 || a.post_scale) && a.od % 8 != 0) return 4;      // the fused output forms live in the full-brick epilogue: whole bricks
-    const long wgs = (long)a.batch * ((a.od + 7) / 8) * ((a.oh + 7) / 8) * ((a.ow + 7) / 8) * (a.coutpad / 64) * (a.parity ? 8 : 1);
-    const char* w = getenv("DM3D_CONV_WIDE_WGS");                      // threshold override (tests force the 8-slice forms onto small shapes with 1)
-    return wgs >= (w ? atol(w) : 512L) ? 8 : 4;
-}
-
-int dm3d_conv_launch_h3v3(ConvArgs& a, int which, hipStream_t st) {
-    if (which == DM3D_CONV_UP) return a.pscale ? launch_td<2, 1>(a, st) : launch_td<2, 0>(a, st);
-    if (a.x_h2) return launch_td<3, 2>(a, st);
-    return a.pscale ? launch_td<3, 1>(a, st) : launch_td<3, 0>(a, st);
+int dm3d_conv_launch_h3v3(const ConvLaunch& r, hipStream_t st) {
+    const ConvArgs& a = r.a;
+    if (r.which == DM3D_CONV_UP) return a.pscale ? launch_td<2, 1>(r, st) : launch_td<2, 0>(r, st);
+    if (a.x_h2) return launch_td<3, 2>(r, st);
+    return a.pscale ? launch_td<3, 1>(r, st) : launch_td<3, 0>(r, st);
 }

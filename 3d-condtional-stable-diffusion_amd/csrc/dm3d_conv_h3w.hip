@@ -3,7 +3,7 @@
 //
 // reference op: Conv3D(width, 3, padding="same") behind BatchNormalization + swish, + time-embedding / bias / residual adds
 // (networks/conditional_dm3d.py:254-268) — the same launches the free-running kernel of dm3d_conv_h3v3.hip serves; this form takes them when
-// the caller supplied the transformed weight image (dm3d_conv_desc.wpk_wino) and the grid is large (dm3d_conv_h3w_serves below).
+// the caller supplied the transformed weight image (dm3d_conv_desc.wpk_wino) and the grid is large (winograd_serves, dm3d_conv.hip).
 //
 // Why.  Round 3 measured the three-pass split-float16 conv at the chip's power limit, not at a scheduling limit: the same instruction stream
 // runs 30 % faster on all-zero operands (2.39 against 1.85 GHz), no reordering of it moved the wall time, and no other
@@ -861,27 +861,27 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_h3w(const ConvArgs p) {
 }
 
 template <int MODE>
-int launch_w(ConvArgs& a, hipStream_t st) {
+int launch_w(const ConvLaunch& r, hipStream_t st) {
     constexpr size_t lds = (size_t)(4 * 2 * 64 * REC + 10 * 10 * 17 * REC) * sizeof(_Float16) + 16;      // 32 KB of weights + 106 KB of image + the split form's ticket word
     static_assert(lds <= 160 * 1024, "one workgroup per CU");
     // (per device: the attribute and the CU count belong to the device the launch goes to)
+    static std::atomic<bool> attr_set[64] = {};
     static std::atomic<int> cus[64] = {};
-    int dev = 0;
-    DM3D_HIP(hipGetDevice(&dev));
-    DM3D_REQUIRE(dev >= 0 && dev < 64, "conv: device ordinal %d", dev);
-    if (cus[dev].load(std::memory_order_acquire) == 0) {       // (two host threads may meet here: both set the same attribute and store the same count)
-        DM3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_igemm_h3w<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int dev = dm3d_dyn_lds(lds, attr_set, "conv", &conv3d_igemm_h3w<MODE>);
+    if (dev < 0) return dev;
+    if (cus[dev].load(std::memory_order_acquire) == 0) {       // (two host threads may meet here: both store the same count)
         int n = 0;
         DM3D_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
         cus[dev].store(n > 0 ? n : 256, std::memory_order_release);
     }
     const int ncu = cus[dev].load(std::memory_order_relaxed);
     H3v2Launch L;
-    if (int rc = dm3d_h3v2_pre_launch(a, 8, L, st, dm3d_conv_h3w_ksplit(a))) return rc;
-    L.k.wpk = a.wpk_wino;
+    if (int rc = dm3d_h3v2_pre_launch(r, L)) return rc;
+    ConvArgs& k = L.k;
+    k.wpk = k.wpk_wino;
     // work items = bricks x column tiles x Cin parts; one persistent workgroup per CU walks its share of the list
     // (DM3D_CONV_WINO_PERSIST=0: one item per workgroup)
-    const long items = (long)a.batch * a.bd * a.bh * a.bw * (a.coutpad / 64) * a.ksplit;
+    const long items = (long)k.batch * k.bd * k.bh * k.bw * (k.coutpad / 64) * k.ksplit;
     static const bool persist = [] { const char* e = getenv("DM3D_CONV_WINO_PERSIST"); return !(e && e[0] == '0'); }();
     long g = items;
     // (a partition that reports fewer than 8 CUs has no whole XCD round: one workgroup per CU, never an empty grid)
@@ -891,55 +891,15 @@ int launch_w(ConvArgs& a, hipStream_t st) {
         const char* cap = getenv("DM3D_CONV_WINO_GRID");
         if (cap && atol(cap) > 0 && atol(cap) < g) g = atol(cap);
     }
-    hipLaunchKernelGGL((conv3d_igemm_h3w<MODE>), dim3((unsigned)g), dim3(256), lds, st, L.k);
+    hipLaunchKernelGGL((conv3d_igemm_h3w<MODE>), dim3((unsigned)g), dim3(256), lds, st, k);
     if (int rc = dm3d_launch_check("conv3d_igemm_h3w")) return rc;
-    return dm3d_h3v2_post_launch(a, L, st);
+    return dm3d_h3v2_post_launch(r.a, L, st);
 }
 
 }  // namespace
 
-// The Winograd form serves a k3 / stride-1 launch when the caller supplied the transformed image (wpk_wino), the volume is whole 8 x 8 x 8
-// bricks, a fused skip conv is short or the main loop long (below), the grid gives every CU two workgroups in turn or exactly one
-// (the same threshold as the 8-slice bricks of the direct kernel: DM3D_CONV_WIDE_WGS) and Cin is at least 32 (two 16-channel chunks,
-// DM3D_CONV_WINO_MINCHUNKS: its unoverlapped prologue and epilogue cost as much as two chunks; at 32 input channels it is still 9 %
-// ahead of the direct kernel, at 64 10-13 %, profiles/r03_wino_ab.log).  The input tensors must be below 4 GB (32-bit lane offsets).  DM3D_CONV_WINO=0 (A/B knob, read per
-// call): never.
-bool dm3d_conv_h3w_serves(const ConvArgs& a, int which) {
-    if (!a.wpk_wino || which != DM3D_CONV_K3S1 || a.parity || a.cout <= 32) return false;
-    // (a fused skip conv needs its weights as operand fragments: dm3d_conv_desc.skip_wpk_frag; raw skip inputs below 4 GB: 32-bit lane offsets)
-    if (a.s_npairs > 0) {
-        if (!a.swpk_f) return false;
-        const long long svox = (long long)a.batch * a.ind * a.inh * a.inw;
-        if (svox * (a.sc1 > a.sc2 ? a.sc1 : a.sc2) * 4 >= (1ll << 32)) return false;
-    }
-    if (a.od % 8 != 0 || a.oh % 8 != 0 || a.ow % 8 != 0 || a.padz != 1 || a.pady != 1 || a.padx != 1) return false;
-    const char* e = getenv("DM3D_CONV_WINO");
-    if (e && e[0] == '0') return false;
-    const char* mc = getenv("DM3D_CONV_WINO_MINCHUNKS");
-    if (a.nchunks < (mc ? atoi(mc) : 2)) return false;
-    const long long vox = (long long)a.batch * a.ind * a.inh * a.inw;
-    if (vox * (a.c1 > a.c2 ? a.c1 : a.c2) * 4 >= (1ll << 32)) return false;
-    const long wgs = (long)a.batch * (a.od / 8) * (a.oh / 8) * (a.ow / 8) * (a.coutpad / 64) * dm3d_conv_h3w_ksplit(a);
-    const char* w = getenv("DM3D_CONV_WIDE_WGS");
-    const long need = w ? atol(w) : 512L;
-    // (one workgroup per CU: exactly 256 workgroups are one full round — B = 4 at 32^3, config 2: 3.21 -> 3.09 ms per step —; between 256
-    // and 512 the second round would be part empty, which two small workgroups per CU of the direct kernel handle better)
-    return wgs >= need || wgs == 256 || (dm3d_conv_h3w_ksplit(a) > 1 && wgs >= (need < 256 ? need : 256L));
-}
-
-// Cin split of the Winograd form: two workgroups per brick and column tile where one would leave at least half of the CUs without work
-// (the 8^3 level at B = 32: 32 bricks x 4 column tiles), each contracting half of the chunks (at least eight) and half of a fused skip
-// conv's pairs; the halves meet inside the launch (the hand-over form, dm3d_conv_h3v2_parts.h: any epilogue, fused statistics and output
-// formats included).  Needs the host's split_counters (and scratch: dm3d_conv_scratch_bytes).  DM3D_CONV_WINO_SPLIT=0: never.
-int dm3d_conv_h3w_ksplit(const ConvArgs& a) {
-    static const bool off = [] { const char* e = getenv("DM3D_CONV_WINO_SPLIT"); return e && e[0] == '0'; }();
-    if (off || !a.split_counters || a.nchunks % 2 != 0 || a.nchunks < 16) return 1;
-    const long wgs = (long)a.batch * (a.od / 8) * (a.oh / 8) * (a.ow / 8) * (a.coutpad / 64);
-    return wgs <= 128 ? 2 : 1;
-}
-
-int dm3d_conv_launch_h3w(ConvArgs& a, int which, hipStream_t st) {
-    (void)which;
-    if (a.x_h2) return launch_w<2>(a, st);
-    return a.pscale ? launch_w<1>(a, st) : launch_w<0>(a, st);
+// (when this form serves a launch, and its Cin split: dm3d_conv_resolve, dm3d_conv.hip)
+int dm3d_conv_launch_h3w(const ConvLaunch& r, hipStream_t st) {
+    if (r.a.x_h2) return launch_w<2>(r, st);
+    return r.a.pscale ? launch_w<1>(r, st) : launch_w<0>(r, st);
 }

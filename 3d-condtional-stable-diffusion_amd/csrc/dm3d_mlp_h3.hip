@@ -457,13 +457,7 @@ extern "C" int dm3d_mlp_fused(const dm3d_mlp_desc* d, void* stream) {
     }
     constexpr size_t lds = 64 * 1040;                       // the x staging area of the prologue; the H slab (32 KB) overlays it afterwards
     static std::atomic<bool> attr_set[64] = {};
-    int dev = 0;
-    DM3D_HIP(hipGetDevice(&dev));
-    DM3D_REQUIRE(dev >= 0 && dev < 64, "mlp_fused: device ordinal %d", dev);
-    if (!attr_set[dev]) {
-        DM3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_h3<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev] = true;
-    }
+    if (int dev = dm3d_dyn_lds(lds, attr_set, "mlp_fused", &mlp_fused_h3<256>); dev < 0) return dev;
     hipLaunchKernelGGL(mlp_fused_h3<256>, dim3((unsigned)((d->m + 63) / 64)), dim3(256), lds, static_cast<hipStream_t>(stream), a);
     return dm3d_launch_check("mlp_fused_h3");
 }

@@ -222,7 +222,8 @@ int64_t dm3d_conv_scratch_bytes(const dm3d_conv_desc* d);
 int32_t dm3d_conv_split_counter_words(const dm3d_conv_desc* d);     /* words of split_counters a descriptor of this shape can use (0: it never splits) */
 /* Which tile form of the 16x16x32 conv kernels serves this descriptor: 8 (8 z-slices per brick, 512 threads, one workgroup per CU — launches
  * with enough bricks to give every CU two such workgroups in turn), 4 (4 slices, 256 threads, two workgroups per CU: small grids, the parity
- * form, launches with a fused skip conv, Cout <= 32), 10 (the Winograd-x form: wpk_wino given and eligible; conv3d_igemm_h3w<MODE>), 0 (another kernel).  Profiling
+ * form, launches with a fused skip conv, and every k3 / stride-1 conv with Cout <= 32: the narrow column forms NCT 2 and 1), 10 (the Winograd-x
+ * form: wpk_wino given and eligible; conv3d_igemm_h3w<MODE>), 0 (another kernel).  The launch and this query read the same resolved decision.  Profiling
  * harnesses use it to name the instantiation a launch runs (rocprofv3 lists conv3d_igemm_h3v3<KS, MODE, TD, NCT> and conv3d_igemm_h3w<MODE>). */
 int32_t dm3d_conv_tile_form(const dm3d_conv_desc* d);
 

@@ -1,7 +1,7 @@
 """The Winograd F(2,3)-along-x form of the k3 / stride-1 split-float16 Conv3d (dm3d_conv_h3w.hip, dm3d_conv_desc.wpk_wino) against a float64
 reference of the same op (Conv3D(padding="same") behind the folded norm + swish, conditional_dm3d.py:254-268) and against the direct kernel on
 the same inputs: plain / prologue / concat / ragged Cin / non-cubic volumes / residual, the DM3D_FMT_H2 hand-off pair (kernel MODE 2 on the
-consumer side), the launch policy (dm3d_conv_tile_form() == 10), and eps of the whole U-Net with and without the second image.
+consumer side), the launch policy (dm3d_conv_tile_form() == 10), launches on exactly the workspace the queries name, and eps of the whole U-Net with and without the second image.
 Tolerance: max|err| / max|ref| <= 2e-5 like every other contraction test (1e-3 is the end-to-end budget north_star states).
 All through the C ABI (ctypes)."""
 import ctypes as C
@@ -207,6 +207,62 @@ def test_winograd_launch_policy(dev, monkeypatch):
     assert form(skip="no fragments") == 4        # ... given the skip weights as operand fragments (skip_wpk_frag); else the direct kernel
     monkeypatch.setenv("DM3D_CONV_WINO", "0")
     assert form() == 8
+
+
+# name, B, edge, c1, cout, second image, DM3D_CONV_WIDE_WGS=1 (admits these small grids to the one-workgroup-per-CU forms), form, splits
+AGREE = [("direct 4-slice, Cin split: 8^3 64->64", 1, 8, 64, 64, False, False, 4, True),
+         ("Winograd, two-way split: 8^3 256->256", 1, 8, 256, 256, True, True, 10, True),
+         ("Winograd, no split: B=2 16^3 32->64", 2, 16, 32, 64, True, True, 10, False),
+         ("narrow, no split: 8^3 16->8", 1, 8, 16, 8, False, False, 4, False)]
+
+
+@pytest.mark.parametrize("case", AGREE, ids=[c[0] for c in AGREE])
+def test_launch_and_queries_agree(dev, monkeypatch, case):
+    """A launch given exactly the workspace its queries name — dm3d_conv_scratch_bytes bytes, dm3d_conv_split_counter_words zeroed ticket
+    words, none where that is 0 — succeeds, runs the form dm3d_conv_tile_form named, and leaves the tickets zero: the launch and the three
+    queries read one resolved description (dm3d_conv_resolve), so a launch that needed more than its query reported would be refused."""
+    from dm3d_amd import ops, _lib
+    name, B, e, cin, cout, with_wino, wide, form, splits = case
+    for v in ("DM3D_CONV_WIDE_WGS", "DM3D_CONV_WINO_MINCHUNKS", "DM3D_CONV_WINO", "DM3D_CONV_V3_TD", "DM3D_CONV_WINO_SPLIT", "DM3D_CONV_KSPLIT"):
+        monkeypatch.delenv(v, raising=False)
+    if wide:
+        monkeypatch.setenv("DM3D_CONV_WIDE_WGS", "1")
+    launches, tickets = [], []
+
+    class Spy:                                   # ops.conv3d's own descriptor, looked at on its way into the launch
+        def __getattr__(self, fn):
+            return getattr(_lib.lib(), fn)
+
+        def dm3d_conv3d_ndhwc(self, d, stream):
+            h, desc = _lib.lib(), d._obj
+            named = h.dm3d_conv_tile_form(d)
+            rc = h.dm3d_conv3d_ndhwc(d, stream)
+            launches.append((named, h.dm3d_conv_scratch_bytes(d), h.dm3d_conv_split_counter_words(d), desc.scratch_bytes if desc.scratch else 0,
+                             desc.split_counter_words if desc.split_counters else 0, rc))
+            return rc
+
+    def exact_tickets(device, words):
+        tickets.append(torch.zeros(words, dtype=torch.int32, device=device))
+        return tickets[-1]
+
+    monkeypatch.setattr(ops, "lib", lambda: Spy())
+    monkeypatch.setattr(ops, "_split_counters", exact_tickets)
+    torch.manual_seed(13)
+    x = torch.randn(B, e, e, e, cin, device=dev)
+    k = torch.randn(3, 3, 3, cin, cout, device=dev) * 0.05
+    wpk, w_exp = ops.pack_weights_h3(k)
+    kw = dict(bias=torch.randn(cout, device=dev), precision=_lib.PREC_H3, w_exp=w_exp, wpk_wino=ops.pack_weights_h3w(k, w_exp) if with_wino else None)
+    y = ops.conv3d(x, wpk, cout, 3, **kw)
+    torch.cuda.synchronize()
+    named, need, words, got_bytes, got_words, rc = launches[0]
+    print(f"{name}: form {named}, scratch {need} bytes, {words} ticket words")
+    assert rc == 0                               # DM3D_OK
+    assert (got_bytes, got_words) == (need, words) and (need > 0) == (words > 0) == splits
+    assert named == form
+    assert all(int(t.abs().max()) == 0 for t in tickets) and len(tickets) == int(splits)
+    assert _rel(y, _ref_conv(x, k, kw["bias"])) < 2e-5
+    if splits:
+        assert not torch.equal(y, ops.conv3d(x, wpk, cout, 3, split=False, **kw)), "the launch did not split"
 
 
 def test_unet_eps_with_and_without_the_winograd_image(dev, monkeypatch):
