@@ -117,7 +117,7 @@ class DdimDesc(C.Structure):
     _fields_ = [
         ("x", _f32p), ("eps", _f32p), ("noise", _f32p), ("out", _f32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
         ("coef", _f32p), ("tau", _i32p), ("t_next", _i32p), ("rows", C.c_int32), ("pos", _i32p), ("t_idx", _i32p),
-        ("seed", C.c_uint64), ("seed_dev", C.c_void_p), ("mode", C.c_int32),
+        ("seed", C.c_uint64), ("seed_dev", C.c_void_p), ("mode", C.c_int32), ("x0_bound", _f32p),
     ]
 
 
@@ -125,6 +125,15 @@ class DpmDesc(C.Structure):
     _fields_ = [
         ("x", _f32p), ("eps", _f32p), ("hist", _f32p), ("out", _f32p), ("x0_out", _f32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
         ("coef", _f32p), ("rows", C.c_int32), ("pos", _i32p), ("t_next", _i32p), ("t_idx", _i32p), ("mode", C.c_int32),
+        ("x0_bound", _f32p),
+    ]
+
+
+class ThreshDesc(C.Structure):
+    _fields_ = [
+        ("x", _f32p), ("eps", _f32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
+        ("coef", _f32p), ("rows", C.c_int32), ("pos", _i32p), ("rank", _i32p), ("frac", _f32p), ("smax", _f32p),
+        ("bound", _f32p), ("scratch", C.c_void_p),
     ]
 
 
@@ -198,6 +207,8 @@ SIGNATURES = {
     "dm3d_ddpm_update": (C.c_int, [C.POINTER(DdpmDesc), C.c_void_p]),
     "dm3d_ddim_update": (C.c_int, [C.POINTER(DdimDesc), C.c_void_p]),
     "dm3d_dpm_update": (C.c_int, [C.POINTER(DpmDesc), C.c_void_p]),
+    "dm3d_x0_threshold": (C.c_int, [C.POINTER(ThreshDesc), C.c_void_p]),
+    "dm3d_x0_threshold_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "dm3d_edit_update": (C.c_int, [C.POINTER(EditDesc), C.c_void_p]),
     "dm3d_guide_update": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p]),
     "dm3d_range_check": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),

@@ -67,6 +67,19 @@ __device__ __forceinline__ float dm3d_act(float v, int act) {
     return v;
 }
 
+// The x0 estimate of the DDIM / DPM-Solver++ updates, (x - sqrt(1-a)*eps) / sqrt(a) as mul, sub, div, each rounded (ddpm_kernel's order).
+// One function for the update kernels and the dynamic threshold's selection: the magnitudes ranked are bitwise the values clamped.
+__device__ __forceinline__ float dm3d_x0_estimate(float x, float eps, float sqab, float sq1ab) {
+    return __fdiv_rn(__fsub_rn(x, __fmul_rn(sq1ab, eps)), sqab);
+}
+// The bounded estimate: clamp(x0, -1, 1), or with a dynamic bound s (include/dm3d.h, dm3d_thresh_desc) clamp(x0, -s, s) / s.  A NaN
+// passes; `dyn` is uniform over the block, so the static path is the one instruction pair it always was.
+__device__ __forceinline__ float dm3d_x0_bounded(float x0, bool dyn, float s) {
+    if (x0 != x0) return x0;
+    if (dyn) return __fdiv_rn(fminf(fmaxf(x0, -s), s), s);
+    return fminf(fmaxf(x0, -1.0f), 1.0f);
+}
+
 // One (tap, Cin-chunk) step of the implicit GEMM for a wave owning MR x NR tiles of 32x32 outputs.
 // v_mfma_f32_32x32x2_f32: lane l supplies A[i = l&31][k = l>>5] and B[k = l>>5][j = l&31]; the two lane halves carry
 // two different k, so with CK channels per chunk half h takes channels [h*CK/2, (h+1)*CK/2) as CK/8 float4 reads and

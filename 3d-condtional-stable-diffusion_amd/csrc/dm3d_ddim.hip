@@ -13,6 +13,7 @@ struct DdimArgs {
     const float* coef; const int* tau; const int* t_next; int rows;
     const int* pos; int* t_idx;
     uint64_t seed; const uint64_t* seed_dev; int mode;
+    const float* x0_bound;
 };
 
 __global__ __launch_bounds__(256) void ddim_kernel(const DdimArgs p) {
@@ -22,6 +23,8 @@ __global__ __launch_bounds__(256) void ddim_kernel(const DdimArgs p) {
     const f32x4 c1 = reinterpret_cast<const f32x4*>(p.coef)[2 * r + 1];      // sigma, clip, -, -
     const float sqab = c0[0], sq1ab = c0[1], a_x0 = c0[2], a_eps = c0[3], sigma = c1[0];
     const bool clip = c1[1] != 0.f, draw = sigma != 0.f;
+    const bool dyn = clip && p.x0_bound != nullptr;                          // the dynamic threshold's bound, read once per block
+    const float s = dyn ? p.x0_bound[b] : 1.0f;
     const int tau = p.tau[r];
     const uint64_t seed = p.seed_dev ? *p.seed_dev : p.seed;
     // the next step's U-Net row; the kernel never reads t_idx, so this one lane per sample races with nobody
@@ -37,8 +40,8 @@ __global__ __launch_bounds__(256) void ddim_kernel(const DdimArgs p) {
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float x0 = __fdiv_rn(__fsub_rn(x[k], __fmul_rn(sq1ab, e[k])), sqab);     // ddpm_kernel's order
-            if (clip) x0 = x0 != x0 ? x0 : fminf(fmaxf(x0, -1.0f), 1.0f);           // a NaN passes, as in ddpm_kernel's clip
+            float x0 = dm3d_x0_estimate(x[k], e[k], sqab, sq1ab);                    // ddpm_kernel's order
+            if (clip) x0 = dm3d_x0_bounded(x0, dyn, s);                              // a NaN passes, as in ddpm_kernel's clip
             o[k] = __fadd_rn(__fadd_rn(__fmul_rn(a_x0, x0), __fmul_rn(a_eps, e[k])), __fmul_rn(sigma, z[k]));
         }
         reinterpret_cast<f32x4*>(dst)[base + i] = o;
@@ -61,7 +64,7 @@ extern "C" int dm3d_ddim_update(const dm3d_ddim_desc* d, void* stream) {
     DdimArgs a{};
     a.x = d->x; a.eps = d->eps; a.noise = d->noise; a.out = d->out; a.per4 = d->per_sample / 4;
     a.coef = d->coef; a.tau = d->tau; a.t_next = d->t_next; a.rows = d->rows; a.pos = d->pos; a.t_idx = d->t_idx;
-    a.seed = d->seed; a.seed_dev = d->seed_dev; a.mode = d->mode;
+    a.seed = d->seed; a.seed_dev = d->seed_dev; a.mode = d->mode; a.x0_bound = d->x0_bound;
     const long blocks = (a.per4 + 255) / 256;
     dim3 grid((unsigned)(blocks > 256 ? 256 : blocks), (unsigned)d->batch);                 // ddpm_kernel's grid
     hipLaunchKernelGGL(ddim_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);

@@ -13,6 +13,7 @@ struct DpmArgs {
     const float* coef; const int* t_next; int rows;
     const int* pos; int* t_idx;
     int mode;
+    const float* x0_bound;
 };
 
 __global__ __launch_bounds__(256) void dpm_kernel(const DpmArgs p) {
@@ -22,6 +23,8 @@ __global__ __launch_bounds__(256) void dpm_kernel(const DpmArgs p) {
     const f32x4 c1 = reinterpret_cast<const f32x4*>(p.coef)[2 * r + 1];      // c_1, clip, -, -
     const float sqab = c0[0], sq1ab = c0[1], c_x = c0[2], c_0 = c0[3], c_1 = c1[0];
     const bool clip = c1[1] != 0.f;
+    const bool dyn = clip && p.x0_bound != nullptr;                          // the dynamic threshold's bound, read once per block
+    const float s = dyn ? p.x0_bound[b] : 1.0f;
     const bool second = c_1 != 0.f && p.hist != nullptr;                     // a first-order row never reads the history
     // the next step's U-Net row; the kernel never reads t_idx, so this one lane per sample races with nobody
     if (p.t_idx && blockIdx.x == 0 && threadIdx.x == 0) p.t_idx[b] = p.t_next[r];
@@ -36,8 +39,8 @@ __global__ __launch_bounds__(256) void dpm_kernel(const DpmArgs p) {
         f32x4 o, x0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float v = __fdiv_rn(__fsub_rn(x[k], __fmul_rn(sq1ab, e[k])), sqab);      // ddim_kernel's order
-            if (clip) v = v != v ? v : fminf(fmaxf(v, -1.0f), 1.0f);                 // a NaN passes, as in ddim_kernel's clip
+            float v = dm3d_x0_estimate(x[k], e[k], sqab, sq1ab);                     // ddim_kernel's order
+            if (clip) v = dm3d_x0_bounded(v, dyn, s);                                // a NaN passes, as in ddim_kernel's clip
             x0[k] = v;
             const float first = __fadd_rn(__fmul_rn(c_x, x[k]), __fmul_rn(c_0, v));
             o[k] = second ? __fadd_rn(first, __fmul_rn(c_1, h[k])) : first;
@@ -64,6 +67,7 @@ extern "C" int dm3d_dpm_update(const dm3d_dpm_desc* d, void* stream) {
     DpmArgs a{};
     a.x = d->x; a.eps = d->eps; a.hist = d->hist; a.out = d->out; a.x0_out = d->x0_out; a.per4 = d->per_sample / 4;
     a.coef = d->coef; a.t_next = d->t_next; a.rows = d->rows; a.pos = d->pos; a.t_idx = d->t_idx; a.mode = d->mode;
+    a.x0_bound = d->x0_bound;
     const long blocks = (a.per4 + 255) / 256;
     dim3 grid((unsigned)(blocks > 256 ? 256 : blocks), (unsigned)d->batch);                 // ddpm_kernel's grid
     hipLaunchKernelGGL(dpm_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);

@@ -4,7 +4,9 @@ reference: networks/conditional_dm3d.py:418-594 (conditional) and networks/dm3d.
 constructor, attributes and method signatures; tensors are PyTorch device tensors (NDHWC float32) instead of tf.Tensor.
 Keyword-only extensions: ``x_T=`` / ``noise=`` inject the random draws (parity tests), ``seed=``
 selects the in-kernel Philox stream, ``use_graph=`` toggles HIP-graph replay of the step; ``guidance_scale=`` /
-``negative_context=`` / ``guidance_rescale=`` turn on classifier-free guidance (include/dm3d.h, dm3d_guide_desc).
+``negative_context=`` / ``guidance_rescale=`` turn on classifier-free guidance (include/dm3d.h, dm3d_guide_desc);
+``dynamic_threshold=`` / ``threshold_max=`` replace the static clamp of the x0 estimate by Imagen's dynamic thresholding in the DDIM
+and DPM-Solver++ chains (include/dm3d.h, dm3d_thresh_desc).
 
 The sampling loop (:559-573) runs with no host synchronisation: the step index lives in device memory, one step
 (U-Net forward + posterior update + index decrement) is captured once into a HIP graph and replayed T times.
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DdimDesc, DdpmDesc, DpmDesc, EditDesc, GuideDesc, check, lib
+from ._lib import DdimDesc, DdpmDesc, DpmDesc, EditDesc, GuideDesc, ThreshDesc, check, lib
 from .betas import BETAS_FIELDS, Betas
 from .unet import UNet
 from .weights import UNetConfig
@@ -87,6 +89,39 @@ def dpm_coefficients(alpha_bar, src, dst, prev, order=2) -> np.ndarray:
     out = np.stack([c_x, A * (1 + g), -A * g], axis=1)
     out[dst < 0] = (0.0, 1.0, 0.0)
     return out
+
+
+def threshold_rank(per_sample: int, ratio) -> tuple:
+    """(i, f) of the dynamic threshold's quantile (include/dm3d.h, dm3d_thresh_desc): q = ratio (N-1) in float64, i = floor(q) and
+    f = float32(q - i), the weight of v_{i+1} in the interpolation between the order statistics v_i and v_{i+1} of N = per_sample
+    magnitudes (numpy's "linear" quantile).  ratio = 1 gives (N-1, 0): the maximum."""
+    q = float(ratio) * (int(per_sample) - 1)
+    i = min(int(math.floor(q)), int(per_sample) - 1)
+    return i, np.float32(q - i)
+
+
+FLOAT32_MAX = float(np.finfo(np.float32).max)
+
+
+def threshold_tables(B: int, per_sample: int, dynamic_threshold, threshold_max=None):
+    """(rank int32 [B], frac float32 [B], smax float32 [B]) host tables of dm3d_thresh_desc, one ratio / cap broadcast or one per
+    volume, validated: 0 < ratio <= 1, cap >= 1 (None: the largest finite float32), all finite."""
+    out = []
+    for name, v in (("dynamic_threshold", dynamic_threshold), ("threshold_max", FLOAT32_MAX if threshold_max is None else threshold_max)):
+        a = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)
+        if a.size not in (1, B):
+            raise ValueError(f"{name} must hold one value or one per volume ({B}), got {a.size}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{name} must be finite")
+        out.append(np.broadcast_to(a, (B,)))
+    p, cap = out
+    if p.min() <= 0 or p.max() > 1:
+        raise ValueError("dynamic_threshold must lie in (0, 1]")
+    if cap.min() < 1 or cap.max() > FLOAT32_MAX:
+        raise ValueError("threshold_max must be >= 1 (and a finite float32)")
+    ranks = [threshold_rank(per_sample, v) for v in p]
+    return (np.array([r[0] for r in ranks], dtype=np.int32), np.array([r[1] for r in ranks], dtype=np.float32),
+            np.ascontiguousarray(cap.astype(np.float32)))
 
 
 def edit_steps(strength, n: int) -> int:
@@ -422,15 +457,18 @@ class DiffusionModel:
         check(lib().dm3d_ddpm_update(C.byref(d), torch.cuda.current_stream().cuda_stream), "ddpm_update")
         return mean, var.reshape(B, 1, 1, 1, 1)
 
-    def ddim_step(self, x_t, pred_noise, t, t_prev, eta=0.0, noise=None, *, clip_x0=True, seed=None):
+    def ddim_step(self, x_t, pred_noise, t, t_prev, eta=0.0, noise=None, *, clip_x0=True, seed=None, dynamic_threshold=None,
+                  threshold_max=None):
         """One DDIM update (include/dm3d.h, dm3d_ddim_desc, mode 0): x_t at timestep ``t`` -> x at ``t_prev`` (-1: the x0
         estimate), the DDIM counterpart of sample().  ``t`` / ``t_prev``: one index or one per sample, -1 <= t_prev < t.
-        ``noise`` (optional): z of the step (eta > 0); None draws it from Philox under ``seed`` (None: a fresh key)."""
-        x_t = torch.as_tensor(x_t, dtype=torch.float32).to(self.device).contiguous()
-        eps = torch.as_tensor(pred_noise, dtype=torch.float32).to(self.device).contiguous()
+        ``noise`` (optional): z of the step (eta > 0); None draws it from Philox under ``seed`` (None: a fresh key).
+        ``dynamic_threshold`` / ``threshold_max``: the x0 estimate is thresholded dynamically, as in generate()."""
+        x_t, eps = torch.as_tensor(x_t, dtype=torch.float32), torch.as_tensor(pred_noise, dtype=torch.float32)
         B = x_t.shape[0]
         if eps.shape != x_t.shape or x_t[0].numel() % 4:
             raise ValueError("x_t / pred_noise disagree")
+        thr = self._threshold_rules(B, x_t[0].numel(), clip_x0, dynamic_threshold, threshold_max)    # before any device buffer exists
+        x_t, eps = x_t.to(self.device).contiguous(), eps.to(self.device).contiguous()
         t, tp = _indices(t, B), _indices(t_prev, B)
         if t.min() < 0 or t.max() >= self.timesteps or tp.min() < -1 or np.any(tp >= t):
             raise ValueError("t must lie in [0, timesteps) and t_prev in [-1, t)")
@@ -444,7 +482,9 @@ class DiffusionModel:
         tau = torch.from_numpy(t.astype(np.int32)).to(self.device)
         pos = torch.arange(B, dtype=torch.int32, device=self.device)
         out = torch.empty_like(x_t)
-        d = self._ddim_desc(x_t, eps, coef, tau, pos, 0, noise=noise, out=out, seed=self.fresh_seed() if seed is None else seed)
+        bound = None if thr is None else self._x0_bound(x_t, eps, coef, pos, thr)
+        d = self._ddim_desc(x_t, eps, coef, tau, pos, 0, noise=noise, out=out, seed=self.fresh_seed() if seed is None else seed,
+                            x0_bound=bound)
         check(lib().dm3d_ddim_update(C.byref(d), torch.cuda.current_stream().cuda_stream), "ddim_update")
         return out
 
@@ -455,18 +495,20 @@ class DiffusionModel:
         tab[:, 5] = 1.0 if clip_x0 else 0.0
         return torch.from_numpy(tab.astype(np.float32))
 
-    def _ddim_desc(self, x, eps, coef, tau, pos, mode, noise=None, out=None, t_next=None, t_idx=None, seed=0) -> DdimDesc:
-        d = _fill(DdimDesc(), x=x, eps=eps, noise=noise, out=out, coef=coef, tau=tau, pos=pos, t_next=t_next, t_idx=t_idx)
+    def _ddim_desc(self, x, eps, coef, tau, pos, mode, noise=None, out=None, t_next=None, t_idx=None, seed=0, x0_bound=None) -> DdimDesc:
+        d = _fill(DdimDesc(), x=x, eps=eps, noise=noise, out=out, coef=coef, tau=tau, pos=pos, t_next=t_next, t_idx=t_idx, x0_bound=x0_bound)
         d.batch, d.per_sample, d.rows = x.shape[0], x[0].numel(), coef.shape[0]
         d.seed, d.mode = int(seed) & (2 ** 64 - 1), mode
         return d
 
-    def dpm_step(self, x_t, pred_noise, t, t_prev, x0_prev=None, t_before=None, *, clip_x0=True):
+    def dpm_step(self, x_t, pred_noise, t, t_prev, x0_prev=None, t_before=None, *, clip_x0=True, dynamic_threshold=None,
+                 threshold_max=None):
         """One DPM-Solver++(2M) update (include/dm3d.h, dm3d_dpm_desc, mode 0): x_t at timestep ``t`` -> x at ``t_prev`` (-1: the x0
         estimate), the single-call counterpart of a sampler="dpmpp" chain's step, as ddim_step is of a DDIM chain.  Returns
         (x_next, x0), x0 being this step's (clipped) estimate: the ``x0_prev`` of the next call.  With ``x0_prev`` and ``t_before``
         (the estimate and the timestep of the step before; given together or not at all) the step is second order, else first order
-        (= ddim_step at eta = 0 where the x0 estimate is not clipped).  ``t`` / ``t_prev`` / ``t_before``: one index or one per sample, -1 <= t_prev < t < t_before."""
+        (= ddim_step at eta = 0 where the x0 estimate is not clipped).  ``t`` / ``t_prev`` / ``t_before``: one index or one per sample, -1 <= t_prev < t < t_before.
+        ``dynamic_threshold`` / ``threshold_max``: the x0 estimate (the one returned too) is thresholded dynamically, as in generate()."""
         if (x0_prev is None) != (t_before is None):
             raise ValueError("x0_prev and t_before are given together or not at all")
         x_t = torch.as_tensor(x_t, dtype=torch.float32)
@@ -484,13 +526,15 @@ class DiffusionModel:
             x0_prev = torch.as_tensor(x0_prev, dtype=torch.float32)
             if x0_prev.shape != x_t.shape:
                 raise ValueError("x0_prev must have x_t's shape")
+        thr = self._threshold_rules(B, x_t[0].numel(), clip_x0, dynamic_threshold, threshold_max)
         dev = self.device
         x_t, eps = x_t.to(dev).contiguous(), eps.to(dev).contiguous()
         hist = None if x0_prev is None else x0_prev.to(dev).contiguous()
         coef = self._dpm_table(t, tp, tb, 2, clip_x0).to(dev)
         pos = torch.arange(B, dtype=torch.int32, device=dev)
         out, x0 = torch.empty_like(x_t), torch.empty_like(x_t)
-        d = self._dpm_desc(x_t, eps, hist, coef, pos, 0, out=out, x0_out=x0)
+        bound = None if thr is None else self._x0_bound(x_t, eps, coef, pos, thr)
+        d = self._dpm_desc(x_t, eps, hist, coef, pos, 0, out=out, x0_out=x0, x0_bound=bound)
         check(lib().dm3d_dpm_update(C.byref(d), torch.cuda.current_stream().cuda_stream), "dpm_update")
         return out, x0
 
@@ -502,10 +546,64 @@ class DiffusionModel:
         tab[:, 5] = 1.0 if clip_x0 else 0.0
         return torch.from_numpy(tab.astype(np.float32))
 
-    def _dpm_desc(self, x, eps, hist, coef, pos, mode, out=None, x0_out=None, t_next=None, t_idx=None) -> DpmDesc:
-        d = _fill(DpmDesc(), x=x, eps=eps, hist=hist, out=out, x0_out=x0_out, coef=coef, pos=pos, t_next=t_next, t_idx=t_idx)
+    def _dpm_desc(self, x, eps, hist, coef, pos, mode, out=None, x0_out=None, t_next=None, t_idx=None, x0_bound=None) -> DpmDesc:
+        d = _fill(DpmDesc(), x=x, eps=eps, hist=hist, out=out, x0_out=x0_out, coef=coef, pos=pos, t_next=t_next, t_idx=t_idx, x0_bound=x0_bound)
         d.batch, d.per_sample, d.rows, d.mode = x.shape[0], x[0].numel(), coef.shape[0], mode
         return d
+
+    # -- dynamic thresholding of the x0 estimate ----------------------------------------------------------------------------------
+    @staticmethod
+    def _threshold_rules(B, per_sample, clip_x0, dynamic_threshold, threshold_max, kind=None):
+        """The argument rules of dynamic thresholding, checked before any plan or device buffer is made: None for a call without it,
+        else the host tables (rank, frac, smax) of threshold_tables()."""
+        if dynamic_threshold is None:
+            if threshold_max is not None:
+                raise ValueError("threshold_max needs dynamic_threshold")
+            return None
+        if kind is not None and kind not in ("ddim", "dpmpp"):
+            raise ValueError("dynamic_threshold / threshold_max belong to sampler='ddim' and 'dpmpp'")
+        if not clip_x0:
+            raise ValueError("dynamic_threshold needs clip_x0=True: it replaces the static clamp of the x0 estimate")
+        return threshold_tables(B, per_sample, dynamic_threshold, threshold_max)
+
+    def _thresh_desc(self, x, eps, coef, pos, rank, frac, smax, bound, scratch) -> ThreshDesc:
+        d = _fill(ThreshDesc(), x=x, eps=eps, coef=coef, pos=pos, rank=rank, frac=frac, smax=smax, bound=bound, scratch=scratch)
+        d.batch, d.per_sample, d.rows = x.shape[0], x[0].numel(), coef.shape[0]
+        return d
+
+    def _thresh_scratch(self, B, per_sample) -> torch.Tensor:
+        n = int(lib().dm3d_x0_threshold_scratch_bytes(B, per_sample))
+        return torch.empty((n + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+
+    def _x0_bound(self, x, eps, coef, pos, tables) -> torch.Tensor:
+        """One dm3d_x0_threshold outside a chain: s [B] of x / eps (device, contiguous) under the coefficient rows coef[pos]."""
+        dev, B = self.device, x.shape[0]
+        rank, frac, smax = (torch.from_numpy(t).to(dev) for t in tables)
+        bound = torch.empty(B, dtype=torch.float32, device=dev)
+        d = self._thresh_desc(x, eps, coef, pos, rank, frac, smax, bound, self._thresh_scratch(B, x[0].numel()))
+        check(lib().dm3d_x0_threshold(C.byref(d), torch.cuda.current_stream().cuda_stream), "x0_threshold")
+        return bound
+
+    def x0_threshold(self, x_t, pred_noise, t, dynamic_threshold, threshold_max=None, *, clip_x0=True):
+        """The dynamic threshold of one x0 estimate (include/dm3d.h, dm3d_thresh_desc): s [B] float32, per volume the
+        ``dynamic_threshold`` quantile of |x0| with x0 = (x_t - sqrt(1-a) pred_noise) / sqrt(a) at timestep ``t`` (one index or one
+        per volume), raised to 1 and capped at ``threshold_max``; the single-call counterpart of a thresholded chain's step, as
+        ddim_step is of a DDIM chain.  The quantile is exact (numpy's "linear" interpolation between two order statistics, in
+        float32).  ``clip_x0=False`` describes a step that does not clip: s = 1 and nothing is ranked."""
+        x_t, eps = torch.as_tensor(x_t, dtype=torch.float32), torch.as_tensor(pred_noise, dtype=torch.float32)
+        if x_t.dim() < 2 or eps.shape != x_t.shape or x_t[0].numel() % 4:
+            raise ValueError("x_t / pred_noise must share one shape [B, ...] with a multiple of 4 elements per volume")
+        B = x_t.shape[0]
+        t = _indices(t, B)
+        if t.min() < 0 or t.max() >= self.timesteps:
+            raise ValueError("t must lie in [0, timesteps)")
+        if dynamic_threshold is None:
+            raise ValueError("x0_threshold needs dynamic_threshold")
+        tables = self._threshold_rules(B, x_t[0].numel(), True, dynamic_threshold, threshold_max)    # clip_x0=False is legal here
+        dev = self.device
+        coef = self._ddim_table(t, np.full(B, -1, dtype=np.int64), 0.0, bool(clip_x0)).to(dev)
+        pos = torch.arange(B, dtype=torch.int32, device=dev)
+        return self._x0_bound(x_t.to(dev).contiguous(), eps.to(dev).contiguous(), coef, pos, tables)
 
     def q_sample(self, x0, t, noise=None, *, seed=None):
         """Forward noising (include/dm3d.h, dm3d_edit_desc, mode 0): sqrt(a) x0 + sqrt(1-a) z with a = alpha_bar[t], in the
@@ -643,22 +741,31 @@ class DiffusionModel:
 
     def sampler(self, shape, context_value=None, *, seed=None, use_graph=True, kind="ddpm", num_steps=None, timesteps=None,
                 eta=0.0, clip_x0=True, guidance_scale=None, negative_context=None, guidance_rescale=0.0, solver_order=2,
-                lower_order_final=True) -> "Sampler":
+                lower_order_final=True, dynamic_threshold=None, threshold_max=None) -> "Sampler":
         """The state of one generate() call: plan, tables, context rows and the captured step graph.  There is one live
         Sampler per (batch, context mode): creating another one for the same plan retires the older (its step() raises).
         ``kind="ddim"``: a DDIM chain over ``ddim_timesteps(T, num_steps, timesteps)`` (S steps) with ``eta`` / ``clip_x0``.
         ``kind="dpmpp"``: a DPM-Solver++(2M) chain over the same schedule with ``clip_x0`` / ``solver_order`` / ``lower_order_final``.
-        ``guidance_scale`` / ``negative_context`` / ``guidance_rescale``: a guided chain, as generate()."""
+        ``guidance_scale`` / ``negative_context`` / ``guidance_rescale``: a guided chain, as generate().
+        ``dynamic_threshold`` / ``threshold_max``: a dynamically thresholded DDIM or DPM-Solver++ chain, as generate()."""
         shape = self._sampler_shape(shape)
-        taus, opts = self._solver_rules(kind, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final)
+        taus, opts = self._solver_rules(kind, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final,
+                                        dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape)
         ctx, guide = self._contexts(shape[0], context_value, guidance_scale, negative_context, guidance_rescale)
         return _CHAINS[kind, False, bool(guide)](self, shape, ctx, seed, use_graph, taus, **opts, **guide)
 
-    def _solver_rules(self, kind, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise=None, what="sampler kind"):
+    def _solver_rules(self, kind, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise=None, what="sampler kind",
+                      dynamic_threshold=None, threshold_max=None, shape=None):
         """The argument rules of the three solvers, checked before any plan or device buffer is made.  Returns the chain's schedule
-        (``kind="ddpm"``: every timestep) and the keywords its sampler class takes besides.  ``noise``: the caller's injected z."""
+        (``kind="ddpm"``: every timestep) and the keywords its sampler class takes besides.  ``noise``: the caller's injected z.
+        ``dynamic_threshold`` / ``threshold_max`` (with the chain's ``shape``) add ``threshold=`` (the host tables of
+        threshold_tables()) to those keywords; without them the keywords are what they always were."""
         if kind not in ("ddpm", "ddim", "dpmpp"):
             raise ValueError(f"{what} must be 'ddpm', 'ddim' or 'dpmpp', got {kind!r}")
+        thr = None
+        if dynamic_threshold is not None or threshold_max is not None:
+            thr = self._threshold_rules(shape[0], int(np.prod(shape[1:])), clip_x0, dynamic_threshold, threshold_max, kind)
+        thr = {} if thr is None else dict(threshold=thr)
         if kind != "dpmpp" and (solver_order != 2 or lower_order_final is not True):
             raise ValueError("solver_order / lower_order_final belong to sampler='dpmpp'")
         if kind == "ddpm":
@@ -676,8 +783,8 @@ class DiffusionModel:
         if not eta >= 0:
             raise ValueError("eta must be >= 0")
         if kind == "dpmpp":
-            return taus, dict(clip_x0=clip_x0, solver_order=solver_order, lower_order_final=lower_order_final)
-        return taus, dict(eta=eta, clip_x0=clip_x0)
+            return taus, dict(clip_x0=clip_x0, solver_order=solver_order, lower_order_final=lower_order_final, **thr)
+        return taus, dict(eta=eta, clip_x0=clip_x0, **thr)
 
     def _contexts(self, B, context_value, guidance_scale, negative_context, guidance_rescale):
         """The context and guidance rules, checked before any plan or device buffer is made: (context rows of the chain's plan, the
@@ -697,7 +804,8 @@ class DiffusionModel:
 
     def generate(self, shape=(1, 16, 16, 16, 16), last_step=0, context_value=None, *, x_T=None, noise=None, seed=None,
                  use_graph=True, steps=None, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0, clip_x0=True,
-                 guidance_scale=None, negative_context=None, guidance_rescale=0.0, solver_order=2, lower_order_final=True):
+                 guidance_scale=None, negative_context=None, guidance_rescale=0.0, solver_order=2, lower_order_final=True,
+                 dynamic_threshold=None, threshold_max=None):
         """conditional_dm3d.py:550-575.  For shape[0] > 1 the single context row is broadcast to every sample.
         ``seed`` (optional): Philox key of x_T and of every step's noise; None (default) draws a fresh key per call, as the
         reference draws fresh tf.random.normal noise, an integer makes the call reproducible.
@@ -718,11 +826,19 @@ class DiffusionModel:
         model has no reserved null context) in one pass over a plan of 2 B rows and continues from eps_neg + w (eps_pos - eps_neg);
         ``guidance_rescale`` = phi in [0, 1] then scales it by phi std(eps_pos) / std(eps_g) + (1 - phi) per volume (Lin et al. 2023).
         w and phi take one value or one per volume; w < 0 and w > 1 are legal, w = 1 is the plain chain under context_value.  The
-        chain draws the x_T and the per-step z of the unguided call of the same B volumes and seed."""
+        chain draws the x_T and the per-step z of the unguided call of the same B volumes and seed.
+        ``dynamic_threshold`` = p in (0, 1] (None, the default: the static clamp, today's path), for ``sampler="ddim"`` and
+        ``"dpmpp"`` with ``clip_x0=True``: dynamic thresholding of the x0 estimate (Saharia et al. 2022, "Imagen", section 2.3;
+        include/dm3d.h, dm3d_thresh_desc).  Every step takes s = the exact p-quantile of |x0| over each volume, raised to 1 and
+        capped at ``threshold_max`` (>= 1; None: no cap), and continues from clamp(x0, -s, s) / s instead of clamp(x0, -1, 1): a
+        guided chain at a high scale keeps its contrast instead of saturating at +-1.  p and the cap take one value or one per
+        volume; a guided chain ranks the x0 of the guided eps.  DDIM carries the model's eps on, DPM-Solver++ uses (and remembers)
+        the thresholded estimate."""
         if not 0 <= last_step <= self.timesteps:
             raise ValueError("last_step out of range")
         shape = self._sampler_shape(shape)
-        taus, opts = self._solver_rules(sampler, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise)
+        taus, opts = self._solver_rules(sampler, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise,
+                                        dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape)
         if sampler != "ddpm" and last_step != 0:
             raise ValueError(f"sampler={sampler!r} runs whole chains: last_step must be 0")
         ctx, guide = self._contexts(shape[0], context_value, guidance_scale, negative_context, guidance_rescale)
@@ -763,7 +879,8 @@ class DiffusionModel:
 
     def edit(self, x0, context_value=None, *, mask=None, strength=1.0, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0,
              clip_x0=True, seed=None, use_graph=True, noise=None, known_noise=None, steps=None, guidance_scale=None,
-             negative_context=None, guidance_rescale=0.0, solver_order=2, lower_order_final=True):
+             negative_context=None, guidance_rescale=0.0, solver_order=2, lower_order_final=True, dynamic_threshold=None,
+             threshold_max=None):
         """Inpainting and image-to-image editing (SDEdit) of latents ``x0`` [B, S, S, S, C]; returns latents of x0's shape.
 
         ``mask`` (1 = regenerate, 0 = keep, in [0, 1]; None: regenerate everything) is pooled to the latent by latent_mask() and
@@ -781,10 +898,13 @@ class DiffusionModel:
         the known latent, the blend and every draw are those of the unguided edit.
         ``sampler="dpmpp"`` / ``solver_order`` / ``lower_order_final``: the DPM-Solver++(2M) chain of generate() over the kept
         schedule; its first step (from x_T or from the q_sample start) is first order, the blend runs after every update as for the
-        other samplers, and the solver's history keeps the model's own x0 estimate, unblended.  ``noise`` does not apply."""
+        other samplers, and the solver's history keeps the model's own x0 estimate, unblended.  ``noise`` does not apply.
+        ``dynamic_threshold`` / ``threshold_max``: dynamic thresholding of the chain's x0 estimate over the whole volume, as generate();
+        the blend follows the thresholded update."""
         x0 = torch.as_tensor(x0, dtype=torch.float32)
         shape = self._sampler_shape(x0.shape)
-        sched, opts = self._solver_rules(sampler, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise, what="sampler")
+        sched, opts = self._solver_rules(sampler, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise, what="sampler",
+                                         dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape)
         n = edit_steps(strength, len(sched))
         full, sched = n == len(sched), sched[:n]
         mask = None if mask is None else latent_mask(mask, shape)
@@ -808,10 +928,11 @@ class DiffusionModel:
     MAX_GRAPHS = 8      # captured step graphs kept per model (one per plan); the least recently used one is destroyed
 
     def _capture(self, smp: "Sampler"):
-        """Capture one step of ``smp`` into a HIP graph, cached per (plan, sampler kind): the Philox key lives in a device scalar of
+        """Capture one step of ``smp`` into a HIP graph, cached per (plan, sampler kind; a dynamically thresholded chain's kind is its
+        own, so it and the plain chain of its class never replay each other's graph): the Philox key lives in a device scalar of
         the plan (dm3d_ddpm_desc.seed_dev), a DDIM chain's schedule, eta and clip and a guided chain's scale and rescale in the
         plan's tables, so one graph serves every seed, every DDIM schedule and every guidance scale."""
-        key = (id(smp.plan), smp.KIND)
+        key = (id(smp.plan), smp.graph_kind)
         if key in self._graphs:
             self._graphs[key] = self._graphs.pop(key)                  # most recently used last
             return self._graphs[key][0]
@@ -884,6 +1005,7 @@ class Sampler:
     COPIES = 1                                # rows of the plan per volume of the chain (a guided chain: 2)
     DRAWS = True                              # whether the update takes a z: step(noise=) applies
     edit = None                               # an edit chain: the blend's descriptor
+    threshold = None                          # a dynamically thresholded DDIM / DPM-Solver++ chain: its host tables (rank, frac, smax)
 
     def __init__(self, model: DiffusionModel, shape, ctx_ids, seed, use_graph, taus=None):
         self.model, self.shape, self.use_graph = model, shape, use_graph
@@ -917,8 +1039,18 @@ class Sampler:
         """The chain's latents [B, ...]: a view of the plan's state."""
         return self._head(self.plan.x)
 
+    @property
+    def graph_kind(self):
+        """The step graph's cache key beside the plan: KIND, and a thresholded chain's own (its step holds more launches)."""
+        return self.KIND if self.threshold is None else self.KIND + "+thr"
+
     def _guide(self, st):
         """Between the U-Net and the update: nothing (a guided chain: eps <- the guided eps)."""
+
+    def _threshold(self, st):
+        """Between the guidance and the update: the x0 estimate's dynamic bound, where the chain asks for one."""
+        if self.threshold is not None:
+            check(lib().dm3d_x0_threshold(C.byref(self._thr_desc), st), "x0_threshold")
 
     def _mirror(self, st):
         """After the update and the blend, before the counter's decrement: nothing (a guided chain: the second half follows)."""
@@ -962,6 +1094,7 @@ class Sampler:
         push, pop = _lib.roctx()
         push(self.SOLVER if self.edit is None else self.KIND)
         self._guide(st)
+        self._threshold(st)
         check(self._launch(C.byref(desc), st), self.UPDATE)
         if self.edit is not None:
             check(lib().dm3d_edit_update(C.byref(self.edit if edit is None else edit), st), "edit_update")
@@ -1011,13 +1144,19 @@ class DdimSampler(Sampler):
     It drives the DDPM Sampler's plan (its full T-row time table serves any schedule) and keeps the chain in tables of that
     plan, rewritten by reset(): coefficient rows, the timestep of each row, the next step's timestep and the device row counter.
     Row n-1 is the first step and row 0 the last, so one step is U-Net + dm3d_ddim_update (which also moves t_idx to the next
-    step's timestep) + counter decrement in either direction, and one captured graph serves every schedule, eta and clip."""
+    step's timestep) + counter decrement in either direction, and one captured graph serves every schedule, eta and clip.
+
+    ``threshold`` (the host tables of threshold_tables()) makes the chain, and every chain built on it, a dynamically thresholded one:
+    dm3d_x0_threshold runs before the update, whose descriptor reads the bound it leaves.  Ranks, fractions and caps are tables of
+    the plan, rewritten by reset(): one captured graph (of a kind of its own) serves every ratio and cap."""
 
     KIND = SOLVER = "ddim"
     UPDATE = "ddim_update"
 
-    def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=True, invert=False):
+    def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=True, invert=False, threshold=None):
         self.eta, self.clip_x0, self.invert = float(eta), bool(clip_x0), bool(invert)
+        if threshold is not None:
+            self.threshold = threshold
         super().__init__(model, shape, ctx_ids, seed, use_graph, taus)
         self.n_steps = len(self.taus) - int(self.invert)
 
@@ -1028,12 +1167,25 @@ class DdimSampler(Sampler):
         for name in ("ddim_tau", "ddim_next"):
             _plan_buffer(plan, name, lambda: torch.zeros(T, dtype=torch.int32, device=dev))
         _plan_buffer(plan, "ddim_pos", lambda: torch.zeros(plan.B, dtype=torch.int32, device=dev))
+        if self.threshold is not None and getattr(self, "_thr_desc", None) is None:
+            # sized for the plan's rows (a guided chain uses the first half, as of every buffer)
+            _plan_buffer(plan, "thr_rank", lambda: torch.zeros(plan.B, dtype=torch.int32, device=dev))
+            for name in ("thr_frac", "thr_smax", "thr_bound"):
+                _plan_buffer(plan, name, lambda: torch.ones(plan.B, dtype=torch.float32, device=dev))
+            _plan_buffer(plan, "thr_scratch", lambda: self.model._thresh_scratch(plan.B, plan.x[0].numel()))
+            h = self._head
+            self._thr_desc = self.model._thresh_desc(self.x, h(plan.eps), getattr(plan, coef), h(plan.ddim_pos), h(plan.thr_rank),
+                                                     h(plan.thr_frac), h(plan.thr_smax), h(plan.thr_bound), plan.thr_scratch)
         return plan
+
+    def _bound(self):
+        """The update descriptor's x0_bound: the plan's bound buffer in a thresholded chain, else nothing (the static clamp)."""
+        return None if self.threshold is None else self._head(self.plan.thr_bound)
 
     def _desc(self, noise=None):
         plan = self._tables("ddim_coef")
         d = self.model._ddim_desc(self.x, self._head(plan.eps), plan.ddim_coef, plan.ddim_tau, plan.ddim_pos, 1, noise=noise,
-                                  t_next=plan.ddim_next, t_idx=plan.t_idx, seed=self.seed)
+                                  t_next=plan.ddim_next, t_idx=plan.t_idx, seed=self.seed, x0_bound=self._bound())
         d.seed_dev = plan.seed_buf.data_ptr()
         return d
 
@@ -1068,6 +1220,9 @@ class DdimSampler(Sampler):
             plan.ddim_next[:n].copy_(torch.from_numpy(np.maximum(dst, 0).astype(np.int32)))
             plan.ddim_pos.fill_(n - 1)
             plan.t_idx.fill_(int(src[n - 1]))
+        if self.threshold is not None:
+            for buf, table in zip((plan.thr_rank, plan.thr_frac, plan.thr_smax), self.threshold):
+                self._head(buf).copy_(torch.from_numpy(table))
 
 
 class DpmSampler(DdimSampler):
@@ -1082,17 +1237,17 @@ class DpmSampler(DdimSampler):
     UPDATE = "dpm_update"
     DRAWS = False
 
-    def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, clip_x0=True, solver_order=2, lower_order_final=True):
+    def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, clip_x0=True, solver_order=2, lower_order_final=True, threshold=None):
         if solver_order not in (1, 2):
             raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
         self.solver_order, self.lower_order_final = int(solver_order), bool(lower_order_final)
-        super().__init__(model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=clip_x0)
+        super().__init__(model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=clip_x0, threshold=threshold)
 
     def _desc(self, noise=None):
         plan = self._tables("dpm_coef")
         _plan_buffer(plan, "dpm_hist", lambda: torch.zeros_like(plan.x))
         return self.model._dpm_desc(self.x, self._head(plan.eps), self._head(plan.dpm_hist), plan.dpm_coef, plan.ddim_pos, 1,
-                                    t_next=plan.ddim_next, t_idx=plan.t_idx)
+                                    t_next=plan.ddim_next, t_idx=plan.t_idx, x0_bound=self._bound())
 
     def _prev(self):
         """The level the step before row r started from (row n-1 runs first), -1 where the row is first order: the chain's first

@@ -69,7 +69,7 @@ def generate_sharded(model, global_shape, last_step: int = 0, context_value=None
     of the GLOBAL batch (each rank takes its slice).  ``gather=True``: one all_gather at the end, every rank returns the whole
     ``global_shape`` tensor in rank order; otherwise the local shard ([hi-lo, ...]; may be empty).  The classifier-free guidance
     keywords of generate() are forwarded; ``guidance_scale`` / ``guidance_rescale`` / ``negative_context`` given per volume of the
-    global batch are sliced per rank as ``context_value`` is."""
+    global batch are sliced per rank as ``context_value`` is; so are ``dynamic_threshold`` / ``threshold_max``."""
     shape = tuple(int(s) for s in global_shape)
     dist_on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
@@ -87,7 +87,7 @@ def generate_sharded(model, global_shape, last_step: int = 0, context_value=None
         return v
 
     ctx = shard("context_value", context_value)
-    for name in ("guidance_scale", "negative_context", "guidance_rescale"):
+    for name in ("guidance_scale", "negative_context", "guidance_rescale", "dynamic_threshold", "threshold_max"):
         if name in generate_kw:
             generate_kw[name] = shard(name, generate_kw[name])
     dev = getattr(model, "device", torch.device("cpu"))

@@ -26,7 +26,7 @@ extern "C" {
                                      training entries), 107 (conv wpk_f8: a float8 cross-term form, removed again in 109), 108 (conv wpk_wino: the Winograd-x form), 109 (wpk_f8 and
                                      dm3d_pack_weights_h3f8 are gone; the Winograd-x image pairs its taps differently; dm3d_mlp_fused; conv skip_wpk_frag, gn_stats; dm3d_groupnorm_finalize2), 110 (dm3d_attn_front), 111 (conv split_counters: the Cin split
                                      meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc, dm3d_edit_update / dm3d_edit_desc,
-                                     dm3d_guide_update / dm3d_guide_desc and dm3d_dpm_update / dm3d_dpm_desc were added within 111 (no existing struct or entry changed): a host built against an older header must be rebuilt */
+                                     dm3d_guide_update / dm3d_guide_desc, dm3d_dpm_update / dm3d_dpm_desc and dm3d_x0_threshold / dm3d_thresh_desc were added within 111 (no existing entry changed; dm3d_ddim_desc and dm3d_dpm_desc grew by one trailing optional pointer, x0_bound, which a zeroed descriptor leaves NULL): a host built against an older header must be rebuilt */
 
 #define DM3D_OK            0
 #define DM3D_EINVAL       -1      /* bad argument (shape, alignment, null pointer) */
@@ -442,6 +442,9 @@ typedef struct dm3d_ddim_desc {
     uint64_t seed;
     const uint64_t* seed_dev;   /* optional: the Philox key is read from device memory instead of `seed` (as dm3d_ddpm_desc) */
     int32_t mode;
+    const float* x0_bound;      /* optional [batch] device: the dynamic threshold s of dm3d_x0_threshold.  Where the row clips, x0 is
+                                   clamp(x0, -s, s) / s (one correctly rounded division; a NaN passes) instead of clamp(x0, -1, 1);
+                                   s == 1 is the static clamp bitwise.  NULL (a zeroed descriptor): the static clamp. */
 } dm3d_ddim_desc;
 
 int dm3d_ddim_update(const dm3d_ddim_desc* d, void* stream);
@@ -477,9 +480,46 @@ typedef struct dm3d_dpm_desc {
     const int32_t* t_next;      /* [rows] device, optional: the timestep the step after row r evaluates */
     int32_t* t_idx;             /* [batch] device, optional: receives t_next[pos[b]] */
     int32_t mode;
+    const float* x0_bound;      /* optional [batch] device: the dynamic threshold s, as dm3d_ddim_desc.x0_bound; the thresholded
+                                   estimate is what the update uses and what hist / x0_out receive.  NULL: the static clamp. */
 } dm3d_dpm_desc;
 
 int dm3d_dpm_update(const dm3d_dpm_desc* d, void* stream);
+
+/* ---- Dynamic thresholding of the x0 estimate (Saharia et al. 2022, "Imagen", section 2.3) ------------------------------------------
+ * Between the U-Net (or the guidance) and dm3d_ddim_update / dm3d_dpm_update: the bound s the update clamps and divides the x0
+ * estimate by, per sample b, from the exact p-quantile of its magnitudes.  With row r = clamp(pos[b], 0, rows-1) of either solver's
+ * coefficient table (only columns 0, 1 and 5 are read) and N = per_sample:
+ *   x0    = (x - sqrt(1-a)*eps) / sqrt(a)             float32, the update kernels' own device function (mul, sub, div, each rounded)
+ *   v_0 <= v_1 <= ... <= v_{N-1}                      the sorted |x0_e|; a NaN sorts last (its bit pattern is above +inf's)
+ *   i     = rank[b], f = frac[b]                      the host's q = p*(N-1) in float64, i = floor(q), f = float32(q - i); i is clamped
+ *                                                     to [0, N-1], and at i = N-1 v_{i+1} stands for v_i (f is 0 there)
+ *   s_raw = v_i + f*(v_{i+1} - v_i)                   float32: sub, mul, add, each rounded
+ *   s     = s_raw is NaN ? s_raw : min(max(s_raw, 1), smax[b])
+ *   bound[b] = s                                      rows with clip == 0 (column 5): bound[b] = 1, no selection work
+ * The update then computes x0 = x0 is NaN ? x0 : clamp(x0, -s, s) / s through its x0_bound field.  Fewer than N-1-i NaNs in a sample
+ * reach only their own elements; more make s NaN and with it every element of the sample.
+ * v_i and v_{i+1} are exact: an MSB-first radix select over the 31 magnitude bits in three counting passes (12, 10 and 9 bits) that
+ * carry both ranks.  The counts are integers summed with atomics, whose result does not depend on the order of arrival, and nothing
+ * else is shared between blocks: runs repeat bitwise.  Graph-capturable without host reads: rank, frac and smax are device tables (one
+ * captured graph serves every ratio and cap), and every launch clears its own counters (a kernel) before it counts.
+ * scratch: dm3d_x0_threshold_scratch_bytes(batch, per_sample) bytes, 16-byte aligned; contents need not survive between launches. */
+typedef struct dm3d_thresh_desc {
+    const float* x;             /* [batch, per_sample] x at the row's level */
+    const float* eps;           /* predicted noise (a guided chain: the guided one) */
+    int32_t batch; int64_t per_sample;     /* batch <= 65535, per_sample % 4 == 0, per_sample < 2^31 */
+    const float* coef;          /* [rows][8] device: either update descriptor's table: sqrt(a), sqrt(1-a), ..., clip in column 5 */
+    int32_t rows;               /* pos[b] is clamped to [0, rows) before the table is indexed */
+    const int32_t* pos;         /* [batch] device: the row of each sample */
+    const int32_t* rank;        /* [batch] device: i */
+    const float* frac;          /* [batch] device: f in [0, 1) */
+    const float* smax;          /* [batch] device: the cap on s, >= 1 */
+    float* bound;               /* [batch] device, out: s */
+    void* scratch;              /* device: histograms, select states and the stashed magnitudes */
+} dm3d_thresh_desc;
+
+int64_t dm3d_x0_threshold_scratch_bytes(int32_t batch, int64_t per_sample);
+int dm3d_x0_threshold(const dm3d_thresh_desc* d, void* stream);
 
 /* ---- Known-latent step of inpainting / image-to-image editing (RePaint's replacement step, SDEdit's start) -------------
  * Row r = clamp(pos[b], 0, rows-1) of the level table gives a target level a' (alpha_bar of a timestep, 1 for "clean"):
