@@ -237,6 +237,7 @@ SIGNATURES = {
     "dm3d_q_sample": (C.c_int, [_f32p, _f32p, _i32p, _f32p, _f32p, C.c_int32, _f32p, C.c_int32, C.c_int64, C.c_void_p]),
     "dm3d_mse_loss_grad": (C.c_int, [_f32p, _f32p, C.c_int64, C.c_double, C.c_void_p, _f32p, C.c_void_p]),
     "dm3d_adam": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "dm3d_adam_ema": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "dm3d_graph_begin": (C.c_int, [C.c_void_p]),
     "dm3d_graph_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "dm3d_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p]),

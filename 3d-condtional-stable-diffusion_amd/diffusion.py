@@ -6,7 +6,9 @@ Keyword-only extensions: ``x_T=`` / ``noise=`` inject the ran
 selects the in-kernel Philox stream, ``use_graph=`` toggles HIP-graph replay of the step; ``guidance_scale=`` /
 ``negative_context=`` / ``guidance_rescale=`` turn on classifier-free guidance (include/dm3d.h, dm3d_guide_desc);
 ``dynamic_threshold=`` / ``threshold_max=`` replace the static clamp of the x0 estimate by Imagen's dynamic thresholding in the DDIM
-and DPM-Solver++ chains (include/dm3d.h, dm3d_thresh_desc).
+and DPM-Solver++ chains (include/dm3d.h, dm3d_thresh_desc).  Training extensions, off by default: ``compile(ema_decay=)`` keeps an
+exponential moving average of the weights in the optimizer's launch (include/dm3d.h, dm3d_adam_ema) and ``use_ema()`` samples from it;
+``compile(context_dropout=, null_context=)`` trains the unconditional branch that classifier-free guidance is defined against.
 
 The sampling loop (:559-573) runs with no host synchronisation: the step index lives in device memory, one step
 (U-Net forward + posterior update + index decrement) is captured once into a HIP graph and replayed T times.
@@ -167,6 +169,22 @@ def latent_mask(mask, latent_shape) -> torch.Tensor:
     return m.expand(B, D, H, W).contiguous()
 
 
+def context_dropout(ids, p, null_context, *, seed=None, drop=None) -> np.ndarray:
+    """The context ids a train step runs on (int32 [B]): ``ids`` with each entry replaced by ``null_context`` where ``drop`` (bool
+    [B]) says so; ``drop`` None draws it, one uniform per sample from numpy's default_rng(``seed``), dropped where it is < ``p``
+    (p = 0: never, p = 1: always)."""
+    ids = np.array(ids, dtype=np.int32).reshape(-1)
+    if drop is None:
+        if not 0 <= float(p) <= 1:                            # a NaN fails the comparison too
+            raise ValueError(f"context_dropout must lie in [0, 1], got {p}")
+        drop = np.random.default_rng(seed).random(ids.size) < float(p)
+    drop = np.asarray(drop.detach().cpu() if torch.is_tensor(drop) else drop)
+    if drop.dtype != np.bool_ or drop.reshape(-1).size != ids.size:
+        raise ValueError(f"drop must hold one bool per sample ({ids.size})")
+    ids[drop.reshape(-1)] = int(null_context)
+    return ids
+
+
 def _indices(v, B: int) -> np.ndarray:
     """One timestep index, or one per sample, as int64 [B] on the host."""
     return np.broadcast_to(np.asarray(torch.as_tensor(v).reshape(-1).cpu(), dtype=np.int64), (B,))
@@ -209,7 +227,7 @@ class DiffusionModel:
     conditional = True
 
     def __init__(self, latent_size, num_embed, latent_channels, vqvae_load_ckpt, args, *, device="cuda", weights=None,
-                 seed=0, precision=None, norm="batch"):
+                 seed=0, precision=None, norm="batch", context_dim=1):
         # conditional_dm3d.py:420-469.  ``args`` is any object with .timesteps .num_gpus .kernel_resize .bs
         self.timesteps = int(args.timesteps)
         self.b = Betas(self.timesteps)
@@ -223,7 +241,8 @@ class DiffusionModel:
         self._precision = precision
         self.network = UNet(
             UNetConfig(img_size=latent_size, img_channels=latent_channels, widths=[64, 128, 256],
-                       has_attention=[False, False, True, True], conditional=self.conditional, norm=norm),
+                       has_attention=[False, False, True, True], conditional=self.conditional, norm=norm,
+                       context_dim=context_dim),
             device=device, weights=weights, seed=seed, precision=precision)
         self.loss_tracker = _LossTracker("loss")
         self.num_gpus = getattr(args, "num_gpus", 1)
@@ -234,6 +253,13 @@ class DiffusionModel:
         self._trainer = None
         self._trainer_dirty = False
         self._pending_optimizer = None          # Adam slots of a loaded checkpoint, applied when the Trainer is first built
+        self._pending_ema = None                # its ema/ entries: they wait on the host likewise (use_ema() samples from them as they are)
+        self._ema_decay, self._ema_warmup = None, True
+        self.context_dropout, self.null_context = 0.0, None
+        self._use_ema = False                   # which weights the sampling network runs on (use_ema())
+        self._network_stale = False             # use_ema() changed: the network still holds the other set
+        self._live_host = None                  # the live weights while the network holds the averaged ones and no Trainer exists
+        self._warned_tf_ema = False
         self.network._before_use = self._sync_from_trainer
         self.network._training_engine = self._engine_for_training_forward
 
@@ -277,12 +303,73 @@ class DiffusionModel:
     def metrics(self):
         return [self.loss_tracker]
 
-    def compile(self, loss=None, optimizer=None):
+    def compile(self, loss=None, optimizer=None, *, ema_decay=None, ema_warmup=True, context_dropout=0.0, null_context=None):
+        """keras ``model.compile``.  Keyword-only extensions, read again by every train_step like the learning rate (so a later compile()
+        takes effect between steps):
+        ``ema_decay`` in [0, 1) (None: off) keeps an exponential moving average of the trainable weights, updated in the optimizer's
+        launch; ``ema_warmup`` holds the decay under (1 + n) / (10 + n) at update n (train.py, ema_decay_at).  use_ema() samples from it.
+        ``null_context``: an id in [0, context_dim] reserved for "no context" (give the constructor ``context_dim`` one more than
+        the classes to have a spare embedding row); guidance then defaults ``negative_context`` to it.  ``context_dropout`` in [0, 1]:
+        train_step replaces each sample's id by ``null_context`` with this probability, which trains the unconditional branch
+        classifier-free guidance is defined against."""
+        from .train import _check_ema_decay
+        if ema_decay is not None:
+            ema_decay = _check_ema_decay(ema_decay)
+        context_dropout = float(context_dropout)
+        if not 0 <= context_dropout <= 1:
+            raise ValueError(f"context_dropout must lie in [0, 1], got {context_dropout}")
+        if (null_context is not None or context_dropout > 0) and not self.conditional:
+            raise ValueError("context_dropout / null_context need the conditional model: there is no context to drop")
+        if null_context is not None:
+            if int(null_context) != null_context or not 0 <= int(null_context) <= self.network.cfg.context_dim:
+                raise ValueError(f"null_context must be an id in [0, {self.network.cfg.context_dim}], got {null_context!r}")
+            null_context = int(null_context)
+        if context_dropout > 0 and null_context is None:
+            raise ValueError("context_dropout needs null_context: the id the dropped samples are trained under")
         self.loss, self.optimizer = loss, optimizer
+        self._ema_decay, self._ema_warmup = ema_decay, bool(ema_warmup)
+        self.context_dropout, self.null_context = context_dropout, null_context
+
+    # -- which weights the sampling network runs on -------------------------------------------------------------------------
+    def _has_ema(self) -> bool:
+        return (self._trainer is not None and self._trainer.ema is not None) or self._pending_ema is not None
+
+    def use_ema(self, flag) -> bool:
+        """Chooses the weights the SAMPLING network runs on (generate, edit, invert, network(...)): the exponential moving average
+        (True) or the live Adam iterate (False, the default).  Returns the previous setting.  train_step and
+        network(..., training=True) always use the live weights, and save_weights() writes them whatever this says.  A change marks
+        the network stale: the other set is loaded before its next use, and the captured graphs are dropped."""
+        flag, prev = bool(flag), self._use_ema
+        if flag and not self._has_ema():
+            raise ValueError("use_ema(True): the model has no averaged weights (train with compile(ema_decay=...) or load a "
+                             "checkpoint that carries ema/ entries)")
+        if flag != prev:
+            self._use_ema, self._network_stale = flag, True
+        return prev
+
+    def _live_state(self):
+        """The live weights by name (host): the Trainer's, else the copy set aside while the network holds the averaged ones, else the network's."""
+        if self._trainer is not None:
+            return self._trainer.state_dict()
+        return dict(self._live_host if self._live_host is not None else self.network.state)
+
+    def _ema_weights(self, live):
+        """The averaged model by name (host): ``live`` with every trainable entry replaced by its average."""
+        if self._trainer is not None and self._trainer.ema is not None:
+            return self._trainer.ema_state_dict()
+        return {**live, **{k[len("ema/"):]: v for k, v in self._pending_ema.items() if k != "ema/num_updates"}}
+
+    def _ema_entries(self):
+        """The ``ema/...`` checkpoint entries of the model, {} without an average."""
+        if self._trainer is not None and self._trainer.ema is not None:
+            return self._trainer.ema_state()
+        return dict(self._pending_ema or {})
 
     def load_state_dict(self, sd, strict=True):
         """Weights by name; ``optimizer/...`` entries (save_weights of a trained model) restore the Adam slots and step count, so a
-        resumed run continues the bias correction where it stopped; without them the optimizer starts afresh."""
+        resumed run continues the bias correction where it stopped; without them the optimizer starts afresh.  ``ema/...`` entries restore
+        the weight average likewise (complete and of the weights' shapes, or the load fails); a checkpoint without them leaves the
+        model without an average, and use_ema() back at False."""
         # validated BEFORE anything is touched: a checkpoint with partial slots fails here with the model as it was (new weights with the
         # old Adam state gone would be a half-loaded model)
         opt = {k: v for k, v in sd.items() if k.startswith("optimizer/")}
@@ -291,12 +378,32 @@ class DiffusionModel:
             if missing:
                 raise ValueError(f"checkpoint carries optimizer state but {len(missing)} entries are missing (first: {missing[:3]}); "
                                  "drop every optimizer/ entry to load the weights alone")
-        self._sync_from_trainer()                                  # a non-strict load fills missing names from the CURRENT (trained) weights
-        self.network.load_state_dict({k: v for k, v in sd.items() if not k.startswith("optimizer/")}, strict)
+        ema = {k: v for k, v in sd.items() if k.startswith("ema/")}
+        if ema:
+            want = {"ema/num_updates": ()}
+            want.update({f"ema/{n}": tuple(self.network.spec[n]) for n in self._trainable_names()})
+            missing = [k for k in want if k not in ema]
+            extra = [k for k in ema if k not in want]
+            wrong = [k for k in want if k in ema and k != "ema/num_updates" and tuple(np.shape(ema[k])) != want[k]]
+            if missing or extra or wrong:
+                raise ValueError(f"checkpoint carries averaged weights but {len(missing)} entries are missing (first: {missing[:3]}), "
+                                 f"{len(extra)} are unknown (first: {extra[:3]}) and {len(wrong)} have another shape (first: {wrong[:3]}); "
+                                 "drop every ema/ entry to load the weights alone")
+        if self._use_ema or self._live_host is not None:           # the network may hold the averaged weights
+            live = self._live_state()
+            self._network_stale = True
+            self.network.load_state_dict(live)
+        else:
+            self._sync_from_trainer()                              # a non-strict load fills missing names from the CURRENT (trained) weights
+        self.network.load_state_dict({k: v for k, v in sd.items() if not k.startswith(("optimizer/", "ema/"))}, strict)
         self._drop_graphs()
         self._trainer, self._trainer_dirty = None, False          # Adam moments belong to the weights they were built for
         # the slots wait until a Trainer exists (an inference-only load builds none: theta, gradients and moments are four copies of the weights)
         self._pending_optimizer = opt or None
+        self._pending_ema = {k: np.array(v, dtype=np.int64 if k == "ema/num_updates" else np.float32) for k, v in ema.items()} or None
+        self._live_host = None
+        self._use_ema = self._use_ema and bool(ema)
+        self._network_stale = self._use_ema                        # the network now holds the live weights
 
     def _trainable_names(self):
         """Names of the parameters Adam updates (everything but the BatchNormalization moving statistics)."""
@@ -319,15 +426,37 @@ class DiffusionModel:
         if any(k.startswith("vqvae_trainer/") for k in rd.entries):
             self.vqvae_trainer.load_weights(path, root=("vqvae_trainer",))
 
-    def save_weights(self, path, root=("network",)):
-        self._sync_from_trainer()
-        # the Adam slots and step count travel with the weights, as in the reference's save_weights_only TF checkpoints of a compiled model
-        opt = self._trainer.optimizer_state() if self._trainer is not None and self._trainer.step_count > 0 else (getattr(self, "_pending_optimizer", None) or {})
-        if str(path).endswith(".npz"):
-            np.savez(path, **self.network.state_dict(), **opt)
+    def save_weights(self, path, root=("network",), weights="live"):
+        """Writes the LIVE weights under the ordinary names, whatever use_ema() says, with the Adam slots; an .npz file also carries
+        the weight average as ``ema/...`` entries.  The TF-format writer holds no second copy of the weights (a warning says so once).
+        ``weights="ema"`` exports the averaged model under the ordinary names instead, without optimizer or ema/ entries, in either
+        format: how an averaged model reaches a reference-format TF checkpoint."""
+        if weights not in ("live", "ema"):
+            raise ValueError(f"weights must be 'live' or 'ema', got {weights!r}")
+        if weights == "ema" and not self._has_ema():
+            raise ValueError("save_weights(weights='ema'): the model has no averaged weights")
+        npz = str(path).endswith(".npz")
+        if weights == "ema":
+            state, opt, ema = self._ema_weights(self._live_state()), {}, {}
+        else:
+            if self._use_ema or self._live_host is not None or self._network_stale:
+                state = self._live_state()
+            else:
+                self._sync_from_trainer()
+                state = self.network.state_dict()
+            # the Adam slots and step count travel with the weights, as in the reference's save_weights_only TF checkpoints of a compiled model
+            opt = self._trainer.optimizer_state() if self._trainer is not None and self._trainer.step_count > 0 else (getattr(self, "_pending_optimizer", None) or {})
+            ema = self._ema_entries()
+        if npz:
+            np.savez(path, **state, **opt, **ema)
             return
+        if ema and not self._warned_tf_ema:
+            import warnings
+            self._warned_tf_ema = True
+            warnings.warn("the TF-format checkpoint holds the live weights only: the weight average is not in this file "
+                          "(save an .npz beside it, or export the averaged model with weights='ema')")
         from . import tf_checkpoint as tc
-        tc.save_unet_checkpoint(str(path), self.network.state_dict(), self.network.cfg, root=tuple(root), optimizer=opt or None)
+        tc.save_unet_checkpoint(str(path), state, self.network.cfg, root=tuple(root), optimizer=opt or None)
 
     def _drop_graphs(self):
         for g in self._graphs.values():
@@ -357,33 +486,71 @@ class DiffusionModel:
         """The training engine (train.py), built on first use from the network's current weights."""
         if self._trainer is None:
             from .train import Trainer
-            self._trainer = Trainer(self.network.cfg, self.network.state_dict(), self.device, lr=self._learning_rate())
+            if self._use_ema or self._live_host is not None or self._network_stale:
+                live = self._live_state()
+            else:
+                live = self.network.state_dict()
+            self._trainer = Trainer(self.network.cfg, live, self.device, lr=self._learning_rate())
+            self._live_host = None
             if getattr(self, "_pending_optimizer", None):
                 self._trainer.load_optimizer_state(self._pending_optimizer)
                 self._pending_optimizer = None
+            self._configure_ema(self._trainer)
         return self._trainer
+
+    def _configure_ema(self, tr):
+        """compile()'s ema_decay / ema_warmup reach the Trainer (re-read like the learning rate); a loaded average continues there."""
+        if self._ema_decay is None:
+            if tr.ema is not None:
+                if self._use_ema:
+                    raise ValueError("compile(ema_decay=None) would drop the averaged weights the sampling network runs on: use_ema(False) first")
+                tr.set_ema(None)
+            return
+        tr.set_ema(self._ema_decay, self._ema_warmup)
+        if self._pending_ema is not None:
+            tr.load_ema_state(self._pending_ema)
+            self._pending_ema = None
 
     def _engine_for_training_forward(self):
         """``network(..., training=True)`` outside train_step runs on the model's own Trainer when it has one, so the moving statistics it
         updates are the ones the next train_step continues from (in Keras both are the same variables)."""
-        if self._trainer is None:
+        if self._trainer is None and not self._use_ema:
             return None
+        tr = self.trainer                          # (under use_ema(True) the network holds the averaged weights: the live ones need a Trainer)
         self._trainer_dirty = True
-        return self._trainer
+        return tr
 
     def _sync_from_trainer(self):
-        """Weights changed by train_step flow back into the sampling network (folded norms, packed images, tables) before it runs."""
-        if self._trainer is not None and self._trainer_dirty:
-            self._trainer_dirty = False
-            self.network.load_state_dict(self._trainer.state_dict())
-            self._drop_graphs()
+        """Weights changed by train_step flow back into the sampling network (folded norms, packed images, tables) before it runs:
+        the live ones, or under use_ema(True) the averaged ones."""
+        if not (self._network_stale or (self._trainer is not None and self._trainer_dirty)):
+            return
+        tr = self._trainer
+        if self._use_ema and tr is not None and tr.ema is not None:
+            state = tr.ema_state_dict()
+        else:
+            live = self._live_state()
+            if self._use_ema and tr is None and self._live_host is None:
+                self._live_host = live                     # the network is about to hold the averaged weights: the live ones wait here
+            state = self._ema_weights(live) if self._use_ema else live
+        if not self._use_ema:
+            self._live_host = None
+        self._trainer_dirty = self._network_stale = False
+        self.network.load_state_dict(state)
+        self._drop_graphs()
 
-    def train_step(self, inputs, *, t=None, noise=None, latents=None):
+    def train_step(self, inputs, *, t=None, noise=None, latents=None, **extensions):
         """conditional_dm3d.py:471-510: ``inputs = (images, mask, context)`` ((images, _) for the unconditional model, dm3d.py:431-433).
         images [b, 16S, 16S, 16S, 1] go through the frozen encoder + quantizer (:478); t ~ U{0..T-1} (:474-476), noise ~ N(0,1) (:481),
         q_sample (:484-490), the network with training=True (:493), loss = MSE_SUM / (global_bs * lc^4) (:496-499), Adam (:501-504),
         loss tracker (:507-510).  Keyword-only extensions: ``t`` / ``noise`` inject the random draws (parity tests), ``latents`` skips the
-        autoencoder (pre-encoded latents [b, S, S, S, lc])."""
+        autoencoder (pre-encoded latents [b, S, S, S, lc]).  Under compile(context_dropout=p, null_context=k) each sample's context id
+        becomes k with probability p, drawn on the host next to t; ``drop`` (bool [b]) injects that draw.  Under compile(ema_decay=)
+        the optimizer's launch also advances the weight average.  The step runs on the live weights whatever use_ema() says.
+        (``drop`` is the one name ``**extensions`` takes, by keyword only: the signature's named keywords stay t, noise and latents.)"""
+        drop = extensions.pop("drop", None)
+        if extensions:
+            raise TypeError(f"train_step() got an unexpected keyword argument {next(iter(extensions))!r}")
         if self.conditional:
             images, _, context = inputs
         else:
@@ -416,8 +583,16 @@ class DiffusionModel:
         ids = None
         if self.conditional:
             ids = self._context_ids(context, B)
+            if drop is not None or self.context_dropout > 0:
+                if self.null_context is None:
+                    raise ValueError("drop= needs compile(null_context=...): the id the dropped samples are trained under")
+                ids = context_dropout(np.broadcast_to(ids, (B,)), self.context_dropout, self.null_context,
+                                      seed=self.fresh_seed() if drop is None else None, drop=drop)
+        elif drop is not None:
+            raise ValueError("drop= needs the conditional model: there is no context to drop")
         tr = self.trainer
         tr.lr = self._learning_rate()               # re-read every step: compile() / optimizer.learning_rate may have changed
+        self._configure_ema(tr)
         tab = self.b.device_tables(dev)
         betas = (tab[BETAS_FIELDS.index("sqrt_alpha_bar")], tab[BETAS_FIELDS.index("sqrt_one_minus_alpha_bar")])
         loss, _ = tr.loss_and_grad(latents, t, noise, ids, betas, T, self.global_bs, self.lc)
@@ -687,7 +862,9 @@ class DiffusionModel:
         if not self.conditional:
             raise ValueError("classifier-free guidance needs the conditional model: there is no context to guide with")
         if negative_context is None:
-            raise ValueError("guidance_scale needs negative_context (the model has no reserved null context)")
+            if self.null_context is None:
+                raise ValueError("guidance_scale needs negative_context (the model has no reserved null context)")
+            negative_context = self.null_context        # compile(null_context=...): the unconditional branch context dropout trains
         w, phi = self._guide_tables(B, guidance_scale, 0.0 if guidance_rescale is None else guidance_rescale)
         neg = self._context_ids(negative_context, B)
         return w, phi, np.ascontiguousarray(np.broadcast_to(neg, (B,)))
@@ -822,8 +999,8 @@ class DiffusionModel:
         eta = 0 wherever the x0 estimate is not clipped (where it is, DDIM carries the model's eps on, this solver the eps the
         clipped estimate implies).  eta must be 0, last_step 0, and ``noise`` does not apply (the chain draws none; ``x_T`` / ``seed`` set the start).
         ``guidance_scale`` = w (None, the default: no guidance, today's path): classifier-free guidance, for either sampler.  Every
-        step evaluates the U-Net under ``context_value`` and under ``negative_context`` (one id or one per volume, always given: the
-        model has no reserved null context) in one pass over a plan of 2 B rows and continues from eps_neg + w (eps_pos - eps_neg);
+        step evaluates the U-Net under ``context_value`` and under ``negative_context`` (one id or one per volume; None stands for
+        compile()'s ``null_context`` and is an error on a model without one) in one pass over a plan of 2 B rows and continues from eps_neg + w (eps_pos - eps_neg);
         ``guidance_rescale`` = phi in [0, 1] then scales it by phi std(eps_pos) / std(eps_g) + (1 - phi) per volume (Lin et al. 2023).
         w and phi take one value or one per volume; w < 0 and w > 1 are legal, w = 1 is the plain chain under context_value.  The
         chain draws the x_T and the per-step z of the unguided call of the same B volumes and seed.

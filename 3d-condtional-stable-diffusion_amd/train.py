@@ -36,6 +36,20 @@ def is_trainable(name: str) -> bool:
     return not name.endswith((".mean", ".var"))
 
 
+def ema_decay_at(decay: float, n: int, warmup: bool = True) -> float:
+    """The decay of the weight average's update number ``n`` (counted from 0), in float64: ``decay``, held under (1 + n) / (10 + n)
+    while ``warmup`` (0.1, 2/11, ... : an average started from the initial weights forgets them within a few steps)."""
+    decay, n = float(decay), int(n)
+    return min(decay, (1.0 + n) / (10.0 + n)) if warmup else decay
+
+
+def _check_ema_decay(decay) -> float:
+    decay = float(decay)
+    if not 0.0 <= decay < 1.0:                            # (a NaN fails the comparison too)
+        raise ValueError(f"ema_decay must lie in [0, 1), got {decay}")
+    return decay
+
+
 class Param:
     """A view of the flat parameter / gradient buffers."""
 
@@ -86,8 +100,10 @@ class Trainer:
     """Owns the trainable state of one U-Net and runs train steps on it."""
 
     def __init__(self, cfg: UNetConfig, state: Dict[str, np.ndarray], device, lr: float = 1e-4, bn_moving_unbiased: bool = True,
-                 forward_only: bool = False):
-        """``forward_only``: no gradient / Adam buffers (a quarter of the memory) — for ``network(..., training=True)`` outside train_step."""
+                 forward_only: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = True):
+        """``forward_only``: no gradient / Adam buffers (a quarter of the memory) — for ``network(..., training=True)`` outside train_step.
+        ``ema_decay`` / ``ema_warmup``: keep an exponential moving average of the trainable weights, as set_ema() (None: none is kept,
+        nothing is allocated and adam_step is the plain dm3d_adam launch)."""
         if cfg.norm != "batch":
             raise ValueError("training is built for the BatchNormalization network the reference trains (norm='batch')")
         _lib.require_device()
@@ -115,6 +131,9 @@ class Trainer:
         self.load_state(state)
         self._bn_acc = None
         self._cache: Dict[str, object] = {}
+        self.ema, self.ema_decay, self.ema_warmup, self.ema_updates = None, None, True, 0
+        if ema_decay is not None:
+            self.set_ema(ema_decay, ema_warmup)
 
     # ---- state --------------------------------------------------------------------------------------------------------------
     def load_state(self, state: Dict[str, np.ndarray]):
@@ -126,8 +145,12 @@ class Trainer:
                 self.moving[n] = arr.clone()
 
     def state_dict(self) -> Dict[str, np.ndarray]:
+        return self._named(self.theta)
+
+    def _named(self, flat: torch.Tensor) -> Dict[str, np.ndarray]:
+        """The state dict whose trainable entries are read from ``flat`` (laid out like theta); moving statistics are the live ones."""
         out = {}
-        host = self.theta.cpu().numpy()
+        host = flat.cpu().numpy()
         base = self.theta.data_ptr()
         for n, shape in self.spec.items():
             if is_trainable(n):
@@ -648,9 +671,67 @@ class Trainer:
                 buf[o:o + arr.size].copy_(torch.from_numpy(arr))
 
     def adam_step(self):
-        """keras.optimizers.Adam.apply_gradients over the flat buffers (one launch)."""
+        """keras.optimizers.Adam.apply_gradients over the flat buffers (one launch).  With an average (set_ema) the launch is
+        dm3d_adam_ema: the same step, bitwise, and ema += ema_rate * (theta_new - ema) in the same pass, ema_rate =
+        float32(1 - ema_decay_at(decay, ema_updates, warmup)) computed here in float64."""
         self.step_count += 1
         tt = self.step_count
         lr_t = self.lr * (1.0 - ADAM_BETA2 ** tt) ** 0.5 / (1.0 - ADAM_BETA1 ** tt)
-        check(lib().dm3d_adam(self.theta.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.total, lr_t,
-                              ADAM_BETA1, ADAM_BETA2, ADAM_EPS, _st()), "adam")
+        if self.ema is None:
+            check(lib().dm3d_adam(self.theta.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.total, lr_t,
+                                  ADAM_BETA1, ADAM_BETA2, ADAM_EPS, _st()), "adam")
+            return
+        rate = float(np.float32(1.0 - ema_decay_at(self.ema_decay, self.ema_updates, self.ema_warmup)))
+        check(lib().dm3d_adam_ema(self.theta.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.ema.data_ptr(),
+                                  self.total, lr_t, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, rate, _st()), "adam_ema")
+        self.ema_updates += 1
+
+    # ---- exponential moving average of the weights (what diffusion models are sampled from) -------------------------------------------
+    def set_ema(self, decay: Optional[float], warmup: bool = True):
+        """Keep ``ema``, a flat buffer laid out like theta, updated by every adam_step with decay ``decay`` in [0, 1) (``warmup``:
+        ema_decay_at).  Turning it on copies theta as it is at that moment and sets ema_updates = 0; with an average already kept only
+        the decay and the warm-up change.  ``None`` frees the buffer.  Data-parallel training needs no collective for it: after
+        allreduce_grads every rank applies the same update to the same theta, so the averages agree as the weights do."""
+        if decay is None:
+            self.ema, self.ema_decay, self.ema_updates = None, None, 0
+            return
+        decay = _check_ema_decay(decay)
+        if self.forward_only:
+            raise ValueError("a forward_only Trainer takes no optimizer step: it keeps no weight average")
+        self.ema_decay, self.ema_warmup = decay, bool(warmup)
+        if self.ema is None:
+            self.ema = self.theta.clone()
+            self.ema_updates = 0
+
+    def ema_state_dict(self) -> Dict[str, np.ndarray]:
+        """state_dict() of the averaged model: the trainable entries come from ``ema``, the BatchNormalization moving statistics are the
+        live ones (buffers are copied, not averaged)."""
+        if self.ema is None:
+            raise ValueError("no weight average is kept (set_ema)")
+        return self._named(self.ema)
+
+    def ema_state(self) -> Dict[str, np.ndarray]:
+        """{"ema/num_updates", "ema/<name>"...}: what a resumed run needs to continue the average, beside optimizer_state()."""
+        if self.ema is None:
+            raise ValueError("no weight average is kept (set_ema)")
+        out = {"ema/num_updates": np.asarray(self.ema_updates, dtype=np.int64)}
+        host, base = self.ema.cpu().numpy(), self.theta.data_ptr()
+        for n, p in self.params.items():
+            o = (p.w.data_ptr() - base) // 4
+            out[f"ema/{n}"] = host[o:o + p.w.numel()].reshape(p.shape).copy()
+        return out
+
+    def load_ema_state(self, st: Dict[str, np.ndarray]):
+        """Continues the average of ema_state(); the decay is the one set_ema() was given."""
+        if self.ema is None:
+            raise ValueError("no weight average is kept (set_ema) to load into")
+        base = self.theta.data_ptr()
+        flat = np.zeros(self.total, dtype=np.float32)
+        for n, p in self.params.items():
+            arr = np.ascontiguousarray(st[f"ema/{n}"], dtype=np.float32).reshape(-1)
+            if arr.size != p.w.numel():
+                raise ValueError(f"averaged {n}: {arr.size} values for a parameter of {p.w.numel()}")
+            o = (p.w.data_ptr() - base) // 4
+            flat[o:o + arr.size] = arr
+        self.ema.copy_(torch.from_numpy(flat))
+        self.ema_updates = int(np.asarray(st["ema/num_updates"]).reshape(-1)[0])

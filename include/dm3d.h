@@ -683,6 +683,15 @@ int dm3d_mse_loss_grad(const float* pred, const float* noise, int64_t n, double 
 /* keras.optimizers.Adam step over a flat parameter buffer: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; w -= lr_t*m/(sqrt(v)+eps),
  * lr_t = lr*sqrt(1-b2^t)/(1-b1^t) (the host supplies it; Keras defaults b1 0.9, b2 0.999, eps 1e-7). */
 int dm3d_adam(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2, float eps, void* stream);
+/* The same step and the exponential moving average of the weights in one launch and one pass over the five buffers: w, m and v
+ * become bitwise what dm3d_adam makes of them (both kernels call one element function), then
+ *     ema += ema_rate * (w_new - ema)          (float32: one sub, one mul, one add)
+ * so ema_rate = 0 leaves ema untouched; ema_rate = 1 stores w_new itself (the three operations could miss it by an ulp).  The host supplies ema_rate = 1 - decay (Trainer: with the
+ * warm-up decay_t = min(decay, (1 + n) / (10 + n)) of n earlier updates).  HBM-bound at 36 B per element (Adam alone 28, Adam and a
+ * separate averaging pass 40).  Checked before the launch (DM3D_EINVAL): every pointer non-NULL and 16-byte aligned, n > 0 and
+ * n % 4 == 0 (float4 accesses), ema_rate finite in [0, 1], ema overlapping none of w, g, m, v. */
+int dm3d_adam_ema(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, float beta1, float beta2, float eps,
+                  float ema_rate, void* stream);
 
 /* ---- HIP graph capture of one denoising step (replaces the eager per-op Python loop of generate, :559-573) -- */
 int dm3d_graph_begin(void* stream);
