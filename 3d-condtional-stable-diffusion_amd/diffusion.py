@@ -17,11 +17,14 @@ Every chain (DDPM, DDIM, DPM-Solver++; plain, edit, guided) is a ``Sampler``: re
 exist once, in that class; a solver subclass names its update entry point and row counter and writes its tables, ``_EditChain``
 and ``_GuidedChain`` mix the blend and the guidance in, and the table ``_CHAINS`` picks the class.  generate(), edit() and invert()
 check their arguments through one rule function (``_solver_rules``) and drive the chain through one loop (``_run``).
+
+Two halves live beside this file.  ``schedules.py``: the host arithmetic (schedules, coefficient rows, threshold and guidance tables,
+mask pooling, context dropout), re-exported here.  ``weight_sets.py``: ``model.weights``, the one owner of the live weights, their
+average, the Trainer and of which set the sampling network holds; compile()'s settings stay on the model and are handed to it.
 """
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Optional
 
 import numpy as np
@@ -30,164 +33,11 @@ import torch
 from . import _lib
 from ._lib import DdimDesc, DdpmDesc, DpmDesc, EditDesc, GuideDesc, ThreshDesc, check, lib
 from .betas import BETAS_FIELDS, Betas
+from .schedules import (FLOAT32_MAX, _host, _indices, context_dropout, ddim_coefficients, ddim_timesteps, dpm_coefficients, edit_levels,
+                        edit_steps, guide_tables, latent_mask, threshold_rank, threshold_tables)
 from .unet import UNet
+from .weight_sets import WeightSets
 from .weights import UNetConfig
-
-
-def ddim_timesteps(T: int, num_steps=None, timesteps=None) -> np.ndarray:
-    """The DDIM schedule tau_0 < ... < tau_{S-1} in [0, T): ``timesteps`` as given (strictly increasing), or for ``num_steps`` = S
-    tau_i = round(i (T-1) / (S-1)) (halves rounded up, in integers) for i = 0..S-1, and [T-1] for S = 1: always holds 0 and T-1.
-    Neither given: every timestep (S = T)."""
-    T = int(T)
-    if num_steps is not None and timesteps is not None:
-        raise ValueError("give num_steps or timesteps, not both")
-    if timesteps is not None:
-        ts = np.asarray(timesteps).reshape(-1)
-        if ts.size == 0 or not np.all(ts == np.round(ts)) or ts.min() < 0 or ts.max() >= T or np.any(np.diff(ts) <= 0):
-            raise ValueError(f"timesteps must be strictly increasing integers in [0, {T})")
-        return ts.astype(np.int64)
-    S = T if num_steps is None else int(num_steps)
-    if not 1 <= S <= T:
-        raise ValueError(f"num_steps must lie in [1, {T}], got {num_steps}")
-    if S == 1:
-        return np.array([T - 1], dtype=np.int64)
-    i = np.arange(S, dtype=np.int64)
-    return (2 * i * (T - 1) + (S - 1)) // (2 * (S - 1))
-
-
-def ddim_coefficients(alpha_bar, src, dst, eta=0.0) -> np.ndarray:
-    """float64 [n, 5] rows (sqrt(a), sqrt(1-a), a_x0, a_eps, sigma) of the DDIM steps src[r] -> dst[r] (include/dm3d.h,
-    dm3d_ddim_desc): a = alpha_bar[src], a' = alpha_bar[dst] (1 where dst < 0), sigma = eta sqrt((1-a')/(1-a)) sqrt(1 - a/a'),
-    a_x0 = sqrt(a'), a_eps = sqrt(max(1 - a' - sigma^2, 0)).  eta = 0 gives sigma = 0 for either direction (inversion: a' < a)."""
-    ab = np.asarray(alpha_bar, dtype=np.float64)
-    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
-    a = ab[src]
-    ap = np.where(dst < 0, 1.0, ab[np.maximum(dst, 0)])
-    sigma = np.zeros_like(a)
-    if eta != 0:
-        sigma = float(eta) * np.sqrt((1 - ap) / (1 - a)) * np.sqrt(1 - a / ap)
-    a_eps = np.sqrt(np.maximum(1 - ap - sigma ** 2, 0.0))
-    return np.stack([np.sqrt(a), np.sqrt(1 - a), np.sqrt(ap), a_eps, sigma], axis=1)
-
-
-def dpm_coefficients(alpha_bar, src, dst, prev, order=2) -> np.ndarray:
-    """float64 [n, 3] rows (c_x, c_0, c_1) of the DPM-Solver++(2M) steps src[r] -> dst[r] (include/dm3d.h, dm3d_dpm_desc):
-    x' = c_x x + c_0 x0 + c_1 x0_prev.  With alpha = sqrt(a), sigma = sqrt(1-a), lambda = log(alpha/sigma) and h = lambda_dst -
-    lambda_src: c_x = sigma_dst / sigma_src and A = alpha_dst (1 - e^-h); a first-order row is (c_x, A, 0), a second-order row with
-    r = (lambda_src - lambda_prev) / h is (c_x, A (1 + 1/(2r)), -A / (2r)), ``prev[r]`` being the level the step before started from.
-    ``prev[r] < 0`` or ``order`` = 1 makes row r first order; ``dst[r] < 0`` (clean, a' = 1) is (0, 1, 0) exactly."""
-    if order not in (1, 2):
-        raise ValueError(f"solver_order must be 1 or 2, got {order!r}")
-    ab = np.asarray(alpha_bar, dtype=np.float64)
-    src, dst, prev = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (src, dst, prev))
-    lam = lambda a: 0.5 * (np.log(a) - np.log1p(-a))            # log(sqrt(a) / sqrt(1-a))
-    a_s, a_t, a_p = ab[src], ab[np.maximum(dst, 0)], ab[np.maximum(prev, 0)]
-    h = lam(a_t) - lam(a_s)
-    c_x = np.sqrt((1 - a_t) / (1 - a_s))
-    A = -np.sqrt(a_t) * np.expm1(-h)
-    second = (prev >= 0) & (dst >= 0) & (order == 2)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        g = np.where(second, h / (2 * (lam(a_s) - lam(a_p))), 0.0)          # 1 / (2r)
-    out = np.stack([c_x, A * (1 + g), -A * g], axis=1)
-    out[dst < 0] = (0.0, 1.0, 0.0)
-    return out
-
-
-def threshold_rank(per_sample: int, ratio) -> tuple:
-    """(i, f) of the dynamic threshold's quantile (include/dm3d.h, dm3d_thresh_desc): q = ratio (N-1) in float64, i = floor(q) and
-    f = float32(q - i), the weight of v_{i+1} in the interpolation between the order statistics v_i and v_{i+1} of N = per_sample
-    magnitudes (numpy's "linear" quantile).  ratio = 1 gives (N-1, 0): the maximum."""
-    q = float(ratio) * (int(per_sample) - 1)
-    i = min(int(math.floor(q)), int(per_sample) - 1)
-    return i, np.float32(q - i)
-
-
-FLOAT32_MAX = float(np.finfo(np.float32).max)
-
-
-def threshold_tables(B: int, per_sample: int, dynamic_threshold, threshold_max=None):
-    """(rank int32 [B], frac float32 [B], smax float32 [B]) host tables of dm3d_thresh_desc, one ratio / cap broadcast or one per
-    volume, validated: 0 < ratio <= 1, cap >= 1 (None: the largest finite float32), all finite."""
-    out = []
-    for name, v in (("dynamic_threshold", dynamic_threshold), ("threshold_max", FLOAT32_MAX if threshold_max is None else threshold_max)):
-        a = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)
-        if a.size not in (1, B):
-            raise ValueError(f"{name} must hold one value or one per volume ({B}), got {a.size}")
-        if not np.all(np.isfinite(a)):
-            raise ValueError(f"{name} must be finite")
-        out.append(np.broadcast_to(a, (B,)))
-    p, cap = out
-    if p.min() <= 0 or p.max() > 1:
-        raise ValueError("dynamic_threshold must lie in (0, 1]")
-    if cap.min() < 1 or cap.max() > FLOAT32_MAX:
-        raise ValueError("threshold_max must be >= 1 (and a finite float32)")
-    ranks = [threshold_rank(per_sample, v) for v in p]
-    return (np.array([r[0] for r in ranks], dtype=np.int32), np.array([r[1] for r in ranks], dtype=np.float32),
-            np.ascontiguousarray(cap.astype(np.float32)))
-
-
-def edit_steps(strength, n: int) -> int:
-    """The steps an edit keeps of an n-step schedule: floor(strength n + 1/2) for strength in (0, 1]; 0 steps is an error."""
-    s = float(strength)
-    if not 0 < s <= 1:                                    # a NaN fails the comparison too
-        raise ValueError(f"strength must lie in (0, 1], got {strength}")
-    k = int(math.floor(s * int(n) + 0.5))
-    if k == 0:
-        raise ValueError(f"strength {strength} keeps no step of a {n}-step schedule")
-    return k
-
-
-def edit_levels(alpha_bar, levels) -> np.ndarray:
-    """float64 [n, 2] rows (sqrt(a'), sqrt(1-a')) of the known-latent levels (include/dm3d.h, dm3d_edit_desc): a' = alpha_bar[level],
-    1 where level < 0 (clean)."""
-    ab = np.asarray(alpha_bar, dtype=np.float64)
-    lv = np.asarray(levels, dtype=np.int64)
-    ap = np.where(lv < 0, 1.0, ab[np.maximum(lv, 0)])
-    return np.stack([np.sqrt(ap), np.sqrt(1 - ap)], axis=1)
-
-
-def latent_mask(mask, latent_shape) -> torch.Tensor:
-    """An edit mask (1 = regenerate, 0 = keep, values in [0, 1]) at latent resolution: ``mask`` is [B|1, D', H', W'] or
-    [B|1, D', H', W', 1] with (D', H', W') = k (D, H, W) for an integer k >= 1 (k = 4: a 128^3 image mask over a 32^3 latent),
-    ``latent_shape`` = (B, D, H, W, C).  Each k^3 block is pooled by its max (a voxel any part of which is regenerated is
-    regenerated) and a batch of one is broadcast: float32 [B, D, H, W] on the mask's device."""
-    B, D, H, W = (int(v) for v in latent_shape[:4])
-    m = (mask if torch.is_tensor(mask) else torch.as_tensor(np.asarray(mask))).to(torch.float32)
-    if m.dim() == 5:
-        if m.shape[-1] != 1:
-            raise ValueError(f"a 5-D mask has one trailing channel, got {tuple(m.shape)}")
-        m = m[..., 0]
-    if m.dim() != 4 or m.shape[0] not in (1, B):
-        raise ValueError(f"mask must be [B|1, D', H', W'(, 1)] with B = {B}, got {tuple(m.shape)}")
-    k = m.shape[1] // D
-    if k < 1 or tuple(m.shape[1:]) != (k * D, k * H, k * W):
-        raise ValueError(f"mask extent {tuple(m.shape[1:])} is no integer multiple of the latent's {(D, H, W)}")
-    if not bool(((m >= 0) & (m <= 1)).all()):
-        raise ValueError("mask values must lie in [0, 1]")
-    if k > 1:
-        m = m.reshape(m.shape[0], D, k, H, k, W, k).amax(dim=(2, 4, 6))
-    return m.expand(B, D, H, W).contiguous()
-
-
-def context_dropout(ids, p, null_context, *, seed=None, drop=None) -> np.ndarray:
-    """The context ids a train step runs on (int32 [B]): ``ids`` with each entry replaced by ``null_context`` where ``drop`` (bool
-    [B]) says so; ``drop`` None draws it, one uniform per sample from numpy's default_rng(``seed``), dropped where it is < ``p``
-    (p = 0: never, p = 1: always)."""
-    ids = np.array(ids, dtype=np.int32).reshape(-1)
-    if drop is None:
-        if not 0 <= float(p) <= 1:                            # a NaN fails the comparison too
-            raise ValueError(f"context_dropout must lie in [0, 1], got {p}")
-        drop = np.random.default_rng(seed).random(ids.size) < float(p)
-    drop = np.asarray(drop.detach().cpu() if torch.is_tensor(drop) else drop)
-    if drop.dtype != np.bool_ or drop.reshape(-1).size != ids.size:
-        raise ValueError(f"drop must hold one bool per sample ({ids.size})")
-    ids[drop.reshape(-1)] = int(null_context)
-    return ids
-
-
-def _indices(v, B: int) -> np.ndarray:
-    """One timestep index, or one per sample, as int64 [B] on the host."""
-    return np.broadcast_to(np.asarray(torch.as_tensor(v).reshape(-1).cpu(), dtype=np.int64), (B,))
 
 
 def _fill(d, **tensors):
@@ -250,18 +100,12 @@ class DiffusionModel:
         self.device = self.network.device
         self._graphs = {}
         self._stream = None
-        self._trainer = None
-        self._trainer_dirty = False
-        self._pending_optimizer = None          # Adam slots of a loaded checkpoint, applied when the Trainer is first built
-        self._pending_ema = None                # its ema/ entries: they wait on the host likewise (use_ema() samples from them as they are)
         self._ema_decay, self._ema_warmup = None, True
         self.context_dropout, self.null_context = 0.0, None
-        self._use_ema = False                   # which weights the sampling network runs on (use_ema())
-        self._network_stale = False             # use_ema() changed: the network still holds the other set
-        self._live_host = None                  # the live weights while the network holds the averaged ones and no Trainer exists
+        self.weights = WeightSets(self.network, self._make_trainer, self._drop_graphs)     # live / averaged weights and the Trainer
         self._warned_tf_ema = False
-        self.network._before_use = self._sync_from_trainer
-        self.network._training_engine = self._engine_for_training_forward
+        self.network._before_use = self.weights.refresh
+        self.network._training_engine = lambda: self.weights.engine_for_training_forward(*self._training_settings())
 
     # -- the autoencoder bracket --------------------------------------------------------------------------------------
     @property
@@ -332,83 +176,24 @@ class DiffusionModel:
 
     # -- which weights the sampling network runs on -------------------------------------------------------------------------
     def _has_ema(self) -> bool:
-        return (self._trainer is not None and self._trainer.ema is not None) or self._pending_ema is not None
+        return self.weights.has_average()
 
     def use_ema(self, flag) -> bool:
         """Chooses the weights the SAMPLING network runs on (generate, edit, invert, network(...)): the exponential moving average
         (True) or the live Adam iterate (False, the default).  Returns the previous setting.  train_step and
-        network(..., training=True) always use the live weights, and save_weights() writes them whatever this says.  A change marks
-        the network stale: the other set is loaded before its next use, and the captured graphs are dropped."""
-        flag, prev = bool(flag), self._use_ema
-        if flag and not self._has_ema():
-            raise ValueError("use_ema(True): the model has no averaged weights (train with compile(ema_decay=...) or load a "
-                             "checkpoint that carries ema/ entries)")
-        if flag != prev:
-            self._use_ema, self._network_stale = flag, True
-        return prev
-
-    def _live_state(self):
-        """The live weights by name (host): the Trainer's, else the copy set aside while the network holds the averaged ones, else the network's."""
-        if self._trainer is not None:
-            return self._trainer.state_dict()
-        return dict(self._live_host if self._live_host is not None else self.network.state)
-
-    def _ema_weights(self, live):
-        """The averaged model by name (host): ``live`` with every trainable entry replaced by its average."""
-        if self._trainer is not None and self._trainer.ema is not None:
-            return self._trainer.ema_state_dict()
-        return {**live, **{k[len("ema/"):]: v for k, v in self._pending_ema.items() if k != "ema/num_updates"}}
-
-    def _ema_entries(self):
-        """The ``ema/...`` checkpoint entries of the model, {} without an average."""
-        if self._trainer is not None and self._trainer.ema is not None:
-            return self._trainer.ema_state()
-        return dict(self._pending_ema or {})
+        network(..., training=True) always use the live weights, and save_weights() writes them whatever this says.  After a change
+        the other set is loaded before the network's next use, and the captured graphs are dropped."""
+        return self.weights.select(bool(flag))
 
     def load_state_dict(self, sd, strict=True):
         """Weights by name; ``optimizer/...`` entries (save_weights of a trained model) restore the Adam slots and step count, so a
         resumed run continues the bias correction where it stopped; without them the optimizer starts afresh.  ``ema/...`` entries restore
         the weight average likewise (complete and of the weights' shapes, or the load fails); a checkpoint without them leaves the
         model without an average, and use_ema() back at False."""
-        # validated BEFORE anything is touched: a checkpoint with partial slots fails here with the model as it was (new weights with the
-        # old Adam state gone would be a half-loaded model)
-        opt = {k: v for k, v in sd.items() if k.startswith("optimizer/")}
-        if opt:
-            missing = [k for k in ["optimizer/iter"] + [f"optimizer/{slot}/{n}" for n in self._trainable_names() for slot in ("m", "v")] if k not in opt]
-            if missing:
-                raise ValueError(f"checkpoint carries optimizer state but {len(missing)} entries are missing (first: {missing[:3]}); "
-                                 "drop every optimizer/ entry to load the weights alone")
-        ema = {k: v for k, v in sd.items() if k.startswith("ema/")}
-        if ema:
-            want = {"ema/num_updates": ()}
-            want.update({f"ema/{n}": tuple(self.network.spec[n]) for n in self._trainable_names()})
-            missing = [k for k in want if k not in ema]
-            extra = [k for k in ema if k not in want]
-            wrong = [k for k in want if k in ema and k != "ema/num_updates" and tuple(np.shape(ema[k])) != want[k]]
-            if missing or extra or wrong:
-                raise ValueError(f"checkpoint carries averaged weights but {len(missing)} entries are missing (first: {missing[:3]}), "
-                                 f"{len(extra)} are unknown (first: {extra[:3]}) and {len(wrong)} have another shape (first: {wrong[:3]}); "
-                                 "drop every ema/ entry to load the weights alone")
-        if self._use_ema or self._live_host is not None:           # the network may hold the averaged weights
-            live = self._live_state()
-            self._network_stale = True
-            self.network.load_state_dict(live)
-        else:
-            self._sync_from_trainer()                              # a non-strict load fills missing names from the CURRENT (trained) weights
-        self.network.load_state_dict({k: v for k, v in sd.items() if not k.startswith(("optimizer/", "ema/"))}, strict)
-        self._drop_graphs()
-        self._trainer, self._trainer_dirty = None, False          # Adam moments belong to the weights they were built for
-        # the slots wait until a Trainer exists (an inference-only load builds none: theta, gradients and moments are four copies of the weights)
-        self._pending_optimizer = opt or None
-        self._pending_ema = {k: np.array(v, dtype=np.int64 if k == "ema/num_updates" else np.float32) for k, v in ema.items()} or None
-        self._live_host = None
-        self._use_ema = self._use_ema and bool(ema)
-        self._network_stale = self._use_ema                        # the network now holds the live weights
+        self.weights.load(sd, strict)
 
     def _trainable_names(self):
-        """Names of the parameters Adam updates (everything but the BatchNormalization moving statistics)."""
-        from .train import is_trainable
-        return [n for n in self.network.spec if is_trainable(n)]
+        return self.weights.trainable_names()
 
     def load_weights(self, path, root=("network",)):
         """keras ``model.load_weights(ckpt)`` (main_conditional_dm.py:207-213): reads the U-Net from a TF2 checkpoint prefix
@@ -435,19 +220,8 @@ class DiffusionModel:
             raise ValueError(f"weights must be 'live' or 'ema', got {weights!r}")
         if weights == "ema" and not self._has_ema():
             raise ValueError("save_weights(weights='ema'): the model has no averaged weights")
-        npz = str(path).endswith(".npz")
-        if weights == "ema":
-            state, opt, ema = self._ema_weights(self._live_state()), {}, {}
-        else:
-            if self._use_ema or self._live_host is not None or self._network_stale:
-                state = self._live_state()
-            else:
-                self._sync_from_trainer()
-                state = self.network.state_dict()
-            # the Adam slots and step count travel with the weights, as in the reference's save_weights_only TF checkpoints of a compiled model
-            opt = self._trainer.optimizer_state() if self._trainer is not None and self._trainer.step_count > 0 else (getattr(self, "_pending_optimizer", None) or {})
-            ema = self._ema_entries()
-        if npz:
+        state, opt, ema = self.weights.checkpoint(weights)
+        if str(path).endswith(".npz"):
             np.savez(path, **state, **opt, **ema)
             return
         if ema and not self._warned_tf_ema:
@@ -481,63 +255,19 @@ class DiffusionModel:
                 return float(getattr(opt, attr))
         return 1e-4
 
+    def _make_trainer(self, live, lr):
+        from .train import Trainer
+        return Trainer(self.network.cfg, live, self.device, lr=lr)
+
+    def _training_settings(self):
+        """What compile() set for the Trainer, re-read whenever one is built or takes a step (so a later compile() takes effect between
+        steps): the learning rate and the average's decay and warm-up."""
+        return self._learning_rate(), self._ema_decay, self._ema_warmup
+
     @property
     def trainer(self):
-        """The training engine (train.py), built on first use from the network's current weights."""
-        if self._trainer is None:
-            from .train import Trainer
-            if self._use_ema or self._live_host is not None or self._network_stale:
-                live = self._live_state()
-            else:
-                live = self.network.state_dict()
-            self._trainer = Trainer(self.network.cfg, live, self.device, lr=self._learning_rate())
-            self._live_host = None
-            if getattr(self, "_pending_optimizer", None):
-                self._trainer.load_optimizer_state(self._pending_optimizer)
-                self._pending_optimizer = None
-            self._configure_ema(self._trainer)
-        return self._trainer
-
-    def _configure_ema(self, tr):
-        """compile()'s ema_decay / ema_warmup reach the Trainer (re-read like the learning rate); a loaded average continues there."""
-        if self._ema_decay is None:
-            if tr.ema is not None:
-                if self._use_ema:
-                    raise ValueError("compile(ema_decay=None) would drop the averaged weights the sampling network runs on: use_ema(False) first")
-                tr.set_ema(None)
-            return
-        tr.set_ema(self._ema_decay, self._ema_warmup)
-        if self._pending_ema is not None:
-            tr.load_ema_state(self._pending_ema)
-            self._pending_ema = None
-
-    def _engine_for_training_forward(self):
-        """``network(..., training=True)`` outside train_step runs on the model's own Trainer when it has one, so the moving statistics it
-        updates are the ones the next train_step continues from (in Keras both are the same variables)."""
-        if self._trainer is None and not self._use_ema:
-            return None
-        tr = self.trainer                          # (under use_ema(True) the network holds the averaged weights: the live ones need a Trainer)
-        self._trainer_dirty = True
-        return tr
-
-    def _sync_from_trainer(self):
-        """Weights changed by train_step flow back into the sampling network (folded norms, packed images, tables) before it runs:
-        the live ones, or under use_ema(True) the averaged ones."""
-        if not (self._network_stale or (self._trainer is not None and self._trainer_dirty)):
-            return
-        tr = self._trainer
-        if self._use_ema and tr is not None and tr.ema is not None:
-            state = tr.ema_state_dict()
-        else:
-            live = self._live_state()
-            if self._use_ema and tr is None and self._live_host is None:
-                self._live_host = live                     # the network is about to hold the averaged weights: the live ones wait here
-            state = self._ema_weights(live) if self._use_ema else live
-        if not self._use_ema:
-            self._live_host = None
-        self._trainer_dirty = self._network_stale = False
-        self.network.load_state_dict(state)
-        self._drop_graphs()
+        """The training engine (train.py), built on first use from the live weights."""
+        return self.weights.ensure_trainer(*self._training_settings())
 
     def train_step(self, inputs, *, t=None, noise=None, latents=None, **extensions):
         """conditional_dm3d.py:471-510: ``inputs = (images, mask, context)`` ((images, _) for the unconditional model, dm3d.py:431-433).
@@ -590,15 +320,13 @@ class DiffusionModel:
                                       seed=self.fresh_seed() if drop is None else None, drop=drop)
         elif drop is not None:
             raise ValueError("drop= needs the conditional model: there is no context to drop")
-        tr = self.trainer
-        tr.lr = self._learning_rate()               # re-read every step: compile() / optimizer.learning_rate may have changed
-        self._configure_ema(tr)
+        tr = self.weights.ensure_trainer(*self._training_settings(), step=True)
         tab = self.b.device_tables(dev)
         betas = (tab[BETAS_FIELDS.index("sqrt_alpha_bar")], tab[BETAS_FIELDS.index("sqrt_one_minus_alpha_bar")])
         loss, _ = tr.loss_and_grad(latents, t, noise, ids, betas, T, self.global_bs, self.lc)
         tr.allreduce_grads(loss)                   # data-parallel replicas (one process per GPU): flat RCCL all-reduces; no-op alone
         tr.adam_step()
-        self._trainer_dirty = True
+        self.weights.trained()
         self.loss_tracker.update_state(float(loss.item()))
         return {"loss": self.loss_tracker.result()}
 
@@ -835,26 +563,12 @@ class DiffusionModel:
         d.batch, d.per_sample, d.mode = int(batch), int(per_sample), mode
         return d
 
-    @staticmethod
-    def _guide_tables(B, guidance_scale, guidance_rescale):
-        """(w, phi): float32 [B] host arrays of the guidance scale and rescale, one value broadcast or one per volume, validated."""
-        out = []
-        for name, v in (("guidance_scale", guidance_scale), ("guidance_rescale", guidance_rescale)):
-            a = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)
-            if a.size not in (1, B):
-                raise ValueError(f"{name} must hold one value or one per volume ({B}), got {a.size}")
-            if not np.all(np.isfinite(a)):
-                raise ValueError(f"{name} must be finite")
-            out.append(np.ascontiguousarray(np.broadcast_to(a, (B,)).astype(np.float32)))
-        if out[1].min() < 0 or out[1].max() > 1:
-            raise ValueError("guidance_rescale must lie in [0, 1]")
-        return out[0], out[1]
+    _guide_tables = staticmethod(guide_tables)
 
     def _guidance(self, B, guidance_scale, negative_context, guidance_rescale):
         """The argument rules of classifier-free guidance, checked before any plan or device buffer is made: None for an unguided
         call, else (w [B] float32, phi [B] float32, negative ids [B] int32)."""
-        rescaled = guidance_rescale is not None and bool(np.any(np.asarray(
-            guidance_rescale.detach().cpu() if torch.is_tensor(guidance_rescale) else guidance_rescale) != 0))
+        rescaled = guidance_rescale is not None and bool(np.any(np.asarray(_host(guidance_rescale)) != 0))
         if guidance_scale is None:
             if negative_context is not None or rescaled:
                 raise ValueError("negative_context / guidance_rescale need guidance_scale")
@@ -903,7 +617,7 @@ class DiffusionModel:
         if context_value is None:
             # the reference builds tf.constant([[None]]) here and fails (conditional_dm3d.py:552, 586-589)
             raise ValueError("context_value is required for the conditional model")
-        ids = np.asarray(context_value.detach().cpu() if torch.is_tensor(context_value) else context_value).astype(np.int64).reshape(-1)
+        ids = np.asarray(_host(context_value)).astype(np.int64).reshape(-1)
         if ids.size != 1 and batch is not None and ids.size != batch:
             raise ValueError(f"context_value must hold one id or one per volume ({batch}), got {ids.size}")
         if ids.min() < 0 or ids.max() > self.network.cfg.context_dim:
@@ -1019,7 +733,7 @@ class DiffusionModel:
         if sampler != "ddpm" and last_step != 0:
             raise ValueError(f"sampler={sampler!r} runs whole chains: last_step must be 0")
         ctx, guide = self._contexts(shape[0], context_value, guidance_scale, negative_context, guidance_rescale)
-        self._sync_from_trainer()
+        self.weights.refresh()
         smp = _CHAINS[sampler, False, bool(guide)](self, shape, ctx, seed, use_graph and noise is None, taus, **opts, **guide)
         return self._run(smp, (x_T,), noise, steps=steps, last_step=last_step)
 
@@ -1050,7 +764,7 @@ class DiffusionModel:
         shape = self._sampler_shape(x0.shape)
         taus = ddim_timesteps(self.timesteps, num_steps, timesteps)
         ctx = self._context_ids(context_value, shape[0]) if self.conditional else None
-        self._sync_from_trainer()
+        self.weights.refresh()
         smp = DdimSampler(self, shape, ctx, seed, use_graph, taus, clip_x0=False, invert=True)
         return self._run(smp, (x0,))
 
@@ -1092,7 +806,7 @@ class DiffusionModel:
         if steps is not None and int(steps) < 0:
             raise ValueError("steps must be >= 0")
         # device work from here on
-        self._sync_from_trainer()
+        self.weights.refresh()
         dev = self.device
         keep = torch.zeros(shape[:4], dtype=torch.float32, device=dev) if mask is None else 1 - mask.to(dev)
         if known_noise is not None:
@@ -1578,3 +1292,4 @@ class GuidedDpmEditSampler(_GuidedChain, DpmEditSampler):
 _CHAINS = {(c.SOLVER, issubclass(c, _EditChain), issubclass(c, _GuidedChain)): c
            for c in (Sampler, DdimSampler, DpmSampler, EditSampler, DdimEditSampler, DpmEditSampler, GuidedSampler, GuidedDdimSampler,
                      GuidedDpmSampler, GuidedEditSampler, GuidedDdimEditSampler, GuidedDpmEditSampler)}
+

@@ -1,0 +1,182 @@
+"""The host arithmetic of the samplers and of training: schedules, coefficient rows, threshold and guidance tables, mask pooling and
+context dropout.  Pure functions of numbers and arrays: none needs the model, the library or a device.  ``diffusion`` re-exports every
+public name."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+
+def _host(v):
+    """``v`` as the host sees it: a tensor detached and on the CPU, anything else as it is."""
+    return v.detach().cpu() if torch.is_tensor(v) else v
+
+
+def _per_volume(name: str, v, B: int) -> np.ndarray:
+    """One value or one per volume, finite, as float64 [B] (a broadcast view)."""
+    a = np.asarray(_host(v), dtype=np.float64).reshape(-1)
+    if a.size not in (1, B):
+        raise ValueError(f"{name} must hold one value or one per volume ({B}), got {a.size}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{name} must be finite")
+    return np.broadcast_to(a, (B,))
+
+
+def ddim_timesteps(T: int, num_steps=None, timesteps=None) -> np.ndarray:
+    """The DDIM schedule tau_0 < ... < tau_{S-1} in [0, T): ``timesteps`` as given (strictly increasing), or for ``num_steps`` = S
+    tau_i = round(i (T-1) / (S-1)) (halves rounded up, in integers) for i = 0..S-1, and [T-1] for S = 1: always holds 0 and T-1.
+    Neither given: every timestep (S = T)."""
+    T = int(T)
+    if num_steps is not None and timesteps is not None:
+        raise ValueError("give num_steps or timesteps, not both")
+    if timesteps is not None:
+        ts = np.asarray(timesteps).reshape(-1)
+        if ts.size == 0 or not np.all(ts == np.round(ts)) or ts.min() < 0 or ts.max() >= T or np.any(np.diff(ts) <= 0):
+            raise ValueError(f"timesteps must be strictly increasing integers in [0, {T})")
+        return ts.astype(np.int64)
+    S = T if num_steps is None else int(num_steps)
+    if not 1 <= S <= T:
+        raise ValueError(f"num_steps must lie in [1, {T}], got {num_steps}")
+    if S == 1:
+        return np.array([T - 1], dtype=np.int64)
+    i = np.arange(S, dtype=np.int64)
+    return (2 * i * (T - 1) + (S - 1)) // (2 * (S - 1))
+
+
+def ddim_coefficients(alpha_bar, src, dst, eta=0.0) -> np.ndarray:
+    """float64 [n, 5] rows (sqrt(a), sqrt(1-a), a_x0, a_eps, sigma) of the DDIM steps src[r] -> dst[r] (include/dm3d.h,
+    dm3d_ddim_desc): a = alpha_bar[src], a' = alpha_bar[dst] (1 where dst < 0), sigma = eta sqrt((1-a')/(1-a)) sqrt(1 - a/a'),
+    a_x0 = sqrt(a'), a_eps = sqrt(max(1 - a' - sigma^2, 0)).  eta = 0 gives sigma = 0 for either direction (inversion: a' < a)."""
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    a = ab[src]
+    ap = np.where(dst < 0, 1.0, ab[np.maximum(dst, 0)])
+    sigma = np.zeros_like(a)
+    if eta != 0:
+        sigma = float(eta) * np.sqrt((1 - ap) / (1 - a)) * np.sqrt(1 - a / ap)
+    a_eps = np.sqrt(np.maximum(1 - ap - sigma ** 2, 0.0))
+    return np.stack([np.sqrt(a), np.sqrt(1 - a), np.sqrt(ap), a_eps, sigma], axis=1)
+
+
+def dpm_coefficients(alpha_bar, src, dst, prev, order=2) -> np.ndarray:
+    """float64 [n, 3] rows (c_x, c_0, c_1) of the DPM-Solver++(2M) steps src[r] -> dst[r] (include/dm3d.h, dm3d_dpm_desc):
+    x' = c_x x + c_0 x0 + c_1 x0_prev.  With alpha = sqrt(a), sigma = sqrt(1-a), lambda = log(alpha/sigma) and h = lambda_dst -
+    lambda_src: c_x = sigma_dst / sigma_src and A = alpha_dst (1 - e^-h); a first-order row is (c_x, A, 0), a second-order row with
+    r = (lambda_src - lambda_prev) / h is (c_x, A (1 + 1/(2r)), -A / (2r)), ``prev[r]`` being the level the step before started from.
+    ``prev[r] < 0`` or ``order`` = 1 makes row r first order; ``dst[r] < 0`` (clean, a' = 1) is (0, 1, 0) exactly."""
+    if order not in (1, 2):
+        raise ValueError(f"solver_order must be 1 or 2, got {order!r}")
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    src, dst, prev = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (src, dst, prev))
+    lam = lambda a: 0.5 * (np.log(a) - np.log1p(-a))            # log(sqrt(a) / sqrt(1-a))
+    a_s, a_t, a_p = ab[src], ab[np.maximum(dst, 0)], ab[np.maximum(prev, 0)]
+    h = lam(a_t) - lam(a_s)
+    c_x = np.sqrt((1 - a_t) / (1 - a_s))
+    A = -np.sqrt(a_t) * np.expm1(-h)
+    second = (prev >= 0) & (dst >= 0) & (order == 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = np.where(second, h / (2 * (lam(a_s) - lam(a_p))), 0.0)          # 1 / (2r)
+    out = np.stack([c_x, A * (1 + g), -A * g], axis=1)
+    out[dst < 0] = (0.0, 1.0, 0.0)
+    return out
+
+
+def threshold_rank(per_sample: int, ratio) -> tuple:
+    """(i, f) of the dynamic threshold's quantile (include/dm3d.h, dm3d_thresh_desc): q = ratio (N-1) in float64, i = floor(q) and
+    f = float32(q - i), the weight of v_{i+1} in the interpolation between the order statistics v_i and v_{i+1} of N = per_sample
+    magnitudes (numpy's "linear" quantile).  ratio = 1 gives (N-1, 0): the maximum."""
+    q = float(ratio) * (int(per_sample) - 1)
+    i = min(int(math.floor(q)), int(per_sample) - 1)
+    return i, np.float32(q - i)
+
+
+FLOAT32_MAX = float(np.finfo(np.float32).max)
+
+
+def threshold_tables(B: int, per_sample: int, dynamic_threshold, threshold_max=None):
+    """(rank int32 [B], frac float32 [B], smax float32 [B]) host tables of dm3d_thresh_desc, one ratio / cap broadcast or one per
+    volume, validated: 0 < ratio <= 1, cap >= 1 (None: the largest finite float32), all finite."""
+    p = _per_volume("dynamic_threshold", dynamic_threshold, B)
+    cap = _per_volume("threshold_max", FLOAT32_MAX if threshold_max is None else threshold_max, B)
+    if p.min() <= 0 or p.max() > 1:
+        raise ValueError("dynamic_threshold must lie in (0, 1]")
+    if cap.min() < 1 or cap.max() > FLOAT32_MAX:
+        raise ValueError("threshold_max must be >= 1 (and a finite float32)")
+    ranks = [threshold_rank(per_sample, v) for v in p]
+    return (np.array([r[0] for r in ranks], dtype=np.int32), np.array([r[1] for r in ranks], dtype=np.float32),
+            np.ascontiguousarray(cap.astype(np.float32)))
+
+
+def guide_tables(B: int, guidance_scale, guidance_rescale):
+    """(w, phi): float32 [B] host arrays of the guidance scale and rescale, one value broadcast or one per volume, validated."""
+    w, phi = (np.ascontiguousarray(_per_volume(name, v, B).astype(np.float32))
+              for name, v in (("guidance_scale", guidance_scale), ("guidance_rescale", guidance_rescale)))
+    if phi.min() < 0 or phi.max() > 1:
+        raise ValueError("guidance_rescale must lie in [0, 1]")
+    return w, phi
+
+
+def edit_steps(strength, n: int) -> int:
+    """The steps an edit keeps of an n-step schedule: floor(strength n + 1/2) for strength in (0, 1]; 0 steps is an error."""
+    s = float(strength)
+    if not 0 < s <= 1:                                    # a NaN fails the comparison too
+        raise ValueError(f"strength must lie in (0, 1], got {strength}")
+    k = int(math.floor(s * int(n) + 0.5))
+    if k == 0:
+        raise ValueError(f"strength {strength} keeps no step of a {n}-step schedule")
+    return k
+
+
+def edit_levels(alpha_bar, levels) -> np.ndarray:
+    """float64 [n, 2] rows (sqrt(a'), sqrt(1-a')) of the known-latent levels (include/dm3d.h, dm3d_edit_desc): a' = alpha_bar[level],
+    1 where level < 0 (clean)."""
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    lv = np.asarray(levels, dtype=np.int64)
+    ap = np.where(lv < 0, 1.0, ab[np.maximum(lv, 0)])
+    return np.stack([np.sqrt(ap), np.sqrt(1 - ap)], axis=1)
+
+
+def latent_mask(mask, latent_shape) -> torch.Tensor:
+    """An edit mask (1 = regenerate, 0 = keep, values in [0, 1]) at latent resolution: ``mask`` is [B|1, D', H', W'] or
+    [B|1, D', H', W', 1] with (D', H', W') = k (D, H, W) for an integer k >= 1 (k = 4: a 128^3 image mask over a 32^3 latent),
+    ``latent_shape`` = (B, D, H, W, C).  Each k^3 block is pooled by its max (a voxel any part of which is regenerated is
+    regenerated) and a batch of one is broadcast: float32 [B, D, H, W] on the mask's device."""
+    B, D, H, W = (int(v) for v in latent_shape[:4])
+    m = (mask if torch.is_tensor(mask) else torch.as_tensor(np.asarray(mask))).to(torch.float32)
+    if m.dim() == 5:
+        if m.shape[-1] != 1:
+            raise ValueError(f"a 5-D mask has one trailing channel, got {tuple(m.shape)}")
+        m = m[..., 0]
+    if m.dim() != 4 or m.shape[0] not in (1, B):
+        raise ValueError(f"mask must be [B|1, D', H', W'(, 1)] with B = {B}, got {tuple(m.shape)}")
+    k = m.shape[1] // D
+    if k < 1 or tuple(m.shape[1:]) != (k * D, k * H, k * W):
+        raise ValueError(f"mask extent {tuple(m.shape[1:])} is no integer multiple of the latent's {(D, H, W)}")
+    if not bool(((m >= 0) & (m <= 1)).all()):
+        raise ValueError("mask values must lie in [0, 1]")
+    if k > 1:
+        m = m.reshape(m.shape[0], D, k, H, k, W, k).amax(dim=(2, 4, 6))
+    return m.expand(B, D, H, W).contiguous()
+
+
+def context_dropout(ids, p, null_context, *, seed=None, drop=None) -> np.ndarray:
+    """The context ids a train step runs on (int32 [B]): ``ids`` with each entry replaced by ``null_context`` where ``drop`` (bool
+    [B]) says so; ``drop`` None draws it, one uniform per sample from numpy's default_rng(``seed``), dropped where it is < ``p``
+    (p = 0: never, p = 1: always)."""
+    ids = np.array(ids, dtype=np.int32).reshape(-1)
+    if drop is None:
+        if not 0 <= float(p) <= 1:                            # a NaN fails the comparison too
+            raise ValueError(f"context_dropout must lie in [0, 1], got {p}")
+        drop = np.random.default_rng(seed).random(ids.size) < float(p)
+    drop = np.asarray(_host(drop))
+    if drop.dtype != np.bool_ or drop.reshape(-1).size != ids.size:
+        raise ValueError(f"drop must hold one bool per sample ({ids.size})")
+    ids[drop.reshape(-1)] = int(null_context)
+    return ids
+
+
+def _indices(v, B: int) -> np.ndarray:
+    """One timestep index, or one per sample, as int64 [B] on the host."""
+    return np.broadcast_to(np.asarray(torch.as_tensor(v).reshape(-1).cpu(), dtype=np.int64), (B,))

@@ -151,9 +151,9 @@ def test_load_state_dict_validates_and_round_trips_the_average(tmp_path):
         with pytest.raises(ValueError, match="ema/"):
             m.load_state_dict(bad)
         now = m.network.state_dict()
-        assert all(np.array_equal(now[k], before[k]) for k in before) and m._pending_ema is None and not m._has_ema()
+        assert all(np.array_equal(now[k], before[k]) for k in before) and m.weights.pending_ema is None and not m._has_ema()
     m.load_state_dict(full)
-    assert m._trainer is None and m._has_ema()
+    assert m.weights.trainer is None and m._has_ema()
     path = str(tmp_path / "ckpt.npz")
     m.save_weights(path)
     back = dict(np.load(path))
@@ -167,7 +167,7 @@ def test_load_state_dict_validates_and_round_trips_the_average(tmp_path):
     assert all(np.array_equal(st[k], full[k]) for k in st if k.endswith((".mean", ".var")))
     m.save_weights(path)
     back = dict(np.load(path))
-    assert all(np.array_equal(back[k], full[k]) for k in full) and m._trainer is None
+    assert all(np.array_equal(back[k], full[k]) for k in full) and m.weights.trainer is None
     m.save_weights(path, weights="ema")
     exported = dict(np.load(path))
     assert set(exported) == set(st) and all(np.array_equal(exported[k], st[k]) for k in st)
@@ -177,7 +177,7 @@ def test_load_state_dict_validates_and_round_trips_the_average(tmp_path):
     # a checkpoint without an average takes the average away, and the switch with it
     m.use_ema(True)
     m.load_state_dict(before)
-    assert not m._has_ema() and m._use_ema is False
+    assert not m._has_ema() and m.weights.want == "live"
     assert all(np.array_equal(m.network.state_dict()[k], before[k]) for k in before)
 
 

@@ -198,11 +198,11 @@ def test_inference_only_load_samples_from_the_average(dev, trained, tmp_path):
     assert other.use_ema(True) is False
     got = _chain(other)
     torch.cuda.synchronize()
-    assert other._trainer is None
+    assert other.weights.trainer is None
     assert torch.equal(got, want) and not torch.equal(got, live_out)
     # a resumed run continues the average where it stopped
     other.compile(optimizer=SimpleNamespace(learning_rate=LR), ema_decay=DECAY)
-    assert other.trainer.ema_updates == 3 and other._pending_ema is None
+    assert other.trainer.ema_updates == 3 and other.weights.pending_ema is None
     ema = other.trainer.ema_state_dict()
     assert all(np.array_equal(_bits(ema[k]), _bits(trained.history[-1][1][k])) for k in ema)
 

@@ -229,10 +229,10 @@ def test_optimizer_state_survives_save_and_load(dev, tmp_path):
     b = cdm.DiffusionModel(8, 1024, 4, None, _args(T, B), weights=W)
     b.compile(optimizer=SimpleNamespace(learning_rate=1e-4))
     b.load_weights(str(tmp_path / "ck.npz"))
-    assert b._trainer is None and b._pending_optimizer is not None      # an inference-only load builds no training buffers
+    assert b.weights.trainer is None and b.weights.pending_optimizer is not None      # an inference-only load builds no training buffers
     b.generate((1, 8, 8, 8, 4), context_value=1, seed=1, steps=1)
-    assert b._trainer is None
-    assert b.trainer.step_count == 2 and b._pending_optimizer is None   # ... the slots land when the Trainer is first built
+    assert b.weights.trainer is None
+    assert b.trainer.step_count == 2 and b.weights.pending_optimizer is None   # ... the slots land when the Trainer is first built
     run(b, [2])
     sa, sb = a.network.state_dict(), b.network.state_dict()
     worst = max(float(np.abs(sa[k] - sb[k]).max()) for k in sa)
@@ -249,7 +249,7 @@ def test_optimizer_state_survives_save_and_load(dev, tmp_path):
     with pytest.raises(ValueError, match="optimizer state"):
         c.load_state_dict(part)
     # ... and leaves the model as it was: same weights, the Trainer and its Adam state still there (validate before mutating)
-    assert c._trainer is not None and c.trainer.step_count == 1
+    assert c.weights.trainer is not None and c.trainer.step_count == 1
     sc2 = c.network.state_dict()
     assert all(np.array_equal(sc[k], sc2[k]) for k in sc)
     # round 5: the TF-format writer carries the Adam slots and the step count too (OptimizerV2 layout: optimizer/iter + slot variables)
@@ -257,7 +257,7 @@ def test_optimizer_state_survives_save_and_load(dev, tmp_path):
     d = cdm.DiffusionModel(8, 1024, 4, None, _args(T, B), weights=W)
     d.compile(optimizer=SimpleNamespace(learning_rate=1e-4))
     d.load_weights(str(tmp_path / "tfck"))
-    assert d._pending_optimizer is not None and int(d._pending_optimizer["optimizer/iter"]) == 3
+    assert d.weights.pending_optimizer is not None and int(d.weights.pending_optimizer["optimizer/iter"]) == 3
     assert d.trainer.step_count == 3
     sd, sa2 = d.network.state_dict(), a.network.state_dict()
     assert all(np.array_equal(sd[k], sa2[k]) for k in sa2)
