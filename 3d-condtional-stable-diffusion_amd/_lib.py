@@ -152,7 +152,22 @@ class GuideDesc(C.Structure):
     ]
 
 
+class PredDesc(C.Structure):
+    _fields_ = [
+        ("pred", _f32p), ("x", _f32p), ("out", _f32p), ("table", _f32p), ("t_idx", _i32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
+        ("timesteps", C.c_int32),
+    ]
+
+
+class LossDesc(C.Structure):
+    _fields_ = [
+        ("pred", _f32p), ("noise", _f32p), ("x0", _f32p), ("coef", _f32p), ("dpred", _f32p), ("partials", C.c_void_p),
+        ("loss_rows", C.c_void_p), ("loss", C.c_void_p), ("batch", C.c_int32), ("per_sample", C.c_int64), ("inv_divisor", C.c_double),
+    ]
+
+
 GUIDE_PARTIAL_BLOCKS = 256          # DM3D_GUIDE_PARTIAL_BLOCKS: GuideDesc.partials holds [batch][256][4] doubles
+LOSS_PARTIAL_BLOCKS = 64            # DM3D_LOSS_PARTIAL_BLOCKS: LossDesc.partials holds [batch][64] doubles
 
 # name -> (restype, argtypes): every symbol include/dm3d.h declares
 SIGNATURES = {
@@ -211,6 +226,8 @@ SIGNATURES = {
     "dm3d_x0_threshold_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "dm3d_edit_update": (C.c_int, [C.POINTER(EditDesc), C.c_void_p]),
     "dm3d_guide_update": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p]),
+    "dm3d_pred_to_eps": (C.c_int, [C.POINTER(PredDesc), C.c_void_p]),
+    "dm3d_objective_loss_grad": (C.c_int, [C.POINTER(LossDesc), C.c_void_p]),
     "dm3d_range_check": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "dm3d_add_i32": (C.c_int, [_i32p, C.c_int32, C.c_int32, C.c_void_p]),
     "dm3d_randn": (C.c_int, [_f32p, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p]),

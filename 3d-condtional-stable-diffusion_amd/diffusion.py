@@ -9,6 +9,9 @@ selects the in-kernel Philox stream, ``use_graph=`` toggles HIP-graph replay of 
 and DPM-Solver++ chains (include/dm3d.h, dm3d_thresh_desc).  Training extensions, off by default: ``compile(ema_decay=)`` keeps an
 exponential moving average of the weights in the optimizer's launch (include/dm3d.h, dm3d_adam_ema) and ``use_ema()`` samples from it;
 ``compile(context_dropout=, null_context=)`` trains the unconditional branch that classifier-free guidance is defined against.
+``prediction="v"`` / ``"x0"`` (constructor) reads the network's output as v (Salimans & Ho 2022) or as x0 instead of eps: every chain
+converts it to eps right after the U-Net (include/dm3d.h, dm3d_pred_desc) and train_step fits the matching target;
+``compile(loss_weighting="min_snr", snr_gamma=)`` weighs each sample's loss by min-SNR-gamma (Hang et al. 2023; dm3d_loss_desc).
 
 The sampling loop (:559-573) runs with no host synchronisation: the step index lives in device memory, one step
 (U-Net forward + posterior update + index decrement) is captured once into a HIP graph and replayed T times.
@@ -31,10 +34,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DdimDesc, DdpmDesc, DpmDesc, EditDesc, GuideDesc, ThreshDesc, check, lib
+from ._lib import DdimDesc, DdpmDesc, DpmDesc, EditDesc, GuideDesc, PredDesc, ThreshDesc, check, lib
 from .betas import BETAS_FIELDS, Betas
-from .schedules import (FLOAT32_MAX, _host, _indices, context_dropout, ddim_coefficients, ddim_timesteps, dpm_coefficients, edit_levels,
-                        edit_steps, guide_tables, latent_mask, threshold_rank, threshold_tables)
+from .schedules import (FLOAT32_MAX, LOSS_WEIGHTINGS, PREDICTIONS, _check_prediction, _host, _indices, context_dropout, ddim_coefficients,
+                        ddim_timesteps, dpm_coefficients, edit_levels, edit_steps, guide_tables, latent_mask, objective_rows,
+                        prediction_table, threshold_rank, threshold_tables)
 from .unet import UNet
 from .weight_sets import WeightSets
 from .weights import UNetConfig
@@ -77,8 +81,12 @@ class DiffusionModel:
     conditional = True
 
     def __init__(self, latent_size, num_embed, latent_channels, vqvae_load_ckpt, args, *, device="cuda", weights=None,
-                 seed=0, precision=None, norm="batch", context_dim=1):
+                 seed=0, precision=None, norm="batch", context_dim=1, prediction="eps"):
         # conditional_dm3d.py:420-469.  ``args`` is any object with .timesteps .num_gpus .kernel_resize .bs
+        # ``prediction``: what the network's output is: "eps" (the reference), "v" = sqrt(a) z - sqrt(1-a) x0 or "x0"
+        self.prediction = _check_prediction(prediction)
+        self._pred_table = None
+        self.loss_weighting, self.snr_gamma = None, 5.0
         self.timesteps = int(args.timesteps)
         self.b = Betas(self.timesteps)
         self.lc = latent_channels
@@ -147,7 +155,8 @@ class DiffusionModel:
     def metrics(self):
         return [self.loss_tracker]
 
-    def compile(self, loss=None, optimizer=None, *, ema_decay=None, ema_warmup=True, context_dropout=0.0, null_context=None):
+    def compile(self, loss=None, optimizer=None, *, ema_decay=None, ema_warmup=True, context_dropout=0.0, null_context=None,
+                loss_weighting=None, snr_gamma=5.0):
         """keras ``model.compile``.  Keyword-only extensions, read again by every train_step like the learning rate (so a later compile()
         takes effect between steps):
         ``ema_decay`` in [0, 1) (None: off) keeps an exponential moving average of the trainable weights, updated in the optimizer's
@@ -155,8 +164,17 @@ class DiffusionModel:
         ``null_context``: an id in [0, context_dim] reserved for "no context" (give the constructor ``context_dim`` one more than
         the classes to have a spare embedding row); guidance then defaults ``negative_context`` to it.  ``context_dropout`` in [0, 1]:
         train_step replaces each sample's id by ``null_context`` with this probability, which trains the unconditional branch
-        classifier-free guidance is defined against."""
+        classifier-free guidance is defined against.
+        ``loss_weighting="min_snr"`` (None: every sample weighs 1) weighs each sample's loss by min-SNR-gamma (Hang et al. 2023) with
+        gamma = ``snr_gamma`` > 0 (schedules.py, objective_rows): the weight that evens out the timesteps' pull on the shared weights,
+        for whichever ``prediction`` the model was built with.  ``snr_gamma`` other than its default needs ``loss_weighting``."""
         from .train import _check_ema_decay
+        if loss_weighting not in LOSS_WEIGHTINGS:
+            raise ValueError(f"loss_weighting must be None or 'min_snr', got {loss_weighting!r}")
+        if not float(snr_gamma) > 0:                         # (a NaN fails the comparison too)
+            raise ValueError(f"snr_gamma must be > 0, got {snr_gamma}")
+        if loss_weighting is None and float(snr_gamma) != 5.0:
+            raise ValueError("snr_gamma needs loss_weighting='min_snr'")
         if ema_decay is not None:
             ema_decay = _check_ema_decay(ema_decay)
         context_dropout = float(context_dropout)
@@ -173,6 +191,7 @@ class DiffusionModel:
         self.loss, self.optimizer = loss, optimizer
         self._ema_decay, self._ema_warmup = ema_decay, bool(ema_warmup)
         self.context_dropout, self.null_context = context_dropout, null_context
+        self.loss_weighting, self.snr_gamma = loss_weighting, float(snr_gamma)
 
     # -- which weights the sampling network runs on -------------------------------------------------------------------------
     def _has_ema(self) -> bool:
@@ -189,7 +208,14 @@ class DiffusionModel:
         """Weights by name; ``optimizer/...`` entries (save_weights of a trained model) restore the Adam slots and step count, so a
         resumed run continues the bias correction where it stopped; without them the optimizer starts afresh.  ``ema/...`` entries restore
         the weight average likewise (complete and of the weights' shapes, or the load fails); a checkpoint without them leaves the
-        model without an average, and use_ema() back at False."""
+        model without an average, and use_ema() back at False.  ``meta/prediction`` (save_weights of a v- or x0-model's .npz) must
+        name this model's ``prediction``, or the load fails before anything is touched; a checkpoint without it loads into any model."""
+        if "meta/prediction" in sd:
+            theirs = str(np.asarray(sd["meta/prediction"]).reshape(-1)[0])
+            if theirs != self.prediction:
+                raise ValueError(f"the checkpoint holds a prediction={theirs!r} model, this model was built with "
+                                 f"prediction={self.prediction!r}: its output would be read as the wrong quantity")
+            sd = {k: v for k, v in sd.items() if k != "meta/prediction"}
         self.weights.load(sd, strict)
 
     def _trainable_names(self):
@@ -215,14 +241,16 @@ class DiffusionModel:
         """Writes the LIVE weights under the ordinary names, whatever use_ema() says, with the Adam slots; an .npz file also carries
         the weight average as ``ema/...`` entries.  The TF-format writer holds no second copy of the weights (a warning says so once).
         ``weights="ema"`` exports the averaged model under the ordinary names instead, without optimizer or ema/ entries, in either
-        format: how an averaged model reaches a reference-format TF checkpoint."""
+        format: how an averaged model reaches a reference-format TF checkpoint.  An .npz file of a v- or x0-model also carries
+        ``meta/prediction`` (an eps model writes no such entry; the TF format has no place for it)."""
         if weights not in ("live", "ema"):
             raise ValueError(f"weights must be 'live' or 'ema', got {weights!r}")
         if weights == "ema" and not self._has_ema():
             raise ValueError("save_weights(weights='ema'): the model has no averaged weights")
         state, opt, ema = self.weights.checkpoint(weights)
         if str(path).endswith(".npz"):
-            np.savez(path, **state, **opt, **ema)
+            meta = {} if self.prediction == "eps" else {"meta/prediction": np.asarray(self.prediction)}
+            np.savez(path, **state, **opt, **ema, **meta)
             return
         if ema and not self._warned_tf_ema:
             import warnings
@@ -277,6 +305,9 @@ class DiffusionModel:
         autoencoder (pre-encoded latents [b, S, S, S, lc]).  Under compile(context_dropout=p, null_context=k) each sample's context id
         becomes k with probability p, drawn on the host next to t; ``drop`` (bool [b]) injects that draw.  Under compile(ema_decay=)
         the optimizer's launch also advances the weight average.  The step runs on the live weights whatever use_ema() says.
+        A ``prediction="v"`` / ``"x0"`` model is fitted to that target, and compile(loss_weighting="min_snr") weighs each sample's loss
+        (dm3d_objective_loss_grad; the Trainer keeps the per-sample losses as ``sample_loss``); an eps model without weighting runs the
+        reference's plain MSE launch.
         (``drop`` is the one name ``**extensions`` takes, by keyword only: the signature's named keywords stay t, noise and latents.)"""
         drop = extensions.pop("drop", None)
         if extensions:
@@ -323,7 +354,10 @@ class DiffusionModel:
         tr = self.weights.ensure_trainer(*self._training_settings(), step=True)
         tab = self.b.device_tables(dev)
         betas = (tab[BETAS_FIELDS.index("sqrt_alpha_bar")], tab[BETAS_FIELDS.index("sqrt_one_minus_alpha_bar")])
-        loss, _ = tr.loss_and_grad(latents, t, noise, ids, betas, T, self.global_bs, self.lc)
+        rows = None
+        if self.prediction != "eps" or self.loss_weighting is not None:
+            rows = objective_rows(self.b.alpha_bar, t, self.prediction, self.loss_weighting, self.snr_gamma)
+        loss, _ = tr.loss_and_grad(latents, t, noise, ids, betas, T, self.global_bs, self.lc, objective=rows)
         tr.allreduce_grads(loss)                   # data-parallel replicas (one process per GPU): flat RCCL all-reduces; no-op alone
         tr.adam_step()
         self.weights.trained()
@@ -344,7 +378,8 @@ class DiffusionModel:
         return d
 
     def sample(self, x_t, pred_noise, curr_time_step, shape):
-        """conditional_dm3d.py:517-548: returns (posterior_mean, posterior 'log_variance' [B,1,1,1,1])."""
+        """conditional_dm3d.py:517-548: returns (posterior_mean, posterior 'log_variance' [B,1,1,1,1]).  ``pred_noise`` is eps,
+        whatever the model's ``prediction``: predict_eps() converts a v- or x0-model's output first."""
         x_t = torch.as_tensor(x_t, dtype=torch.float32).to(self.device).contiguous()
         eps = torch.as_tensor(pred_noise, dtype=torch.float32).to(self.device).contiguous()
         B = int(shape[0])
@@ -365,7 +400,8 @@ class DiffusionModel:
         """One DDIM update (include/dm3d.h, dm3d_ddim_desc, mode 0): x_t at timestep ``t`` -> x at ``t_prev`` (-1: the x0
         estimate), the DDIM counterpart of sample().  ``t`` / ``t_prev``: one index or one per sample, -1 <= t_prev < t.
         ``noise`` (optional): z of the step (eta > 0); None draws it from Philox under ``seed`` (None: a fresh key).
-        ``dynamic_threshold`` / ``threshold_max``: the x0 estimate is thresholded dynamically, as in generate()."""
+        ``dynamic_threshold`` / ``threshold_max``: the x0 estimate is thresholded dynamically, as in generate().
+        ``pred_noise`` is eps, whatever the model's ``prediction``: predict_eps() converts a v- or x0-model's output first."""
         x_t, eps = torch.as_tensor(x_t, dtype=torch.float32), torch.as_tensor(pred_noise, dtype=torch.float32)
         B = x_t.shape[0]
         if eps.shape != x_t.shape or x_t[0].numel() % 4:
@@ -411,7 +447,8 @@ class DiffusionModel:
         (x_next, x0), x0 being this step's (clipped) estimate: the ``x0_prev`` of the next call.  With ``x0_prev`` and ``t_before``
         (the estimate and the timestep of the step before; given together or not at all) the step is second order, else first order
         (= ddim_step at eta = 0 where the x0 estimate is not clipped).  ``t`` / ``t_prev`` / ``t_before``: one index or one per sample, -1 <= t_prev < t < t_before.
-        ``dynamic_threshold`` / ``threshold_max``: the x0 estimate (the one returned too) is thresholded dynamically, as in generate()."""
+        ``dynamic_threshold`` / ``threshold_max``: the x0 estimate (the one returned too) is thresholded dynamically, as in generate().
+        ``pred_noise`` is eps, whatever the model's ``prediction``: predict_eps() converts a v- or x0-model's output first."""
         if (x0_prev is None) != (t_before is None):
             raise ValueError("x0_prev and t_before are given together or not at all")
         x_t = torch.as_tensor(x_t, dtype=torch.float32)
@@ -492,7 +529,8 @@ class DiffusionModel:
         ``dynamic_threshold`` quantile of |x0| with x0 = (x_t - sqrt(1-a) pred_noise) / sqrt(a) at timestep ``t`` (one index or one
         per volume), raised to 1 and capped at ``threshold_max``; the single-call counterpart of a thresholded chain's step, as
         ddim_step is of a DDIM chain.  The quantile is exact (numpy's "linear" interpolation between two order statistics, in
-        float32).  ``clip_x0=False`` describes a step that does not clip: s = 1 and nothing is ranked."""
+        float32).  ``clip_x0=False`` describes a step that does not clip: s = 1 and nothing is ranked.  ``pred_noise`` is eps, whatever
+        the model's ``prediction``: predict_eps() converts a v- or x0-model's output first."""
         x_t, eps = torch.as_tensor(x_t, dtype=torch.float32), torch.as_tensor(pred_noise, dtype=torch.float32)
         if x_t.dim() < 2 or eps.shape != x_t.shape or x_t[0].numel() % 4:
             raise ValueError("x_t / pred_noise must share one shape [B, ...] with a multiple of 4 elements per volume")
@@ -507,6 +545,37 @@ class DiffusionModel:
         coef = self._ddim_table(t, np.full(B, -1, dtype=np.int64), 0.0, bool(clip_x0)).to(dev)
         pos = torch.arange(B, dtype=torch.int32, device=dev)
         return self._x0_bound(x_t.to(dev).contiguous(), eps.to(dev).contiguous(), coef, pos, tables)
+
+    # -- what the network predicts -------------------------------------------------------------------------------------------------
+    def _prediction_table(self) -> torch.Tensor:
+        """The model's [T, 2] device table of dm3d_pred_desc (schedules.py, prediction_table), made on first use."""
+        if self._pred_table is None:
+            self._pred_table = torch.from_numpy(prediction_table(self.b.alpha_bar, self.prediction)).to(self.device)
+        return self._pred_table
+
+    def _pred_desc(self, pred, x, t_idx, out=None) -> PredDesc:
+        d = _fill(PredDesc(), pred=pred, x=x, out=out, table=self._prediction_table(), t_idx=t_idx)
+        d.batch, d.per_sample, d.timesteps = x.shape[0], x[0].numel(), self.timesteps
+        return d
+
+    def predict_eps(self, x_t, pred, t):
+        """The network's output ``pred`` on ``x_t`` at timestep ``t`` (one index or one per volume) as eps (include/dm3d.h,
+        dm3d_pred_desc): c_p pred + c_x x_t with the model's ``prediction`` table, in float32 (mul, mul, add); the single-call
+        counterpart of the conversion every chain of a v- or x0-model runs after its U-Net, as ddim_step is of a DDIM chain.  An eps
+        model's table is (1, 0).  Returns a new tensor; the inputs are left untouched."""
+        x_t, pred = torch.as_tensor(x_t, dtype=torch.float32), torch.as_tensor(pred, dtype=torch.float32)
+        if x_t.dim() < 2 or pred.shape != x_t.shape or x_t[0].numel() % 4:
+            raise ValueError("x_t / pred must share one shape [B, ...] with a multiple of 4 elements per volume")
+        B = x_t.shape[0]
+        t = _indices(t, B)
+        if t.min() < 0 or t.max() >= self.timesteps:
+            raise ValueError("t must lie in [0, timesteps)")
+        dev = self.device
+        x_t, pred = x_t.to(dev).contiguous(), pred.to(dev).contiguous()
+        out = torch.empty_like(pred)
+        d = self._pred_desc(pred, x_t, torch.from_numpy(t.astype(np.int32)).to(dev), out=out)
+        check(lib().dm3d_pred_to_eps(C.byref(d), torch.cuda.current_stream().cuda_stream), "pred_to_eps")
+        return out
 
     def q_sample(self, x0, t, noise=None, *, seed=None):
         """Forward noising (include/dm3d.h, dm3d_edit_desc, mode 0): sqrt(a) x0 + sqrt(1-a) z with a = alpha_bar[t], in the
@@ -588,7 +657,8 @@ class DiffusionModel:
         float32 (sub, mul, add), then with guidance_rescale = phi != 0 scaled by phi std(eps_pos) / std(eps_g) + (1 - phi) per
         volume (population standard deviations over the whole volume); the single-call counterpart of a guided chain's step, as
         ddim_step is of a DDIM chain.  ``guidance_scale`` / ``guidance_rescale``: one value or one per volume.  Returns a new
-        tensor; the inputs are left untouched."""
+        tensor; the inputs are left untouched.  Both inputs are eps, whatever the model's ``prediction`` (a chain guides the converted
+        eps; Lin et al. 2023 state the rescale for v-prediction models, where it acts on the same quantity)."""
         eps_pos = torch.as_tensor(eps_pos, dtype=torch.float32)
         eps_neg = torch.as_tensor(eps_neg, dtype=torch.float32)
         if eps_pos.dim() < 2 or eps_neg.shape != eps_pos.shape or eps_pos[0].numel() % 4:
@@ -886,7 +956,8 @@ class Sampler:
     with ``use_graph`` the three are one HIP-graph replay.  A chain has ``n_steps`` steps (T): step() past its end raises until reset().
     The plan (buffers, step index, Philox key) belongs to the newest Sampler made for it; an older one raises on use.
 
-    reset(), step() and _enqueue() exist once, here.  A solver subclass names its update entry point (UPDATE) and its device row counter
+    reset(), step() and _enqueue() exist once, here; a step is U-Net, predict (a v- or x0-model's output -> eps), guide, threshold,
+    update, blend, mirror, decrement.  A solver subclass names its update entry point (UPDATE) and its device row counter
     (_pos), builds its descriptor (_desc) and writes its tables (_schedule, _coefficients); _EditChain adds the blend after the update and
     _GuidedChain fills the hooks around it (_guide, _mirror, _head).  _CHAINS lists the combinations."""
 
@@ -917,6 +988,8 @@ class Sampler:
         plan._owner_gen = getattr(plan, "_owner_gen", 0) + 1
         self._gen = plan._owner_gen
         self._launch = getattr(lib(), "dm3d_" + self.UPDATE)
+        # a v- or x0-model: every row of the plan (a guided chain: both halves) becomes eps right after the U-Net
+        self._pred_d = None if model.prediction == "eps" else model._pred_desc(plan.eps, plan.x, plan.t_idx)
         self.desc = self._desc()
         self.desc.seed_dev = plan.seed_buf.data_ptr()
         self._t = -1                          # host mirror of the device step index; -1: no chain in progress
@@ -932,8 +1005,15 @@ class Sampler:
 
     @property
     def graph_kind(self):
-        """The step graph's cache key beside the plan: KIND, and a thresholded chain's own (its step holds more launches)."""
-        return self.KIND if self.threshold is None else self.KIND + "+thr"
+        """The step graph's cache key beside the plan: KIND, and a thresholded chain's and a converting chain's own (their steps
+        hold more launches)."""
+        return self.KIND + ("" if self.threshold is None else "+thr") + ("" if getattr(self, "_pred_d", None) is None else "+pred")
+
+    def _predict(self, st):
+        """Between the U-Net and the guidance: nothing for an eps model; a v- or x0-model's output becomes eps in place, on every row
+        of the plan (t_idx is still the timestep the network was evaluated at: the update moves it)."""
+        if self._pred_d is not None:
+            check(lib().dm3d_pred_to_eps(C.byref(self._pred_d), st), "pred_to_eps")
 
     def _guide(self, st):
         """Between the U-Net and the update: nothing (a guided chain: eps <- the guided eps)."""
@@ -984,6 +1064,7 @@ class Sampler:
         self.plan.run(st)
         push, pop = _lib.roctx()
         push(self.SOLVER if self.edit is None else self.KIND)
+        self._predict(st)
         self._guide(st)
         self._threshold(st)
         check(self._launch(C.byref(desc), st), self.UPDATE)

@@ -1,5 +1,5 @@
-"""The host arithmetic of the samplers and of training: schedules, coefficient rows, threshold and guidance tables, mask pooling and
-context dropout.  Pure functions of numbers and arrays: none needs the model, the library or a device.  ``diffusion`` re-exports every
+"""The host arithmetic of the samplers and of training: schedules, coefficient rows, threshold and guidance tables, the prediction
+and objective tables (eps, v, x0; min-SNR), mask pooling and context dropout.  Pure functions of numbers and arrays: none needs the model, the library or a device.  ``diffusion`` re-exports every
 public name."""
 from __future__ import annotations
 
@@ -116,6 +116,61 @@ def guide_tables(B: int, guidance_scale, guidance_rescale):
     if phi.min() < 0 or phi.max() > 1:
         raise ValueError("guidance_rescale must lie in [0, 1]")
     return w, phi
+
+
+PREDICTIONS = ("eps", "v", "x0")          # what the network's output is read as (DiffusionModel(prediction=))
+LOSS_WEIGHTINGS = (None, "min_snr")       # compile(loss_weighting=)
+
+
+def _check_prediction(prediction) -> str:
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"prediction must be 'eps', 'v' or 'x0', got {prediction!r}")
+    return prediction
+
+
+def prediction_table(alpha_bar, prediction) -> np.ndarray:
+    """float32 [T, 2] rows (c_p, c_x) of dm3d_pred_desc (include/dm3d.h): eps = c_p pred + c_x x_t at every timestep, in float64 from
+    the float32 alpha_bar table the kernels use, rounded once.  With a = sqrt(alpha_bar) and s = sqrt(1 - alpha_bar): "v" (Salimans &
+    Ho 2022, v = a z - s x0) gives (a, s), "x0" gives (-a/s, 1/s) and "eps" (1, 0)."""
+    _check_prediction(prediction)
+    ab = np.asarray(alpha_bar, dtype=np.float64).reshape(-1)
+    a, s = np.sqrt(ab), np.sqrt(1 - ab)
+    if prediction == "v":
+        rows = (a, s)
+    elif prediction == "x0":
+        rows = (-a / s, 1 / s)
+    else:
+        rows = (np.ones_like(a), np.zeros_like(a))
+    return np.stack(rows, axis=1).astype(np.float32)
+
+
+def objective_rows(alpha_bar, t, prediction, loss_weighting=None, snr_gamma=5.0) -> np.ndarray:
+    """float32 [B, 4] rows (a_z, a_0, w, 0) of dm3d_loss_desc (include/dm3d.h) for the timesteps ``t``: the training target is
+    a_z noise + a_0 x0 and w the sample's loss weight, in float64 from the float32 alpha_bar table, rounded once.  Targets, with
+    a = sqrt(alpha_bar[t]) and s = sqrt(1 - alpha_bar[t]): "eps" (1, 0), "v" (a, -s), "x0" (0, 1).  w = 1 without ``loss_weighting``;
+    "min_snr" (Hang et al. 2023) with SNR = alpha_bar / (1 - alpha_bar) and gamma = ``snr_gamma``: min(SNR, gamma) / SNR for eps,
+    min(SNR, gamma) / (SNR + 1) for v and min(SNR, gamma) for x0 (one weight on the x0 error, written in each target's own units)."""
+    _check_prediction(prediction)
+    if loss_weighting not in LOSS_WEIGHTINGS:
+        raise ValueError(f"loss_weighting must be None or 'min_snr', got {loss_weighting!r}")
+    gamma = float(snr_gamma)
+    if not gamma > 0:                                     # a NaN fails the comparison too
+        raise ValueError(f"snr_gamma must be > 0, got {snr_gamma}")
+    ab = np.asarray(alpha_bar, dtype=np.float64).reshape(-1)[np.asarray(_host(t), dtype=np.int64).reshape(-1)]
+    a, s = np.sqrt(ab), np.sqrt(1 - ab)
+    rows = np.zeros((ab.size, 4), dtype=np.float64)
+    if prediction == "v":
+        rows[:, 0], rows[:, 1] = a, -s
+    elif prediction == "x0":
+        rows[:, 1] = 1.0
+    else:
+        rows[:, 0] = 1.0
+    rows[:, 2] = 1.0
+    if loss_weighting == "min_snr":
+        snr = ab / (1 - ab)
+        clipped = np.minimum(snr, gamma)
+        rows[:, 2] = clipped / snr if prediction == "eps" else clipped / (snr + 1) if prediction == "v" else clipped
+    return rows.astype(np.float32)
 
 
 def edit_steps(strength, n: int) -> int:

@@ -19,8 +19,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, ConvDesc, GemmDesc, WgradDesc, check, lib
+from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, ConvDesc, GemmDesc, LossDesc, WgradDesc, check, lib
 from .betas import time_embedding_table
+from .schedules import _host
 from .weights import UNetConfig, walk
 
 BN_EPS, LN_EPS, BN_MOMENTUM = 1e-3, 1e-3, 0.99          # Keras defaults
@@ -132,6 +133,7 @@ class Trainer:
         self._bn_acc = None
         self._cache: Dict[str, object] = {}
         self.ema, self.ema_decay, self.ema_warmup, self.ema_updates = None, None, True, 0
+        self.sample_loss = None                              # [B] float64 device: the per-sample losses of the last step with an objective
         if ema_decay is not None:
             self.set_ema(ema_decay, ema_warmup)
 
@@ -589,8 +591,11 @@ class Trainer:
         check(lib().dm3d_fill(self.grad.data_ptr(), self.grad.numel(), 0.0, _st()), "fill")
 
     def loss_and_grad(self, latents: torch.Tensor, t: torch.Tensor, noise: torch.Tensor, ctx_ids, betas_dev, timesteps: int, global_bs: int,
-                      lc: int, update_moving: bool = True):
-        """q_sample -> training forward -> loss -> backward.  Returns (loss [1] float64 device tensor, pred)."""
+                      lc: int, update_moving: bool = True, objective=None):
+        """q_sample -> training forward -> loss -> backward.  Returns (loss [1] float64 device tensor, pred).  ``objective`` (None: the
+        reference's plain MSE on the noise, dm3d_mse_loss_grad) holds the [B, 4] float32 rows (a_z, a_0, w, 0) of
+        schedules.objective_rows(): the loss is then w |pred - (a_z noise + a_0 latents)|^2 per sample (dm3d_objective_loss_grad),
+        summed in a fixed order, and ``sample_loss`` ([B] float64 device tensor) keeps each sample's share of it."""
         B = latents.shape[0]
         dev = self.device
         t_dev = t.to(dev, torch.int32)
@@ -608,8 +613,22 @@ class Trainer:
         loss = torch.zeros(1, dtype=torch.float64, device=dev)
         pred.g = torch.empty_like(pred.v)
         inv = 1.0 / (float(latents.shape[-1]) * float(global_bs) * float(lc) ** 4)
-        check(lib().dm3d_mse_loss_grad(pred.v.data_ptr(), noise.data_ptr(), pred.v.numel(), inv, loss.data_ptr(), pred.g.data_ptr(), _st()),
-              "mse_loss_grad")
+        if objective is None:
+            self.sample_loss = None
+            check(lib().dm3d_mse_loss_grad(pred.v.data_ptr(), noise.data_ptr(), pred.v.numel(), inv, loss.data_ptr(), pred.g.data_ptr(), _st()),
+                  "mse_loss_grad")
+        else:
+            rows = np.ascontiguousarray(_host(objective), dtype=np.float32)
+            if rows.shape != (B, 4):
+                raise ValueError(f"objective must hold one row (a_z, a_0, w, 0) per sample [{B}, 4], got {rows.shape}")
+            coef = torch.from_numpy(rows).to(dev)
+            partials = torch.empty(B * _lib.LOSS_PARTIAL_BLOCKS, dtype=torch.float64, device=dev)
+            self.sample_loss = torch.empty(B, dtype=torch.float64, device=dev)
+            d = LossDesc()
+            d.pred, d.noise, d.x0, d.coef, d.dpred = pred.v.data_ptr(), noise.data_ptr(), latents.data_ptr(), coef.data_ptr(), pred.g.data_ptr()
+            d.partials, d.loss_rows, d.loss = partials.data_ptr(), self.sample_loss.data_ptr(), loss.data_ptr()
+            d.batch, d.per_sample, d.inv_divisor = B, latents[0].numel(), inv
+            check(lib().dm3d_objective_loss_grad(C.byref(d), _st()), "objective_loss_grad")
         self.backward()
         self._cache = {}
         return loss, pred.v

@@ -26,7 +26,8 @@ extern "C" {
                                      training entries), 107 (conv wpk_f8: a float8 cross-term form, removed again in 109), 108 (conv wpk_wino: the Winograd-x form), 109 (wpk_f8 and
                                      dm3d_pack_weights_h3f8 are gone; the Winograd-x image pairs its taps differently; dm3d_mlp_fused; conv skip_wpk_frag, gn_stats; dm3d_groupnorm_finalize2), 110 (dm3d_attn_front), 111 (conv split_counters: the Cin split
                                      meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc, dm3d_edit_update / dm3d_edit_desc,
-                                     dm3d_guide_update / dm3d_guide_desc, dm3d_dpm_update / dm3d_dpm_desc and dm3d_x0_threshold / dm3d_thresh_desc were added within 111 (no existing entry changed; dm3d_ddim_desc and dm3d_dpm_desc grew by one trailing optional pointer, x0_bound, which a zeroed descriptor leaves NULL): a host built against an older header must be rebuilt */
+                                     dm3d_guide_update / dm3d_guide_desc, dm3d_dpm_update / dm3d_dpm_desc and dm3d_x0_threshold / dm3d_thresh_desc were added within 111 (no existing entry changed; dm3d_ddim_desc and dm3d_dpm_desc grew by one trailing optional pointer, x0_bound, which a zeroed descriptor leaves NULL),
+                                     and dm3d_pred_to_eps / dm3d_pred_desc and dm3d_objective_loss_grad / dm3d_loss_desc likewise (new entries and structs only): a host built against an older header must be rebuilt */
 
 #define DM3D_OK            0
 #define DM3D_EINVAL       -1      /* bad argument (shape, alignment, null pointer) */
@@ -586,6 +587,56 @@ typedef struct dm3d_guide_desc {
 } dm3d_guide_desc;
 
 int dm3d_guide_update(const dm3d_guide_desc* d, void* stream);
+
+/* ---- What the network predicts: eps, v (Salimans & Ho 2022) or x0; min-SNR-gamma loss weighting (Hang et al. 2023) ----------------
+ * The solvers above read the network output as eps.  A model trained to predict v = sqrt(a)*z - sqrt(1-a)*x0 or x0 itself (a =
+ * alpha_bar[t], x_t = sqrt(a)*x0 + sqrt(1-a)*z) is brought into that frame between the U-Net and the guidance of a step:
+ *   eps = c_p*pred + c_x*x          float32, in that order: mul, mul, add, each rounded;  (c_p, c_x) = table[clamp(t_idx[b], 0, timesteps-1)]
+ *   v:  (sqrt(a), sqrt(1-a))        x0: (-sqrt(a)/sqrt(1-a), 1/sqrt(1-a))        eps: (1, 0)   (the host computes the table in float64
+ *                                   from the float32 alpha_bar and rounds once)
+ * It writes over pred, or to out when out is given; out may be pred or x themselves (a lane reads its own 16 bytes of both before it
+ * stores) or apart from both.  One HBM stream of 12 B per element, 16 B per lane.  Checked before the launch (DM3D_EINVAL): pred, x,
+ * table, t_idx non-NULL; pred, x, out 16-byte aligned; per_sample a positive multiple of 4; batch in [1, 65535]; timesteps > 0; out
+ * not overlapping pred or x partially (nor, in place, pred overlapping x partially).
+ * Known price of converting rather than teaching the update kernels x0: at a = 4e-5 (t = T-1 of T = 1000) the round trip
+ * v -> eps -> x0 loses about 6e-8*|x|/sqrt(a) = 1e-5 absolute in x0 (an estimate from the roundings, not a measurement). */
+typedef struct dm3d_pred_desc {
+    float* pred;                /* [batch, per_sample] the network's output; becomes eps when out is NULL */
+    const float* x;             /* [batch, per_sample] x_t, the state the network was evaluated on */
+    float* out;                 /* optional [batch, per_sample]: eps goes here and pred is left as it is */
+    const float* table;         /* [timesteps][2] device, (c_p, c_x) per timestep */
+    const int32_t* t_idx;       /* [batch] device, the evaluated timestep of each row */
+    int32_t batch; int64_t per_sample;     /* batch <= 65535, per_sample % 4 == 0 */
+    int32_t timesteps;
+} dm3d_pred_desc;
+int dm3d_pred_to_eps(const dm3d_pred_desc* d, void* stream);
+
+/* The training loss of a prediction against its target, per sample b with coef[b] = (a_z, a_0, w, 0):
+ *   target = a_z*noise + a_0*x0     float32: mul, mul, add       (eps: (1, 0); v: (sqrt(a), -sqrt(1-a)); x0: (0, 1))
+ *   d      = pred - target          float32
+ *   dpred  = d * (float)(2*inv_divisor*w)                         (NULL: not wanted)
+ *   loss_rows[b] = w*inv_divisor*sum d^2  (float64),  loss[0] = sum_b loss_rows[b]     (both written, not accumulated into)
+ * w is the loss weight of the sample (1, or min-SNR-gamma's: min(SNR, gamma)/SNR for eps, /(SNR+1) for v, min(SNR, gamma) for x0).
+ * The grid is (min(ceil(per_sample/4/256), DM3D_LOSS_PARTIAL_BLOCKS), batch); every block leaves its float64 sum of d^2 in
+ * partials[b][block], and a second launch of one block inside this entry adds each sample's partials, then the samples, in index order:
+ * no atomics, so the loss repeats bitwise (dm3d_mse_loss_grad's does not).  With coef = (1, 0, 1) dpred is bitwise dm3d_mse_loss_grad's.
+ * Checked before the launch (DM3D_EINVAL): every pointer but dpred non-NULL; pred, noise, x0, dpred, coef 16-byte aligned and the
+ * float64 buffers 8-byte aligned; per_sample a positive multiple of 4; batch in [1, 65535]; inv_divisor finite; dpred apart from
+ * pred, noise and x0. */
+#define DM3D_LOSS_PARTIAL_BLOCKS 64        /* partials holds [batch][DM3D_LOSS_PARTIAL_BLOCKS] doubles */
+typedef struct dm3d_loss_desc {
+    const float* pred;          /* [batch, per_sample] */
+    const float* noise;         /* [batch, per_sample] z of q_sample */
+    const float* x0;            /* [batch, per_sample] the clean latents */
+    const float* coef;          /* [batch][4] device */
+    float* dpred;               /* optional [batch, per_sample] */
+    double* partials;           /* [batch][64] device scratch */
+    double* loss_rows;          /* [batch] device */
+    double* loss;               /* [1] device */
+    int32_t batch; int64_t per_sample;     /* batch <= 65535, per_sample % 4 == 0 */
+    double inv_divisor;
+} dm3d_loss_desc;
+int dm3d_objective_loss_grad(const dm3d_loss_desc* d, void* stream);
 
 /* p[i] = max(p[i] + delta, 0) (the loop counter of generate kept on the device so a captured step replays unchanged; it
  * saturates at 0, so a step issued past the end of a chain never indexes row -1 of a table). */
