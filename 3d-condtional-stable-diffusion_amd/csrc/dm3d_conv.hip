@@ -228,11 +228,11 @@ int launch_conv(ConvArgs& a, hipStream_t st) {
 // ---- the launch decision: dm3d_conv_resolve turns a descriptor into a ConvLaunch; the launch entry and the three queries all read it -----
 
 // The policy's environment knobs with their defaults (README.md lists them).  The first seven are read once per process — the weight layout
-// and the Cin split must not change between packing / sizing the workspace and the launch —, the last four on every call (tests and A/B
+// and the Cin split must not change between packing / sizing the workspace and the launch —, the last five on every call (tests and A/B
 // tools switch them inside one process).
 struct ConvKnobs {
     bool pair_off; int ksplit_mode; long split_wgs, split_target; int split_minchunks, split_maxparts; bool wino_split_off;
-    int v3_td; long wide_wgs; bool wino_off; int wino_minchunks;
+    int v3_td; long wide_wgs; bool wino_off; int wino_minchunks, wino_split_minchunks;
 };
 static ConvKnobs conv_knobs() {
     auto num = [](const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; };
@@ -245,12 +245,13 @@ static ConvKnobs conv_knobs() {
         (int)num("DM3D_CONV_SPLIT_MINCHUNKS", 2),       // least 16-channel chunks per part
         (int)num("DM3D_CONV_SPLIT_MAXPARTS", 16),       // most parts
         zero("DM3D_CONV_WINO_SPLIT"),                   // =0: the Winograd-x form never splits Cin
-        0, 0, false, 0};
+        0, 0, false, 0, 0};
     ConvKnobs k = once;
     k.v3_td = (int)num("DM3D_CONV_V3_TD", 0);           // 4 = always 4-slice bricks; 8 = 8 wherever the grid allows; else auto
     k.wide_wgs = num("DM3D_CONV_WIDE_WGS", 512);        // workgroups from which the one-workgroup-per-CU forms (8-slice bricks, Winograd-x) serve
     k.wino_off = zero("DM3D_CONV_WINO");                // =0: never the Winograd-x form
     k.wino_minchunks = (int)num("DM3D_CONV_WINO_MINCHUNKS", 2);     // smallest Cin in chunks that takes the Winograd-x form
+    k.wino_split_minchunks = (int)num("DM3D_CONV_WINO_SPLIT_MINCHUNKS", 16);      // smallest Cin in chunks whose Winograd-x launch splits (tests: small shapes)
     return k;
 }
 
@@ -280,7 +281,7 @@ static int direct_ksplit(const ConvArgs& a, const ConvKnobs& K) {
 // half of a fused skip conv's pairs; the halves meet inside the launch (the hand-over form, dm3d_conv_h3v2_parts.h: any epilogue, fused
 // statistics and output formats included).
 static int winograd_ksplit(const ConvArgs& a, const ConvKnobs& K) {
-    if (K.wino_split_off || a.nchunks % 2 != 0 || a.nchunks < 16) return 1;
+    if (K.wino_split_off || a.nchunks % 2 != 0 || a.nchunks < K.wino_split_minchunks) return 1;
     const long wgs = (long)a.batch * (a.od / 8) * (a.oh / 8) * (a.ow / 8) * (a.coutpad / 64);
     return wgs <= 128 ? 2 : 1;
 }

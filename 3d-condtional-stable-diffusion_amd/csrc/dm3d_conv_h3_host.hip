@@ -77,14 +77,18 @@ __global__ __launch_bounds__(256) void pack_weights_h3v2_kernel(const float* __r
         // four consecutive channels (epilogue_cq, dm3d_conv_h3v2_parts.h)
         const int ci = chunk * 16 + k, co = nt * 64 + (mode == 3 ? 4 * c + (pos >> 4) : (pos & ~15) + c);
         float v = 0.f;
+        bool fold = false;               // the Winograd image's pad half: tap (0, 2)'s hi pieces again, lo pieces zero
         if (ci < cin && co < cout && tap < taps) {
             if (mode == 3) {
                 // Winograd F(2,3) along x (dm3d_conv_h3w.hip): virtual tap = 2 * step + h, step = 5 * t + tap pair; the pair's two (dz, dy)
-                // taps, lane half h picking one: (dz, 0) | (dz, 1) for pairs 0-2, (0, 2) | zero pad, (1, 2) | (2, 2) — two per-lane operand
-                // bases serve all five (the kernel's a_pair); transform term t of the tap's three x taps
+                // taps, lane half h picking one: (dz, 0) | (dz, 1) for pairs 0-2, (0, 2) | pad, (1, 2) | (2, 2) — two per-lane operand
+                // bases serve all five (the kernel's a_pair); transform term t of the tap's three x taps.  The pad half repeats the hi
+                // pieces of (0, 2) over zero lo pieces: the kernel's lane half 1 holds the LO piece of (0, 2)'s voxels at that step, so
+                // one MFMA makes ah.bh + al.bh and the lo pass (bl | 0) ah.bl alone
                 const int step = tap >> 1, t = step / 5;
-                const int tq = (step % 5) < 3 ? (step % 5) * 3 + (tap & 1) : ((step % 5) == 3 ? ((tap & 1) ? -1 : 2) : ((tap & 1) ? 8 : 5));
-                if (tq >= 0) {
+                const int tq = (step % 5) < 3 ? (step % 5) * 3 + (tap & 1) : ((step % 5) == 3 ? 2 : ((tap & 1) ? 8 : 5));
+                fold = (step % 5) == 3 && (tap & 1);
+                {
                     const float g0 = w[((long)(tq * 3 + 0) * cin + ci) * cout + co], g1 = w[((long)(tq * 3 + 1) * cin + ci) * cout + co],
                                 g2 = w[((long)(tq * 3 + 2) * cin + ci) * cout + co];
                     v = t == 0 ? g0 : (t == 1 ? 0.5f * ((g0 + g2) + g1) : (t == 2 ? 0.5f * ((g0 + g2) - g1) : g2));
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(256) void pack_weights_h3v2_kernel(const float* __r
         _Float16* r = out + ((long)par * nrec + rec) * REC;
         const int sw = (pos >> 2) & 3;
         r[(((k >> 3) ^ sw) << 3) + (k & 7)] = hi;
-        r[(((2 + (k >> 3)) ^ sw) << 3) + (k & 7)] = (_Float16)(v - (float)hi);
+        r[(((2 + (k >> 3)) ^ sw) << 3) + (k & 7)] = fold ? (_Float16)0.0f : (_Float16)(v - (float)hi);
     }
 }
 

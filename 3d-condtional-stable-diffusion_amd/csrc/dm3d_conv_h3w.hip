@@ -34,8 +34,8 @@
 // Output channels: column j of column tile ni computes channel 64 ntile + 4 j + ni (the packers' choice — dm3d_pack_weights_h3w and the skip conv's
 // operand fragments —, NOT the direct kernel's 16 ni + j): a lane's four column tiles are four consecutive channels of one voxel, and the
 // epilogue (epilogue_cq, dm3d_conv_h3v2_parts.h) stores 16-byte pieces without a transpose, 256 contiguous bytes per voxel and row group.
-// A step = one pair of (dz, dy) taps (the lane half picks the tap; the tenth tap is a zero pad) x one transform term: 20 steps per
-// 16-channel chunk, TERM-MAJOR (t = step / 5), three passes of 16 MFMAs each (al.bh, ah.bh, ah.bl) on registers; weights by LDS-DMA
+// A step = one pair of (dz, dy) taps (the lane half picks the tap; there is no tenth tap: see the pad step below) x one transform term: 20
+// steps per 16-channel chunk, TERM-MAJOR (t = step / 5), three passes of 16 MFMAs each (al.bh, ah.bh, ah.bl) on registers; weights by LDS-DMA
 // through a ring of four 8 KB buffers, one barrier per step.  Term-major order is what keeps the staging out of the register file: the
 // image's records of term t are dead five steps into the chunk's t-th block, so the NEXT chunk's records of t = 0, 1, 2 are stored as soon
 // as they are computed and only its t = 3 quarter (32 registers) waits for the last step's barrier.
@@ -54,7 +54,11 @@
 // limit leaves on real data (2.38 on zeros; profiles/r03_clocks_under_load.log), and takes 10-21 % less time than the direct kernel from
 // 32 input channels up (profiles/r03_wino_ab.log).  The prologue and the epilogue (the shared one, once per slice) run unoverlapped — one
 // workgroup per CU — and cost 10 % of a 12-chunk workgroup, a quarter of a 4-chunk one: one-chunk launches stay on the direct kernel.
-// A tenth of the MFMAs multiply the zero pad tap (5-9.5 % of the time: profiles/r03_wino_pad_cost.log; DESIGN.md section 8 on removing it).
+// The pad step (tap pair 3 = (0, 2) | pad) runs TWO passes.  Its upper K half used to multiply the voxels of (1, 2) by zero weights in all
+// three passes (5-9.5 % of the time: profiles/r03_wino_pad_cost.log; removing the pad does not fit the LDS, docs/EXPERIMENTS.md).  Now lane
+// half 1 reads the LO piece of tap (0, 2)'s own records and the packer repeats (0, 2)'s hi pieces in the pad half over zero lo pieces:
+// [ah | al] . [bh | bh] = ah.bh + al.bh in one MFMA, [ah | al] . [bl | 0] = ah.bl — 14 passes per term, 56 per chunk, and one set of fragment
+// reads less (the step loop below; nine-shape kernel sum -4.7 %, step 13.34 -> 13.04 ms: profiles/wino_fold_*.{csv,log}).
 #include <cstdlib>
 #include "dm3d_conv_h3v2_parts.h"
 
@@ -86,6 +90,9 @@ __device__ __forceinline__ void static_for(F&& f) {
         static_for<N, I + 1>(f);
     }
 }
+
+// the chunk's executed passes: three per step, two per pad step (s % 5 == 3) — pass A of step s is number pass_of(s) of 56
+constexpr int pass_of(int s) { return 3 * s - (s + 1) / 5; }
 
 // MODE 0: float32 input as is; 1: float32 input through the fused norm + SiLU prologue; 2: x1 already activated and split (DM3D_FMT_H2)
 // The workgroup is PERSISTENT: it walks a list of work items, and the next item's first image and weight steps are staged during the last
@@ -177,7 +184,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_h3w(const ConvArgs p) {
         st_addr = in_addr + (unsigned)(srow * RREC * REC + ((piece ^ ((srow % HH) & 2)) << 3)) * 2u;
         // operand addressing: lane (half, q, row): row = 4 * xpair + y inside a group, half = tap of the pair, q = 8-channel piece.
         // A step's tap pair = two (dz, dy) taps, the lane half picks one: pairs 0-2 = (dz, 0) | (dz, 1) for dz = 0, 1, 2; pair 3 = (0, 2) | the
-        // pad (the voxels of (1, 2) against zero weights); pair 4 = (1, 2) | (2, 2).  So TWO lane-dependent bases serve all five (the swizzled
+        // pad (half 1: the lo piece of (0, 2)'s records, an address made in the step loop from a_pair[1]); pair 4 = (1, 2) | (2, 2).  So TWO lane-dependent bases serve all five (the swizzled
         // slot depends on dy only) and the pair is an immediate: a_pair[0] + dz * DZB, a_pair[1] + {0, DZB}; hi piece (lo: ^ 32)
         const int ay = row & 3, xq = (row >> 2) ^ (row >> 3);           // row group g of the fragment = x-pair g ^ (g >> 1) (0, 1, 3, 2: see the file comment)
         const unsigned a_base = in_addr + (unsigned)((((2 * wave) * HH + ay) * RREC + xq) * (REC * 2));
@@ -423,41 +430,46 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_h3w(const ConvArgs p) {
 #undef DM3D_RB
         }
     };
-    // ---- staging work by gap G = 16 * (3 * step + pass) + g (0 .. 959), at most 8 cycles of vector issue per gap (MI355X_MICROARCH.md,
+    // ---- staging work by gap G = 16 * E + g (0 .. 895), E = the EXECUTED pass of the chunk (0 .. 55: three per step, two per pad step —
+    // pass_of below), at most 8 cycles of vector issue per gap (MI355X_MICROARCH.md,
     // 'vector-instruction ISSUE cost': an MFMA holds the vector issue for 8 of its 16 cycles, a plain VALU for 4, a transcendental for 8,
     // packed float32 VALU far more beside MFMAs — so plain scalar arithmetic, two plain instructions or one transcendental per gap):
-    //   207            the next chunk's keep masks
-    //   208 .. 567     norm + SiLU, 18 gaps per 4 channels (channels 0-3 / 4-7 of halo voxel hx: quad i = 2 hx + h at 208 + 18 i; voxel pair
-    //                  i >> 2 was requested in pass B of step i >> 2, the barrier heads since have waited past it): y = x * scale + shift
-    //                  (2 gaps), z = -y log2 e (2), 2^z (4), + 1 (2), 1 / . (4), y * . (2), the mask (2)
-    //   576 .. 623     term 0: unit u = x-pair u >> 2, channel pair u & 3 at 576 + 3 u: the term, hi = f16(x) and x0 - hi, x1 - hi and lo.
-    //   624 .. 671     term 1                The steps are term-major, so the image's records of term t are dead once every wave is past
-    //   688 .. 735     term 2 (pass 43 on)   the barrier of step 5t + 4: a finished record goes to LDS at the head of the next pass (one or
-    //   880 .. 927     term 3 (passes 55-57) two transient records in registers, not the whole image); only the four t = 3 records wait in
-    //                                        registers for the barrier of the last step (pass 58).
+    //   191            the next chunk's keep masks
+    //   192 .. 551     norm + SiLU, 18 gaps per 4 channels (channels 0-3 / 4-7 of halo voxel hx: quad i = 2 hx + h at 192 + 18 i; voxel pair
+    //                  i >> 2 was requested in the barrier pass of step i >> 2, the barrier heads since have waited past it — pair 0 at the
+    //                  head of pass 12, step 4's): y = x * scale + shift (2 gaps), z = -y log2 e (2), 2^z (4), + 1 (2), 1 / . (4), y * . (2),
+    //                  the mask (2)
+    //   560 .. 607     term 0: unit u = x-pair u >> 2, channel pair u & 3 at 560 + 3 u: the term, hi = f16(x) and x0 - hi, x1 - hi and lo.
+    //   608 .. 655     term 1                The steps are term-major, so the image's records of term t are dead once every wave is past
+    //   656 .. 703     term 2 (pass 41 on)   the barrier of step 5t + 4 (passes 12, 26, 40, 54): a finished record goes to LDS at the head of
+    //   816 .. 863     term 3 (passes 51-53) the next pass (one or two transient records in registers, not the whole image); only the four
+    //                                        t = 3 records wait in registers for the barrier of the last step (pass 54).
+    // (Before the pad step lost its third pass the table ran 16 gaps later up to term 1 and left passes 42, 46-54 empty; what sat in the four
+    // dropped passes — 16 SiLU gaps, 16 of term 1 — moved into those, no gap holds more than before.)
     f32x4 g_y, g_z;
     float g_x0 = 0.f, g_x1 = 0.f, g_r0 = 0.f;
     unsigned int g_a = 0u;
     // ds_write_b128 issued at the head of pass p (the waits count them): the records finished in pass p - 1
+    constexpr int NPASS = 3 * NS - NS / 5;                           // executed passes per chunk: 56
     auto stores_at_head = [&](int p) {
-        p = (p + 60) % 60;
-        if (p == 37 || p == 38 || p == 40 || p == 41 || p == 44 || p == 45) return 2;
-        if (p == 39 || p == 42 || p == 46) return 4;
-        return p == 58 ? 8 : 0;
+        p = (p + NPASS) % NPASS;
+        if (p == 36 || p == 37 || p == 39 || p == 40 || p == 42 || p == 43) return 2;
+        if (p == 38 || p == 41 || p == 44) return 4;
+        return p == 54 ? 8 : 0;
     };
     auto head_stores = [&](const int p) {
-        if (p == 37) store_record(0, 0); else if (p == 38) store_record(0, 1); else if (p == 39) { store_record(0, 2); store_record(0, 3); }
-        else if (p == 40) store_record(1, 0); else if (p == 41) store_record(1, 1); else if (p == 42) { store_record(1, 2); store_record(1, 3); }
-        else if (p == 44) store_record(2, 0); else if (p == 45) store_record(2, 1); else if (p == 46) { store_record(2, 2); store_record(2, 3); }
-        else if (p == 58) {
+        if (p == 36) store_record(0, 0); else if (p == 37) store_record(0, 1); else if (p == 38) { store_record(0, 2); store_record(0, 3); }
+        else if (p == 39) store_record(1, 0); else if (p == 40) store_record(1, 1); else if (p == 41) { store_record(1, 2); store_record(1, 3); }
+        else if (p == 42) store_record(2, 0); else if (p == 43) store_record(2, 1); else if (p == 44) { store_record(2, 2); store_record(2, 3); }
+        else if (p == 54) {
 #pragma unroll
             for (int xt = 0; xt < 4; ++xt) store_record(3, xt);
         }
     };
     auto slot_gap = [&](const int G) {
-        if (G == 207) { chunk_masks(); return; }
-        if (G >= 208 && G < 568) {
-            const int i = (G - 208) / 18, r = (G - 208) % 18;
+        if (G == 191) { chunk_masks(); return; }
+        if (G >= 192 && G < 552) {
+            const int i = (G - 192) / 18, r = (G - 192) % 18;
             const int hx = i >> 1, h = i & 1, col = hx == 0 ? 0 : (hx == 9 ? 2 : 1);
             if (xh2) {
                 // the split pair back to one float32 per channel: (float)hi + (float)lo as ONE v_fma_mix_f32 (hi * 1.0 + lo, both read as
@@ -533,9 +545,9 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_h3w(const ConvArgs p) {
         }
         // (term 3 last, right in front of the barrier that frees its place: its four records then live three passes, not twelve, beside the
         // ten voxels they are made from — the step loop's register peak)
-        if ((G >= 576 && G < 672) || (G >= 688 && G < 736) || (G >= 880 && G < 928)) {
-            const int t = G < 624 ? 0 : (G < 672 ? 1 : (G < 736 ? 2 : 3));
-            const int q = G - (t == 0 ? 576 : (t == 1 ? 624 : (t == 2 ? 688 : 880)));
+        if ((G >= 560 && G < 704) || (G >= 816 && G < 864)) {
+            const int t = G < 608 ? 0 : (G < 656 ? 1 : (G < 704 ? 2 : 3));
+            const int q = G - (t == 0 ? 560 : (t == 1 ? 608 : (t == 2 ? 656 : 816)));
             const int u = q / 3, st = q % 3, xt = u >> 2, j = u & 3, h = j >> 1, c = 2 * (j & 1);
             if (st == 0) {
                 auto d = [&](const int k, const int e) { return va[2 * xt + k][h][c + e]; };
@@ -586,36 +598,58 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_h3w(const ConvArgs p) {
         static_for<NS>([&](auto S_) {
             constexpr int s = decltype(S_)::value, sn = (s + 1) % NS;
             constexpr int t = s / 5, ws = s & (RING - 1), ws1 = (s + 1) & (RING - 1);
-            // ---- pass A: al(s).bh(s), row-group major.  al(s) (requested in pass A of the step before) and bh(s) (in its pass B) are back
-            // once at most the four ah reads of its pass C — and the stores at that pass's head — are out.
+            // The pad step (s % 5 == 3) runs TWO passes, not three: its A fragment is MIXED — lane half 0 holds the hi piece of tap (0, 2),
+            // half 1 the lo piece of the same records — and the weight slice carries bh of (0, 2) in both halves (lo pieces of the pad half:
+            // zero), so mixed.bh = ah.bh + al.bh in one MFMA and mixed.bl = ah.bl.  The mixed fragment travels in the lo set's place
+            // (requested in pass A of the step before); the step has no hi fragment, so the hi set is idle: it takes the lo fragment of the
+            // next step (requested in pass A as always), the mixed set — free row group by row group in the second pass — the next hi
+            // fragment, and the two sets have changed roles behind every pad step (four per chunk: the roles are back at its end).
+            constexpr bool pad = s % 5 == 3, pre_pad = s % 5 == 2, post_pad = s % 5 == 4;
+            constexpr int E = pass_of(s);                                      // this step's pass A among the chunk's executed passes
+            constexpr bool swapped = (((s + 1) / 5) & 1) != 0;
+            h8 (&fh)[4] = swapped ? al : ah;                                   // this step's hi fragment (idle in a pad step)
+            h8 (&fl)[4] = swapped ? ah : al;                                   // its lo fragment (a pad step: the mixed one)
+            h8 (&fl_n)[4] = pad ? fh : fl;                                     // where the next step's lo / hi fragments go
+            h8 (&fh_n)[4] = pad ? fl : fh;
+            // ---- pass A: al(s).bh(s), row-group major (a pad step: mixed.bh).  al(s) (requested in pass A of the step before) and bh(s)
+            // (in its barrier pass) are back once at most the four hi reads of its last pass — and the stores at that pass's head — are
+            // out.  The last pass in front of a pad step requests nothing; a pad step's second pass stores at its head BEFORE it requests
+            // bh(s + 1), and requests the four hi fragments after it.
             {
-                constexpr int n_out = 4;
-                switch (stores_at_head(3 * s - 1)) {
+                constexpr int n_out = pad ? 0 : 4;
+                switch (post_pad ? 0 : stores_at_head(E - 1)) {
                 case 0: DM3D_WAIT_LGKM(n_out); break;
                 case 2: DM3D_WAIT_LGKM(n_out + 2); break;
                 case 4: DM3D_WAIT_LGKM(n_out + 4); break;
                 default: DM3D_WAIT_LGKM(n_out + 8); break;
                 }
             }
-            head_stores(3 * s);
+            head_stores(E);
             __builtin_amdgcn_sched_barrier(0);
             unsigned b_lo = 0u, a_lo = 0u;
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                DM3D_MFMA(t, g >> 2, g & 3, al, bh);
-                slot_gap(16 * (3 * s) + g);
+                DM3D_MFMA(t, g >> 2, g & 3, fl, bh);
+                slot_gap(16 * E + g);
                 if (g == 2) b_lo = lo_of(wb_hi);
                 if (g == 3) { read_b(bl, ws, 0, b_lo); read_b(bl, ws, 1, b_lo); }
-                if (g == 6) a_lo = lo_of(a_hi(sn));
-                if (g == 7) { read_b(bl, ws, 2, b_lo); read_b(bl, ws, 3, b_lo); read_a(al, sn, 0, a_lo); }
-                if (g == 11) { read_a(al, sn, 1, a_lo); read_a(al, sn, 2, a_lo); }
-                if (g == 15) read_a(al, sn, 3, a_lo);
+                if (pre_pad) {
+                    // the mixed fragment's address: half 0 the hi piece of (0, 2) = a_pair[1]; half 1 the lo piece of the same record (its
+                    // a_pair[1] points one z further: the voxels of (1, 2), which the pad half used to multiply by zeros)
+                    if (g == 4) asm volatile("v_subrev_u32 %0, %2, %1" : "=v"(a_lo) : "v"(a_pair[1]), "n"(DZB));
+                    if (g == 5) asm volatile("v_xor_b32 %0, 32, %0" : "+v"(a_lo));
+                    if (g == 6) asm volatile("v_cndmask_b32_e64 %0, %1, %0, %2" : "+v"(a_lo) : "v"(a_pair[1]), "s"(0xffffffff00000000ull));
+                } else if (g == 6) a_lo = lo_of(a_hi(sn));
+                if (g == 7) { read_b(bl, ws, 2, b_lo); read_b(bl, ws, 3, b_lo); read_a(fl_n, sn, 0, a_lo); }
+                if (g == 11) { read_a(fl_n, sn, 1, a_lo); read_a(fl_n, sn, 2, a_lo); }
+                if (g == 15) read_a(fl_n, sn, 3, a_lo);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            // ---- pass B: ah(s).bh(s), column-tile major.  Its head is the step's one barrier: behind this wave's lgkmcnt(4) (its reads of
-            // step s's buffer — bh, bl — are back; al of the next step may be out) and vmcnt(N) (its pieces of step s + 1 have landed) it
-            // frees step s's buffer for the DMA of step s + 4 and makes step s + 1 visible to everyone.  Newer than this wave's pieces of
-            // step s + 1 (issued in B(s - 3)): the pieces of steps s + 2, s + 3 and the halo requests of B(s - 3) .. B(s - 1).
+            // ---- pass B: ah(s).bh(s), column-tile major (a pad step: mixed.bl, row-group major, its last pass).  Its head is the step's one
+            // barrier: behind this wave's lgkmcnt(4) (its reads of step s's buffer — bh, bl — are back; al of the next step may be out) and
+            // vmcnt(N) (its pieces of step s + 1 have landed) it frees step s's buffer for the DMA of step s + 4 and makes step s + 1 visible
+            // to everyone.  Newer than this wave's pieces of step s + 1 (issued in B(s - 3)): the pieces of steps s + 2, s + 3 and the halo
+            // requests of B(s - 3) .. B(s - 1).
             {
                 constexpr int DMA_BEHIND = 2 * WSLOT;
                 const int extra = halo_ops(s - 3) + halo_ops(s - 2) + halo_ops(s - 1);
@@ -636,28 +670,41 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_h3w(const ConvArgs p) {
             __builtin_amdgcn_sched_barrier(0);
             const unsigned w_src = s + RING < NS ? w_cur + (s + RING) * (WPAIR * 2) : w_nxt + (s + RING - NS) * (WPAIR * 2);      // step s + 4
             fetch_w1(w_src, ws, 0);                  // into the buffer step s just left (an LDS-DMA piece costs ~60 cycles of issue: the second one two gaps on)
-            head_stores(3 * s + 1);
+            head_stores(E + 1);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                DM3D_MFMA(t, g & 3, g >> 2, ah, bh);
-                slot_gap(16 * (3 * s + 1) + g);
-                if ((g & 3) == 3) read_b(bh, ws1, g >> 2, wb_hi);
+                if (pad) {
+                    // bh is idle: the next step's weights early (pass A of that step waits for them with the four hi reads out); the
+                    // next hi fragment into the mixed set as its row groups retire
+                    DM3D_MFMA(t, g >> 2, g & 3, fl, bl);
+                    slot_gap(16 * (E + 1) + g);
+                    if (g == 2) { read_b(bh, ws1, 0, wb_hi); read_b(bh, ws1, 1, wb_hi); }
+                    if (g == 3) { read_b(bh, ws1, 2, wb_hi); read_b(bh, ws1, 3, wb_hi); }
+                    if (g == 4) read_a(fh_n, sn, 0, a_hi(sn));
+                    if (g == 7 || g == 11 || g == 15) read_a(fh_n, sn, g >> 2, a_hi(sn));
+                } else {
+                    DM3D_MFMA(t, g & 3, g >> 2, fh, bh);
+                    slot_gap(16 * (E + 1) + g);
+                    if ((g & 3) == 3) read_b(bh, ws1, g >> 2, wb_hi);
+                }
                 if (g == 1) fetch_w1(w_src, ws, 1);
                 if (s < NLD && g == 5) load_voxel(ch_next, 2 * s);
                 if (s < NLD && g == 9) load_voxel(ch_next, 2 * s + 1);
                 if (s == 0 && g == 13) load_chunk_params(ch_next);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            // ---- pass C: ah(s).bl(s), row-group major; requests ah of the next step
-            head_stores(3 * s + 2);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                DM3D_MFMA(t, g >> 2, g & 3, ah, bl);
-                slot_gap(16 * (3 * s + 2) + g);
-                if ((g & 3) == 3) read_a(ah, sn, g >> 2, a_hi(sn));
+            // ---- pass C: ah(s).bl(s), row-group major; requests ah of the next step (not in front of a pad step, which has none)
+            if constexpr (!pad) {
+                head_stores(E + 2);
                 __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    DM3D_MFMA(t, g >> 2, g & 3, fh, bl);
+                    slot_gap(16 * (E + 2) + g);
+                    if (!pre_pad && (g & 3) == 3) read_a(fh, sn, g >> 2, a_hi(sn));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
         });
         w_cur = w_nxt;
