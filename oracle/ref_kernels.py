@@ -4,6 +4,8 @@ entry, written from the comments of ``include/dm3d.h``.
 TEST INFRASTRUCTURE ONLY: the product never imports it.  Every backward formula exists twice: the closed form the header states
 (``*_bwd``) and ``torch.autograd`` applied to the float64 forward (``*_bwd_autograd``); ``tests/test_ref_kernels.py`` holds the two
 against each other, ``tests/test_gpu_train_kernels.py`` holds the HIP kernels against the closed forms.
+The last section restates the inference entries (conv, GEMM, attention, the fused attention-block kernels, the DDPM update) for
+``tests/test_gpu_infer_kernels.py``, on top of the layer functions of ``oracle/ref_torch.py``.
 
 Tensors are torch float64 unless a function says otherwise; the data-movement entries are numpy and keep the dtype they are given
 (they are compared bitwise).
@@ -287,3 +289,130 @@ def adam(w, g, m, v, lr_t, b1, b2, eps):
     m = b1 * m + (1 - b1) * g
     v = b2 * v + (1 - b2) * g * g
     return w - lr_t * m / (torch.sqrt(v) + eps), m, v
+
+
+# ---- inference entries (tests/test_gpu_infer_kernels.py) -----------------------------------------------------------------------------------
+def conv3d_fused(x1, kernel, *, x2=None, ksize=3, stride=1, upsample=False, transpose=False, bias=None, pro=None, vec=None, vec_idx=None,
+                 relu=False, prelu_alpha=None, res=None, relu_out=False, skip=None, post=None):
+    """dm3d_conv3d_ndhwc in float64, in the order include/dm3d.h states: prologue silu(x*scale + shift) on concat(x1, x2) (pro = (scale,
+    shift), each [c] or per sample [batch, c]), the convolution (Conv3D 'same' k1 / k3 at stride 1 or 2, k4 at stride 2; on the nearest-2x
+    upsampled tensor; Conv3DTranspose k4 s2 with a [4,4,4,Cout,Cin] kernel), + bias + vec[vec_idx[b]], ReLU, PReLU (alpha
+    [out_d,out_h,out_w,cout]), + res, + the fused 1x1 skip conv of the raw skip = (x, kernel [cin, cout]), ReLU after the add, and the
+    consumer's silu(v*scale + shift) (post)."""
+    from oracle import ref_torch as rt
+    x = f64(x1) if x2 is None else torch.cat([f64(x1), f64(x2)], -1)
+    B = x.shape[0]
+    if pro is not None:
+        s, t = f64(pro[0]), f64(pro[1])
+        if s.dim() == 2:
+            s, t = s[:, None, None, None, :], t[:, None, None, None, :]
+        x = rt._swish(x * s + t)
+    k = f64(kernel)
+    if transpose:
+        y = rt._conv3d_transpose_k4s2(x, k, None)
+    elif ksize == 4:
+        y = rt._conv3d_k4s2(x, k, None)
+    else:
+        y = rt._conv3d(rt._upsample2(x) if upsample else x, k, None, stride)
+    if bias is not None:
+        y = y + f64(bias)
+    if vec is not None:
+        rows = torch.arange(B) if vec_idx is None else torch.as_tensor(np.asarray(vec_idx)).long()
+        y = y + f64(vec)[rows][:, None, None, None, :y.shape[-1]]
+    if relu:
+        y = torch.relu(y)
+    if prelu_alpha is not None:
+        y = rt._prelu(y, f64(prelu_alpha))
+    if res is not None:
+        y = y + f64(res)
+    if skip is not None:
+        y = y + f64(skip[0]) @ f64(skip[1])
+    if relu_out:
+        y = torch.relu(y)
+    if post is not None:
+        y = rt._swish(y * f64(post[0]) + f64(post[1]))
+    return y
+
+
+def gemm_tn(a, b, *, alpha=1.0, bias=None, bias_along_m=False, kind=ACT_NONE, res=None, res2=None):
+    """out[b][m][n] = act(alpha * sum_k A[b][m][k] B[b][n][k] + bias) + res + res2; a [batch, m, k], b [batch or 1, n, k]."""
+    y = alpha * torch.einsum("bmk,bnk->bmn", f64(a), f64(b).expand(a.shape[0], -1, -1))
+    if bias is not None:
+        y = y + (f64(bias)[:, None] if bias_along_m else f64(bias))
+    y = act(y, kind)
+    for r in (res, res2):
+        if r is not None:
+            y = y + f64(r)
+    return y
+
+
+def attention(q, k, v, scale, res=None):
+    """softmax(q k^T * scale) v + res per sample: q [batch, lq, c]; k, v [batch or 1, lk, c].  ref_torch._attention with the factor
+    passed (it fixes units^-0.5)."""
+    from oracle import ref_torch as rt
+    q, k, v = f64(q), f64(k).expand(q.shape[0], -1, -1), f64(v).expand(q.shape[0], -1, -1)
+    y = rt._attention(q * (scale * float(q.shape[-1]) ** 0.5), k, v, q.shape[-1])
+    return y if res is None else y + f64(res)
+
+
+def mlp_fused(x, w0, b0, w1, b1, res=None, res2=None, tail=None):
+    """Dense_1(relu(Dense_0(x))) + res + res2 with weights [out, in]; tail = (w2, b2, res3): relu(Dense_2(that)) + res3."""
+    y = torch.relu(f64(x) @ f64(w0).T + f64(b0)) @ f64(w1).T + f64(b1)
+    for r in (res, res2):
+        if r is not None:
+            y = y + f64(r)
+    if tail is not None:
+        y = torch.relu(y @ f64(tail[0]).T + f64(tail[1]))
+        if tail[2] is not None:
+            y = y + f64(tail[2])
+    return y
+
+
+def layernorm(x, gamma, beta, eps):
+    x = f64(x)
+    return F.layer_norm(x, (x.shape[-1],), f64(gamma), f64(beta), eps)
+
+
+def attn_front(x, w_in, b_in, w_qk, b_qk, w_v, b_v, norms, eps):
+    """dm3d_attn_front: y = relu(x W_in^T + b_in), n_i = LayerNormalization_i(y), q|k = n1 W_qk^T + b_qk, v^T, q2 = n2 W_qk[:u]^T + b_qk[:u], n3."""
+    u = f64(w_in).shape[0]
+    y = torch.relu(f64(x) @ f64(w_in).T + f64(b_in))
+    n1, n2, n3 = (layernorm(y, g, b, eps) for g, b in norms)
+    return dict(y=y, qk=n1 @ f64(w_qk).T + f64(b_qk), vt=(n1 @ f64(w_v).T + f64(b_v)).T.contiguous(),
+                q2=n2 @ f64(w_qk)[:u].T + f64(b_qk)[:u], n3=n3)
+
+
+def affine_act(x, scale, shift, kind):
+    u = f64(x)
+    if scale is not None:
+        u = u * f64(scale) + f64(shift)
+    return act(u, kind)
+
+
+def vq_assign_f32(z, sim, esq):
+    """float32 numpy, each operation rounded, in the header's order: argmin_k (|z_r|^2 + esq[k]) - 2*sim[r][k], lowest index on ties.
+    |z_r|^2 is the float64 sum rounded once (the kernel's summation order is its own: callers keep candidates apart or exactly tied)."""
+    zz = (np.asarray(z, np.float64) ** 2).sum(-1).astype(np.float32)
+    d = (zz[:, None] + np.asarray(esq, np.float32)[None, :]).astype(np.float32) - (np.float32(2) * np.asarray(sim, np.float32)).astype(np.float32)
+    return np.argmin(d, -1).astype(np.int32), d
+
+
+def ddpm_update(tables, x, eps, t, noise=None):
+    """dm3d_ddpm_update in float64 on the float32 tables (a ref_torch.Betas): (mean, var) of mode 0 and the mode-1 state
+    clip(mean) + sqrt(max(var, 1e-20)) * z with z = 0 where t == 0; t is clamped to the tables first."""
+    from oracle import ref_torch as rt
+
+    class _T:
+        pass
+    tab = _T()
+    for n in rt.Betas.NAMES:
+        setattr(tab, n, f64(getattr(tables, n)))
+    tt = torch.as_tensor(np.clip(np.asarray(t), 0, len(tab.beta) - 1)).long()
+    x5 = f64(x).reshape(x.shape[0], 1, 1, 1, -1)
+    e5 = f64(eps).reshape(x5.shape)
+    mean, var = rt.ddpm_sample(tab, x5, e5, tt)
+    step = None
+    if noise is not None:
+        z = f64(noise).reshape(x5.shape) * (tt > 0).double().reshape(-1, 1, 1, 1, 1)
+        step = rt.ddpm_step(tab, x5, e5, tt, z).reshape(x.shape)
+    return mean.reshape(x.shape), var.reshape(-1), step
