@@ -133,7 +133,7 @@ class ThreshDesc(C.Structure):
     _fields_ = [
         ("x", _f32p), ("eps", _f32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
         ("coef", _f32p), ("rows", C.c_int32), ("pos", _i32p), ("rank", _i32p), ("frac", _f32p), ("smax", _f32p),
-        ("bound", _f32p), ("scratch", C.c_void_p),
+        ("bound", _f32p), ("scratch", C.c_void_p), ("frame", _f32p),
     ]
 
 
@@ -222,6 +222,8 @@ SIGNATURES = {
     "dm3d_ddpm_update": (C.c_int, [C.POINTER(DdpmDesc), C.c_void_p]),
     "dm3d_ddim_update": (C.c_int, [C.POINTER(DdimDesc), C.c_void_p]),
     "dm3d_dpm_update": (C.c_int, [C.POINTER(DpmDesc), C.c_void_p]),
+    "dm3d_ddim_update_frame": (C.c_int, [C.POINTER(DdimDesc), _f32p, C.c_void_p]),
+    "dm3d_dpm_update_frame": (C.c_int, [C.POINTER(DpmDesc), _f32p, C.c_void_p]),
     "dm3d_x0_threshold": (C.c_int, [C.POINTER(ThreshDesc), C.c_void_p]),
     "dm3d_x0_threshold_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "dm3d_edit_update": (C.c_int, [C.POINTER(EditDesc), C.c_void_p]),

@@ -1,6 +1,8 @@
 """Noise schedule and sinusoidal time embedding tables (host side).
 
 ``Betas`` follows reference networks/conditional_dm3d.py:215-235: float64 NumPy arithmetic, stored as float32.
+``Betas(T, zero_terminal_snr=True)`` rescales that schedule to a terminal SNR of zero (Lin et al. 2023, "Common Diffusion Noise Schedules
+and Sample Steps are Flawed", Algorithm 1).
 ``time_embedding_table`` follows ``TimeEmbedding`` (:198-212) in its float32 operation order.
 """
 from __future__ import annotations
@@ -14,16 +16,27 @@ BETAS_FIELDS = ("beta", "alpha", "sqrt_alpha", "alpha_bar", "alpha_bar_prev", "s
 
 
 class Betas:
-    def __init__(self, timesteps: int):
+    def __init__(self, timesteps: int, zero_terminal_snr: bool = False):
+        """``zero_terminal_snr``: shift and scale r = sqrt(alpha_bar) of the linear schedule so that r[T-1] = 0 exactly (x_{T-1} is pure
+        noise, which is what every chain starts from) and r[0] keeps its value; alpha and beta follow from the new alpha_bar, so
+        alpha[T-1] = 0 and beta[T-1] = 1.  The default builds the reference's tables, bitwise."""
         beta = np.linspace(0.0001, 0.02, timesteps)
         alpha = 1 - beta
-        sqrt_alpha = np.sqrt(alpha)
         alpha_bar = np.cumprod(alpha, 0)
+        if zero_terminal_snr:
+            if int(timesteps) < 2:
+                raise ValueError("zero_terminal_snr needs at least two timesteps")
+            r = np.sqrt(alpha_bar)
+            r = r[0] * ((r - r[-1]) / (r[0] - r[-1]))        # r[T-1] - r[T-1] is 0 and the quotient at 0 is 1, both exactly
+            alpha_bar = r ** 2
+            alpha = np.append(alpha_bar[0], alpha_bar[1:] / alpha_bar[:-1])
+            beta = 1 - alpha
+        sqrt_alpha = np.sqrt(alpha)
         alpha_bar_prev = np.append(1.0, alpha_bar[:-1])
         sqrt_alpha_bar = np.sqrt(alpha_bar)
         sqrt_alpha_bar_prev = np.sqrt(alpha_bar_prev)
         sqrt_one_minus_alpha_bar = np.sqrt(1 - alpha_bar)
-        self.timesteps = int(timesteps)
+        self.timesteps, self.zero_terminal_snr = int(timesteps), bool(zero_terminal_snr)
         self.beta = beta.astype(np.float32)
         self.alpha = alpha.astype(np.float32)
         self.sqrt_alpha = sqrt_alpha.astype(np.float32)

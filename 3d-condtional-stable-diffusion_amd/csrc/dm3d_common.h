@@ -72,6 +72,12 @@ __device__ __forceinline__ float dm3d_act(float v, int act) {
 __device__ __forceinline__ float dm3d_x0_estimate(float x, float eps, float sqab, float sq1ab) {
     return __fdiv_rn(__fsub_rn(x, __fmul_rn(sq1ab, eps)), sqab);
 }
+// The same estimate, and ddim_kernel's eps, from the network's output p in its own frame (include/dm3d.h, dm3d_ddim_update_frame): one row
+// (k0x, k0p, kex, kep) of the host's frame table gives x0 = k0x*x + k0p*p and eps = kex*x + kep*p, each as mul, mul, add, each rounded.
+// No division: a v-model's row is (a, -s, s, a), finite where sqrt(alpha_bar) is 0 (the zero-terminal-SNR schedule's last timestep).
+__device__ __forceinline__ float dm3d_frame_estimate(float x, float p, float kx, float kp) {
+    return __fadd_rn(__fmul_rn(kx, x), __fmul_rn(kp, p));
+}
 // The bounded estimate: clamp(x0, -1, 1), or with a dynamic bound s (include/dm3d.h, dm3d_thresh_desc) clamp(x0, -s, s) / s.  A NaN
 // passes; `dyn` is uniform over the block, so the static path is the one instruction pair it always was.
 __device__ __forceinline__ float dm3d_x0_bounded(float x0, bool dyn, float s) {

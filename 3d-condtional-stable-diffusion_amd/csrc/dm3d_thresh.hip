@@ -35,7 +35,7 @@ constexpr int64_t HEAD_BYTES = 2 * (int64_t)sizeof(SelState);
 struct ThreshArgs {
     const float* x; const float* eps;
     long per4;                                     // float4 per sample
-    const float* coef; int rows; const int* pos;
+    const float* coef; const float* frame; int rows; const int* pos;
     const int* rank; const float* frac; const float* smax; float* bound;
     SelState* st1; SelState* st2;                  // [batch]: after pass 1's / pass 2's histogram
     uint32_t* h1; uint32_t* h2; uint32_t* h3;      // [batch][BINS1], [batch][2][BINS2], [batch][2][BINS3]
@@ -108,14 +108,9 @@ __global__ __launch_bounds__(256) void thresh_clear_kernel(u32x4* __restrict__ h
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) h[i] = zero;
 }
 
-__global__ __launch_bounds__(256) void thresh_pass1_kernel(const ThreshArgs p) {
-    __shared__ uint32_t h[BINS1];
-    const int b = blockIdx.y;
-    float sqab, sq1ab;
-    if (!row_clips(p, b, sqab, sq1ab)) return;                           // uniform over the block
-    for (int j = threadIdx.x; j < BINS1; j += 256) h[j] = 0;
-    __syncthreads();
-    const long base = (long)b * p.per4;
+// FRAME: `eps` holds the network's output in its own frame and (ka, kb) = (k0x, k0p) of its row; else (sqrt(ab), sqrt(1-ab)).
+template <bool FRAME>
+__device__ __forceinline__ void pass1_stream(const ThreshArgs& p, uint32_t* h, long base, float ka, float kb) {
     for (long i0 = (long)blockIdx.x * 256; i0 < p.per4; i0 += (long)gridDim.x * 256) {      // uniform: hist_add needs whole waves
         const long i = i0 + threadIdx.x;
         const bool valid = i < p.per4;
@@ -124,11 +119,28 @@ __global__ __launch_bounds__(256) void thresh_pass1_kernel(const ThreshArgs p) {
             const f32x4 x = reinterpret_cast<const f32x4*>(p.x)[base + i];
             const f32x4 e = reinterpret_cast<const f32x4*>(p.eps)[base + i];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) m[k] = __float_as_uint(dm3d_x0_estimate(x[k], e[k], sqab, sq1ab)) & 0x7fffffffu;
+            for (int k = 0; k < 4; ++k)
+                m[k] = __float_as_uint(FRAME ? dm3d_frame_estimate(x[k], e[k], ka, kb) : dm3d_x0_estimate(x[k], e[k], ka, kb)) & 0x7fffffffu;
             reinterpret_cast<u32x4*>(p.mag)[base + i] = m;
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) hist_add(h, valid, m[k] >> (BITS2 + BITS3));
+    }
+}
+
+__global__ __launch_bounds__(256) void thresh_pass1_kernel(const ThreshArgs p) {
+    __shared__ uint32_t h[BINS1];
+    const int b = blockIdx.y;
+    float sqab, sq1ab;
+    if (!row_clips(p, b, sqab, sq1ab)) return;                           // uniform over the block
+    for (int j = threadIdx.x; j < BINS1; j += 256) h[j] = 0;
+    __syncthreads();
+    const long base = (long)b * p.per4;
+    if (p.frame) {                                                       // uniform over the grid; cols 0 and 1 of coef are not used
+        const f32x4 kf = reinterpret_cast<const f32x4*>(p.frame)[min(max(p.pos[b], 0), p.rows - 1)];
+        pass1_stream<true>(p, h, base, kf[0], kf[1]);
+    } else {
+        pass1_stream<false>(p, h, base, sqab, sq1ab);
     }
     __syncthreads();
     merge_hist(p.h1 + (long)b * BINS1, h, BINS1);
@@ -229,12 +241,12 @@ extern "C" int dm3d_x0_threshold(const dm3d_thresh_desc* d, void* stream) {
                  (long long)d->per_sample);
     DM3D_REQUIRE(d->rows > 0, "thresh: rows=%d", d->rows);
     DM3D_REQUIRE(d->rank && d->frac && d->smax && d->bound && d->scratch, "thresh: rank/frac/smax/bound/scratch must be non-null");
-    DM3D_REQUIRE(dm3d_aligned16(d->x) && dm3d_aligned16(d->eps) && dm3d_aligned16(d->coef) && dm3d_aligned16(d->scratch),
-                 "thresh: x/eps/coef/scratch must be 16-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned16(d->x) && dm3d_aligned16(d->eps) && dm3d_aligned16(d->coef) && dm3d_aligned16(d->scratch) &&
+                 dm3d_aligned16(d->frame), "thresh: x/eps/coef/scratch/frame must be 16-byte aligned");
     const int64_t B = d->batch;
     char* s = static_cast<char*>(d->scratch);
     ThreshArgs a{};
-    a.x = d->x; a.eps = d->eps; a.per4 = d->per_sample / 4; a.coef = d->coef; a.rows = d->rows; a.pos = d->pos;
+    a.x = d->x; a.eps = d->eps; a.per4 = d->per_sample / 4; a.coef = d->coef; a.frame = d->frame; a.rows = d->rows; a.pos = d->pos;
     a.rank = d->rank; a.frac = d->frac; a.smax = d->smax; a.bound = d->bound;
     a.st1 = reinterpret_cast<SelState*>(s); a.st2 = a.st1 + B;
     a.h1 = reinterpret_cast<uint32_t*>(s + B * HEAD_BYTES); a.h2 = a.h1 + B * BINS1; a.h3 = a.h2 + B * 2 * BINS2;

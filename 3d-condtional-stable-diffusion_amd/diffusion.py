@@ -12,6 +12,9 @@ exponential moving average of the weights in the optimizer's launch (include/dm3
 ``prediction="v"`` / ``"x0"`` (constructor) reads the network's output as v (Salimans & Ho 2022) or as x0 instead of eps: every chain
 converts it to eps right after the U-Net (include/dm3d.h, dm3d_pred_desc) and train_step fits the matching target;
 ``compile(loss_weighting="min_snr", snr_gamma=)`` weighs each sample's loss by min-SNR-gamma (Hang et al. 2023; dm3d_loss_desc).
+``zero_terminal_snr=True`` (constructor, with ``prediction="v"`` or ``"x0"``) rescales the schedule so that alpha_bar[T-1] = 0 (Lin et
+al. 2023): the DDIM and DPM-Solver++ chains of such a model hand the network's raw output to update kernels that read it in its own
+frame (include/dm3d.h, dm3d_ddim_update_frame), because x0 = (x - s eps) / a has no value at a = 0.
 
 The sampling loop (:559-573) runs with no host synchronisation: the step index lives in device memory, one step
 (U-Net forward + posterior update + index decrement) is captured once into a HIP graph and replayed T times.
@@ -37,8 +40,8 @@ from . import _lib
 from ._lib import DdimDesc, DdpmDesc, DpmDesc, EditDesc, GuideDesc, PredDesc, ThreshDesc, check, lib
 from .betas import BETAS_FIELDS, Betas
 from .schedules import (FLOAT32_MAX, LOSS_WEIGHTINGS, PREDICTIONS, _check_prediction, _host, _indices, context_dropout, ddim_coefficients,
-                        ddim_timesteps, dpm_coefficients, edit_levels, edit_steps, guide_tables, latent_mask, objective_rows,
-                        prediction_table, threshold_rank, threshold_tables)
+                        ddim_timesteps, dpm_coefficients, edit_levels, edit_steps, frame_table, guide_tables, latent_mask,
+                        objective_rows, prediction_table, threshold_rank, threshold_tables)
 from .unet import UNet
 from .weight_sets import WeightSets
 from .weights import UNetConfig
@@ -81,14 +84,19 @@ class DiffusionModel:
     conditional = True
 
     def __init__(self, latent_size, num_embed, latent_channels, vqvae_load_ckpt, args, *, device="cuda", weights=None,
-                 seed=0, precision=None, norm="batch", context_dim=1, prediction="eps"):
+                 seed=0, precision=None, norm="batch", context_dim=1, prediction="eps", zero_terminal_snr=False):
         # conditional_dm3d.py:420-469.  ``args`` is any object with .timesteps .num_gpus .kernel_resize .bs
         # ``prediction``: what the network's output is: "eps" (the reference), "v" = sqrt(a) z - sqrt(1-a) x0 or "x0"
+        # ``zero_terminal_snr``: the schedule rescaled to alpha_bar[T-1] = 0 (betas.py); the DDIM / DPM-Solver++ chains then run in the
+        # network's own frame.  Not with "eps": at alpha_bar = 0 the noise says nothing about x0
         self.prediction = _check_prediction(prediction)
-        self._pred_table = None
+        self.zero_terminal_snr = bool(zero_terminal_snr)
+        if self.zero_terminal_snr and self.prediction == "eps":
+            raise ValueError("zero_terminal_snr needs prediction='v' or 'x0': eps carries no information at alpha_bar = 0")
+        self._pred_table, self._frame_tables = None, {}
         self.loss_weighting, self.snr_gamma = None, 5.0
         self.timesteps = int(args.timesteps)
-        self.b = Betas(self.timesteps)
+        self.b = Betas(self.timesteps, self.zero_terminal_snr)
         self.lc = latent_channels
         # The VQ-VAE bracket (networks/vqvae3d_monai.py; conditional_dm3d.py:425-460) is built lazily on first use of
         # .vqvae_trainer / .encoder / .quantizer / .decoder — Keras, too, creates its weights only on the first call.
@@ -209,13 +217,20 @@ class DiffusionModel:
         resumed run continues the bias correction where it stopped; without them the optimizer starts afresh.  ``ema/...`` entries restore
         the weight average likewise (complete and of the weights' shapes, or the load fails); a checkpoint without them leaves the
         model without an average, and use_ema() back at False.  ``meta/prediction`` (save_weights of a v- or x0-model's .npz) must
-        name this model's ``prediction``, or the load fails before anything is touched; a checkpoint without it loads into any model."""
+        name this model's ``prediction``, or the load fails before anything is touched; a checkpoint without it loads into any model.
+        ``meta/zero_terminal_snr`` (a zero-terminal-SNR model's .npz) follows the same rules against ``zero_terminal_snr``."""
         if "meta/prediction" in sd:
             theirs = str(np.asarray(sd["meta/prediction"]).reshape(-1)[0])
             if theirs != self.prediction:
                 raise ValueError(f"the checkpoint holds a prediction={theirs!r} model, this model was built with "
                                  f"prediction={self.prediction!r}: its output would be read as the wrong quantity")
             sd = {k: v for k, v in sd.items() if k != "meta/prediction"}
+        if "meta/zero_terminal_snr" in sd:
+            theirs = bool(np.asarray(sd["meta/zero_terminal_snr"]).reshape(-1)[0])
+            if theirs != self.zero_terminal_snr:
+                raise ValueError(f"the checkpoint holds a zero_terminal_snr={theirs} model, this model was built with "
+                                 f"zero_terminal_snr={self.zero_terminal_snr}: it was trained on another noise schedule")
+            sd = {k: v for k, v in sd.items() if k != "meta/zero_terminal_snr"}
         self.weights.load(sd, strict)
 
     def _trainable_names(self):
@@ -242,7 +257,8 @@ class DiffusionModel:
         the weight average as ``ema/...`` entries.  The TF-format writer holds no second copy of the weights (a warning says so once).
         ``weights="ema"`` exports the averaged model under the ordinary names instead, without optimizer or ema/ entries, in either
         format: how an averaged model reaches a reference-format TF checkpoint.  An .npz file of a v- or x0-model also carries
-        ``meta/prediction`` (an eps model writes no such entry; the TF format has no place for it)."""
+        ``meta/prediction`` (an eps model writes no such entry; the TF format has no place for it), and a zero-terminal-SNR model's
+        ``meta/zero_terminal_snr``."""
         if weights not in ("live", "ema"):
             raise ValueError(f"weights must be 'live' or 'ema', got {weights!r}")
         if weights == "ema" and not self._has_ema():
@@ -250,6 +266,8 @@ class DiffusionModel:
         state, opt, ema = self.weights.checkpoint(weights)
         if str(path).endswith(".npz"):
             meta = {} if self.prediction == "eps" else {"meta/prediction": np.asarray(self.prediction)}
+            if self.zero_terminal_snr:
+                meta["meta/zero_terminal_snr"] = np.asarray(True)
             np.savez(path, **state, **opt, **ema, **meta)
             return
         if ema and not self._warned_tf_ema:
@@ -379,7 +397,11 @@ class DiffusionModel:
 
     def sample(self, x_t, pred_noise, curr_time_step, shape):
         """conditional_dm3d.py:517-548: returns (posterior_mean, posterior 'log_variance' [B,1,1,1,1]).  ``pred_noise`` is eps,
-        whatever the model's ``prediction``: predict_eps() converts a v- or x0-model's output first."""
+        whatever the model's ``prediction``: predict_eps() converts a v- or x0-model's output first.  A zero-terminal-SNR model has no
+        DDPM posterior at its last timestep: use ddim_step(..., eta=1.0, prediction=...)."""
+        if self.zero_terminal_snr:
+            raise ValueError("sample() is the DDPM posterior, which a zero_terminal_snr model does not have at alpha_bar = 0: "
+                             "use ddim_step(..., eta=1.0, prediction=model.prediction)")
         x_t = torch.as_tensor(x_t, dtype=torch.float32).to(self.device).contiguous()
         eps = torch.as_tensor(pred_noise, dtype=torch.float32).to(self.device).contiguous()
         B = int(shape[0])
@@ -396,16 +418,20 @@ class DiffusionModel:
         return mean, var.reshape(B, 1, 1, 1, 1)
 
     def ddim_step(self, x_t, pred_noise, t, t_prev, eta=0.0, noise=None, *, clip_x0=True, seed=None, dynamic_threshold=None,
-                  threshold_max=None):
+                  threshold_max=None, prediction=None):
         """One DDIM update (include/dm3d.h, dm3d_ddim_desc, mode 0): x_t at timestep ``t`` -> x at ``t_prev`` (-1: the x0
         estimate), the DDIM counterpart of sample().  ``t`` / ``t_prev``: one index or one per sample, -1 <= t_prev < t.
         ``noise`` (optional): z of the step (eta > 0); None draws it from Philox under ``seed`` (None: a fresh key).
         ``dynamic_threshold`` / ``threshold_max``: the x0 estimate is thresholded dynamically, as in generate().
-        ``pred_noise`` is eps, whatever the model's ``prediction``: predict_eps() converts a v- or x0-model's output first."""
+        ``pred_noise`` is eps, whatever the model's ``prediction``: predict_eps() converts a v- or x0-model's output first.
+        ``prediction="v"`` / ``"x0"`` (None: today's call): ``pred_noise`` is the network's raw output in that frame instead and the
+        launch carries the frame rows (schedules.py, frame_table): the form a zero-terminal-SNR model's chain takes, and the only one
+        with a value at alpha_bar[t] = 0."""
         x_t, eps = torch.as_tensor(x_t, dtype=torch.float32), torch.as_tensor(pred_noise, dtype=torch.float32)
         B = x_t.shape[0]
         if eps.shape != x_t.shape or x_t[0].numel() % 4:
             raise ValueError("x_t / pred_noise disagree")
+        self._frame_rules(prediction)
         thr = self._threshold_rules(B, x_t[0].numel(), clip_x0, dynamic_threshold, threshold_max)    # before any device buffer exists
         x_t, eps = x_t.to(self.device).contiguous(), eps.to(self.device).contiguous()
         t, tp = _indices(t, B), _indices(t_prev, B)
@@ -421,10 +447,11 @@ class DiffusionModel:
         tau = torch.from_numpy(t.astype(np.int32)).to(self.device)
         pos = torch.arange(B, dtype=torch.int32, device=self.device)
         out = torch.empty_like(x_t)
-        bound = None if thr is None else self._x0_bound(x_t, eps, coef, pos, thr)
+        frame = self._frame_rows(prediction, t)
+        bound = None if thr is None else self._x0_bound(x_t, eps, coef, pos, thr, frame)
         d = self._ddim_desc(x_t, eps, coef, tau, pos, 0, noise=noise, out=out, seed=self.fresh_seed() if seed is None else seed,
                             x0_bound=bound)
-        check(lib().dm3d_ddim_update(C.byref(d), torch.cuda.current_stream().cuda_stream), "ddim_update")
+        check(self._update_call("ddim_update", d, frame, torch.cuda.current_stream().cuda_stream), "ddim_update")
         return out
 
     def _ddim_table(self, src, dst, eta, clip_x0) -> torch.Tensor:
@@ -434,6 +461,14 @@ class DiffusionModel:
         tab[:, 5] = 1.0 if clip_x0 else 0.0
         return torch.from_numpy(tab.astype(np.float32))
 
+    @staticmethod
+    def _update_call(entry, desc, frame, st):
+        """One launch of dm3d_<entry> (``frame`` None) or of dm3d_<entry>_frame with the frame rows ``frame`` (a device tensor the caller
+        keeps alive): the raw-prediction form of the DDIM and DPM-Solver++ updates."""
+        if frame is None:
+            return getattr(lib(), "dm3d_" + entry)(C.byref(desc), st)
+        return getattr(lib(), "dm3d_" + entry + "_frame")(C.byref(desc), frame.data_ptr(), st)
+
     def _ddim_desc(self, x, eps, coef, tau, pos, mode, noise=None, out=None, t_next=None, t_idx=None, seed=0, x0_bound=None) -> DdimDesc:
         d = _fill(DdimDesc(), x=x, eps=eps, noise=noise, out=out, coef=coef, tau=tau, pos=pos, t_next=t_next, t_idx=t_idx, x0_bound=x0_bound)
         d.batch, d.per_sample, d.rows = x.shape[0], x[0].numel(), coef.shape[0]
@@ -441,16 +476,18 @@ class DiffusionModel:
         return d
 
     def dpm_step(self, x_t, pred_noise, t, t_prev, x0_prev=None, t_before=None, *, clip_x0=True, dynamic_threshold=None,
-                 threshold_max=None):
+                 threshold_max=None, prediction=None):
         """One DPM-Solver++(2M) update (include/dm3d.h, dm3d_dpm_desc, mode 0): x_t at timestep ``t`` -> x at ``t_prev`` (-1: the x0
         estimate), the single-call counterpart of a sampler="dpmpp" chain's step, as ddim_step is of a DDIM chain.  Returns
         (x_next, x0), x0 being this step's (clipped) estimate: the ``x0_prev`` of the next call.  With ``x0_prev`` and ``t_before``
         (the estimate and the timestep of the step before; given together or not at all) the step is second order, else first order
         (= ddim_step at eta = 0 where the x0 estimate is not clipped).  ``t`` / ``t_prev`` / ``t_before``: one index or one per sample, -1 <= t_prev < t < t_before.
         ``dynamic_threshold`` / ``threshold_max``: the x0 estimate (the one returned too) is thresholded dynamically, as in generate().
-        ``pred_noise`` is eps, whatever the model's ``prediction``: predict_eps() converts a v- or x0-model's output first."""
+        ``pred_noise`` is eps, whatever the model's ``prediction``: predict_eps() converts a v- or x0-model's output first.
+        ``prediction="v"`` / ``"x0"`` (None: today's call): ``pred_noise`` is the network's raw output in that frame, as ddim_step."""
         if (x0_prev is None) != (t_before is None):
             raise ValueError("x0_prev and t_before are given together or not at all")
+        self._frame_rules(prediction)
         x_t = torch.as_tensor(x_t, dtype=torch.float32)
         eps = torch.as_tensor(pred_noise, dtype=torch.float32)
         B = x_t.shape[0]
@@ -473,9 +510,10 @@ class DiffusionModel:
         coef = self._dpm_table(t, tp, tb, 2, clip_x0).to(dev)
         pos = torch.arange(B, dtype=torch.int32, device=dev)
         out, x0 = torch.empty_like(x_t), torch.empty_like(x_t)
-        bound = None if thr is None else self._x0_bound(x_t, eps, coef, pos, thr)
+        frame = self._frame_rows(prediction, t)
+        bound = None if thr is None else self._x0_bound(x_t, eps, coef, pos, thr, frame)
         d = self._dpm_desc(x_t, eps, hist, coef, pos, 0, out=out, x0_out=x0, x0_bound=bound)
-        check(lib().dm3d_dpm_update(C.byref(d), torch.cuda.current_stream().cuda_stream), "dpm_update")
+        check(self._update_call("dpm_update", d, frame, torch.cuda.current_stream().cuda_stream), "dpm_update")
         return out, x0
 
     def _dpm_table(self, src, dst, prev, order, clip_x0) -> torch.Tensor:
@@ -506,8 +544,8 @@ class DiffusionModel:
             raise ValueError("dynamic_threshold needs clip_x0=True: it replaces the static clamp of the x0 estimate")
         return threshold_tables(B, per_sample, dynamic_threshold, threshold_max)
 
-    def _thresh_desc(self, x, eps, coef, pos, rank, frac, smax, bound, scratch) -> ThreshDesc:
-        d = _fill(ThreshDesc(), x=x, eps=eps, coef=coef, pos=pos, rank=rank, frac=frac, smax=smax, bound=bound, scratch=scratch)
+    def _thresh_desc(self, x, eps, coef, pos, rank, frac, smax, bound, scratch, frame=None) -> ThreshDesc:
+        d = _fill(ThreshDesc(), x=x, eps=eps, coef=coef, pos=pos, rank=rank, frac=frac, smax=smax, bound=bound, scratch=scratch, frame=frame)
         d.batch, d.per_sample, d.rows = x.shape[0], x[0].numel(), coef.shape[0]
         return d
 
@@ -515,25 +553,28 @@ class DiffusionModel:
         n = int(lib().dm3d_x0_threshold_scratch_bytes(B, per_sample))
         return torch.empty((n + 15) // 16 * 2, dtype=torch.int64, device=self.device)
 
-    def _x0_bound(self, x, eps, coef, pos, tables) -> torch.Tensor:
-        """One dm3d_x0_threshold outside a chain: s [B] of x / eps (device, contiguous) under the coefficient rows coef[pos]."""
+    def _x0_bound(self, x, eps, coef, pos, tables, frame=None) -> torch.Tensor:
+        """One dm3d_x0_threshold outside a chain: s [B] of x / eps (device, contiguous) under the coefficient rows coef[pos] (and the
+        frame rows frame[pos], where eps is a raw prediction)."""
         dev, B = self.device, x.shape[0]
         rank, frac, smax = (torch.from_numpy(t).to(dev) for t in tables)
         bound = torch.empty(B, dtype=torch.float32, device=dev)
-        d = self._thresh_desc(x, eps, coef, pos, rank, frac, smax, bound, self._thresh_scratch(B, x[0].numel()))
+        d = self._thresh_desc(x, eps, coef, pos, rank, frac, smax, bound, self._thresh_scratch(B, x[0].numel()), frame)
         check(lib().dm3d_x0_threshold(C.byref(d), torch.cuda.current_stream().cuda_stream), "x0_threshold")
         return bound
 
-    def x0_threshold(self, x_t, pred_noise, t, dynamic_threshold, threshold_max=None, *, clip_x0=True):
+    def x0_threshold(self, x_t, pred_noise, t, dynamic_threshold, threshold_max=None, *, clip_x0=True, prediction=None):
         """The dynamic threshold of one x0 estimate (include/dm3d.h, dm3d_thresh_desc): s [B] float32, per volume the
         ``dynamic_threshold`` quantile of |x0| with x0 = (x_t - sqrt(1-a) pred_noise) / sqrt(a) at timestep ``t`` (one index or one
         per volume), raised to 1 and capped at ``threshold_max``; the single-call counterpart of a thresholded chain's step, as
         ddim_step is of a DDIM chain.  The quantile is exact (numpy's "linear" interpolation between two order statistics, in
         float32).  ``clip_x0=False`` describes a step that does not clip: s = 1 and nothing is ranked.  ``pred_noise`` is eps, whatever
-        the model's ``prediction``: predict_eps() converts a v- or x0-model's output first."""
+        the model's ``prediction``: predict_eps() converts a v- or x0-model's output first.  ``prediction="v"`` / ``"x0"`` (None: today's
+        call): ``pred_noise`` is the network's raw output in that frame and x0 = k0x x_t + k0p pred_noise, as ddim_step."""
         x_t, eps = torch.as_tensor(x_t, dtype=torch.float32), torch.as_tensor(pred_noise, dtype=torch.float32)
         if x_t.dim() < 2 or eps.shape != x_t.shape or x_t[0].numel() % 4:
             raise ValueError("x_t / pred_noise must share one shape [B, ...] with a multiple of 4 elements per volume")
+        self._frame_rules(prediction)
         B = x_t.shape[0]
         t = _indices(t, B)
         if t.min() < 0 or t.max() >= self.timesteps:
@@ -544,7 +585,7 @@ class DiffusionModel:
         dev = self.device
         coef = self._ddim_table(t, np.full(B, -1, dtype=np.int64), 0.0, bool(clip_x0)).to(dev)
         pos = torch.arange(B, dtype=torch.int32, device=dev)
-        return self._x0_bound(x_t.to(dev).contiguous(), eps.to(dev).contiguous(), coef, pos, tables)
+        return self._x0_bound(x_t.to(dev).contiguous(), eps.to(dev).contiguous(), coef, pos, tables, self._frame_rows(prediction, t))
 
     # -- what the network predicts -------------------------------------------------------------------------------------------------
     def _prediction_table(self) -> torch.Tensor:
@@ -552,6 +593,25 @@ class DiffusionModel:
         if self._pred_table is None:
             self._pred_table = torch.from_numpy(prediction_table(self.b.alpha_bar, self.prediction)).to(self.device)
         return self._pred_table
+
+    def _frame_rules(self, prediction):
+        """The argument rule of the single-call forms' ``prediction=``, checked before any device buffer is made."""
+        if prediction is not None and prediction not in ("v", "x0"):
+            raise ValueError(f"prediction must be None (pred_noise is eps), 'v' or 'x0' (pred_noise is the raw output), got {prediction!r}")
+
+    def _frame_table(self, prediction=None) -> torch.Tensor:
+        """The [T, 4] device table of the updates' ``frame`` for ``prediction`` (None: the model's own; schedules.py,
+        frame_table), made on first use."""
+        prediction = self.prediction if prediction is None else prediction
+        if prediction not in self._frame_tables:
+            self._frame_tables[prediction] = torch.from_numpy(frame_table(self.b.alpha_bar, prediction)).to(self.device)
+        return self._frame_tables[prediction]
+
+    def _frame_rows(self, prediction, t):
+        """The frame rows of a single call at the timesteps ``t`` (host int64 [B]); None without ``prediction``."""
+        if prediction is None:
+            return None
+        return self._frame_table(prediction)[torch.from_numpy(np.ascontiguousarray(t)).to(self.device)].contiguous()
 
     def _pred_desc(self, pred, x, t_idx, out=None) -> PredDesc:
         d = _fill(PredDesc(), pred=pred, x=x, out=out, table=self._prediction_table(), t_idx=t_idx)
@@ -723,6 +783,9 @@ class DiffusionModel:
         threshold_tables()) to those keywords; without them the keywords are what they always were."""
         if kind not in ("ddpm", "ddim", "dpmpp"):
             raise ValueError(f"{what} must be 'ddpm', 'ddim' or 'dpmpp', got {kind!r}")
+        if kind == "ddpm" and self.zero_terminal_snr:
+            raise ValueError("a zero_terminal_snr model has no DDPM ancestral chain (its posterior divides by alpha_bar[T-1] = 0): "
+                             "use sampler='ddim', eta=1.0")
         thr = None
         if dynamic_threshold is not None or threshold_max is not None:
             thr = self._threshold_rules(shape[0], int(np.prod(shape[1:])), clip_x0, dynamic_threshold, threshold_max, kind)
@@ -830,6 +893,9 @@ class DiffusionModel:
         i = 0..S-2 eps = U-Net(x, tau_i) and the deterministic update (sigma = 0, no clip) to tau_{i+1}: S-1 U-Net evaluations.
         Returns x at tau_{S-1}, which sampler='ddim' with eta=0 (clip_x0=False) maps back near ``x0``.  ``seed`` only keys the
         (unused) Philox stream."""
+        if self.zero_terminal_snr:
+            raise ValueError("invert() needs sqrt(1 - a/a') at its last target level, where a' = 0 in a zero_terminal_snr model: "
+                             "invert with a model on the plain schedule, or edit(strength < 1) from q_sample's start")
         x0 = torch.as_tensor(x0, dtype=torch.float32)
         shape = self._sampler_shape(x0.shape)
         taus = ddim_timesteps(self.timesteps, num_steps, timesteps)
@@ -968,6 +1034,7 @@ class Sampler:
     DRAWS = True                              # whether the update takes a z: step(noise=) applies
     edit = None                               # an edit chain: the blend's descriptor
     threshold = None                          # a dynamically thresholded DDIM / DPM-Solver++ chain: its host tables (rank, frac, smax)
+    native = False                            # a zero-terminal-SNR model's chain: the update reads the raw output through frame rows
 
     def __init__(self, model: DiffusionModel, shape, ctx_ids, seed, use_graph, taus=None):
         self.model, self.shape, self.use_graph = model, shape, use_graph
@@ -987,9 +1054,12 @@ class Sampler:
         _plan_buffer(plan, "seed_buf", lambda: torch.zeros(1, dtype=torch.int64, device=model.device))
         plan._owner_gen = getattr(plan, "_owner_gen", 0) + 1
         self._gen = plan._owner_gen
-        self._launch = getattr(lib(), "dm3d_" + self.UPDATE)
         # a v- or x0-model: every row of the plan (a guided chain: both halves) becomes eps right after the U-Net
-        self._pred_d = None if model.prediction == "eps" else model._pred_desc(plan.eps, plan.x, plan.t_idx)
+        # (a zero-terminal-SNR model's chains convert nothing: their update kernels read the raw output through the frame rows)
+        self.native = bool(model.zero_terminal_snr)
+        self._pred_d = None if model.prediction == "eps" or self.native else model._pred_desc(plan.eps, plan.x, plan.t_idx)
+        # the update's entry, bound once: a native chain's takes the frame rows between the descriptor and the stream
+        self._launch = getattr(lib(), "dm3d_" + self.UPDATE + ("_frame" if self.native else ""))
         self.desc = self._desc()
         self.desc.seed_dev = plan.seed_buf.data_ptr()
         self._t = -1                          # host mirror of the device step index; -1: no chain in progress
@@ -1006,8 +1076,9 @@ class Sampler:
     @property
     def graph_kind(self):
         """The step graph's cache key beside the plan: KIND, and a thresholded chain's and a converting chain's own (their steps
-        hold more launches)."""
-        return self.KIND + ("" if self.threshold is None else "+thr") + ("" if getattr(self, "_pred_d", None) is None else "+pred")
+        hold more launches), and a native-frame chain's (its update and threshold carry the frame rows)."""
+        return (self.KIND + ("" if self.threshold is None else "+thr") + ("" if getattr(self, "_pred_d", None) is None else "+pred")
+                + ("+frame" if getattr(self, "native", False) else ""))
 
     def _predict(self, st):
         """Between the U-Net and the guidance: nothing for an eps model; a v- or x0-model's output becomes eps in place, on every row
@@ -1017,6 +1088,10 @@ class Sampler:
 
     def _guide(self, st):
         """Between the U-Net and the update: nothing (a guided chain: eps <- the guided eps)."""
+
+    def _frame(self):
+        """The frame rows the update and the threshold read: the plan's in a zero-terminal-SNR model's chain, else nothing (eps is eps)."""
+        return self.plan.frame if self.native else None
 
     def _threshold(self, st):
         """Between the guidance and the update: the x0 estimate's dynamic bound, where the chain asks for one."""
@@ -1067,7 +1142,7 @@ class Sampler:
         self._predict(st)
         self._guide(st)
         self._threshold(st)
-        check(self._launch(C.byref(desc), st), self.UPDATE)
+        check(self._launch(C.byref(desc), *((self.plan.frame.data_ptr(),) if self.native else ()), st), self.UPDATE)
         if self.edit is not None:
             check(lib().dm3d_edit_update(C.byref(self.edit if edit is None else edit), st), "edit_update")
         self._mirror(st)
@@ -1139,6 +1214,8 @@ class DdimSampler(Sampler):
         for name in ("ddim_tau", "ddim_next"):
             _plan_buffer(plan, name, lambda: torch.zeros(T, dtype=torch.int32, device=dev))
         _plan_buffer(plan, "ddim_pos", lambda: torch.zeros(plan.B, dtype=torch.int32, device=dev))
+        if self.native:
+            _plan_buffer(plan, "frame", lambda: torch.zeros(T, 4, dtype=torch.float32, device=dev))
         if self.threshold is not None and getattr(self, "_thr_desc", None) is None:
             # sized for the plan's rows (a guided chain uses the first half, as of every buffer)
             _plan_buffer(plan, "thr_rank", lambda: torch.zeros(plan.B, dtype=torch.int32, device=dev))
@@ -1147,7 +1224,7 @@ class DdimSampler(Sampler):
             _plan_buffer(plan, "thr_scratch", lambda: self.model._thresh_scratch(plan.B, plan.x[0].numel()))
             h = self._head
             self._thr_desc = self.model._thresh_desc(self.x, h(plan.eps), getattr(plan, coef), h(plan.ddim_pos), h(plan.thr_rank),
-                                                     h(plan.thr_frac), h(plan.thr_smax), h(plan.thr_bound), plan.thr_scratch)
+                                                     h(plan.thr_frac), h(plan.thr_smax), h(plan.thr_bound), plan.thr_scratch, self._frame())
         return plan
 
     def _bound(self):
@@ -1192,6 +1269,8 @@ class DdimSampler(Sampler):
             plan.ddim_next[:n].copy_(torch.from_numpy(np.maximum(dst, 0).astype(np.int32)))
             plan.ddim_pos.fill_(n - 1)
             plan.t_idx.fill_(int(src[n - 1]))
+            if self.native:                           # row r reads the network's output at src[r]
+                plan.frame[:n].copy_(self.model._frame_table()[torch.from_numpy(np.ascontiguousarray(src)).to(self.model.device)])
         if self.threshold is not None:
             for buf, table in zip((plan.thr_rank, plan.thr_frac, plan.thr_smax), self.threshold):
                 self._head(buf).copy_(torch.from_numpy(table))

@@ -65,19 +65,22 @@ def dpm_coefficients(alpha_bar, src, dst, prev, order=2) -> np.ndarray:
     x' = c_x x + c_0 x0 + c_1 x0_prev.  With alpha = sqrt(a), sigma = sqrt(1-a), lambda = log(alpha/sigma) and h = lambda_dst -
     lambda_src: c_x = sigma_dst / sigma_src and A = alpha_dst (1 - e^-h); a first-order row is (c_x, A, 0), a second-order row with
     r = (lambda_src - lambda_prev) / h is (c_x, A (1 + 1/(2r)), -A / (2r)), ``prev[r]`` being the level the step before started from.
-    ``prev[r] < 0`` or ``order`` = 1 makes row r first order; ``dst[r] < 0`` (clean, a' = 1) is (0, 1, 0) exactly."""
+    ``prev[r] < 0`` or ``order`` = 1 makes row r first order; ``dst[r] < 0`` (clean, a' = 1) is (0, 1, 0) exactly.
+    A level with a = 0 (the zero-terminal-SNR schedule's last) has lambda = -inf: a row from it has h = +inf and is
+    (sigma_dst, alpha_dst, 0), first order whatever ``prev`` says; the row after it has r = inf, 1/(2r) = 0 and c_1 = 0, so the
+    history is not read.  No row holds a NaN."""
     if order not in (1, 2):
         raise ValueError(f"solver_order must be 1 or 2, got {order!r}")
     ab = np.asarray(alpha_bar, dtype=np.float64)
     src, dst, prev = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (src, dst, prev))
-    lam = lambda a: 0.5 * (np.log(a) - np.log1p(-a))            # log(sqrt(a) / sqrt(1-a))
+    lam = lambda a: 0.5 * (np.log(a) - np.log1p(-a))            # log(sqrt(a) / sqrt(1-a)); -inf at a = 0
     a_s, a_t, a_p = ab[src], ab[np.maximum(dst, 0)], ab[np.maximum(prev, 0)]
-    h = lam(a_t) - lam(a_s)
-    c_x = np.sqrt((1 - a_t) / (1 - a_s))
-    A = -np.sqrt(a_t) * np.expm1(-h)
-    second = (prev >= 0) & (dst >= 0) & (order == 2)
     with np.errstate(divide="ignore", invalid="ignore"):
-        g = np.where(second, h / (2 * (lam(a_s) - lam(a_p))), 0.0)          # 1 / (2r)
+        h = lam(a_t) - lam(a_s)                                 # +inf from a level with a = 0: expm1(-h) = -1, A = alpha_dst
+        c_x = np.sqrt((1 - a_t) / (1 - a_s))
+        A = -np.sqrt(a_t) * np.expm1(-h)
+        second = (prev >= 0) & (dst >= 0) & (order == 2) & (a_s > 0)
+        g = np.where(second, h / (2 * (lam(a_s) - lam(a_p))), 0.0)          # 1 / (2r); 0 where lambda_prev = -inf
     out = np.stack([c_x, A * (1 + g), -A * g], axis=1)
     out[dst < 0] = (0.0, 1.0, 0.0)
     return out
@@ -144,12 +147,35 @@ def prediction_table(alpha_bar, prediction) -> np.ndarray:
     return np.stack(rows, axis=1).astype(np.float32)
 
 
+def frame_table(alpha_bar, prediction) -> np.ndarray:
+    """float32 [T, 4] rows (k0x, k0p, kex, kep) of the update descriptors' ``frame`` (include/dm3d.h, dm3d_ddim_desc): at every
+    timestep x0 = k0x x_t + k0p pred and eps = kex x_t + kep pred, in float64 from the float32 alpha_bar table the kernels use, rounded
+    once.  With a = sqrt(alpha_bar) and s = sqrt(1 - alpha_bar): "v" gives (a, -s, s, a), no division anywhere; "x0" gives
+    (0, 1, 1/s, -a/s), s > 0 at every timestep; "eps" gives (1/a, -s/a, 0, 1) and is an error where any alpha_bar is 0 (the
+    zero-terminal-SNR schedule: eps carries no information about x0 there)."""
+    _check_prediction(prediction)
+    ab = np.asarray(alpha_bar, dtype=np.float64).reshape(-1)
+    a, s = np.sqrt(ab), np.sqrt(1 - ab)
+    zero, one = np.zeros_like(a), np.ones_like(a)
+    if prediction == "v":
+        rows = (a, -s, s, a)
+    elif prediction == "x0":
+        rows = (zero, one, 1 / s, -a / s)
+    else:
+        if np.any(ab == 0):
+            raise ValueError("the eps frame divides by sqrt(alpha_bar), which is 0 in this schedule: use prediction='v' or 'x0'")
+        rows = (1 / a, -s / a, zero, one)
+    return np.stack(rows, axis=1).astype(np.float32)
+
+
 def objective_rows(alpha_bar, t, prediction, loss_weighting=None, snr_gamma=5.0) -> np.ndarray:
     """float32 [B, 4] rows (a_z, a_0, w, 0) of dm3d_loss_desc (include/dm3d.h) for the timesteps ``t``: the training target is
     a_z noise + a_0 x0 and w the sample's loss weight, in float64 from the float32 alpha_bar table, rounded once.  Targets, with
     a = sqrt(alpha_bar[t]) and s = sqrt(1 - alpha_bar[t]): "eps" (1, 0), "v" (a, -s), "x0" (0, 1).  w = 1 without ``loss_weighting``;
     "min_snr" (Hang et al. 2023) with SNR = alpha_bar / (1 - alpha_bar) and gamma = ``snr_gamma``: min(SNR, gamma) / SNR for eps,
-    min(SNR, gamma) / (SNR + 1) for v and min(SNR, gamma) for x0 (one weight on the x0 error, written in each target's own units)."""
+    min(SNR, gamma) / (SNR + 1) for v and min(SNR, gamma) for x0 (one weight on the x0 error, written in each target's own units).
+    At alpha_bar = 0 (the zero-terminal-SNR schedule's last timestep) the v and x0 rows are finite and SNR = 0: "min_snr" weighs that
+    timestep 0 for both (x_t holds nothing of x0 there), no weighting weighs it 1."""
     _check_prediction(prediction)
     if loss_weighting not in LOSS_WEIGHTINGS:
         raise ValueError(f"loss_weighting must be None or 'min_snr', got {loss_weighting!r}")

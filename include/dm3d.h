@@ -26,7 +26,7 @@ extern "C" {
                                      training entries), 107 (conv wpk_f8: a float8 cross-term form, removed again in 109), 108 (conv wpk_wino: the Winograd-x form), 109 (wpk_f8 and
                                      dm3d_pack_weights_h3f8 are gone; the Winograd-x image pairs its taps differently; dm3d_mlp_fused; conv skip_wpk_frag, gn_stats; dm3d_groupnorm_finalize2), 110 (dm3d_attn_front), 111 (conv split_counters: the Cin split
                                      meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc, dm3d_edit_update / dm3d_edit_desc,
-                                     dm3d_guide_update / dm3d_guide_desc, dm3d_dpm_update / dm3d_dpm_desc and dm3d_x0_threshold / dm3d_thresh_desc were added within 111 (no existing entry changed; dm3d_ddim_desc and dm3d_dpm_desc grew by one trailing optional pointer, x0_bound, which a zeroed descriptor leaves NULL),
+                                     dm3d_guide_update / dm3d_guide_desc, dm3d_dpm_update / dm3d_dpm_desc and dm3d_x0_threshold / dm3d_thresh_desc were added within 111 (no existing entry changed; dm3d_ddim_desc and dm3d_dpm_desc grew by one trailing optional pointer, x0_bound, which a zeroed descriptor leaves NULL; dm3d_thresh_desc then by one, frame, likewise, and dm3d_ddim_update_frame / dm3d_dpm_update_frame are new entries),
                                      and dm3d_pred_to_eps / dm3d_pred_desc and dm3d_objective_loss_grad / dm3d_loss_desc likewise (new entries and structs only): a host built against an older header must be rebuilt */
 
 #define DM3D_OK            0
@@ -427,7 +427,17 @@ int dm3d_ddpm_update(const dm3d_ddpm_desc* d, void* stream);
  *   mode 0 (DiffusionModel.ddim_step): out = res, x untouched.
  *   mode 1 (generate / invert):        x <- res.
  * Graph-capturable without host reads: the row comes from device memory (advanced with dm3d_add_i32 after each step), and with t_idx
- * set the kernel writes t_idx[b] = t_next[pos[b]] (the U-Net row of the next step; the kernel does not read t_idx). */
+ * set the kernel writes t_idx[b] = t_next[pos[b]] (the U-Net row of the next step; the kernel does not read t_idx).
+ * dm3d_ddim_update_frame takes a frame table beside the descriptor (which stays as it is: x0_bound remains its last member).  With
+ * `frame` non-NULL, `eps` holds the network's raw output p in its own frame (v or x0) and row r of the table, (k0x, k0p, kex, kep),
+ * replaces the first line and supplies the model's eps:
+ *                         x0  = k0x*x + k0p*p                           (float32: mul, mul, add, each rounded; no division)
+ *                         eps = kex*x + kep*p                           (likewise)
+ * then clip and res as above.  The host writes the rows in float64 from the float32 alpha_bar table, rounded once (schedules.py,
+ * frame_table): with a = sqrt(alpha_bar), s = sqrt(1 - alpha_bar), v gives (a, -s, s, a) and x0 gives (0, 1, 1/s, -a/s), both finite
+ * at alpha_bar = 0 (the zero-terminal-SNR schedule's last timestep, where the eps frame's 1/a is not).  Columns 0 and 1 of `coef` are
+ * not read then.  frame: [rows][4] device, 16-byte aligned, indexed by the same clamped row as `coef`; NULL is dm3d_ddim_update itself
+ * (the arithmetic and results of before). */
 typedef struct dm3d_ddim_desc {
     float* x;                   /* [batch, per_sample] x at tau[pos[b]] (updated in place in mode 1) */
     const float* eps;           /* predicted noise */
@@ -449,6 +459,7 @@ typedef struct dm3d_ddim_desc {
 } dm3d_ddim_desc;
 
 int dm3d_ddim_update(const dm3d_ddim_desc* d, void* stream);
+int dm3d_ddim_update_frame(const dm3d_ddim_desc* d, const float* frame, void* stream);
 
 /* ---- DPM-Solver++(2M) step over a timestep schedule (Lu et al. 2022, "DPM-Solver++", Algorithm 2) -------------------------------
  * A second-order multistep solver of the sampling ODE in the data-prediction form: one U-Net evaluation per step, as DDIM, plus the
@@ -467,7 +478,11 @@ int dm3d_ddim_update(const dm3d_ddim_desc* d, void* stream);
  *                                     every row is then computed as a first-order row).
  *   mode 1 (generate / edit):         x <- res, hist <- x0.
  * Graph-capturable without host reads, as dm3d_ddim_desc: the row comes from device memory and, with t_idx set, the kernel writes
- * t_idx[b] = t_next[pos[b]] (the kernel does not read t_idx). */
+ * t_idx[b] = t_next[pos[b]] (the kernel does not read t_idx).
+ * dm3d_dpm_update_frame takes a frame table beside the descriptor, as dm3d_ddim_update_frame (NULL: dm3d_dpm_update itself).  With it,
+ * `eps` holds the network's raw output p (v or x0) and x0 = k0x*x + k0p*p (float32: mul, mul, add, each rounded) from
+ * row r of the frame table replaces the first line; columns 0 and 1 of `coef` are not read, columns 2 and 3 of the
+ * frame row neither (the solver needs no eps).  A row from a level with alpha_bar = 0 is (sigma_t, alpha_t, 0): lambda_s = -inf, h = +inf. */
 typedef struct dm3d_dpm_desc {
     float* x;                   /* [batch, per_sample] x at the row's level (updated in place in mode 1) */
     const float* eps;           /* predicted noise */
@@ -486,6 +501,7 @@ typedef struct dm3d_dpm_desc {
 } dm3d_dpm_desc;
 
 int dm3d_dpm_update(const dm3d_dpm_desc* d, void* stream);
+int dm3d_dpm_update_frame(const dm3d_dpm_desc* d, const float* frame, void* stream);
 
 /* ---- Dynamic thresholding of the x0 estimate (Saharia et al. 2022, "Imagen", section 2.3) ------------------------------------------
  * Between the U-Net (or the guidance) and dm3d_ddim_update / dm3d_dpm_update: the bound s the update clamps and divides the x0
@@ -504,7 +520,9 @@ int dm3d_dpm_update(const dm3d_dpm_desc* d, void* stream);
  * carry both ranks.  The counts are integers summed with atomics, whose result does not depend on the order of arrival, and nothing
  * else is shared between blocks: runs repeat bitwise.  Graph-capturable without host reads: rank, frac and smax are device tables (one
  * captured graph serves every ratio and cap), and every launch clears its own counters (a kernel) before it counts.
- * scratch: dm3d_x0_threshold_scratch_bytes(batch, per_sample) bytes, 16-byte aligned; contents need not survive between launches. */
+ * scratch: dm3d_x0_threshold_scratch_bytes(batch, per_sample) bytes, 16-byte aligned; contents need not survive between launches.
+ * With `frame` set (the update's own table), `eps` holds the raw prediction p and x0 = k0x*x + k0p*p with the update kernels' device
+ * function (mul, mul, add, each rounded): the magnitudes ranked stay bitwise the values clamped.  Only column 5 of `coef` is read then. */
 typedef struct dm3d_thresh_desc {
     const float* x;             /* [batch, per_sample] x at the row's level */
     const float* eps;           /* predicted noise (a guided chain: the guided one) */
@@ -517,6 +535,8 @@ typedef struct dm3d_thresh_desc {
     const float* smax;          /* [batch] device: the cap on s, >= 1 */
     float* bound;               /* [batch] device, out: s */
     void* scratch;              /* device: histograms, select states and the stashed magnitudes */
+    const float* frame;         /* optional [rows][4] device, 16-byte aligned: the table of dm3d_ddim_update_frame.  NULL (a zeroed
+                                   descriptor): `eps` is eps, the arithmetic and results of before. */
 } dm3d_thresh_desc;
 
 int64_t dm3d_x0_threshold_scratch_bytes(int32_t batch, int64_t per_sample);
