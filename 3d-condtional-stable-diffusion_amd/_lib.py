@@ -129,6 +129,10 @@ class DpmDesc(C.Structure):
     ]
 
 
+class DpmSdeDesc(C.Structure):
+    _fields_ = DpmDesc._fields_ + [("noise", _f32p), ("tau", _i32p), ("seed", C.c_uint64), ("seed_dev", C.c_void_p)]
+
+
 class ThreshDesc(C.Structure):
     _fields_ = [
         ("x", _f32p), ("eps", _f32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
@@ -224,6 +228,8 @@ SIGNATURES = {
     "dm3d_dpm_update": (C.c_int, [C.POINTER(DpmDesc), C.c_void_p]),
     "dm3d_ddim_update_frame": (C.c_int, [C.POINTER(DdimDesc), _f32p, C.c_void_p]),
     "dm3d_dpm_update_frame": (C.c_int, [C.POINTER(DpmDesc), _f32p, C.c_void_p]),
+    "dm3d_dpm_sde_update": (C.c_int, [C.POINTER(DpmSdeDesc), C.c_void_p]),
+    "dm3d_dpm_sde_update_frame": (C.c_int, [C.POINTER(DpmSdeDesc), _f32p, C.c_void_p]),
     "dm3d_x0_threshold": (C.c_int, [C.POINTER(ThreshDesc), C.c_void_p]),
     "dm3d_x0_threshold_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "dm3d_edit_update": (C.c_int, [C.POINTER(EditDesc), C.c_void_p]),

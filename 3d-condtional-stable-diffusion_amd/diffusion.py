@@ -6,7 +6,8 @@ Keyword-only extensions: ``x_T=`` / ``noise=`` inject the ran
 selects the in-kernel Philox stream, ``use_graph=`` toggles HIP-graph replay of the step; ``guidance_scale=`` /
 ``negative_context=`` / ``guidance_rescale=`` turn on classifier-free guidance (include/dm3d.h, dm3d_guide_desc);
 ``dynamic_threshold=`` / ``threshold_max=`` replace the static clamp of the x0 estimate by Imagen's dynamic thresholding in the DDIM
-and DPM-Solver++ chains (include/dm3d.h, dm3d_thresh_desc).  Training extensions, off by default: ``compile(ema_decay=)`` keeps an
+and DPM-Solver++ chains (include/dm3d.h, dm3d_thresh_desc); ``sampler="dpmpp_sde"`` / ``sde_eta=`` is the stochastic form of the
+DPM-Solver++(2M) chain (include/dm3d.h, dm3d_dpm_sde_desc).  Training extensions, off by default: ``compile(ema_decay=)`` keeps an
 exponential moving average of the weights in the optimizer's launch (include/dm3d.h, dm3d_adam_ema) and ``use_ema()`` samples from it;
 ``compile(context_dropout=, null_context=)`` trains the unconditional branch that classifier-free guidance is defined against.
 ``prediction="v"`` / ``"x0"`` (constructor) reads the network's output as v (Salimans & Ho 2022) or as x0 instead of eps: every chain
@@ -37,10 +38,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DdimDesc, DdpmDesc, DpmDesc, EditDesc, GuideDesc, PredDesc, ThreshDesc, check, lib
+from ._lib import DdimDesc, DdpmDesc, DpmDesc, DpmSdeDesc, EditDesc, GuideDesc, PredDesc, ThreshDesc, check, lib
 from .betas import BETAS_FIELDS, Betas
 from .schedules import (FLOAT32_MAX, LOSS_WEIGHTINGS, PREDICTIONS, _check_prediction, _host, _indices, context_dropout, ddim_coefficients,
-                        ddim_timesteps, dpm_coefficients, edit_levels, edit_steps, frame_table, guide_tables, latent_mask,
+                        ddim_timesteps, dpm_coefficients, dpm_sde_coefficients, edit_levels, edit_steps, frame_table, guide_tables, latent_mask,
                         objective_rows, prediction_table, threshold_rank, threshold_tables)
 from .unet import UNet
 from .weight_sets import WeightSets
@@ -401,7 +402,7 @@ class DiffusionModel:
         DDPM posterior at its last timestep: use ddim_step(..., eta=1.0, prediction=...)."""
         if self.zero_terminal_snr:
             raise ValueError("sample() is the DDPM posterior, which a zero_terminal_snr model does not have at alpha_bar = 0: "
-                             "use ddim_step(..., eta=1.0, prediction=model.prediction)")
+                             "use ddim_step(..., eta=1.0, prediction=model.prediction), or the chain sampler='dpmpp_sde'")
         x_t = torch.as_tensor(x_t, dtype=torch.float32).to(self.device).contiguous()
         eps = torch.as_tensor(pred_noise, dtype=torch.float32).to(self.device).contiguous()
         B = int(shape[0])
@@ -476,7 +477,7 @@ class DiffusionModel:
         return d
 
     def dpm_step(self, x_t, pred_noise, t, t_prev, x0_prev=None, t_before=None, *, clip_x0=True, dynamic_threshold=None,
-                 threshold_max=None, prediction=None):
+                 threshold_max=None, prediction=None, sde_eta=None, noise=None, seed=None):
         """One DPM-Solver++(2M) update (include/dm3d.h, dm3d_dpm_desc, mode 0): x_t at timestep ``t`` -> x at ``t_prev`` (-1: the x0
         estimate), the single-call counterpart of a sampler="dpmpp" chain's step, as ddim_step is of a DDIM chain.  Returns
         (x_next, x0), x0 being this step's (clipped) estimate: the ``x0_prev`` of the next call.  With ``x0_prev`` and ``t_before``
@@ -484,9 +485,15 @@ class DiffusionModel:
         (= ddim_step at eta = 0 where the x0 estimate is not clipped).  ``t`` / ``t_prev`` / ``t_before``: one index or one per sample, -1 <= t_prev < t < t_before.
         ``dynamic_threshold`` / ``threshold_max``: the x0 estimate (the one returned too) is thresholded dynamically, as in generate().
         ``pred_noise`` is eps, whatever the model's ``prediction``: predict_eps() converts a v- or x0-model's output first.
-        ``prediction="v"`` / ``"x0"`` (None: today's call): ``pred_noise`` is the network's raw output in that frame, as ddim_step."""
+        ``prediction="v"`` / ``"x0"`` (None: today's call): ``pred_noise`` is the network's raw output in that frame, as ddim_step.
+        ``sde_eta`` (None: today's launch of dm3d_dpm_update): the step of a sampler="dpmpp_sde" chain at that eta instead (include/dm3d.h,
+        dm3d_dpm_sde_desc, mode 0; finite, >= 0; 0 is the ODE step bitwise).  ``noise`` (optional): z of the step; None draws it from
+        Philox under ``seed`` (None: a fresh key).  ``noise`` / ``seed`` need ``sde_eta``."""
         if (x0_prev is None) != (t_before is None):
             raise ValueError("x0_prev and t_before are given together or not at all")
+        if sde_eta is None and (noise is not None or seed is not None):
+            raise ValueError("noise / seed belong to the stochastic step: give sde_eta")
+        sde_eta = self._sde_eta_rules(sde_eta)
         self._frame_rules(prediction)
         x_t = torch.as_tensor(x_t, dtype=torch.float32)
         eps = torch.as_tensor(pred_noise, dtype=torch.float32)
@@ -504,17 +511,41 @@ class DiffusionModel:
             if x0_prev.shape != x_t.shape:
                 raise ValueError("x0_prev must have x_t's shape")
         thr = self._threshold_rules(B, x_t[0].numel(), clip_x0, dynamic_threshold, threshold_max)
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32)
+            if noise.shape != x_t.shape:
+                raise ValueError("noise must have x_t's shape")
         dev = self.device
         x_t, eps = x_t.to(dev).contiguous(), eps.to(dev).contiguous()
         hist = None if x0_prev is None else x0_prev.to(dev).contiguous()
-        coef = self._dpm_table(t, tp, tb, 2, clip_x0).to(dev)
+        if sde_eta is None:
+            coef = self._dpm_table(t, tp, tb, 2, clip_x0).to(dev)
+        else:
+            coef = self._dpm_sde_table(t, tp, tb, 2, clip_x0, sde_eta).to(dev)
         pos = torch.arange(B, dtype=torch.int32, device=dev)
         out, x0 = torch.empty_like(x_t), torch.empty_like(x_t)
         frame = self._frame_rows(prediction, t)
         bound = None if thr is None else self._x0_bound(x_t, eps, coef, pos, thr, frame)
-        d = self._dpm_desc(x_t, eps, hist, coef, pos, 0, out=out, x0_out=x0, x0_bound=bound)
-        check(self._update_call("dpm_update", d, frame, torch.cuda.current_stream().cuda_stream), "dpm_update")
+        st = torch.cuda.current_stream().cuda_stream
+        if sde_eta is None:
+            d = self._dpm_desc(x_t, eps, hist, coef, pos, 0, out=out, x0_out=x0, x0_bound=bound)
+            check(self._update_call("dpm_update", d, frame, st), "dpm_update")
+            return out, x0
+        tau = torch.from_numpy(t.astype(np.int32)).to(dev)
+        d = self._dpm_sde_desc(x_t, eps, hist, coef, tau, pos, 0, noise=None if noise is None else noise.to(dev).contiguous(), out=out,
+                               x0_out=x0, seed=self.fresh_seed() if seed is None else seed, x0_bound=bound)
+        check(self._update_call("dpm_sde_update", d, frame, st), "dpm_sde_update")
         return out, x0
+
+    @staticmethod
+    def _sde_eta_rules(sde_eta):
+        """The argument rule of ``sde_eta``, checked before any device buffer is made: None stays None, else a finite float >= 0."""
+        if sde_eta is None:
+            return None
+        eta = float(sde_eta)
+        if not (eta >= 0 and np.isfinite(eta)):              # (a NaN fails the comparison too)
+            raise ValueError(f"sde_eta must be finite and >= 0, got {sde_eta!r}")
+        return eta
 
     def _dpm_table(self, src, dst, prev, order, clip_x0) -> torch.Tensor:
         """The [n, 8] float32 coefficient rows of dm3d_dpm_desc, from the float32 alpha_bar table the kernels use, in float64."""
@@ -523,6 +554,23 @@ class DiffusionModel:
         tab[:, 2:5] = dpm_coefficients(self.b.alpha_bar, src, dst, prev, order)
         tab[:, 5] = 1.0 if clip_x0 else 0.0
         return torch.from_numpy(tab.astype(np.float32))
+
+    def _dpm_sde_table(self, src, dst, prev, order, clip_x0, eta) -> torch.Tensor:
+        """The [n, 8] float32 coefficient rows of dm3d_dpm_sde_desc: _dpm_table's with c_z in column 6."""
+        tab = np.zeros((len(src), 8), dtype=np.float64)
+        tab[:, :2] = ddim_coefficients(self.b.alpha_bar, src, dst)[:, :2]
+        rows = dpm_sde_coefficients(self.b.alpha_bar, src, dst, prev, order, eta)
+        tab[:, 2:5], tab[:, 6] = rows[:, :3], rows[:, 3]
+        tab[:, 5] = 1.0 if clip_x0 else 0.0
+        return torch.from_numpy(tab.astype(np.float32))
+
+    def _dpm_sde_desc(self, x, eps, hist, coef, tau, pos, mode, noise=None, out=None, x0_out=None, t_next=None, t_idx=None, seed=0,
+                      x0_bound=None) -> DpmSdeDesc:
+        d = _fill(DpmSdeDesc(), x=x, eps=eps, hist=hist, out=out, x0_out=x0_out, coef=coef, pos=pos, t_next=t_next, t_idx=t_idx,
+                  x0_bound=x0_bound, noise=noise, tau=tau)
+        d.batch, d.per_sample, d.rows, d.mode = x.shape[0], x[0].numel(), coef.shape[0], mode
+        d.seed = int(seed) & (2 ** 64 - 1)
+        return d
 
     def _dpm_desc(self, x, eps, hist, coef, pos, mode, out=None, x0_out=None, t_next=None, t_idx=None, x0_bound=None) -> DpmDesc:
         d = _fill(DpmDesc(), x=x, eps=eps, hist=hist, out=out, x0_out=x0_out, coef=coef, pos=pos, t_next=t_next, t_idx=t_idx, x0_bound=x0_bound)
@@ -538,7 +586,7 @@ class DiffusionModel:
             if threshold_max is not None:
                 raise ValueError("threshold_max needs dynamic_threshold")
             return None
-        if kind is not None and kind not in ("ddim", "dpmpp"):
+        if kind is not None and kind not in ("ddim", "dpmpp", "dpmpp_sde"):
             raise ValueError("dynamic_threshold / threshold_max belong to sampler='ddim' and 'dpmpp'")
         if not clip_x0:
             raise ValueError("dynamic_threshold needs clip_x0=True: it replaces the static clamp of the x0 estimate")
@@ -762,51 +810,62 @@ class DiffusionModel:
 
     def sampler(self, shape, context_value=None, *, seed=None, use_graph=True, kind="ddpm", num_steps=None, timesteps=None,
                 eta=0.0, clip_x0=True, guidance_scale=None, negative_context=None, guidance_rescale=0.0, solver_order=2,
-                lower_order_final=True, dynamic_threshold=None, threshold_max=None) -> "Sampler":
+                lower_order_final=True, dynamic_threshold=None, threshold_max=None, sde_eta=None) -> "Sampler":
         """The state of one generate() call: plan, tables, context rows and the captured step graph.  There is one live
         Sampler per (batch, context mode): creating another one for the same plan retires the older (its step() raises).
         ``kind="ddim"``: a DDIM chain over ``ddim_timesteps(T, num_steps, timesteps)`` (S steps) with ``eta`` / ``clip_x0``.
         ``kind="dpmpp"``: a DPM-Solver++(2M) chain over the same schedule with ``clip_x0`` / ``solver_order`` / ``lower_order_final``.
+        ``kind="dpmpp_sde"``: its stochastic form at ``sde_eta`` (None: 1.0), as generate(); step(noise=) injects a step's z.
         ``guidance_scale`` / ``negative_context`` / ``guidance_rescale``: a guided chain, as generate().
         ``dynamic_threshold`` / ``threshold_max``: a dynamically thresholded DDIM or DPM-Solver++ chain, as generate()."""
         shape = self._sampler_shape(shape)
         taus, opts = self._solver_rules(kind, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final,
-                                        dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape)
+                                        dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape, sde_eta=sde_eta)
         ctx, guide = self._contexts(shape[0], context_value, guidance_scale, negative_context, guidance_rescale)
-        return _CHAINS[kind, False, bool(guide)](self, shape, ctx, seed, use_graph, taus, **opts, **guide)
+        return _chain_class(kind, False, bool(guide))(self, shape, ctx, seed, use_graph, taus, **opts, **guide)
 
     def _solver_rules(self, kind, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise=None, what="sampler kind",
-                      dynamic_threshold=None, threshold_max=None, shape=None):
-        """The argument rules of the three solvers, checked before any plan or device buffer is made.  Returns the chain's schedule
+                      dynamic_threshold=None, threshold_max=None, shape=None, sde_eta=None):
+        """The argument rules of the solvers ("dpmpp_sde": the DPM-Solver++ chain in its stochastic mode, ``sde_eta`` among its
+        keywords), checked before any plan or device buffer is made.  Returns the chain's schedule
         (``kind="ddpm"``: every timestep) and the keywords its sampler class takes besides.  ``noise``: the caller's injected z.
         ``dynamic_threshold`` / ``threshold_max`` (with the chain's ``shape``) add ``threshold=`` (the host tables of
         threshold_tables()) to those keywords; without them the keywords are what they always were."""
-        if kind not in ("ddpm", "ddim", "dpmpp"):
-            raise ValueError(f"{what} must be 'ddpm', 'ddim' or 'dpmpp', got {kind!r}")
+        if kind not in ("ddpm", "ddim", "dpmpp", "dpmpp_sde"):
+            raise ValueError(f"{what} must be 'ddpm', 'ddim', 'dpmpp' or 'dpmpp_sde', got {kind!r}")
         if kind == "ddpm" and self.zero_terminal_snr:
             raise ValueError("a zero_terminal_snr model has no DDPM ancestral chain (its posterior divides by alpha_bar[T-1] = 0): "
-                             "use sampler='ddim', eta=1.0")
+                             "use sampler='ddim', eta=1.0, or sampler='dpmpp_sde'")
+        sde = kind == "dpmpp_sde"
+        if sde_eta is not None and not sde:
+            raise ValueError("sde_eta belongs to sampler='dpmpp_sde'")
+        if sde:
+            sde_eta = self._sde_eta_rules(1.0 if sde_eta is None else sde_eta)
         thr = None
         if dynamic_threshold is not None or threshold_max is not None:
             thr = self._threshold_rules(shape[0], int(np.prod(shape[1:])), clip_x0, dynamic_threshold, threshold_max, kind)
         thr = {} if thr is None else dict(threshold=thr)
-        if kind != "dpmpp" and (solver_order != 2 or lower_order_final is not True):
-            raise ValueError("solver_order / lower_order_final belong to sampler='dpmpp'")
+        if kind not in ("dpmpp", "dpmpp_sde") and (solver_order != 2 or lower_order_final is not True):
+            raise ValueError("solver_order / lower_order_final belong to sampler='dpmpp' and 'dpmpp_sde'")
         if kind == "ddpm":
             if num_steps is not None or timesteps is not None or eta != 0.0 or clip_x0 is not True:
                 raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim' and 'dpmpp'")
             return np.arange(self.timesteps, dtype=np.int64), {}
-        if kind == "dpmpp":
+        if kind in ("dpmpp", "dpmpp_sde"):
+            if eta != 0 and sde:
+                raise ValueError("eta is DDIM's keyword and must stay 0 for sampler='dpmpp_sde': its noise level is sde_eta")
             if eta != 0:
-                raise ValueError("sampler='dpmpp' is the deterministic solver: eta must be 0 (the SDE variant is not implemented)")
+                raise ValueError("sampler='dpmpp' is the deterministic solver: eta must be 0 (sampler='dpmpp_sde' is its stochastic form)")
             if solver_order not in (1, 2):
                 raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
-            if noise is not None:
-                raise ValueError("sampler='dpmpp' draws no noise: noise= does not apply (x_T= sets the start)")
+            if noise is not None and not sde:
+                raise ValueError("sampler='dpmpp' draws no noise: noise= does not apply (x_T= sets the start; sampler='dpmpp_sde' draws)")
         taus = ddim_timesteps(self.timesteps, num_steps, timesteps)
         if not eta >= 0:
             raise ValueError("eta must be >= 0")
-        if kind == "dpmpp":
+        if sde:
+            thr = dict(thr, sde_eta=sde_eta)
+        if kind in ("dpmpp", "dpmpp_sde"):
             return taus, dict(clip_x0=clip_x0, solver_order=solver_order, lower_order_final=lower_order_final, **thr)
         return taus, dict(eta=eta, clip_x0=clip_x0, **thr)
 
@@ -829,7 +888,7 @@ class DiffusionModel:
     def generate(self, shape=(1, 16, 16, 16, 16), last_step=0, context_value=None, *, x_T=None, noise=None, seed=None,
                  use_graph=True, steps=None, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0, clip_x0=True,
                  guidance_scale=None, negative_context=None, guidance_rescale=0.0, solver_order=2, lower_order_final=True,
-                 dynamic_threshold=None, threshold_max=None):
+                 dynamic_threshold=None, threshold_max=None, sde_eta=None):
         """conditional_dm3d.py:550-575.  For shape[0] > 1 the single context row is broadcast to every sample.
         ``seed`` (optional): Philox key of x_T and of every step's noise; None (default) draws a fresh key per call, as the
         reference draws fresh tf.random.normal noise, an integer makes the call reproducible.
@@ -845,6 +904,12 @@ class DiffusionModel:
         extrapolating over it costs more than the second order gains.  ``solver_order=1`` makes every step first order: DDIM at
         eta = 0 wherever the x0 estimate is not clipped (where it is, DDIM carries the model's eps on, this solver the eps the
         clipped estimate implies).  eta must be 0, last_step 0, and ``noise`` does not apply (the chain draws none; ``x_T`` / ``seed`` set the start).
+        ``sampler="dpmpp_sde"``: the stochastic form of that solver (Lu et al. 2022, appendix; k-diffusion's dpmpp_2m_sde; include/dm3d.h,
+        dm3d_dpm_sde_desc): every step but the one to the clean sample adds c_z z, and x and the x0 estimates weigh accordingly.
+        ``sde_eta`` >= 0 (None: 1.0, the paper's solver; 0: the "dpmpp" chain bitwise) sets the noise level; ``eta`` stays DDIM's keyword
+        and must be 0.  ``solver_order`` / ``lower_order_final`` / ``clip_x0``, guidance and thresholding apply as for "dpmpp";
+        ``noise`` is [S, *shape] with row k the z of the step from tau_k, as for DDIM (such a call runs eagerly); ``sde_eta`` with any
+        other sampler is an error.  A zero_terminal_snr model runs the chain natively: its first step is alpha_t x0 + sigma_t z.
         ``guidance_scale`` = w (None, the default: no guidance, today's path): classifier-free guidance, for either sampler.  Every
         step evaluates the U-Net under ``context_value`` and under ``negative_context`` (one id or one per volume; None stands for
         compile()'s ``null_context`` and is an error on a model without one) in one pass over a plan of 2 B rows and continues from eps_neg + w (eps_pos - eps_neg);
@@ -862,12 +927,14 @@ class DiffusionModel:
             raise ValueError("last_step out of range")
         shape = self._sampler_shape(shape)
         taus, opts = self._solver_rules(sampler, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise,
-                                        dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape)
+                                        dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape, sde_eta=sde_eta)
+        if noise is not None and sampler != "ddpm" and tuple(noise.shape) != (len(taus),) + shape:      # (_run repeats it for every chain)
+            raise ValueError(f"noise must be [S={len(taus)}, *shape] for sampler={sampler!r}")
         if sampler != "ddpm" and last_step != 0:
             raise ValueError(f"sampler={sampler!r} runs whole chains: last_step must be 0")
         ctx, guide = self._contexts(shape[0], context_value, guidance_scale, negative_context, guidance_rescale)
         self.weights.refresh()
-        smp = _CHAINS[sampler, False, bool(guide)](self, shape, ctx, seed, use_graph and noise is None, taus, **opts, **guide)
+        smp = _chain_class(sampler, False, bool(guide))(self, shape, ctx, seed, use_graph and noise is None, taus, **opts, **guide)
         return self._run(smp, (x_T,), noise, steps=steps, last_step=last_step)
 
     def _run(self, smp, start, noise=None, known_noise=None, steps=None, last_step=0):
@@ -878,7 +945,7 @@ class DiffusionModel:
         if noise is not None:
             noise = torch.as_tensor(noise, dtype=torch.float32).to(self.device)
             if tuple(noise.shape) != (n,) + smp.shape:
-                raise ValueError("noise must be [timesteps, *shape]" if smp.SOLVER == "ddpm" else f"noise must be [S={n}, *shape] for sampler='ddim'")
+                raise ValueError("noise must be [timesteps, *shape]" if smp.SOLVER == "ddpm" else f"noise must be [S={n}, *shape] for sampler={smp.SOLVER!r}")
         smp.reset(*start)
         row = lambda rows, i: None if rows is None else rows[i].contiguous()
         count = n - last_step if steps is None else min(int(steps), n - last_step)
@@ -907,7 +974,7 @@ class DiffusionModel:
     def edit(self, x0, context_value=None, *, mask=None, strength=1.0, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0,
              clip_x0=True, seed=None, use_graph=True, noise=None, known_noise=None, steps=None, guidance_scale=None,
              negative_context=None, guidance_rescale=0.0, solver_order=2, lower_order_final=True, dynamic_threshold=None,
-             threshold_max=None):
+             threshold_max=None, sde_eta=None):
         """Inpainting and image-to-image editing (SDEdit) of latents ``x0`` [B, S, S, S, C]; returns latents of x0's shape.
 
         ``mask`` (1 = regenerate, 0 = keep, in [0, 1]; None: regenerate everything) is pooled to the latent by latent_mask() and
@@ -926,12 +993,13 @@ class DiffusionModel:
         ``sampler="dpmpp"`` / ``solver_order`` / ``lower_order_final``: the DPM-Solver++(2M) chain of generate() over the kept
         schedule; its first step (from x_T or from the q_sample start) is first order, the blend runs after every update as for the
         other samplers, and the solver's history keeps the model's own x0 estimate, unblended.  ``noise`` does not apply.
+        ``sampler="dpmpp_sde"`` / ``sde_eta``: the stochastic form of that chain, as generate(); ``noise`` / ``known_noise`` as for DDIM.
         ``dynamic_threshold`` / ``threshold_max``: dynamic thresholding of the chain's x0 estimate over the whole volume, as generate();
         the blend follows the thresholded update."""
         x0 = torch.as_tensor(x0, dtype=torch.float32)
         shape = self._sampler_shape(x0.shape)
         sched, opts = self._solver_rules(sampler, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise, what="sampler",
-                                         dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape)
+                                         dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape, sde_eta=sde_eta)
         n = edit_steps(strength, len(sched))
         full, sched = n == len(sched), sched[:n]
         mask = None if mask is None else latent_mask(mask, shape)
@@ -948,7 +1016,7 @@ class DiffusionModel:
         if known_noise is not None:
             known_noise = torch.as_tensor(known_noise, dtype=torch.float32).to(dev)
         eager = noise is not None or known_noise is not None
-        smp = _CHAINS[sampler, True, bool(guide)](self, shape, ctx, seed, use_graph and not eager, sched, full, **opts, **guide)
+        smp = _chain_class(sampler, True, bool(guide))(self, shape, ctx, seed, use_graph and not eager, sched, full, **opts, **guide)
         start = (x0.to(dev), keep, None if known_noise is None else known_noise[n].contiguous())
         return self._run(smp, start, noise, known_noise, steps)
 
@@ -1035,6 +1103,7 @@ class Sampler:
     edit = None                               # an edit chain: the blend's descriptor
     threshold = None                          # a dynamically thresholded DDIM / DPM-Solver++ chain: its host tables (rank, frac, smax)
     native = False                            # a zero-terminal-SNR model's chain: the update reads the raw output through frame rows
+    sde_eta = None                            # a DPM-Solver++ chain in its stochastic mode: the noise level (None: the ODE solver)
 
     def __init__(self, model: DiffusionModel, shape, ctx_ids, seed, use_graph, taus=None):
         self.model, self.shape, self.use_graph = model, shape, use_graph
@@ -1076,8 +1145,9 @@ class Sampler:
     @property
     def graph_kind(self):
         """The step graph's cache key beside the plan: KIND, and a thresholded chain's and a converting chain's own (their steps
-        hold more launches), and a native-frame chain's (its update and threshold carry the frame rows)."""
-        return (self.KIND + ("" if self.threshold is None else "+thr") + ("" if getattr(self, "_pred_d", None) is None else "+pred")
+        hold more launches), a native-frame chain's (its update and threshold carry the frame rows) and a stochastic DPM-Solver++
+        chain's (another update entry and descriptor)."""
+        return (self.KIND + ("" if getattr(self, "sde_eta", None) is None else "+sde") + ("" if self.threshold is None else "+thr") + ("" if getattr(self, "_pred_d", None) is None else "+pred")
                 + ("+frame" if getattr(self, "native", False) else ""))
 
     def _predict(self, st):
@@ -1282,19 +1352,36 @@ class DpmSampler(DdimSampler):
     It shares the DDIM chain's frame: the plan's schedule tables (ddim_tau / ddim_next / ddim_pos) and row counter, with a
     coefficient table of its own (plan.dpm_coef, rows (sqrt(a), sqrt(1-a), c_x, c_0, c_1, clip, 0, 0)) and the history buffer
     plan.dpm_hist, the x0 estimate of the step before.  reset() rewrites the tables, so one captured graph serves every schedule,
-    order and lower_order_final.  The history is never cleared: the first row of every chain has c_1 = 0 and does not read it."""
+    order and lower_order_final.  The history is never cleared: the first row of every chain has c_1 = 0 and does not read it.
+
+    ``sde_eta`` (None: the ODE solver) makes the chain, and every chain built on it, the stochastic form (generate(sampler="dpmpp_sde")):
+    the update is dm3d_dpm_sde_update on a dm3d_dpm_sde_desc that adds the DDIM chain's plan.ddim_tau and the plan's Philox key, the rows
+    (..., c_z in column 6) come from dpm_sde_coefficients into a table of their own, plan.dpm_sde_coef, and step(noise=) applies.  eta,
+    like schedule and order, is table contents: one captured graph, of a kind of its own ("+sde"), serves every sde_eta."""
 
     KIND = SOLVER = "dpmpp"
     UPDATE = "dpm_update"
     DRAWS = False
 
-    def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, clip_x0=True, solver_order=2, lower_order_final=True, threshold=None):
+    def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, clip_x0=True, solver_order=2, lower_order_final=True, threshold=None,
+                 sde_eta=None):
         if solver_order not in (1, 2):
             raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
         self.solver_order, self.lower_order_final = int(solver_order), bool(lower_order_final)
+        if sde_eta is not None:
+            self.sde_eta = model._sde_eta_rules(sde_eta)
+            self.UPDATE, self.DRAWS, self.SOLVER = "dpm_sde_update", True, "dpmpp_sde"
         super().__init__(model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=clip_x0, threshold=threshold)
 
     def _desc(self, noise=None):
+        if self.sde_eta is not None:
+            plan = self._tables("dpm_sde_coef")
+            _plan_buffer(plan, "dpm_hist", lambda: torch.zeros_like(plan.x))
+            d = self.model._dpm_sde_desc(self.x, self._head(plan.eps), self._head(plan.dpm_hist), plan.dpm_sde_coef, plan.ddim_tau,
+                                         plan.ddim_pos, 1, noise=noise, t_next=plan.ddim_next, t_idx=plan.t_idx, seed=self.seed,
+                                         x0_bound=self._bound())
+            d.seed_dev = plan.seed_buf.data_ptr()
+            return d
         plan = self._tables("dpm_coef")
         _plan_buffer(plan, "dpm_hist", lambda: torch.zeros_like(plan.x))
         return self.model._dpm_desc(self.x, self._head(plan.eps), self._head(plan.dpm_hist), plan.dpm_coef, plan.ddim_pos, 1,
@@ -1312,6 +1399,8 @@ class DpmSampler(DdimSampler):
         return prev
 
     def _coefficients(self, src, dst):
+        if self.sde_eta is not None:
+            return self.plan.dpm_sde_coef, self.model._dpm_sde_table(src, dst, self._prev(), self.solver_order, self.clip_x0, self.sde_eta)
         return self.plan.dpm_coef, self.model._dpm_table(src, dst, self._prev(), self.solver_order, self.clip_x0)
 
 
@@ -1448,8 +1537,13 @@ class GuidedDpmEditSampler(_GuidedChain, DpmEditSampler):
     KIND = "dpmpp-edit-cfg"
 
 
-# (generate()'s ``sampler=``, edit chain?, guided?) -> the chain's class: the one place that picks it
+# (generate()'s ``sampler=``, edit chain?, guided?) -> the chain's class: the one place that picks it ("dpmpp_sde" is the "dpmpp"
+# classes' stochastic mode, not a class: _chain_class maps the name)
 _CHAINS = {(c.SOLVER, issubclass(c, _EditChain), issubclass(c, _GuidedChain)): c
            for c in (Sampler, DdimSampler, DpmSampler, EditSampler, DdimEditSampler, DpmEditSampler, GuidedSampler, GuidedDdimSampler,
                      GuidedDpmSampler, GuidedEditSampler, GuidedDdimEditSampler, GuidedDpmEditSampler)}
 
+
+def _chain_class(sampler, edit, guided):
+    """The chain class of a public sampler name: "dpmpp_sde" runs the "dpmpp" classes (with ``sde_eta`` among their keywords)."""
+    return _CHAINS["dpmpp" if sampler == "dpmpp_sde" else sampler, edit, guided]

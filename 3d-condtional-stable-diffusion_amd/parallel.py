@@ -71,7 +71,9 @@ def generate_sharded(model, global_shape, last_step: int = 0, context_value=None
     keywords of generate() are forwarded; ``guidance_scale`` / ``guidance_rescale`` / ``negative_context`` given per volume of the
     global batch are sliced per rank as ``context_value`` is; so are ``dynamic_threshold`` / ``threshold_max``.  ``negative_context``
     left out stands for the model's ``null_context`` on every rank, as in generate().  Which weights a rank samples from is the
-    model's own use_ema() setting; the averages of data-parallel replicas agree as their weights do, so no collective carries them."""
+    model's own use_ema() setting; the averages of data-parallel replicas agree as their weights do, so no collective carries them.
+    ``sampler="dpmpp_sde"`` / ``sde_eta`` are forwarded like every sampler keyword: one noise level for the whole batch, each rank's
+    draws under its own key."""
     shape = tuple(int(s) for s in global_shape)
     dist_on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)

@@ -86,6 +86,42 @@ def dpm_coefficients(alpha_bar, src, dst, prev, order=2) -> np.ndarray:
     return out
 
 
+def dpm_sde_coefficients(alpha_bar, src, dst, prev, order=2, eta=1.0) -> np.ndarray:
+    """float64 [n, 4] rows (c_x, c_0, c_1, c_z) of the stochastic DPM-Solver++(2M) steps src[r] -> dst[r] (include/dm3d.h,
+    dm3d_dpm_sde_desc): x' = c_x x + c_0 x0 + c_1 x0_prev + c_z z.  With alpha, sigma, lambda and h as dpm_coefficients and
+    ``eta`` >= 0 (1: the solver of Lu et al. 2022, 0: the ODE solver): c_x = (sigma_dst / sigma_src) e^(-eta h),
+    A = alpha_dst (1 - e^(-(1 + eta) h)) and c_z = sigma_dst sqrt(1 - e^(-2 eta h)); a first-order row is (c_x, A, 0, c_z), a
+    second-order row (c_x, A (1 + g), -A g, c_z) with dpm_coefficients' g = 1 / (2r) (the midpoint form).  ``prev``, ``order`` and the row
+    to clean, (0, 1, 0, 0) exactly, follow dpm_coefficients.  A row from a level with a = 0 (h = +inf) is written out, never through
+    0 * inf: (sigma_dst, alpha_dst, 0, 0) at eta = 0 and (0, alpha_dst, 0, sigma_dst) at eta > 0; the row after it has g = 0.  At
+    eta = 0 columns 0-2 are dpm_coefficients' own (that function is called) and column 3 is 0.  No row holds a NaN."""
+    eta = float(eta)
+    if not (eta >= 0 and math.isfinite(eta)):                   # (a NaN fails the comparison too)
+        raise ValueError(f"sde_eta must be finite and >= 0, got {eta}")
+    ode = dpm_coefficients(alpha_bar, src, dst, prev, order)
+    out = np.zeros((len(ode), 4), dtype=np.float64)
+    out[:, :3] = ode
+    if eta == 0:
+        return out
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    src, dst, prev = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (src, dst, prev))
+    lam = lambda a: 0.5 * (np.log(a) - np.log1p(-a))            # dpm_coefficients' expressions
+    a_s, a_t, a_p = ab[src], ab[np.maximum(dst, 0)], ab[np.maximum(prev, 0)]
+    blind = a_s == 0                                            # lambda_src = -inf: nothing of x survives, all of z enters
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h = np.where(blind, 0.0, lam(a_t) - lam(a_s))           # (a finite stand-in: the blind rows are written out below)
+        c_x = np.sqrt((1 - a_t) / (1 - a_s)) * np.exp(-eta * h)
+        A = -np.sqrt(a_t) * np.expm1(-(1 + eta) * h)
+        c_z = np.sqrt(1 - a_t) * np.sqrt(-np.expm1(-2 * eta * h))
+        second = (prev >= 0) & (dst >= 0) & (order == 2) & ~blind
+        g = np.where(second, h / (2 * (lam(a_s) - lam(a_p))), 0.0)          # 1 / (2r); 0 where lambda_prev = -inf
+    out = np.stack([c_x, A * (1 + g), -A * g, c_z], axis=1)
+    zero = np.zeros_like(a_t)
+    out[blind] = np.stack([zero, np.sqrt(a_t), zero, np.sqrt(1 - a_t)], axis=1)[blind]
+    out[dst < 0] = (0.0, 1.0, 0.0, 0.0)
+    return out
+
+
 def threshold_rank(per_sample: int, ratio) -> tuple:
     """(i, f) of the dynamic threshold's quantile (include/dm3d.h, dm3d_thresh_desc): q = ratio (N-1) in float64, i = floor(q) and
     f = float32(q - i), the weight of v_{i+1} in the interpolation between the order statistics v_i and v_{i+1} of N = per_sample

@@ -27,7 +27,7 @@ extern "C" {
                                      dm3d_pack_weights_h3f8 are gone; the Winograd-x image pairs its taps differently; dm3d_mlp_fused; conv skip_wpk_frag, gn_stats; dm3d_groupnorm_finalize2), 110 (dm3d_attn_front), 111 (conv split_counters: the Cin split
                                      meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc, dm3d_edit_update / dm3d_edit_desc,
                                      dm3d_guide_update / dm3d_guide_desc, dm3d_dpm_update / dm3d_dpm_desc and dm3d_x0_threshold / dm3d_thresh_desc were added within 111 (no existing entry changed; dm3d_ddim_desc and dm3d_dpm_desc grew by one trailing optional pointer, x0_bound, which a zeroed descriptor leaves NULL; dm3d_thresh_desc then by one, frame, likewise, and dm3d_ddim_update_frame / dm3d_dpm_update_frame are new entries),
-                                     and dm3d_pred_to_eps / dm3d_pred_desc and dm3d_objective_loss_grad / dm3d_loss_desc likewise (new entries and structs only): a host built against an older header must be rebuilt */
+                                     and dm3d_pred_to_eps / dm3d_pred_desc, dm3d_objective_loss_grad / dm3d_loss_desc and dm3d_dpm_sde_update(_frame) / dm3d_dpm_sde_desc likewise (new entries and structs only): a host built against an older header must be rebuilt */
 
 #define DM3D_OK            0
 #define DM3D_EINVAL       -1      /* bad argument (shape, alignment, null pointer) */
@@ -502,6 +502,45 @@ typedef struct dm3d_dpm_desc {
 
 int dm3d_dpm_update(const dm3d_dpm_desc* d, void* stream);
 int dm3d_dpm_update_frame(const dm3d_dpm_desc* d, const float* frame, void* stream);
+
+/* ---- Stochastic DPM-Solver++(2M) step: the SDE form (Lu et al. 2022, "DPM-Solver++", appendix; k-diffusion's dpmpp_2m_sde) -----------
+ * dm3d_dpm_update's multistep update of the data-prediction form with one noise term per step.  With alpha, sigma, lambda and
+ * h = lambda_t - lambda_s as there and eta >= 0 (1: the paper's solver, 0: the ODE solver dm3d_dpm_update):
+ *   c_x = (sigma_t/sigma_s)*exp(-eta*h)      A = alpha_t*(1 - exp(-(1+eta)*h))      c_z = sigma_t*sqrt(1 - exp(-2*eta*h))
+ *   first order:   res = c_x*x + A*x0 + c_z*z
+ *   second order:  res = c_x*x + A*(1 + g)*x0 - A*g*hist + c_z*z,    g = 1/(2r) = h / (2*(lambda_s - lambda_p))   (the midpoint form)
+ *   to "clean" (a' = 1): res = x0, no noise, always first order
+ *   from a level with alpha_bar = 0 (h = +inf): res = sigma_t*x + alpha_t*x0 at eta = 0 and alpha_t*x0 + sigma_t*z at eta > 0
+ * x0 and its clip are dm3d_dpm_update's.  The host folds a step into one row (c_x, c_0, c_1, c_z), in float64 from the float32
+ * alpha_bar table, rounded once to float32 (schedules.py, dpm_sde_coefficients):
+ *   res = ((c_x*x + c_0*x0) + c_1*hist) + c_z*z         (float32, in that order, each operation rounded)
+ * where c_1 == 0 hist is not read and its add is skipped; where c_z == 0 nothing is drawn, `noise` is not read and the last add is
+ * skipped: such a row is dm3d_dpm_update's result bitwise.  Then hist <- x0 (the clipped estimate).  z = noise (if given) or Philox
+ * N(0,1) keyed by (seed, tau[r], element) as in dm3d_ddim_update, under a stream constant of this kernel's own (never ddim_update's
+ * draws).  Modes, graph capture, t_idx / t_next and x0_bound: as dm3d_dpm_desc.  dm3d_dpm_sde_update_frame takes a frame table beside
+ * the descriptor, as dm3d_dpm_update_frame (NULL: dm3d_dpm_sde_update itself). */
+typedef struct dm3d_dpm_sde_desc {
+    float* x;                   /* [batch, per_sample] x at the row's level (updated in place in mode 1) */
+    const float* eps;           /* predicted noise */
+    float* hist;                /* the x0 estimate of the step before, same shape (mode 1: required, replaced by this step's) */
+    float* out;                 /* mode 0: the result, same shape */
+    float* x0_out;              /* mode 0, optional: this step's x0 estimate, same shape */
+    int32_t batch; int64_t per_sample;     /* batch <= 65535, per_sample % 4 == 0 */
+    const float* coef;          /* [rows][8] device: sqrt(a), sqrt(1-a), c_x, c_0, c_1, clip (nonzero: clamp x0), c_z, 0 */
+    int32_t rows;               /* pos[b] is clamped to [0, rows) before any table is indexed */
+    const int32_t* pos;         /* [batch] device: the row of each sample */
+    const int32_t* t_next;      /* [rows] device, optional: the timestep the step after row r evaluates */
+    int32_t* t_idx;             /* [batch] device, optional: receives t_next[pos[b]] */
+    int32_t mode;
+    const float* x0_bound;      /* optional [batch] device: the dynamic threshold s, as dm3d_dpm_desc.x0_bound.  NULL: the static clamp. */
+    const float* noise;         /* optional injected z, same shape as x (read only where the row's c_z != 0) */
+    const int32_t* tau;         /* [rows] device, required: the timestep each row steps from (the Philox counter) */
+    uint64_t seed;
+    const uint64_t* seed_dev;   /* optional: the Philox key is read from device memory instead of `seed` (as dm3d_ddim_desc) */
+} dm3d_dpm_sde_desc;
+
+int dm3d_dpm_sde_update(const dm3d_dpm_sde_desc* d, void* stream);
+int dm3d_dpm_sde_update_frame(const dm3d_dpm_sde_desc* d, const float* frame, void* stream);
 
 /* ---- Dynamic thresholding of the x0 estimate (Saharia et al. 2022, "Imagen", section 2.3) ------------------------------------------
  * Between the U-Net (or the guidance) and dm3d_ddim_update / dm3d_dpm_update: the bound s the update clamps and divides the x0
