@@ -6,6 +6,9 @@ TEST INFRASTRUCTURE ONLY: the product never imports it.  Every backward formula 
 against each other, ``tests/test_gpu_train_kernels.py`` holds the HIP kernels against the closed forms.
 The last section restates the inference entries (conv, GEMM, attention, the fused attention-block kernels, the DDPM update) for
 ``tests/test_gpu_infer_kernels.py``, on top of the layer functions of ``oracle/ref_torch.py``.
+After it come the sampler entries (the DDIM / DPM-Solver++ / stochastic DPM-Solver++ updates, the dynamic threshold, the edit blend, the
+guidance, pred_to_eps and the objective loss) for ``tests/test_gpu_sampler_kernels.py``: numpy, each with an ``order`` switch between
+the header's individually rounded float32 operations (the kernels match it bit for bit) and the same formula in float64.
 
 Tensors are torch float64 unless a function says otherwise; the data-movement entries are numpy and keep the dtype they are given
 (they are compared bitwise).
@@ -416,3 +419,161 @@ def ddpm_update(tables, x, eps, t, noise=None):
         z = f64(noise).reshape(x5.shape) * (tt > 0).double().reshape(-1, 1, 1, 1, 1)
         step = rt.ddpm_step(tab, x5, e5, tt, z).reshape(x.shape)
     return mean.reshape(x.shape), var.reshape(-1), step
+
+
+# ---- the sampler entries (tests/test_gpu_sampler_kernels.py) --------------------------------------------------------------------------
+# numpy, [batch, per_sample] arrays and the raw tables the descriptors point to.  order="f32": every operation the header lists is one
+# numpy operation on float32 operands, so each is rounded on its own, in the header's order (IEEE add, sub, mul and div are correctly
+# rounded on either side: the result is the kernel's bit for bit).  order="f64": the same formula on the same float32 table values in
+# float64.  Branches are taken on the table values, as the kernels take them; a value a branch does not read is never mixed in.
+def _dt(order):
+    return {"f32": np.float32, "f64": np.float64}[order]
+
+
+def _rows_of(pos, rows):
+    return np.clip(np.asarray(pos, np.int64), 0, rows - 1)
+
+
+def _col(table, r, c, dt):
+    """Column c of the rows r of a table, as a [batch, 1] array of dt."""
+    return np.asarray(table)[r, c].astype(dt).reshape(-1, 1)
+
+
+def x0_estimate(x, p, coef, pos, frame=None, order="f32"):
+    """The raw x0 estimate and the model's eps of the update kernels.  Without a frame: x0 = (x - sqrt(1-a)*p) / sqrt(a) (mul, sub, div),
+    eps = p.  With a frame row (k0x, k0p, kex, kep): x0 = k0x*x + k0p*p, eps = kex*x + kep*p (mul, mul, add each)."""
+    dt = _dt(order)
+    r = _rows_of(pos, len(coef))
+    x, p = np.asarray(x).astype(dt), np.asarray(p).astype(dt)
+    with np.errstate(all="ignore"):
+        if frame is None:
+            return (x - _col(coef, r, 1, dt) * p) / _col(coef, r, 0, dt), p
+        return (_col(frame, r, 0, dt) * x + _col(frame, r, 1, dt) * p, _col(frame, r, 2, dt) * x + _col(frame, r, 3, dt) * p)
+
+
+def x0_bounded(x0, clip, bound=None):
+    """clamp(x0, -1, 1) on the rows with clip, or clamp(x0, -s, s) / s with the dynamic bound s [batch]; a NaN passes."""
+    dt = x0.dtype.type
+    clip = np.asarray(clip, bool).reshape(-1, 1)
+    with np.errstate(all="ignore"):
+        if bound is None:
+            lim = np.minimum(np.maximum(x0, dt(-1)), dt(1))
+        else:
+            s = np.asarray(bound).astype(dt).reshape(-1, 1)
+            lim = np.minimum(np.maximum(x0, -s), s) / s
+    return np.where(clip, lim, x0)
+
+
+def ddim_update(x, eps, coef, pos, noise=None, frame=None, x0_bound=None, order="f32"):
+    """dm3d_ddim_update[_frame]: res = (a_x0*x0 + a_eps*eps) + sigma*z with z = noise where the row's sigma != 0 and 0 elsewhere."""
+    dt = _dt(order)
+    r = _rows_of(pos, len(coef))
+    x0, ek = x0_estimate(x, eps, coef, pos, frame, order)
+    x0 = x0_bounded(x0, np.asarray(coef)[r, 5] != 0, x0_bound)
+    sigma = _col(coef, r, 4, dt)
+    z = np.zeros_like(x0) if noise is None else np.where(sigma != 0, np.asarray(noise).astype(dt), dt(0))
+    with np.errstate(all="ignore"):
+        return (_col(coef, r, 2, dt) * x0 + _col(coef, r, 3, dt) * ek) + sigma * z
+
+
+def dpm_sde_update(x, eps, coef, pos, hist=None, noise=None, frame=None, x0_bound=None, order="f32"):
+    """dm3d_dpm_sde_update[_frame]: (res, x0) with res = ((c_x*x + c_0*x0) + c_1*hist) + c_z*z; the hist add only where c_1 != 0 and a
+    history is given, the noise add only where c_z != 0 (column 6)."""
+    dt = _dt(order)
+    r = _rows_of(pos, len(coef))
+    x0, _ = x0_estimate(x, eps, coef, pos, frame, order)
+    x0 = x0_bounded(x0, np.asarray(coef)[r, 5] != 0, x0_bound)
+    c_1, c_z = _col(coef, r, 4, dt), (_col(coef, r, 6, dt) if noise is not None else None)
+    with np.errstate(all="ignore"):
+        res = _col(coef, r, 2, dt) * np.asarray(x).astype(dt) + _col(coef, r, 3, dt) * x0
+        if hist is not None:
+            res = np.where(c_1 != 0, res + c_1 * np.asarray(hist).astype(dt), res)
+        if noise is not None:
+            res = np.where(c_z != 0, res + c_z * np.asarray(noise).astype(dt), res)
+    return res, x0
+
+
+def dpm_update(x, eps, coef, pos, hist=None, frame=None, x0_bound=None, order="f32"):
+    """dm3d_dpm_update[_frame]: (res, x0) with res = (c_x*x + c_0*x0) + c_1*hist; column 6 is not read."""
+    return dpm_sde_update(x, eps, coef, pos, hist, None, frame, x0_bound, order)
+
+
+def x0_bound(x, eps, coef, pos, rank, frac, smax, frame=None, order="f32"):
+    """dm3d_x0_threshold: bound[b] = s from the sorted magnitudes of the raw x0 estimate (np.sort: a NaN last); 1 on rows with clip == 0."""
+    dt = _dt(order)
+    r = _rows_of(pos, len(coef))
+    x0, _ = x0_estimate(x, eps, coef, pos, frame, order)
+    out = np.ones(len(r), dt)
+    n = x0.shape[1]
+    for b in range(len(r)):
+        if np.asarray(coef)[r[b], 5] == 0:
+            continue
+        v = np.sort(np.abs(x0[b]))
+        i = int(np.clip(int(rank[b]), 0, n - 1))
+        v0, v1 = v[i], v[min(i + 1, n - 1)]
+        with np.errstate(all="ignore"):
+            raw = v0 + dt(frac[b]) * (v1 - v0)
+        out[b] = raw if np.isnan(raw) else min(max(raw, dt(1)), dt(smax[b]))
+    return out
+
+
+def edit_update(x0, levels, pos, noise, mode=0, x=None, w=None, channels=1, order="f32"):
+    """dm3d_edit_update: known_t = sqrt(a')*x0 + sqrt(1-a')*z (x0 itself where sqrt(1-a') == 0); mode 1 blends it into x with the
+    per-voxel weight w [batch, per_sample / channels]: x where w == 0, known_t where w == 1, w*known_t + (1-w)*x between."""
+    dt = _dt(order)
+    r = _rows_of(pos, len(levels))
+    x0 = np.asarray(x0).astype(dt)
+    sq1 = _col(levels, r, 1, dt)
+    with np.errstate(all="ignore"):
+        known = np.where(sq1 == 0, x0, _col(levels, r, 0, dt) * x0 + sq1 * np.asarray(noise).astype(dt))
+        if mode == 0:
+            return known
+        we = np.repeat(np.asarray(w).astype(dt), channels, axis=1)
+        x = np.asarray(x).astype(dt)
+        return np.where(we == 0, x, np.where(we == 1, known, we * known + (dt(1) - we) * x))
+
+
+def guide_update(eps_pos, eps_neg, scale, rescale=None, order="f32"):
+    """dm3d_guide_update modes 0 and 1: (eps_g, f, out).  eps_g = eps_neg + w*(eps_pos - eps_neg) (sub, mul, add), eps_pos at w == 1 and
+    eps_neg at w == 0; f[b] = phi*std(eps_pos)/std(eps_g) + (1 - phi) from float64 sums of the values and their squares (1 where
+    std(eps_g) == 0), rounded once to float32 at order="f32"; out = f*eps_g on the rows with phi != 0, eps_g itself elsewhere."""
+    dt = _dt(order)
+    ep, en = np.asarray(eps_pos).astype(dt), np.asarray(eps_neg).astype(dt)
+    w = np.asarray(scale).astype(dt).reshape(-1, 1)
+    with np.errstate(all="ignore"):
+        g = np.where(w == 1, ep, np.where(w == 0, en, en + w * (ep - en)))
+    phi = np.zeros(len(w)) if rescale is None else np.asarray(rescale).astype(np.float64)
+    n = float(ep.shape[1])
+    f = np.ones(len(w), np.float64)
+    out = g.copy()
+    for b in np.nonzero(phi != 0)[0]:
+        a, c = ep[b].astype(np.float64), g[b].astype(np.float64)
+        var_p = max(float((a * a).sum()) / n - (float(a.sum()) / n) ** 2, 0.0)
+        var_g = max(float((c * c).sum()) / n - (float(c.sum()) / n) ** 2, 0.0)
+        f[b] = 1.0 if var_g == 0.0 else phi[b] * np.sqrt(var_p / var_g) + (1.0 - phi[b])
+        out[b] = dt(f[b]) * g[b]
+    return g, f.astype(dt), out
+
+
+def pred_to_eps(pred, x, table, t_idx, order="f32"):
+    """dm3d_pred_to_eps: eps = c_p*pred + c_x*x (mul, mul, add) with (c_p, c_x) = table[clamp(t_idx[b])]."""
+    dt = _dt(order)
+    r = _rows_of(t_idx, len(table))
+    with np.errstate(all="ignore"):
+        return _col(table, r, 0, dt) * np.asarray(pred).astype(dt) + _col(table, r, 1, dt) * np.asarray(x).astype(dt)
+
+
+def objective_loss(pred, noise, x0, coef, inv, want_dpred=True, order="f32"):
+    """dm3d_objective_loss_grad: (dpred, loss_rows, loss).  d = pred - (a_z*noise + a_0*x0); dpred = d * (float)(2*inv*w);
+    loss_rows[b] = w*inv*sum d^2 in float64; loss = their sum in index order."""
+    dt = _dt(order)
+    coef = np.asarray(coef)
+    rows = np.arange(len(coef))
+    d = np.asarray(pred).astype(dt) - (_col(coef, rows, 0, dt) * np.asarray(noise).astype(dt) + _col(coef, rows, 1, dt) * np.asarray(x0).astype(dt))
+    w = coef[:, 2].astype(np.float64)
+    dpred = d * (2.0 * inv * w).astype(dt).reshape(-1, 1) if want_dpred else None
+    loss_rows = w * inv * (d.astype(np.float64) ** 2).sum(1)
+    loss = 0.0
+    for v in loss_rows:
+        loss += float(v)
+    return dpred, loss_rows, loss

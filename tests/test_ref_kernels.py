@@ -4,6 +4,8 @@
    and upsample2 / sumpool2 are adjoint.  These are the references tests/test_gpu_train_kernels.py holds the HIP kernels against.
 2. Every training and normalisation entry of the C ABI refuses each documented bad argument with DM3D_EINVAL and a message, before
    any launch (fake aligned non-null pointers: nothing is ever dereferenced, so no GPU is needed).
+3. The sampler restatements of oracle/ref_kernels.py against independent statements: the paper forms in lambda / h of the GPU sampler
+   tests, np.quantile, the textbook guidance formula, autograd; and their float32 order within 1e-6 of their float64 one.
 """
 import ctypes as C
 
@@ -290,3 +292,202 @@ def test_training_entries_refuse_bad_arguments(built_library):
     assert not failures, "\n".join(failures)
     assert seen == set(ENTRIES)
     assert lib.dm3d_groupnorm_partials_bytes(0, 8, 8) == 0 and lib.dm3d_groupnorm_partials_bytes(3, 65, 20) == 3 * 2 * 20 * 8
+
+
+# ---- 3. the sampler restatements (oracle/ref_kernels.py, last section) against independent statements ----------------------------------
+# The folded-row forms at order="f64" against the paper forms in lambda / h that the GPU sampler tests carry, with schedules' tables
+# (handed over unrounded, in float64, so that the comparison is of the formulas alone); x0_bound against np.quantile; guide_update
+# against the textbook lines; and order="f32" within 1e-6 of order="f64" on O(1) inputs.
+T_S, SCHED = 1000, [0, 250, 500, 749, 999]
+F64_TOL = 1e-11
+
+
+def _ab():
+    import dm3d_amd
+    return np.asarray(dm3d_amd.Betas(T_S).alpha_bar, np.float64)
+
+
+def _steps():
+    """src, dst, prev of a 5-step chain, one row per step: the first step first order, the last one to clean."""
+    src = SCHED[::-1]
+    return src, src[1:] + [-1], [-1] + src[:-1]
+
+
+def _xs(seed, B, n=64, k=4):
+    rng = np.random.default_rng(seed)
+    return [rng.standard_normal((B, n)) for _ in range(k)]
+
+
+@pytest.mark.parametrize("clip", [True, False])
+def test_dpm_update_f64_is_the_paper_form(clip):
+    from dm3d_amd import schedules
+    from test_gpu_dpm import _dpm64
+    ab = _ab()
+    src, dst, prev = _steps()
+    coef = np.zeros((5, 8))
+    coef[:, :2] = schedules.ddim_coefficients(ab, src, dst)[:, :2]
+    coef[:, 2:5] = schedules.dpm_coefficients(ab, src, dst, prev)
+    coef[:, 5] = float(clip)
+    x, e, h, _ = _xs(1, 5)
+    res, x0 = rk.dpm_update(x, e, coef, np.arange(5), h, order="f64")
+    for b in range(5):
+        ref, ref0 = _dpm64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), ab, src[b], dst[b], prev[b] if dst[b] >= 0 else -1, torch.from_numpy(h[b]), clip)
+        assert _rel(res[b], ref) < F64_TOL and _rel(x0[b], ref0) < F64_TOL, b
+    assert coef[0, 4] == 0 and coef[1, 4] != 0 and coef[4, 4] == 0           # first order, second order, to clean
+    # without a history the add of c_1*hist is skipped, whatever c_1 holds: the paper's first-order step on the rows that are first order
+    first, _ = rk.dpm_update(x, e, coef, np.arange(5), None, order="f64")
+    for b in (0, 4):
+        ref, _ = _dpm64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), ab, src[b], dst[b], -1, None, clip)
+        assert _rel(first[b], ref) < F64_TOL, b
+    assert _rel(first, coef[:, 2:3] * x + coef[:, 3:4] * x0) < F64_TOL
+
+
+@pytest.mark.parametrize("eta", [0.5, 1.0])
+def test_dpm_sde_update_f64_is_the_paper_form(eta):
+    from dm3d_amd import schedules
+    from test_gpu_dpm_sde import _step64
+    ab = _ab()
+    src, dst, prev = _steps()
+    coef = np.zeros((5, 8))
+    coef[:, :2] = schedules.ddim_coefficients(ab, src, dst)[:, :2]
+    rows = schedules.dpm_sde_coefficients(ab, src, dst, prev, 2, eta)
+    coef[:, 2:5], coef[:, 6], coef[:, 5] = rows[:, :3], rows[:, 3], 1.0
+    x, e, h, z = _xs(2, 5)
+    res, x0 = rk.dpm_sde_update(x, e, coef, np.arange(5), h, z, order="f64")
+    for b in range(5):
+        ref, ref0 = _step64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), torch.from_numpy(z[b]), ab, src[b], dst[b],
+                            prev[b] if dst[b] >= 0 else -1, eta, torch.from_numpy(h[b]))
+        assert _rel(res[b], ref) < F64_TOL and _rel(x0[b], ref0) < F64_TOL, b
+    assert coef[0, 6] != 0 and coef[4, 6] == 0                               # the row to clean draws nothing
+    # c_z = 0 everywhere: dpm_update's result
+    ode = coef.copy()
+    ode[:, 6] = 0
+    a, b = rk.dpm_sde_update(x, e, ode, np.arange(5), h, z), rk.dpm_update(x, e, ode, np.arange(5), h)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[0].dtype == np.float32
+
+
+@pytest.mark.parametrize("eta", [0.0, 0.7])
+def test_ddim_update_f64_is_the_paper_form(eta):
+    from dm3d_amd import schedules
+    from test_gpu_guidance import _ddim64
+    ab = _ab()
+    src, dst, _ = _steps()
+    coef = np.zeros((5, 8))
+    coef[:, :5] = schedules.ddim_coefficients(ab, src, dst, eta)
+    coef[:, 5] = 1.0
+    x, e, z, _ = _xs(3, 5)
+    res = rk.ddim_update(x, e, coef, np.arange(5), z, order="f64")
+    for b in range(5):
+        ref = _ddim64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), ab[src[b]], ab[dst[b]] if dst[b] >= 0 else 1.0, eta, torch.from_numpy(z[b]))
+        assert _rel(res[b], ref) < F64_TOL, b
+
+
+@pytest.mark.parametrize("kind", ["v", "x0"])
+def test_frame_rows_give_the_eps_frames_estimate(kind):
+    """x0 and eps from a frame row of schedules.frame_table equal the eps-frame estimate of the eps that prediction stands for."""
+    from dm3d_amd import schedules
+    ab = _ab()
+    t = np.array([3, 400, 998])
+    a, s = np.sqrt(ab[t])[:, None], np.sqrt(1 - ab[t])[:, None]
+    x0_true, z = _xs(4, 3, k=2)
+    x = a * x0_true + s * z
+    pred = a * z - s * x0_true if kind == "v" else x0_true
+    frame = schedules.frame_table(ab.astype(np.float32), kind).astype(np.float64)
+    coef = np.zeros((T_S, 8))
+    coef[:, 0], coef[:, 1] = np.sqrt(ab), np.sqrt(1 - ab)
+    x0, eps = rk.x0_estimate(x, pred, coef, t, frame, order="f64")
+    assert np.abs(x0 - x0_true).max() < 1e-5 and np.abs(eps - z).max() < 1e-5       # (the table is rounded to float32)
+    x0_e, _ = rk.x0_estimate(x, z, coef, t, None, order="f64")
+    assert np.abs(x0_e - x0_true).max() < 1e-9
+
+
+def test_x0_bound_is_the_linear_quantile():
+    rng = np.random.default_rng(5)
+    B, n = 4, 1004
+    x, e = rng.standard_normal((B, n)) * 2, rng.standard_normal((B, n))
+    coef = np.zeros((2, 8))
+    coef[:, 0], coef[:, 1], coef[0, 5] = 0.8, 0.6, 1.0
+    from dm3d_amd import schedules
+    p = [1e-9, 0.37, 0.995, 1.0]
+    rank, frac, smax = schedules.threshold_tables(B, n, p, 1e9)
+    got = rk.x0_bound(x, e, coef, [0] * B, rank, frac, smax, order="f64")
+    for b in range(B):
+        q = float(np.quantile(np.abs((x[b] - 0.6 * e[b]) / 0.8), p[b], method="linear"))
+        assert abs(got[b] - max(q, 1.0)) < 1e-6 * max(q, 1.0), (b, got[b], q)     # frac is a float32
+    assert got[0] == 1.0 and got[3] > 3.0
+    assert np.array_equal(rk.x0_bound(x, e, coef, [0, 1, 0, 5], rank, frac, np.full(B, 2.5, np.float32), order="f64") == 1.0, [True, True, False, True])
+    assert rk.x0_bound(x, e, coef, [0] * B, rank, frac, np.full(B, 2.5, np.float32))[3] == np.float32(2.5)
+    # a NaN sorts last: it reaches the bound only from the top rank
+    x[1, 7] = np.nan
+    top = rk.x0_bound(x, e, coef, [0] * B, [n - 1] * B, [0.0] * B, smax)
+    assert np.isnan(top[1]) and np.isfinite(top[[0, 2, 3]]).all()
+    assert np.isfinite(rk.x0_bound(x, e, coef, [0] * B, [n - 3] * B, [0.5] * B, smax)).all()
+
+
+def test_guide_update_is_the_textbook_formula():
+    ep, en = (v + 0.5 for v in _xs(6, 4, 1004, 2))
+    w, phi = np.array([7.5, -1.0, 0.0, 1.0]), np.array([0.7, 0.0, 1.0, 0.3])
+    g, f, out = rk.guide_update(ep, en, w, phi, order="f64")
+    for b in range(4):
+        gb = en[b] + w[b] * (ep[b] - en[b])
+        fb = phi[b] * ep[b].std() / gb.std() + (1 - phi[b])
+        assert np.abs(g[b] - gb).max() < 1e-12 and abs(f[b] - fb) < 1e-12 and np.abs(out[b] - fb * gb).max() < 1e-11
+    assert np.array_equal(g[2], en[2]) and np.array_equal(g[3], ep[3]) and f[1] == 1.0 and np.array_equal(out[1], g[1])
+    flat = np.full_like(en, 0.25)
+    assert rk.guide_update(ep, flat, np.zeros(4), np.ones(4), order="f64")[1].tolist() == [1.0] * 4     # std(eps_g) == 0
+
+
+def test_edit_pred_and_loss_restatements():
+    x0, z, x, p = _xs(7, 3, 24)
+    levels = np.array([[0.6, 0.8, 5, 0], [1.0, 0.0, -1, 0], [0.3, 0.9, 7, 0]])
+    known = rk.edit_update(x0, levels, [0, 1, 9], z, order="f64")
+    assert np.abs(known[0] - (0.6 * x0[0] + 0.8 * z[0])).max() < 1e-15 and np.array_equal(known[1], x0[1])
+    assert np.abs(known[2] - (0.3 * x0[2] + 0.9 * z[2])).max() < 1e-15
+    w = np.tile(np.array([0.0, 1.0, 0.25, 0.5]), (3, 1))                     # 4 voxels of 6 channels
+    got = rk.edit_update(x0, levels, [0, 1, 2], z, 1, x, w, 6, order="f64").reshape(3, 4, 6)
+    k3, x3 = known.reshape(3, 4, 6), x.reshape(3, 4, 6)
+    assert np.array_equal(got[:, 0], x3[:, 0]) and np.array_equal(got[:, 1], k3[:, 1])
+    assert np.abs(got[:, 2] - (0.25 * k3[:, 2] + 0.75 * x3[:, 2])).max() < 1e-15
+    table = np.array([[0.5, 2.0], [-1.5, 0.25]])
+    eps = rk.pred_to_eps(p, x, table, [-4, 1, 6], order="f64")
+    assert np.abs(eps[0] - (0.5 * p[0] + 2.0 * x[0])).max() < 1e-15 and np.abs(eps[2] - (-1.5 * p[2] + 0.25 * x[2])).max() < 1e-15
+    coef = np.array([[1, 0, 1, 0], [0.6, -0.8, 0.5, 0], [0, 1, 2.0, 0]], np.float64)
+    inv = 1.0 / 48
+    dpred, rows, loss = rk.objective_loss(p, z, x0, coef, inv, order="f64")
+    pt, tgt = torch.from_numpy(p).requires_grad_(True), torch.from_numpy(coef[:, :1] * z + coef[:, 1:2] * x0)
+    per = (torch.from_numpy(coef[:, 2]) * inv * ((pt - tgt) ** 2).sum(1))
+    per.sum().backward()
+    assert _rel(dpred, pt.grad) < TOL and _rel(rows, per.detach()) < TOL and abs(loss - float(per.detach().sum())) < 1e-12 * loss
+    assert rk.objective_loss(p, z, x0, coef, inv, want_dpred=False)[0] is None
+
+
+def test_f32_orders_stay_within_1e6_of_f64():
+    rng = np.random.default_rng(8)
+    B, n = 4, 1004
+    x, e, h, z = (rng.standard_normal((B, n)).astype(np.float32) for _ in range(4))
+    coef = (rng.uniform(0.5, 1.5, (B, 8)) * rng.choice([-1, 1], (B, 8))).astype(np.float32)
+    coef[:, 0] = np.abs(coef[:, 0])
+    coef[1, 5] = coef[2, 4] = coef[3, 6] = 0
+    frame = rng.uniform(-1, 1, (B, 4)).astype(np.float32)
+    pos, bound = np.arange(B), np.array([1.0, 1.3, 2.0, 1.1], np.float32)
+    worst = 0.0
+    for fr in (None, frame):
+        for bd in (None, bound):
+            pairs = [(rk.ddim_update(x, e, coef, pos, z, fr, bd, order=o),) + rk.dpm_update(x, e, coef, pos, h, fr, bd, order=o)
+                     + rk.dpm_sde_update(x, e, coef, pos, h, z, fr, bd, order=o) for o in ("f32", "f64")]
+            for a, b in zip(*pairs):
+                assert a.dtype == np.float32 and b.dtype == np.float64
+                worst = max(worst, float(np.abs(a - b).max() / max(1.0, np.abs(b).max())))
+    levels = np.array([[0.6, 0.8, 5, 0], [1.0, 0.0, -1, 0], [0.3, 0.9, 7, 0], [0.9, 0.4, 2, 0]], np.float32)
+    w = rng.choice([0.0, 1.0, 0.3, 0.6], (B, n // 4)).astype(np.float32)
+    table = rng.uniform(-1.5, 1.5, (5, 2)).astype(np.float32)
+    lc = np.array([[1, 0, 1, 0], [0.6, -0.8, 0.5, 0], [0, 1, 2.0, 0], [0.3, 0.9, 0.1, 0]], np.float32)
+    scale, phi = np.array([2.5, 0, 1, -0.7], np.float32), np.array([0.7, 0.2, 0, 1.0], np.float32)
+    for fn in (lambda o: rk.edit_update(x, levels, pos, z, 1, e, w, 4, order=o), lambda o: rk.pred_to_eps(x, e, table, pos, order=o),
+               lambda o: rk.objective_loss(x, z, e, lc, 0.01, order=o)[0], lambda o: rk.guide_update(x, e, scale, phi, order=o)[2],
+               lambda o: rk.guide_update(x, e, scale, phi, order=o)[1], lambda o: rk.objective_loss(x, z, e, lc, 0.01, order=o)[1],
+               lambda o: rk.x0_bound(x, e, coef, pos, [0, n // 2, n - 2, n - 1], [0.3] * B, [1e9] * B, order=o)):
+        a, b = np.asarray(fn("f32"), np.float64), np.asarray(fn("f64"), np.float64)
+        worst = max(worst, float(np.abs(a - b).max() / max(1.0, np.abs(b).max())))
+    print(f"f32 against f64 restatements: worst {worst:.2e}")
+    assert worst < 1e-6
