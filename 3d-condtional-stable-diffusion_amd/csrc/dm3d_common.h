@@ -30,6 +30,11 @@ static inline int dm3d_launch_check(const char* what) {
 }
 static inline bool dm3d_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int64_t dm3d_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+// The grid of a stream kernel over [batch][per4] float4 (ddpm_kernel's): at most 256 blocks of 256 lanes a sample, which stride over it.
+static inline dim3 dm3d_stream_grid(long per4, int batch) {
+    const long blocks = (per4 + 255) / 256;
+    return dim3((unsigned)(blocks > 256 ? 256 : blocks), (unsigned)batch);
+}
 
 // Raises the dynamic-LDS limit of `kernels` to `lds` bytes on the device the launch goes to (the attribute belongs to the device), once per
 // device: `set` is the caller's static array of 64 flags, one array per kernel instantiation (atomic: two host threads may meet in a first
@@ -65,25 +70,6 @@ __device__ __forceinline__ float dm3d_act(float v, int act) {
     if (act == DM3D_ACT_RELU) return fmaxf(v, 0.0f);
     if (act == DM3D_ACT_SILU) return dm3d_silu(v);
     return v;
-}
-
-// The x0 estimate of the DDIM / DPM-Solver++ updates, (x - sqrt(1-a)*eps) / sqrt(a) as mul, sub, div, each rounded (ddpm_kernel's order).
-// One function for the update kernels and the dynamic threshold's selection: the magnitudes ranked are bitwise the values clamped.
-__device__ __forceinline__ float dm3d_x0_estimate(float x, float eps, float sqab, float sq1ab) {
-    return __fdiv_rn(__fsub_rn(x, __fmul_rn(sq1ab, eps)), sqab);
-}
-// The same estimate, and ddim_kernel's eps, from the network's output p in its own frame (include/dm3d.h, dm3d_ddim_update_frame): one row
-// (k0x, k0p, kex, kep) of the host's frame table gives x0 = k0x*x + k0p*p and eps = kex*x + kep*p, each as mul, mul, add, each rounded.
-// No division: a v-model's row is (a, -s, s, a), finite where sqrt(alpha_bar) is 0 (the zero-terminal-SNR schedule's last timestep).
-__device__ __forceinline__ float dm3d_frame_estimate(float x, float p, float kx, float kp) {
-    return __fadd_rn(__fmul_rn(kx, x), __fmul_rn(kp, p));
-}
-// The bounded estimate: clamp(x0, -1, 1), or with a dynamic bound s (include/dm3d.h, dm3d_thresh_desc) clamp(x0, -s, s) / s.  A NaN
-// passes; `dyn` is uniform over the block, so the static path is the one instruction pair it always was.
-__device__ __forceinline__ float dm3d_x0_bounded(float x0, bool dyn, float s) {
-    if (x0 != x0) return x0;
-    if (dyn) return __fdiv_rn(fminf(fmaxf(x0, -s), s), s);
-    return fminf(fmaxf(x0, -1.0f), 1.0f);
 }
 
 // One (tap, Cin-chunk) step of the implicit GEMM for a wave owning MR x NR tiles of 32x32 outputs.

@@ -3,87 +3,24 @@
 // (include/dm3d.h, dm3d_dpm_desc), so first-order rows (the DDIM eta = 0 step), second-order rows and the step to the clean sample
 // share one kernel.  A pure HBM stream like ddim_kernel: 16 B per lane, read x, eps and (second-order rows only) the previous x0
 // estimate, write x and this step's x0 estimate.  No noise term: no Philox.
-#include "dm3d_common.h"
+// The body and its arguments are dm3d_update.h's, shared with the SDE form (dm3d_dpm_sde.hip); these two kernels are its SDE = false
+// instantiations.
+#include "dm3d_update.h"
 
 namespace {
 
-struct DpmArgs {
-    float* x; const float* eps; float* hist; float* out; float* x0_out;
-    long per4;                                     // float4 per sample
-    const float* coef; const int* t_next; int rows;
-    const int* pos; int* t_idx;
-    int mode;
-    const float* x0_bound;
-    const float* frame;
-};
-
-// One block's share of the update.  FRAME: `eps` holds the network's output in its own frame and (k0x, k0p) of row r of p.frame turn
-// it into x0; cols 0 and 1 of coef are not used then.  Two kernels, chosen by the host, so that the eps kernel is the one it always was.
-template <bool FRAME>
-__device__ __forceinline__ void dpm_block(const DpmArgs& p) {
-    const int b = blockIdx.y;
-    const int r = min(max(p.pos[b], 0), p.rows - 1);
-    const f32x4 c0 = reinterpret_cast<const f32x4*>(p.coef)[2 * r];          // sqrt(ab), sqrt(1-ab), c_x, c_0
-    const f32x4 c1 = reinterpret_cast<const f32x4*>(p.coef)[2 * r + 1];      // c_1, clip, -, -
-    float ka = c0[0], kb = c0[1];
-    if (FRAME) {
-        const f32x4 kf = reinterpret_cast<const f32x4*>(p.frame)[r];         // k0x, k0p, kex, kep
-        ka = kf[0], kb = kf[1];
-    }
-    const float c_x = c0[2], c_0 = c0[3], c_1 = c1[0];
-    const bool clip = c1[1] != 0.f;
-    const bool dyn = clip && p.x0_bound != nullptr;                          // the dynamic threshold's bound, read once per block
-    const float s = dyn ? p.x0_bound[b] : 1.0f;
-    const bool second = c_1 != 0.f && p.hist != nullptr;                     // a first-order row never reads the history
-    // the next step's U-Net row; the kernel never reads t_idx, so this one lane per sample races with nobody
-    if (p.t_idx && blockIdx.x == 0 && threadIdx.x == 0) p.t_idx[b] = p.t_next[r];
-    float* dst = p.mode == 0 ? p.out : p.x;
-    float* x0_dst = p.mode == 0 ? p.x0_out : p.hist;
-    const long base = (long)b * p.per4;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < p.per4; i += (long)gridDim.x * 256) {
-        const f32x4 x = reinterpret_cast<const f32x4*>(p.x)[base + i];
-        const f32x4 e = reinterpret_cast<const f32x4*>(p.eps)[base + i];
-        f32x4 h = {0.f, 0.f, 0.f, 0.f};
-        if (second) h = reinterpret_cast<const f32x4*>(p.hist)[base + i];
-        f32x4 o, x0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float v = FRAME ? dm3d_frame_estimate(x[k], e[k], ka, kb)
-                            : dm3d_x0_estimate(x[k], e[k], ka, kb);                  // ddim_kernel's order
-            if (clip) v = dm3d_x0_bounded(v, dyn, s);                                // a NaN passes, as in ddim_kernel's clip
-            x0[k] = v;
-            const float first = __fadd_rn(__fmul_rn(c_x, x[k]), __fmul_rn(c_0, v));
-            o[k] = second ? __fadd_rn(first, __fmul_rn(c_1, h[k])) : first;
-        }
-        reinterpret_cast<f32x4*>(dst)[base + i] = o;
-        if (x0_dst) reinterpret_cast<f32x4*>(x0_dst)[base + i] = x0;
-    }
-}
-
-__global__ __launch_bounds__(256) void dpm_kernel(const DpmArgs p) { dpm_block<false>(p); }
-__global__ __launch_bounds__(256) void dpm_frame_kernel(const DpmArgs p) { dpm_block<true>(p); }
+// FRAME: `eps` holds the network's output in its own frame.  Two kernels, chosen by the host, so that the eps kernel is the one it always was.
+__global__ __launch_bounds__(256) void dpm_kernel(const dm3d_dpm_args p) { dm3d_dpm_block<false, false>(p); }
+__global__ __launch_bounds__(256) void dpm_frame_kernel(const dm3d_dpm_args p) { dm3d_dpm_block<true, false>(p); }
 
 }  // namespace
 
 extern "C" int dm3d_dpm_update_frame(const dm3d_dpm_desc* d, const float* frame, void* stream) {
     DM3D_REQUIRE(d != nullptr, "dpm: null descriptor");
-    DM3D_REQUIRE(d->x && d->eps && d->coef && d->pos, "dpm: x/eps/coef/pos must be non-null");
-    DM3D_REQUIRE(d->batch > 0 && d->batch <= 65535 && d->per_sample > 0 && d->per_sample % 4 == 0,
-                 "dpm: batch=%d per_sample=%lld (must be a positive multiple of 4)", d->batch, (long long)d->per_sample);
-    DM3D_REQUIRE(d->rows > 0, "dpm: rows=%d", d->rows);
-    DM3D_REQUIRE(d->mode == 0 || d->mode == 1, "dpm: mode %d not in {0,1}", d->mode);
-    DM3D_REQUIRE(d->mode == 1 || d->out, "dpm: mode 0 needs out");
-    DM3D_REQUIRE(d->mode == 0 || d->hist, "dpm: mode 1 needs hist");
-    DM3D_REQUIRE(!d->t_idx || d->t_next, "dpm: t_idx needs t_next");
-    DM3D_REQUIRE(dm3d_aligned16(d->x) && dm3d_aligned16(d->eps) && dm3d_aligned16(d->hist) && dm3d_aligned16(d->out) &&
-                 dm3d_aligned16(d->x0_out) && dm3d_aligned16(d->coef) && dm3d_aligned16(frame), "dpm: pointers must be 16-byte aligned");
-    DpmArgs a{};
-    a.x = d->x; a.eps = d->eps; a.hist = d->hist; a.out = d->out; a.x0_out = d->x0_out; a.per4 = d->per_sample / 4;
-    a.coef = d->coef; a.t_next = d->t_next; a.rows = d->rows; a.pos = d->pos; a.t_idx = d->t_idx; a.mode = d->mode;
-    a.x0_bound = d->x0_bound; a.frame = frame;
-    const long blocks = (a.per4 + 255) / 256;
-    dim3 grid((unsigned)(blocks > 256 ? 256 : blocks), (unsigned)d->batch);                 // ddpm_kernel's grid
-    hipLaunchKernelGGL(frame ? dpm_frame_kernel : dpm_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    dm3d_dpm_args a{};
+    if (int rc = dm3d_dpm_args_of("dpm", d, frame, true, "", nullptr, a)) return rc;
+    hipLaunchKernelGGL(frame ? dpm_frame_kernel : dpm_kernel, dm3d_stream_grid(a.per4, d->batch), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a);
     return dm3d_launch_check(frame ? "dpm_frame_kernel" : "dpm_kernel");
 }
 

@@ -84,8 +84,6 @@ extern "C" int dm3d_edit_update(const dm3d_edit_desc* d, void* stream) {
     a.channels = d->channels; a.vox = d->per_sample / d->channels;
     a.levels = d->levels; a.rows = d->rows; a.pos = d->pos;
     a.seed = d->seed; a.seed_dev = d->seed_dev; a.mode = d->mode;
-    const long blocks = (a.per4 + 255) / 256;
-    dim3 grid((unsigned)(blocks > 256 ? 256 : blocks), (unsigned)d->batch);                 // ddpm_kernel's grid
-    hipLaunchKernelGGL(edit_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(edit_kernel, dm3d_stream_grid(a.per4, d->batch), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     return dm3d_launch_check("edit_kernel");
 }

@@ -637,8 +637,7 @@ extern "C" int dm3d_ddpm_update(const dm3d_ddpm_desc* d, void* stream) {
     a.sqabp = d->sqrt_alpha_bar_prev; a.sq1ab = d->sqrt_one_minus_alpha_bar;
     a.seed = d->seed; a.mode = d->mode; a.mean_out = d->mean_out; a.var_out = d->var_out;
     a.seed_dev = d->seed_dev; a.timesteps = d->timesteps;
-    dim3 grid(grid_for(a.per4, 256), (unsigned)d->batch);
-    hipLaunchKernelGGL(ddpm_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(ddpm_kernel, dm3d_stream_grid(a.per4, d->batch), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     return dm3d_launch_check("ddpm_kernel");
 }
 

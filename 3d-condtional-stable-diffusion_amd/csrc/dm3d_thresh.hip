@@ -17,7 +17,7 @@
 // 32-fold (two values, half the lanes each), a few-fold on a smooth volume ("Counting" and the measurement paragraph).  Nothing else is shared between blocks, so runs repeat bitwise.  The
 // histograms are cleared by a kernel of their own at the head of every launch (a kernel node like the others, so a captured step
 // stays one chain of kernels); no host read anywhere: graph-capturable.
-#include "dm3d_common.h"
+#include "dm3d_update.h"
 
 namespace {
 
@@ -44,10 +44,9 @@ struct ThreshArgs {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ bool row_clips(const ThreshArgs& p, int b, float& sqab, float& sq1ab) {
-    const int r = min(max(p.pos[b], 0), p.rows - 1);
-    sqab = p.coef[8 * r], sq1ab = p.coef[8 * r + 1];
-    return p.coef[8 * r + 5] != 0.f;
+// whether the row of volume b clips: passes 2, 3 and final need no more of it
+__device__ __forceinline__ bool row_clips(const ThreshArgs& p, int b) {
+    return dm3d_row_decode<false>(p.coef, nullptr, p.pos, p.rows, nullptr, b).clip;
 }
 
 // h[digit] += 1 for the lanes with `valid`; every lane of the wave calls it.  The lanes that share the first valid lane's digit add
@@ -108,9 +107,9 @@ __global__ __launch_bounds__(256) void thresh_clear_kernel(u32x4* __restrict__ h
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) h[i] = zero;
 }
 
-// FRAME: `eps` holds the network's output in its own frame and (ka, kb) = (k0x, k0p) of its row; else (sqrt(ab), sqrt(1-ab)).
+// FRAME: `eps` holds the network's output in its own frame (dm3d_update.h, dm3d_row).
 template <bool FRAME>
-__device__ __forceinline__ void pass1_stream(const ThreshArgs& p, uint32_t* h, long base, float ka, float kb) {
+__device__ __forceinline__ void pass1_stream(const ThreshArgs& p, uint32_t* h, long base, const dm3d_row& w) {
     for (long i0 = (long)blockIdx.x * 256; i0 < p.per4; i0 += (long)gridDim.x * 256) {      // uniform: hist_add needs whole waves
         const long i = i0 + threadIdx.x;
         const bool valid = i < p.per4;
@@ -119,8 +118,7 @@ __device__ __forceinline__ void pass1_stream(const ThreshArgs& p, uint32_t* h, l
             const f32x4 x = reinterpret_cast<const f32x4*>(p.x)[base + i];
             const f32x4 e = reinterpret_cast<const f32x4*>(p.eps)[base + i];
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                m[k] = __float_as_uint(FRAME ? dm3d_frame_estimate(x[k], e[k], ka, kb) : dm3d_x0_estimate(x[k], e[k], ka, kb)) & 0x7fffffffu;
+            for (int k = 0; k < 4; ++k) m[k] = __float_as_uint(dm3d_row_estimate<FRAME>(w, x[k], e[k])) & 0x7fffffffu;
             reinterpret_cast<u32x4*>(p.mag)[base + i] = m;
         }
 #pragma unroll
@@ -131,17 +129,13 @@ __device__ __forceinline__ void pass1_stream(const ThreshArgs& p, uint32_t* h, l
 __global__ __launch_bounds__(256) void thresh_pass1_kernel(const ThreshArgs p) {
     __shared__ uint32_t h[BINS1];
     const int b = blockIdx.y;
-    float sqab, sq1ab;
-    if (!row_clips(p, b, sqab, sq1ab)) return;                           // uniform over the block
+    const dm3d_row w = dm3d_row_decode<false>(p.coef, nullptr, p.pos, p.rows, nullptr, b);      // no bound: these passes make it
+    if (!w.clip) return;                                                 // uniform over the block
     for (int j = threadIdx.x; j < BINS1; j += 256) h[j] = 0;
     __syncthreads();
     const long base = (long)b * p.per4;
-    if (p.frame) {                                                       // uniform over the grid; cols 0 and 1 of coef are not used
-        const f32x4 kf = reinterpret_cast<const f32x4*>(p.frame)[min(max(p.pos[b], 0), p.rows - 1)];
-        pass1_stream<true>(p, h, base, kf[0], kf[1]);
-    } else {
-        pass1_stream<false>(p, h, base, sqab, sq1ab);
-    }
+    if (p.frame) pass1_stream<true>(p, h, base, dm3d_row_decode<true>(p.coef, p.frame, p.pos, p.rows, nullptr, b));    // uniform over the grid
+    else pass1_stream<false>(p, h, base, w);
     __syncthreads();
     merge_hist(p.h1 + (long)b * BINS1, h, BINS1);
 }
@@ -155,8 +149,7 @@ __global__ __launch_bounds__(256) void thresh_pass_kernel(const ThreshArgs p) {
     __shared__ uint32_t h[2][NB];
     __shared__ uint32_t wave_sum[4], res[2];
     const int b = blockIdx.y;
-    float sqab, sq1ab;
-    if (!row_clips(p, b, sqab, sq1ab)) return;
+    if (!row_clips(p, b)) return;
     const long n = p.per4 * 4;
     SelState s;
     const uint32_t* prev;
@@ -204,8 +197,7 @@ __global__ __launch_bounds__(256) void thresh_pass_kernel(const ThreshArgs p) {
 __global__ __launch_bounds__(256) void thresh_final_kernel(const ThreshArgs p) {
     __shared__ uint32_t wave_sum[4], res[2];
     const int b = blockIdx.x;
-    float sqab, sq1ab;
-    if (!row_clips(p, b, sqab, sq1ab)) {
+    if (!row_clips(p, b)) {
         if (threadIdx.x == 0) p.bound[b] = 1.0f;
         return;
     }

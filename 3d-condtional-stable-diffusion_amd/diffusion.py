@@ -428,22 +428,11 @@ class DiffusionModel:
         ``prediction="v"`` / ``"x0"`` (None: today's call): ``pred_noise`` is the network's raw output in that frame instead and the
         launch carries the frame rows (schedules.py, frame_table): the form a zero-terminal-SNR model's chain takes, and the only one
         with a value at alpha_bar[t] = 0."""
-        x_t, eps = torch.as_tensor(x_t, dtype=torch.float32), torch.as_tensor(pred_noise, dtype=torch.float32)
-        B = x_t.shape[0]
-        if eps.shape != x_t.shape or x_t[0].numel() % 4:
-            raise ValueError("x_t / pred_noise disagree")
-        self._frame_rules(prediction)
-        thr = self._threshold_rules(B, x_t[0].numel(), clip_x0, dynamic_threshold, threshold_max)    # before any device buffer exists
-        x_t, eps = x_t.to(self.device).contiguous(), eps.to(self.device).contiguous()
-        t, tp = _indices(t, B), _indices(t_prev, B)
-        if t.min() < 0 or t.max() >= self.timesteps or tp.min() < -1 or np.any(tp >= t):
-            raise ValueError("t must lie in [0, timesteps) and t_prev in [-1, t)")
         if not eta >= 0:
             raise ValueError("eta must be >= 0")
-        if noise is not None:
-            noise = torch.as_tensor(noise, dtype=torch.float32).to(self.device).contiguous()
-            if noise.shape != x_t.shape:
-                raise ValueError("noise must have x_t's shape")
+        host, t, tp, thr = self._step_rules(x_t, pred_noise, t, t_prev, noise, prediction, clip_x0, dynamic_threshold, threshold_max)
+        x_t, eps, noise, _ = self._staged(host)
+        B = x_t.shape[0]
         coef = self._ddim_table(t, tp, eta, clip_x0).to(self.device)
         tau = torch.from_numpy(t.astype(np.int32)).to(self.device)
         pos = torch.arange(B, dtype=torch.int32, device=self.device)
@@ -454,6 +443,33 @@ class DiffusionModel:
                             x0_bound=bound)
         check(self._update_call("ddim_update", d, frame, torch.cuda.current_stream().cuda_stream), "ddim_update")
         return out
+
+    def _step_rules(self, x_t, pred_noise, t, t_prev, noise, prediction, clip_x0, dynamic_threshold, threshold_max, x0_prev=None):
+        """The argument rules ddim_step and dpm_step share, checked before any device buffer is made: x_t / pred_noise (and ``noise`` /
+        ``x0_prev``, where given) of one shape with a multiple of 4 elements per sample, -1 <= t_prev < t < timesteps, ``prediction``
+        and the threshold's.  Returns (x_t, pred_noise, noise, x0_prev) as float32 host tensors (None stays None), t and t_prev as
+        host int64 [B], and the host tables of threshold_tables() (None without dynamic_threshold)."""
+        x_t, eps = torch.as_tensor(x_t, dtype=torch.float32), torch.as_tensor(pred_noise, dtype=torch.float32)
+        B = x_t.shape[0]
+        if eps.shape != x_t.shape or x_t[0].numel() % 4:
+            raise ValueError("x_t / pred_noise disagree")
+        self._frame_rules(prediction)
+        t, tp = _indices(t, B), _indices(t_prev, B)
+        if t.min() < 0 or t.max() >= self.timesteps or tp.min() < -1 or np.any(tp >= t):
+            raise ValueError("t must lie in [0, timesteps) and t_prev in [-1, t)")
+        thr = self._threshold_rules(B, x_t[0].numel(), clip_x0, dynamic_threshold, threshold_max)
+        like = []
+        for name, v in (("noise", noise), ("x0_prev", x0_prev)):
+            if v is not None:
+                v = torch.as_tensor(v, dtype=torch.float32)
+                if v.shape != x_t.shape:
+                    raise ValueError(f"{name} must have x_t's shape")
+            like.append(v)
+        return (x_t, eps, *like), t, tp, thr
+
+    def _staged(self, tensors):
+        """Host tensors on the device, contiguous (None stays None): what a single-call form hands its descriptor."""
+        return [None if v is None else v.to(self.device).contiguous() for v in tensors]
 
     def _ddim_table(self, src, dst, eta, clip_x0) -> torch.Tensor:
         """The [n, 8] float32 coefficient rows of dm3d_ddim_desc, from the float32 alpha_bar table the kernels use, in float64."""
@@ -494,47 +510,25 @@ class DiffusionModel:
         if sde_eta is None and (noise is not None or seed is not None):
             raise ValueError("noise / seed belong to the stochastic step: give sde_eta")
         sde_eta = self._sde_eta_rules(sde_eta)
-        self._frame_rules(prediction)
-        x_t = torch.as_tensor(x_t, dtype=torch.float32)
-        eps = torch.as_tensor(pred_noise, dtype=torch.float32)
-        B = x_t.shape[0]
-        if eps.shape != x_t.shape or x_t[0].numel() % 4:
-            raise ValueError("x_t / pred_noise disagree")
-        t, tp = _indices(t, B), _indices(t_prev, B)
+        host, t, tp, thr = self._step_rules(x_t, pred_noise, t, t_prev, noise, prediction, clip_x0, dynamic_threshold, threshold_max, x0_prev)
+        B = host[0].shape[0]
         tb = np.full(B, -1, dtype=np.int64) if t_before is None else _indices(t_before, B)
-        if t.min() < 0 or t.max() >= self.timesteps or tp.min() < -1 or np.any(tp >= t):
-            raise ValueError("t must lie in [0, timesteps) and t_prev in [-1, t)")
-        if t_before is not None:
-            if np.any(tb <= t) or tb.max() >= self.timesteps:
-                raise ValueError("t_before must lie in (t, timesteps)")
-            x0_prev = torch.as_tensor(x0_prev, dtype=torch.float32)
-            if x0_prev.shape != x_t.shape:
-                raise ValueError("x0_prev must have x_t's shape")
-        thr = self._threshold_rules(B, x_t[0].numel(), clip_x0, dynamic_threshold, threshold_max)
-        if noise is not None:
-            noise = torch.as_tensor(noise, dtype=torch.float32)
-            if noise.shape != x_t.shape:
-                raise ValueError("noise must have x_t's shape")
+        if t_before is not None and (np.any(tb <= t) or tb.max() >= self.timesteps):
+            raise ValueError("t_before must lie in (t, timesteps)")
         dev = self.device
-        x_t, eps = x_t.to(dev).contiguous(), eps.to(dev).contiguous()
-        hist = None if x0_prev is None else x0_prev.to(dev).contiguous()
-        if sde_eta is None:
-            coef = self._dpm_table(t, tp, tb, 2, clip_x0).to(dev)
-        else:
-            coef = self._dpm_sde_table(t, tp, tb, 2, clip_x0, sde_eta).to(dev)
+        x_t, eps, noise, hist = self._staged(host)
+        coef = self._dpm_sde_table(t, tp, tb, 2, clip_x0, sde_eta).to(dev)
         pos = torch.arange(B, dtype=torch.int32, device=dev)
         out, x0 = torch.empty_like(x_t), torch.empty_like(x_t)
         frame = self._frame_rows(prediction, t)
         bound = None if thr is None else self._x0_bound(x_t, eps, coef, pos, thr, frame)
-        st = torch.cuda.current_stream().cuda_stream
         if sde_eta is None:
-            d = self._dpm_desc(x_t, eps, hist, coef, pos, 0, out=out, x0_out=x0, x0_bound=bound)
-            check(self._update_call("dpm_update", d, frame, st), "dpm_update")
-            return out, x0
-        tau = torch.from_numpy(t.astype(np.int32)).to(dev)
-        d = self._dpm_sde_desc(x_t, eps, hist, coef, tau, pos, 0, noise=None if noise is None else noise.to(dev).contiguous(), out=out,
-                               x0_out=x0, seed=self.fresh_seed() if seed is None else seed, x0_bound=bound)
-        check(self._update_call("dpm_sde_update", d, frame, st), "dpm_sde_update")
+            entry, d = "dpm_update", self._dpm_desc(x_t, eps, hist, coef, pos, 0, out=out, x0_out=x0, x0_bound=bound)
+        else:
+            tau = torch.from_numpy(t.astype(np.int32)).to(dev)
+            entry, d = "dpm_sde_update", self._dpm_sde_desc(x_t, eps, hist, coef, tau, pos, 0, noise=noise, out=out, x0_out=x0,
+                                                            seed=self.fresh_seed() if seed is None else seed, x0_bound=bound)
+        check(self._update_call(entry, d, frame, torch.cuda.current_stream().cuda_stream), entry)
         return out, x0
 
     @staticmethod
@@ -549,32 +543,30 @@ class DiffusionModel:
 
     def _dpm_table(self, src, dst, prev, order, clip_x0) -> torch.Tensor:
         """The [n, 8] float32 coefficient rows of dm3d_dpm_desc, from the float32 alpha_bar table the kernels use, in float64."""
-        tab = np.zeros((len(src), 8), dtype=np.float64)
-        tab[:, :2] = ddim_coefficients(self.b.alpha_bar, src, dst)[:, :2]
-        tab[:, 2:5] = dpm_coefficients(self.b.alpha_bar, src, dst, prev, order)
-        tab[:, 5] = 1.0 if clip_x0 else 0.0
-        return torch.from_numpy(tab.astype(np.float32))
+        return DiffusionModel._dpm_sde_table(self, src, dst, prev, order, clip_x0)         # (of ``self`` only ``b`` is read)
 
-    def _dpm_sde_table(self, src, dst, prev, order, clip_x0, eta) -> torch.Tensor:
-        """The [n, 8] float32 coefficient rows of dm3d_dpm_sde_desc: _dpm_table's with c_z in column 6."""
+    def _dpm_sde_table(self, src, dst, prev, order, clip_x0, eta=None) -> torch.Tensor:
+        """The [n, 8] float32 coefficient rows of dm3d_dpm_sde_desc: _dpm_table's with c_z in column 6, which ``eta`` None (the ODE
+        solver's table) leaves at 0, as eta = 0 does: dpm_sde_coefficients returns dpm_coefficients' own rows then."""
         tab = np.zeros((len(src), 8), dtype=np.float64)
         tab[:, :2] = ddim_coefficients(self.b.alpha_bar, src, dst)[:, :2]
-        rows = dpm_sde_coefficients(self.b.alpha_bar, src, dst, prev, order, eta)
+        rows = dpm_sde_coefficients(self.b.alpha_bar, src, dst, prev, order, 0.0 if eta is None else eta)
         tab[:, 2:5], tab[:, 6] = rows[:, :3], rows[:, 3]
         tab[:, 5] = 1.0 if clip_x0 else 0.0
         return torch.from_numpy(tab.astype(np.float32))
 
-    def _dpm_sde_desc(self, x, eps, hist, coef, tau, pos, mode, noise=None, out=None, x0_out=None, t_next=None, t_idx=None, seed=0,
-                      x0_bound=None) -> DpmSdeDesc:
-        d = _fill(DpmSdeDesc(), x=x, eps=eps, hist=hist, out=out, x0_out=x0_out, coef=coef, pos=pos, t_next=t_next, t_idx=t_idx,
-                  x0_bound=x0_bound, noise=noise, tau=tau)
+    def _dpm_desc(self, x, eps, hist, coef, pos, mode, out=None, x0_out=None, t_next=None, t_idx=None, x0_bound=None, desc=DpmDesc,
+                  **own) -> DpmDesc:
+        """A dm3d_dpm_desc; ``desc`` and ``own`` are _dpm_sde_desc's: the extended descriptor and the pointers only it has."""
+        d = _fill(desc(), x=x, eps=eps, hist=hist, out=out, x0_out=x0_out, coef=coef, pos=pos, t_next=t_next, t_idx=t_idx,
+                  x0_bound=x0_bound, **own)
         d.batch, d.per_sample, d.rows, d.mode = x.shape[0], x[0].numel(), coef.shape[0], mode
-        d.seed = int(seed) & (2 ** 64 - 1)
         return d
 
-    def _dpm_desc(self, x, eps, hist, coef, pos, mode, out=None, x0_out=None, t_next=None, t_idx=None, x0_bound=None) -> DpmDesc:
-        d = _fill(DpmDesc(), x=x, eps=eps, hist=hist, out=out, x0_out=x0_out, coef=coef, pos=pos, t_next=t_next, t_idx=t_idx, x0_bound=x0_bound)
-        d.batch, d.per_sample, d.rows, d.mode = x.shape[0], x[0].numel(), coef.shape[0], mode
+    def _dpm_sde_desc(self, x, eps, hist, coef, tau, pos, mode, noise=None, out=None, x0_out=None, t_next=None, t_idx=None, seed=0,
+                      x0_bound=None) -> DpmSdeDesc:
+        d = self._dpm_desc(x, eps, hist, coef, pos, mode, out, x0_out, t_next, t_idx, x0_bound, desc=DpmSdeDesc, noise=noise, tau=tau)
+        d.seed = int(seed) & (2 ** 64 - 1)
         return d
 
     # -- dynamic thresholding of the x0 estimate ----------------------------------------------------------------------------------
@@ -1362,6 +1354,7 @@ class DpmSampler(DdimSampler):
     KIND = SOLVER = "dpmpp"
     UPDATE = "dpm_update"
     DRAWS = False
+    COEF = "dpm_coef"                         # the plan's coefficient table; the stochastic form keeps one of its own
 
     def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, clip_x0=True, solver_order=2, lower_order_final=True, threshold=None,
                  sde_eta=None):
@@ -1370,22 +1363,19 @@ class DpmSampler(DdimSampler):
         self.solver_order, self.lower_order_final = int(solver_order), bool(lower_order_final)
         if sde_eta is not None:
             self.sde_eta = model._sde_eta_rules(sde_eta)
-            self.UPDATE, self.DRAWS, self.SOLVER = "dpm_sde_update", True, "dpmpp_sde"
+            self.UPDATE, self.DRAWS, self.SOLVER, self.COEF = "dpm_sde_update", True, "dpmpp_sde", "dpm_sde_coef"
         super().__init__(model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=clip_x0, threshold=threshold)
 
     def _desc(self, noise=None):
-        if self.sde_eta is not None:
-            plan = self._tables("dpm_sde_coef")
-            _plan_buffer(plan, "dpm_hist", lambda: torch.zeros_like(plan.x))
-            d = self.model._dpm_sde_desc(self.x, self._head(plan.eps), self._head(plan.dpm_hist), plan.dpm_sde_coef, plan.ddim_tau,
-                                         plan.ddim_pos, 1, noise=noise, t_next=plan.ddim_next, t_idx=plan.t_idx, seed=self.seed,
-                                         x0_bound=self._bound())
-            d.seed_dev = plan.seed_buf.data_ptr()
-            return d
-        plan = self._tables("dpm_coef")
+        plan = self._tables(self.COEF)
         _plan_buffer(plan, "dpm_hist", lambda: torch.zeros_like(plan.x))
-        return self.model._dpm_desc(self.x, self._head(plan.eps), self._head(plan.dpm_hist), plan.dpm_coef, plan.ddim_pos, 1,
-                                    t_next=plan.ddim_next, t_idx=plan.t_idx, x0_bound=self._bound())
+        args = self.x, self._head(plan.eps), self._head(plan.dpm_hist), getattr(plan, self.COEF)
+        kw = dict(t_next=plan.ddim_next, t_idx=plan.t_idx, x0_bound=self._bound())
+        if self.sde_eta is None:
+            return self.model._dpm_desc(*args, plan.ddim_pos, 1, **kw)
+        d = self.model._dpm_sde_desc(*args, plan.ddim_tau, plan.ddim_pos, 1, noise=noise, seed=self.seed, **kw)
+        d.seed_dev = plan.seed_buf.data_ptr()
+        return d
 
     def _prev(self):
         """The level the step before row r started from (row n-1 runs first), -1 where the row is first order: the chain's first
@@ -1399,9 +1389,7 @@ class DpmSampler(DdimSampler):
         return prev
 
     def _coefficients(self, src, dst):
-        if self.sde_eta is not None:
-            return self.plan.dpm_sde_coef, self.model._dpm_sde_table(src, dst, self._prev(), self.solver_order, self.clip_x0, self.sde_eta)
-        return self.plan.dpm_coef, self.model._dpm_table(src, dst, self._prev(), self.solver_order, self.clip_x0)
+        return getattr(self.plan, self.COEF), self.model._dpm_sde_table(src, dst, self._prev(), self.solver_order, self.clip_x0, self.sde_eta)
 
 
 class _EditChain:

@@ -7,8 +7,8 @@
     dm3d_dpm_sde_update at eta = 1 (in-kernel Philox) and at eta = 0 (c_z = 0: dpm_kernel's work), of dm3d_dpm_update, and of
     dm3d_ddim_update at eta = 0 and eta = 1 (in-kernel Philox): blocks of 200 launches between two device events, the kinds
     alternating block by block, the median of --reps blocks after one warm block.  ``--parent-lib PATH`` (a libdm3d_hip.so built from
-    the parent commit; the output records its file name) times the three existing kernels of that library in the same process, its
-    blocks alternating with this build's.  The expectation the output states: dpm_sde (eta = 1) = dpm + (ddim eta 1 - ddim eta 0), the
+    the parent commit; the output records its file name) times the kernels of that library too in the same process, its blocks
+    alternating with this build's.  The expectation the output states: dpm_sde (eta = 1) = dpm + (ddim eta 1 - ddim eta 0), the
     new kernel moving dpm_kernel's bytes and doing ddim_kernel's Philox work; ``margin_us`` is the largest block-to-block spread
     (max - min) of the kinds involved.
   * step: ms per step (graph replay) of an S = --chain-steps "dpmpp_sde" chain against the "dpmpp" chain of the same S on the same
@@ -107,11 +107,12 @@ def main():
         handles = {"this": lib}
         if args.parent_lib:
             handles["parent"] = C.CDLL(os.path.abspath(args.parent_lib))
-            for name in ("dm3d_ddim_update", "dm3d_dpm_update"):
+            for name in ("dm3d_ddim_update", "dm3d_dpm_update", "dm3d_dpm_sde_update"):
                 getattr(handles["parent"], name).restype, getattr(handles["parent"], name).argtypes = _lib.SIGNATURES[name]
-        launches = {"dpm_sde_eta1_this": lambda: _lib.check(lib.dm3d_dpm_sde_update(C.byref(s1), st), "dpm_sde_update"),
-                    "dpm_sde_eta0_this": lambda: _lib.check(lib.dm3d_dpm_sde_update(C.byref(s0), st), "dpm_sde_update")}
+        launches = {}
         for who, hnd in handles.items():
+            launches[f"dpm_sde_eta1_{who}"] = lambda hnd=hnd: _lib.check(hnd.dm3d_dpm_sde_update(C.byref(s1), st), "dpm_sde_update")
+            launches[f"dpm_sde_eta0_{who}"] = lambda hnd=hnd: _lib.check(hnd.dm3d_dpm_sde_update(C.byref(s0), st), "dpm_sde_update")
             launches[f"dpm_{who}"] = lambda hnd=hnd: _lib.check(hnd.dm3d_dpm_update(C.byref(q0), st), "dpm_update")
             launches[f"ddim_eta0_{who}"] = lambda hnd=hnd: _lib.check(hnd.dm3d_ddim_update(C.byref(d0), st), "ddim_update")
             launches[f"ddim_eta1_{who}"] = lambda hnd=hnd: _lib.check(hnd.dm3d_ddim_update(C.byref(d1), st), "ddim_update")
