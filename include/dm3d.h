@@ -391,6 +391,36 @@ int dm3d_affine_act(const float* x, float* y, int64_t rows, int32_t c, const flo
 /* *flag = 1 if any |x[i]| > limit (the H3 range guard for a tensor no dm3d kernel produced, e.g. the caller's x_t). n % 4 == 0. */
 int dm3d_range_check(const float* x, int64_t n, float limit, int32_t* flag, void* stream);
 
+/* ---- What "seeded" means: the N(0,1) stream of every entry that draws its own noise ----------------------------------
+ * The draws are a function of the key, the element's position and two counter words, and of nothing else: not of the grid, the batch
+ * split, the mode, a mask, or a graph replay.  oracle/ref_philox.py restates this block on the host from the Philox paper, and the GPU
+ * tests hold every drawing entry to it element by element (tests/philox_cases.py: the bar), so a change to anything below changes every
+ * seeded result and is a change of contract.
+ *
+ * Generator: Philox4x32-10 (Salmon et al., SC'11): multipliers 0xD2511F53 (word 0) and 0xCD9E8D57 (word 2), the key bumped by
+ *   (0x9E3779B9, 0xBB67AE85) after each of the ten rounds.
+ * Key: (k0, k1) = (seed & 0xffffffff, seed >> 32) of the 64-bit `seed`, or of *seed_dev where that pointer is set (the same 64 bits;
+ *   a host that keeps the key in an int64 tensor writes seed - 2^64 for seed >= 2^63).
+ * Counter: one block of four words per float4 of output, (i & 0xffffffff, i >> 32, word 2, word 3), where i is the flat float4 index
+ *   into the tensor — element / 4 for dm3d_randn, b * (per_sample / 4) + (element of the sample) / 4 for the batched entries — and
+ *
+ *     entry                                     word 2                                      word 3 (stream constant)
+ *     dm3d_randn                                stream_id                                   0x5eed
+ *     dm3d_ddpm_update (mode 1, t > 0)          t[b], clamped to [0, timesteps)             0xd1f0
+ *     dm3d_ddim_update[_frame]                  tau[r], r = clamp(pos[b])                   0xdd1a
+ *     dm3d_dpm_sde_update[_frame]               tau[r], r = clamp(pos[b])                   0x5de2
+ *     dm3d_edit_update                          (int32)levels[r][2], r = clamp(pos[b])      0xed17
+ *
+ *   An element a row or a mask leaves without noise (t == 0, sigma == 0, c_z == 0, a clean level, w == 0) draws nothing and shifts
+ *   nobody else's counter.  The host's own dm3d_randn calls use stream_id 0x7fffffff (x_T of a chain) and 0x7ffffffe (training noise).
+ * Uniforms, in float32, each operation rounded (the library is built without contraction), from the output words (c0, c1, c2, c3):
+ *   u0 = ((float)c0 + 0.5f) * 2^-32, u1 = (float)c1 * 2^-32, u2 = ((float)c2 + 0.5f) * 2^-32, u3 = (float)c3 * 2^-32;
+ *   u0 and u2 lie in (0, 1] (never 0; 1 after rounding gives r = 0), u1 and u3 in [0, 1].
+ * Box-Muller: r0 = sqrtf(-2 logf(u0)), r1 = sqrtf(-2 logf(u2)), a1 = 6.283185307179586f * u1, a3 = 6.283185307179586f * u3; the four
+ *   elements of the float4, in order, are (r0 cos a1, r0 sin a1, r1 cos a3, r1 sin a3).  logf, sqrtf, sinf and cosf are the device
+ *   library's: they are not correctly rounded, so the float64 evaluation of these formulas is met to an absolute error on z, not
+ *   bitwise (docs/EXPERIMENTS.md records the measured error and the bar). */
+
 /* ---- DDPM posterior step: DiffusionModel.sample + the loop body of generate (:517-548, 571-573) --------------
  * Coefficients are gathered at t[b] and combined in float32 in the reference's order.
  *   mode 0 (sample):   mean_out = posterior mean, var_out[b] = posterior variance (no clip, no noise).

@@ -27,7 +27,8 @@ Entries and forms covered
   dm3d_attention      three-launch form (lq 64, lk 48; broadcast keys; scratch guarded) and fused form (c 256, lq 128, lk 32 / 96,
                       scratch NULL);  dm3d_attention_group: self + broadcast cross pass, fused and fallback, bitwise against single calls.
   dm3d_mlp_fused, dm3d_attn_front; dm3d_layernorm3[_h2], dm3d_softmax_rows[_h2], dm3d_affine_act, dm3d_split_h2, dm3d_vq_assign,
-  dm3d_gather_rows, dm3d_randn, dm3d_range_check, dm3d_ddpm_update (clamped t, seed_dev, all seven tables poisoned around).
+  dm3d_gather_rows, dm3d_randn, dm3d_range_check, dm3d_ddpm_update (clamped t, seed_dev, all seven tables poisoned around).  The N(0,1)
+  stream dm3d_randn and dm3d_ddpm_update draw is held to a host reference element by element in tests/test_gpu_philox.py, not here.
   The range guard (range_flag / range_limit), guard site by guard site (every DM3D_AMAX of the sources has a plant case that reaches it,
   the Winograd-x form's ragged-cout branch and both GEMM tile forms included): plant -> 1 (some plants negative), control -> exactly 0,
   limit 0 means 65504, and the lanes a partial tile masks must not speak.

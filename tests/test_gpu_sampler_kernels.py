@@ -31,7 +31,13 @@ Entries and cases
       *_frame(d, NULL) against the plain entry; the clip fraction of every clipping row between 0.2 and 0.8.
   in-kernel Philox (ddim, dpm_sde, edit): the draw recovered through a unit row and injected into a general row equals the drawn
       result bitwise; seed_dev; other seeds, other tau, the other kernels differ; (4, P) read flat equals (1, 4P) (one side wraps the
-      grid); mean and variance at tests/test_gpu_ddim.py's bars.
+      grid); mean and variance at tests/test_gpu_ddim.py's bars.  Against the host reference oracle/ref_philox.py (Philox4x32-10 from
+      the paper, the float32 uniforms restated exactly, Box-Muller in float64), EVERY element within philox_cases.Z_BAR: the four
+      sizes; seven seeds up to 2^64 - 1 by value and through seed_dev written as the int64 a chain writes, and a flipped bit 40 of
+      the key; a table of three timesteps under pos = [2, 0, 1]; the _frame kernels bitwise the plain ones (the wrapped grid too);
+      edit mode 1 under a mask of 0, 1 and fractions at channels 1, 3 and 8 (the surviving elements hold the z of their own index);
+      a seeded call on general rows against the float64 update fed the reference z.  tests/test_gpu_philox.py does the same for
+      dm3d_randn, dm3d_ddpm_update and the Python layer.
   dm3d_x0_threshold / _scratch_bytes: ranks 0, N-2, N-1, past the end, negative; frac 0 and general; smax binding and not; a
       non-clipping row and an all-non-clipping call (scratch: cleared histograms, everything else untouched); frame; two calls on one
       scratch; a heavy tie at the large size.  The bound is bitwise np.sort's.
@@ -46,7 +52,8 @@ Not covered, and why.  The factor f of the guidance rescale and the float64 loss
 f is held to the float64 bar and to "the output is bitwise f' x eps_g for a float32 f' within one ulp of the reference f"; the loss to
 1e-10.  A read outside a payload whose value is masked afterwards cannot be seen.  A NaN bound / more NaNs than ranks in the threshold
 (tests/test_gpu_threshold.py), batch > 6, per_sample near 2^31, and refused arguments (DM3D_EINVAL: the host tests) are not repeated.
-The Philox stream itself has no host reference: only its identities and moments are checked.
+Of the Philox stream: the high word of the float4 index (more than 2^34 elements: tests/test_philox_host.py checks it in the reference
+only) and the tail of the normal beyond what these counters reach (max |z| about 5.3).
 A miscount in the threshold's wave-aggregated counting shows at the large tied volume only: at the small sizes two lanes of a wave
 rarely share a digit under the selected prefix (docs/EXPERIMENTS.md, mutation (c)).
 
@@ -58,8 +65,10 @@ import numpy as np
 import pytest
 import torch
 
+import philox_cases as pc
 from guarded_buffers import IN, OUT, POISON_WORD, SENTINEL_WORD, Guarded
 from oracle import ref_kernels as rk
+from oracle import ref_philox as rp
 
 pytestmark = pytest.mark.gpu
 
@@ -143,6 +152,11 @@ def _sentinels(*shape):
     return np.full(shape, SENT, np.float32)
 
 
+def _seed_dev(seed_dev):
+    """The 8 bytes behind seed_dev: an int as uint64, or the int64 array a chain would write (philox_cases.seed_words)."""
+    return seed_dev if isinstance(seed_dev, np.ndarray) else np.array([seed_dev], np.uint64)
+
+
 def _check_inputs(bufs):
     for b in bufs.values():
         if b.role == IN:
@@ -206,7 +220,7 @@ def _run_update(dev, kind, x, eps, coef, pos, *, mode=0, noise=None, hist=None, 
             bufs["noise"] = _gin(dev, noise)
             d.noise = bufs["noise"].ptr
         if seed_dev is not None:
-            bufs["seed_dev"] = _gin(dev, np.array([seed_dev], np.uint64))
+            bufs["seed_dev"] = _gin(dev, _seed_dev(seed_dev))
             d.seed_dev = bufs["seed_dev"].ptr
     if bound is not None:
         bufs["bound"] = _gin(dev, np.asarray(bound, np.float32))
@@ -439,7 +453,7 @@ def _run_edit(dev, x0, levels, pos, *, mode=0, noise=None, x=None, w=None, chann
         bufs["noise"] = _gin(dev, noise)
         d.noise = bufs["noise"].ptr
     if seed_dev is not None:
-        bufs["seed_dev"] = _gin(dev, np.array([seed_dev], np.uint64))
+        bufs["seed_dev"] = _gin(dev, _seed_dev(seed_dev))
         d.seed_dev = bufs["seed_dev"].ptr
     if mode == 1:
         bufs["x"], bufs["w"] = _gout(dev, x), _gin(dev, w)
@@ -494,18 +508,24 @@ P_SMALL, P_FLAT = 65796, 4 * 65796                                           # (
 TAU, SEED = 517, 987654321
 
 
-def _draw(dev, kind, shape, seed=SEED, tau=TAU, seed_dev=None):
-    """The draw itself through a unit row: a_x0 = a_eps = 0, sigma = 1 / c_x = c_0 = c_1 = 0, c_z = 1 / sqrt(a') = 0, sqrt(1-a') = 1."""
+def _draw(dev, kind, shape, seed=SEED, tau=TAU, seed_dev=None, pos=None, frame=None):
+    """The draw itself through a unit row: a_x0 = a_eps = 0, sigma = 1 / c_x = c_0 = c_1 = 0, c_z = 1 / sqrt(a') = 0, sqrt(1-a') = 1.
+    `tau`: one timestep (a table of one row) or one per row of the table, every row a unit row; `pos` (default all 0) picks each
+    sample's row; `frame`: a frame table, through the _frame kernels (x = p = 0, so the estimate is 0 whatever the row holds)."""
     B, per = shape
     zero = np.zeros(shape, np.float32)
+    taus = np.atleast_1d(np.asarray(tau, np.int64))
+    pos = [0] * B if pos is None else pos
     if kind == "edit":
-        levels = np.array([[0, 1, tau, POISON]], np.float32)
-        return _run_edit(dev, zero, levels, [0] * B, seed=seed, seed_dev=seed_dev)
-    coef = np.full((1, 8), POISON, np.float32)
-    coef[0, :6] = (1, 1, 0, 0, 1, 0) if kind == "ddim" else (1, 1, 0, 0, 0, 0)
+        levels = np.array([[0, 1, t, POISON] for t in taus], np.float32)
+        return _run_edit(dev, zero, levels, pos, seed=seed, seed_dev=seed_dev)
+    coef = np.full((len(taus), 8), POISON, np.float32)
+    coef[:, :6] = (1, 1, 0, 0, 1, 0) if kind == "ddim" else (1, 1, 0, 0, 0, 0)
     if kind == "sde":
-        coef[0, 6] = 1
-    return _run_update(dev, kind, zero, zero, coef, [0] * B, tau=[tau], seed=seed, seed_dev=seed_dev, x0_out=False).res
+        coef[:, 6] = 1
+    if frame is not None:
+        coef[:, :2] = POISON
+    return _run_update(dev, kind, zero, zero, coef, pos, tau=taus.astype(np.int32), seed=seed, seed_dev=seed_dev, x0_out=False, frame=frame).res
 
 
 @pytest.mark.parametrize("kind", ["ddim", "sde", "edit"])
@@ -541,6 +561,109 @@ def test_philox_draws(dev, rng, kind):
         a = _run_update(dev, kind, x, eps, coef, pos, hist=hist, tau=tau, seed=SEED).res
         b = _run_update(dev, kind, x, eps, coef, pos, hist=hist, tau=tau, noise=zs).res
     _same(f"philox {kind} drawn is injected", a, b)
+
+
+# ---- the stream against its host reference (oracle/ref_philox.py): every element, at philox_cases.Z_BAR ------------------------------
+PHILOX_KINDS = ["ddim", "sde", "edit"]
+REF_Z = {"ddim": rp.ddim, "sde": rp.dpm_sde, "edit": rp.edit}
+TAU_TABLE, TAU_POS = [3, 517, 999], [2, 0, 1]                               # pos is no identity and no row index is a timestep
+
+
+def _z_close(name, got, ref, bar=pc.Z_BAR):
+    pc.z_close(WORST, name, got, ref, bar)
+
+
+@pytest.mark.parametrize("per", SIZES)
+@pytest.mark.parametrize("kind", PHILOX_KINDS)
+def test_philox_reference_sizes(dev, kind, per):
+    """One float4, a partial block, two blocks, the wrapped grid (batch 2: the second sample's counters start at per / 4)."""
+    B = 2 if per == BIG else 3
+    z = _draw(dev, kind, (B, per), seed=pc.SEED64)
+    _z_close(kind, z, REF_Z[kind](B, per, TAU, pc.SEED64))
+
+
+@pytest.mark.parametrize("seed", pc.SEEDS, ids=hex)
+@pytest.mark.parametrize("kind", PHILOX_KINDS)
+def test_philox_reference_seeds(dev, kind, seed):
+    """Both key words, by value and through seed_dev written as the int64 a chain writes (negative from 2^63 up)."""
+    shape = (2, 1004)
+    ref = REF_Z[kind](*shape, TAU, seed)
+    z = _draw(dev, kind, shape, seed=seed)
+    _z_close(kind, z, ref)
+    _same(f"philox {kind} seed_dev int64", _draw(dev, kind, shape, seed=5, seed_dev=pc.seed_words(seed)), z)
+    assert pc.independent(z, _draw(dev, kind, shape, seed=seed ^ (1 << 40)))  # a bit of the key's high word
+
+
+@pytest.mark.parametrize("kind", PHILOX_KINDS)
+def test_philox_reference_tau_of_the_row(dev, rng, kind):
+    """Three rows with three timesteps and pos = [2, 0, 1]: word 2 is tau[pos[b]] (the level of row pos[b]), not tau[b], not the row
+    index; the _frame kernels draw the same z bitwise."""
+    shape = (3, 1004)
+    want_tau = [TAU_TABLE[p] for p in TAU_POS]
+    ref = REF_Z[kind](*shape, want_tau, pc.SEED64)
+    assert pc.independent(ref, REF_Z[kind](*shape, TAU_TABLE, pc.SEED64)) and pc.independent(ref, REF_Z[kind](*shape, TAU_POS, pc.SEED64))
+    z = _draw(dev, kind, shape, seed=pc.SEED64, tau=TAU_TABLE, pos=TAU_POS)
+    _z_close(f"{kind} tau table", z, ref)
+    if kind != "edit":
+        for per in (1004, BIG):
+            B = 2 if per == BIG else 3
+            plain = z if per == 1004 else _draw(dev, kind, (B, per), seed=pc.SEED64, tau=TAU_TABLE, pos=TAU_POS[:B])
+            framed = _draw(dev, kind, (B, per), seed=pc.SEED64, tau=TAU_TABLE, pos=TAU_POS[:B], frame=_frame(rng, 3, kind))
+            _same(f"philox {kind} frame kernel", framed, plain)
+
+
+@pytest.mark.parametrize("channels", [1, 3, 8])
+def test_philox_reference_edit_mask(dev, rng, channels):
+    """Mode 1 on the unit level (known_t = z): an element with w = 1 holds the reference z of ITS OWN index — the skipped ones around
+    it shifted no counter, and the 3-channel path (a lane's four elements on two voxels) indexes as the others do; w = 0 keeps x
+    bitwise.  Where 0 < w < 1 the element is fl(fl(w z) + fl((1-w) x)) with 1-w exact (w >= 0.25), three roundings of at most
+    2^-24 (|w z| + |(1-w) x|) each way, so z recovered as (out - (1-w) x) / w carries at most 2^-23 (|z| + (1-w) |x| / w) more than the
+    bar: added per element."""
+    per = EDIT_SIZES[channels][2]
+    B = 3
+    x = np.clip(_f32(rng, B, per), -3, 3)
+    w = _weights(rng, B, per // channels)
+    levels = np.array([[0, 1, t, POISON] for t in TAU_TABLE], np.float32)
+    got = _run_edit(dev, np.zeros((B, per), np.float32), levels, TAU_POS, mode=1, x=x, w=w, channels=channels, seed=pc.SEED64)
+    ref = rp.edit(B, per, [TAU_TABLE[p] for p in TAU_POS], pc.SEED64)
+    we = np.repeat(w, channels, axis=1)
+    assert (we == 0).sum() > per // 4 and (we == 1).sum() > per // 4 and ((we > 0) & (we < 1)).sum() > per // 4
+    assert np.array_equal(_bits(got)[we == 0], _bits(x)[we == 0]), "an element with w = 0 was written"
+    _z_close(f"edit mode 1 w = 1, channels {channels}", got[we == 1], ref[we == 1])
+    mid = (we > 0) & (we < 1)
+    w64, x64 = we[mid].astype(np.float64), x[mid].astype(np.float64)
+    one_m_w = (np.float32(1) - we[mid]).astype(np.float64)
+    z_mid = (got[mid].astype(np.float64) - one_m_w * x64) / w64
+    bar = pc.Z_BAR + 2.0 ** -23 * (np.abs(ref[mid]) + one_m_w * np.abs(x64) / w64)
+    _z_close(f"edit mode 1 0 < w < 1 (recovered), channels {channels}", z_mid, ref[mid], bar)
+
+
+@pytest.mark.parametrize("kind", PHILOX_KINDS)
+def test_philox_reference_general_row(dev, rng, kind):
+    """A seeded call on general rows against the float64 update fed the REFERENCE z: host arithmetic end to end, nothing of the device's
+    own draw injected.  The bar is the entry's own plus |coefficient of z| x the z bar."""
+    B, per = 4, 1004
+    x, eps, hist = (_f32(rng, B, per) for _ in range(3))
+    if kind == "edit":
+        levels = _levels(rng)
+        levels[:, 2] = [3, -1, 517, 999]
+        pos = np.array([3, 1, 0, 2])
+        z = rp.edit(B, per, levels[pos, 2].astype(np.int64), pc.SEED64)
+        got = _run_edit(dev, x, levels, pos, seed=pc.SEED64)
+        ref = rk.edit_update(x, levels, pos, z, order="f64")
+        bar = EDIT_BAR + np.abs(levels[pos, 1].astype(np.float64)) * pc.Z_BAR
+    else:
+        coef = _coef(rng, kind)
+        col = 4 if kind == "ddim" else 6
+        noisy = [r for r in range(len(coef)) if coef[r, col] != 0]           # rows with a noise term
+        pos = np.array(noisy[::-1] + noisy)[:B]
+        assert len(noisy) >= 3
+        tau = (np.arange(len(coef)) * 37 + 11).astype(np.int32)
+        z = REF_Z[kind](B, per, tau[pos], pc.SEED64)
+        got = _run_update(dev, kind, x, eps, coef, pos, hist=hist, tau=tau, seed=pc.SEED64).res
+        ref, _ = _ref_update(kind, "f64", x, eps, coef, pos, noise=z, hist=hist)
+        bar = _bars(kind, coef, pos, None, float(np.abs(z).max()))[0] + np.abs(coef[pos, col].astype(np.float64)) * pc.Z_BAR
+    _close(f"dm3d_{NAMES.get(kind, 'edit')}_update seeded, reference z", got, ref, bar)
 
 
 # ======================================================================================================================================
