@@ -170,8 +170,13 @@ class LossDesc(C.Structure):
     ]
 
 
+class GradScaleDesc(C.Structure):
+    _fields_ = [("g", _f32p), ("n", C.c_int64), ("partials", C.c_void_p), ("state", _f32p), ("clip_norm", C.c_float), ("pre_scale", C.c_float)]
+
+
 GUIDE_PARTIAL_BLOCKS = 256          # DM3D_GUIDE_PARTIAL_BLOCKS: GuideDesc.partials holds [batch][256][4] doubles
 LOSS_PARTIAL_BLOCKS = 64            # DM3D_LOSS_PARTIAL_BLOCKS: LossDesc.partials holds [batch][64] doubles
+GRADNORM_PARTIAL_BLOCKS = 1024      # DM3D_GRADNORM_PARTIAL_BLOCKS: GradScaleDesc.partials holds [1024] doubles
 
 # name -> (restype, argtypes): every symbol include/dm3d.h declares
 SIGNATURES = {
@@ -263,6 +268,9 @@ SIGNATURES = {
     "dm3d_mse_loss_grad": (C.c_int, [_f32p, _f32p, C.c_int64, C.c_double, C.c_void_p, _f32p, C.c_void_p]),
     "dm3d_adam": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "dm3d_adam_ema": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "dm3d_grad_scale": (C.c_int, [C.POINTER(GradScaleDesc), C.c_void_p]),
+    "dm3d_adam_scaled": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _f32p,
+                                    C.c_void_p]),
     "dm3d_graph_begin": (C.c_int, [C.c_void_p]),
     "dm3d_graph_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "dm3d_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p]),

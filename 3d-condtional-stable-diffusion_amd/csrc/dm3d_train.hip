@@ -598,12 +598,19 @@ __global__ __launch_bounds__(256) void mse_loss_grad_kernel(const float* __restr
 
 // keras.optimizers.Adam (beta_1, beta_2, epsilon; main_conditional_dm.py:153): m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
 // w -= lr_t * m / (sqrt(v) + eps), lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t) computed by the host
-// (one element; adam_kernel and adam_ema_kernel share it, so turning the average on cannot move the training trajectory)
+// (one element; adam_kernel, adam_ema_kernel and adam_scaled_kernel share it, so turning the average or the clipping on cannot move the
+// training trajectory by more than the factor says)
 __device__ __forceinline__ void adam_element(float& wi, float gi, float& m_io, float& v_io, float lr_t, float b1, float b2, float eps) {
     const float mi = b1 * m_io + (1.0f - b1) * gi;
     const float vi = b2 * v_io + (1.0f - b2) * gi * gi;
     m_io = mi; v_io = vi;
     wi -= lr_t * mi / (sqrtf(vi) + eps);
+}
+
+// ema + rate * (w_new - ema) as sub, mul, add (adam_ema_kernel and adam_scaled_kernel share it)
+__device__ __forceinline__ float ema_lerp(float e, float wi, float rate) {
+    const float lerp = e + rate * (wi - e);
+    return rate == 1.0f ? wi : lerp;                         // (e + (w - e) can miss w by an ulp where the two differ in magnitude)
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
@@ -631,13 +638,98 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ w, co
             float wi = wv[e], mi = mv[e], vi = vv[e];
             adam_element(wi, gv[e], mi, vi, lr_t, b1, b2, eps);
             wv[e] = wi; mv[e] = mi; vv[e] = vi;
-            const float lerp = ev[e] + rate * (wi - ev[e]);
-            ev[e] = rate == 1.0f ? wi : lerp;                // (e + (w - e) can miss w by an ulp where the two differ in magnitude)
+            ev[e] = ema_lerp(ev[e], wi, rate);
         }
         reinterpret_cast<f32x4*>(m)[i] = mv;
         reinterpret_cast<f32x4*>(v)[i] = vv;
         reinterpret_cast<f32x4*>(w)[i] = wv;
         reinterpret_cast<f32x4*>(ema)[i] = ev;
+    }
+}
+
+// ---- global-norm clipping and gradient accumulation (include/dm3d.h, dm3d_gradscale_desc) ---------------------------------------------
+// Pass 1: each block leaves the float64 sum of g^2 over its grid-stride share in partials[blockIdx.x].  (double)g * g is exact, the
+// thread's sum runs in a fixed order, the wave's through an xor butterfly (every lane ends with the same bits), the block's over its
+// four wave slots in index order: a slot is a function of g, n and the grid alone, and the grid is a function of n alone.  The slots
+// past the grid are written as 0, so nothing a previous launch left in partials is ever read.  HBM-bound: 4 B per element, read once;
+// four independent float4 loads per lane and round keep enough of them in flight.
+constexpr int GN_PARTS = DM3D_GRADNORM_PARTIAL_BLOCKS;
+
+__device__ __forceinline__ double sq4(const f32x4 q) {
+    return (((double)q[0] * (double)q[0] + (double)q[1] * (double)q[1]) + (double)q[2] * (double)q[2]) + (double)q[3] * (double)q[3];
+}
+
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* __restrict__ g, long n4, double* __restrict__ partials) {
+    const long stride = (long)gridDim.x * 256;
+    const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g);
+    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const f32x4 a = g4[i], b = g4[i + stride], c = g4[i + 2 * stride], d = g4[i + 3 * stride];
+        s0 += sq4(a); s1 += sq4(b); s2 += sq4(c); s3 += sq4(d);
+    }
+    for (; i < n4; i += stride) s0 += sq4(g4[i]);
+    double s = (s0 + s1) + (s2 + s3);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    for (long slot = (long)gridDim.x + (long)blockIdx.x * 256 + threadIdx.x; slot < GN_PARTS; slot += stride) partials[slot] = 0.0;
+}
+
+// Pass 2: one block of 256 threads adds the 1024 slots in one fixed tree: thread t adds slots 4t .. 4t+3 in index order, a wave
+// reduces through the xor butterfly, the four wave slots (32 B of LDS) are added in index order.  The tree is a function of nothing, so
+// the sum does not depend on the order the blocks of pass 1 ran in.  state = (norm of pre_scale * g, the factor the optimizer multiplies
+// g by, 1 if the sum is not finite, 0).
+static_assert(GN_PARTS == 4 * 256, "grad_scale_finalize_kernel reads four slots per thread");
+__global__ __launch_bounds__(256) void grad_scale_finalize_kernel(const double* __restrict__ partials, float clip_norm, float pre_scale,
+                                                                  float* __restrict__ state) {
+    const double* p = partials + 4 * threadIdx.x;
+    double s = ((p[0] + p[1]) + p[2]) + p[3];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const double sum = ((red[0] + red[1]) + red[2]) + red[3];
+    const double norm = (double)pre_scale * sqrt(sum);
+    const double factor = norm > (double)clip_norm ? (double)clip_norm / norm : 1.0;       // (a NaN norm compares false: the flag below skips the step)
+    f32x4 st;
+    st[0] = (float)norm;
+    st[1] = (float)((double)pre_scale * factor);
+    st[2] = isfinite(sum) ? 0.0f : 1.0f;
+    st[3] = 0.0f;
+    *reinterpret_cast<f32x4*>(state) = st;
+}
+
+// dm3d_adam_ema (EMA) / dm3d_adam (not EMA) on g scaled by the device scalar state[1]; state[2] != 0 (a non-finite gradient) skips the
+// step: nothing is stored.  s * g is one float32 multiply and the rest is adam_element and ema_lerp, so with s = 1 the results are
+// bitwise those of the unscaled kernels.
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_scaled_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, float* __restrict__ ema, long n4, float lr_t, float b1,
+                                                          float b2, float eps, float rate, const float* __restrict__ state) {
+    const float s = state[1];
+    if (state[2] != 0.0f) return;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        f32x4 wv = reinterpret_cast<f32x4*>(w)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+        f32x4 ev;
+        if (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
+        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float wi = wv[e], mi = mv[e], vi = vv[e];
+            adam_element(wi, __fmul_rn(s, gv[e]), mi, vi, lr_t, b1, b2, eps);
+            wv[e] = wi; mv[e] = mi; vv[e] = vi;
+            if (EMA) ev[e] = ema_lerp(ev[e], wi, rate);
+        }
+        reinterpret_cast<f32x4*>(m)[i] = mv;
+        reinterpret_cast<f32x4*>(v)[i] = vv;
+        reinterpret_cast<f32x4*>(w)[i] = wv;
+        if (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
     }
 }
 
@@ -876,4 +968,45 @@ extern "C" int dm3d_adam_ema(float* w, const float* g, float* m, float* v, float
     }
     hipLaunchKernelGGL(adam_ema_kernel, dim3(tgrid(n / 4)), dim3(256), 0, TR_ST, w, g, m, v, ema, (long)(n / 4), lr_t, beta1, beta2, eps, ema_rate);
     return dm3d_launch_check("adam_ema_kernel");
+}
+
+extern "C" int dm3d_grad_scale(const dm3d_gradscale_desc* d, void* stream) {
+    DM3D_REQUIRE(d != nullptr, "grad_scale: null descriptor");
+    DM3D_REQUIRE(d->g && d->partials && d->state, "grad_scale: null pointer");
+    DM3D_REQUIRE(dm3d_aligned16(d->g) && dm3d_aligned16(d->state) && (reinterpret_cast<uintptr_t>(d->partials) & 7u) == 0,
+                 "grad_scale: g and state must be 16-byte aligned, partials 8-byte aligned");
+    DM3D_REQUIRE(d->n > 0 && d->n % 4 == 0, "grad_scale: n=%lld must be a positive multiple of 4", (long long)d->n);
+    DM3D_REQUIRE(d->clip_norm > 0.0f, "grad_scale: clip_norm %g must be > 0 (+inf: no clipping)", (double)d->clip_norm);      // (a NaN fails)
+    DM3D_REQUIRE(d->pre_scale > 0.0f && isfinite(d->pre_scale), "grad_scale: pre_scale %g must be finite and > 0", (double)d->pre_scale);
+    const long n4 = (long)(d->n / 4);
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(tgrid(n4, DM3D_GRADNORM_PARTIAL_BLOCKS)), dim3(256), 0, TR_ST, d->g, n4, d->partials);
+    if (int rc = dm3d_launch_check("grad_sqnorm_kernel")) return rc;
+    hipLaunchKernelGGL(grad_scale_finalize_kernel, dim3(1), dim3(256), 0, TR_ST, d->partials, d->clip_norm, d->pre_scale, d->state);
+    return dm3d_launch_check("grad_scale_finalize_kernel");
+}
+
+extern "C" int dm3d_adam_scaled(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, float beta1, float beta2,
+                                float eps, float ema_rate, const float* state, void* stream) {
+    DM3D_REQUIRE(w && g && m && v && state, "adam_scaled: null pointer");
+    DM3D_REQUIRE(dm3d_aligned16(w) && dm3d_aligned16(g) && dm3d_aligned16(m) && dm3d_aligned16(v) && dm3d_aligned16(ema) && dm3d_aligned16(state),
+                 "adam_scaled: pointers must be 16-byte aligned");
+    DM3D_REQUIRE(n > 0 && n % 4 == 0, "adam_scaled: n=%lld must be a positive multiple of 4", (long long)n);
+    DM3D_REQUIRE(ema_rate >= 0.0f && ema_rate <= 1.0f, "adam_scaled: ema_rate %g must lie in [0, 1]", (double)ema_rate);   // (a NaN fails both)
+    const long n4 = (long)(n / 4);
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(state), bytes = (uintptr_t)n * sizeof(float);
+    for (const void* p : {(const void*)w, (const void*)m, (const void*)v, (const void*)ema}) {          // (the kernel stores to these while it reads state)
+        const uintptr_t p0 = reinterpret_cast<uintptr_t>(p);
+        DM3D_REQUIRE(p == nullptr || s0 + 16 <= p0 || p0 + bytes <= s0, "adam_scaled: state overlaps a buffer the step writes");
+    }
+    if (ema == nullptr) {
+        hipLaunchKernelGGL(adam_scaled_kernel<false>, dim3(tgrid(n4)), dim3(256), 0, TR_ST, w, g, m, v, ema, n4, lr_t, beta1, beta2, eps, ema_rate, state);
+        return dm3d_launch_check("adam_scaled_kernel");
+    }
+    const uintptr_t e0 = reinterpret_cast<uintptr_t>(ema);
+    for (const void* p : {(const void*)w, (const void*)g, (const void*)m, (const void*)v}) {
+        const uintptr_t p0 = reinterpret_cast<uintptr_t>(p);
+        DM3D_REQUIRE(e0 + bytes <= p0 || p0 + bytes <= e0, "adam_scaled: ema overlaps another buffer");
+    }
+    hipLaunchKernelGGL(adam_scaled_kernel<true>, dim3(tgrid(n4)), dim3(256), 0, TR_ST, w, g, m, v, ema, n4, lr_t, beta1, beta2, eps, ema_rate, state);
+    return dm3d_launch_check("adam_scaled_kernel");
 }

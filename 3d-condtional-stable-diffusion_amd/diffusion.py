@@ -9,7 +9,9 @@ selects the in-kernel Philox stream, ``use_graph=`` toggles HIP-graph replay of 
 and DPM-Solver++ chains (include/dm3d.h, dm3d_thresh_desc); ``sampler="dpmpp_sde"`` / ``sde_eta=`` is the stochastic form of the
 DPM-Solver++(2M) chain (include/dm3d.h, dm3d_dpm_sde_desc).  Training extensions, off by default: ``compile(ema_decay=)`` keeps an
 exponential moving average of the weights in the optimizer's launch (include/dm3d.h, dm3d_adam_ema) and ``use_ema()`` samples from it;
-``compile(context_dropout=, null_context=)`` trains the unconditional branch that classifier-free guidance is defined against.
+``compile(context_dropout=, null_context=)`` trains the unconditional branch that classifier-free guidance is defined against;
+``compile(global_clipnorm=, grad_accum_steps=)`` clips the gradient by its global norm and applies the mean of k micro-batches, both as
+device scalars the optimizer's launch reads (include/dm3d.h, dm3d_grad_scale / dm3d_adam_scaled).
 ``prediction="v"`` / ``"x0"`` (constructor) reads the network's output as v (Salimans & Ho 2022) or as x0 instead of eps: every chain
 converts it to eps right after the U-Net (include/dm3d.h, dm3d_pred_desc) and train_step fits the matching target;
 ``compile(loss_weighting="min_snr", snr_gamma=)`` weighs each sample's loss by min-SNR-gamma (Hang et al. 2023; dm3d_loss_desc).
@@ -119,6 +121,7 @@ class DiffusionModel:
         self._stream = None
         self._ema_decay, self._ema_warmup = None, True
         self.context_dropout, self.null_context = 0.0, None
+        self._global_clipnorm, self._grad_accum_steps, self._warned_skip = None, 1, False
         self.weights = WeightSets(self.network, self._make_trainer, self._drop_graphs)     # live / averaged weights and the Trainer
         self._warned_tf_ema = False
         self.network._before_use = self.weights.refresh
@@ -165,7 +168,7 @@ class DiffusionModel:
         return [self.loss_tracker]
 
     def compile(self, loss=None, optimizer=None, *, ema_decay=None, ema_warmup=True, context_dropout=0.0, null_context=None,
-                loss_weighting=None, snr_gamma=5.0):
+                loss_weighting=None, snr_gamma=5.0, global_clipnorm=None, grad_accum_steps=1):
         """keras ``model.compile``.  Keyword-only extensions, read again by every train_step like the learning rate (so a later compile()
         takes effect between steps):
         ``ema_decay`` in [0, 1) (None: off) keeps an exponential moving average of the trainable weights, updated in the optimizer's
@@ -176,8 +179,14 @@ class DiffusionModel:
         classifier-free guidance is defined against.
         ``loss_weighting="min_snr"`` (None: every sample weighs 1) weighs each sample's loss by min-SNR-gamma (Hang et al. 2023) with
         gamma = ``snr_gamma`` > 0 (schedules.py, objective_rows): the weight that evens out the timesteps' pull on the shared weights,
-        for whichever ``prediction`` the model was built with.  ``snr_gamma`` other than its default needs ``loss_weighting``."""
-        from .train import _check_ema_decay
+        for whichever ``prediction`` the model was built with.  ``snr_gamma`` other than its default needs ``loss_weighting``.
+        ``global_clipnorm`` (None: off; else finite and > 0) scales each applied gradient by min(1, global_clipnorm / |g|), |g| the L2
+        norm over all trainable weights; a step whose gradient holds an inf or a NaN is skipped on the device (weights, Adam slots and
+        the average stay as they are; ``trainer.skipped_steps`` counts them, ``trainer.grad_norm`` is the last norm).
+        ``grad_accum_steps`` = k (an int >= 1): every k-th train_step applies the mean gradient of the last k calls, the others only add
+        to the gradient buffer; a change in mid-cycle takes effect at the next cycle boundary."""
+        from .train import _check_clipping, _check_ema_decay
+        global_clipnorm, grad_accum_steps = _check_clipping(global_clipnorm, grad_accum_steps)
         if loss_weighting not in LOSS_WEIGHTINGS:
             raise ValueError(f"loss_weighting must be None or 'min_snr', got {loss_weighting!r}")
         if not float(snr_gamma) > 0:                         # (a NaN fails the comparison too)
@@ -201,6 +210,7 @@ class DiffusionModel:
         self._ema_decay, self._ema_warmup = ema_decay, bool(ema_warmup)
         self.context_dropout, self.null_context = context_dropout, null_context
         self.loss_weighting, self.snr_gamma = loss_weighting, float(snr_gamma)
+        self._global_clipnorm, self._grad_accum_steps = global_clipnorm, grad_accum_steps
 
     # -- which weights the sampling network runs on -------------------------------------------------------------------------
     def _has_ema(self) -> bool:
@@ -259,7 +269,9 @@ class DiffusionModel:
         ``weights="ema"`` exports the averaged model under the ordinary names instead, without optimizer or ema/ entries, in either
         format: how an averaged model reaches a reference-format TF checkpoint.  An .npz file of a v- or x0-model also carries
         ``meta/prediction`` (an eps model writes no such entry; the TF format has no place for it), and a zero-terminal-SNR model's
-        ``meta/zero_terminal_snr``."""
+        ``meta/zero_terminal_snr``.  Checkpoints carry no half-filled accumulation cycle: under compile(grad_accum_steps=k) a save in
+        mid-cycle writes the weights and slots as they are and the gradients gathered so far are not in the file, so save at cycle
+        boundaries (after a train_step that applied an update)."""
         if weights not in ("live", "ema"):
             raise ValueError(f"weights must be 'live' or 'ema', got {weights!r}")
         if weights == "ema" and not self._has_ema():
@@ -327,6 +339,11 @@ class DiffusionModel:
         A ``prediction="v"`` / ``"x0"`` model is fitted to that target, and compile(loss_weighting="min_snr") weighs each sample's loss
         (dm3d_objective_loss_grad; the Trainer keeps the per-sample losses as ``sample_loss``); an eps model without weighting runs the
         reference's plain MSE launch.
+        Under compile(grad_accum_steps=k) call j = 0..k-1 of a cycle adds its gradient to the buffer (the first zeroes it), and only call
+        k-1 all-reduces, clips (compile(global_clipnorm=)), applies the mean of the k gradients and reads the norm and the skip flag
+        back; the others leave the weights, the Adam slots, the average and their counters untouched.  The loss tracker takes every
+        call's loss and the BatchNormalization moving statistics update on every call, as Keras would on every forward.  A step skipped
+        for a non-finite gradient raises nothing and warns once per model.
         (``drop`` is the one name ``**extensions`` takes, by keyword only: the signature's named keywords stay t, noise and latents.)"""
         drop = extensions.pop("drop", None)
         if extensions:
@@ -376,11 +393,20 @@ class DiffusionModel:
         rows = None
         if self.prediction != "eps" or self.loss_weighting is not None:
             rows = objective_rows(self.b.alpha_bar, t, self.prediction, self.loss_weighting, self.snr_gamma)
-        loss, _ = tr.loss_and_grad(latents, t, noise, ids, betas, T, self.global_bs, self.lc, objective=rows)
-        tr.allreduce_grads(loss)                   # data-parallel replicas (one process per GPU): flat RCCL all-reduces; no-op alone
-        tr.adam_step()
-        self.weights.trained()
+        tr.set_clipping(self._global_clipnorm, self._grad_accum_steps)      # (re-read at every step, like the learning rate)
+        accumulate, last = tr.micro_step()
+        loss, _ = tr.loss_and_grad(latents, t, noise, ids, betas, T, self.global_bs, self.lc, objective=rows, accumulate=accumulate)
+        tr.micro_step_done()                       # (only now: a call that raised has added nothing and is not counted)
+        if last:
+            tr.allreduce_grads(loss)               # data-parallel replicas (one process per GPU): flat RCCL all-reduces; no-op alone
+            tr.adam_step()
+        self.weights.trained()                     # (every call: the forward moved the moving statistics even where no step was applied)
         self.loss_tracker.update_state(float(loss.item()))
+        if last and tr.finish_step() and not self._warned_skip:              # (after loss.item(): the stream has been waited for)
+            import warnings
+            self._warned_skip = True
+            warnings.warn("train_step: the gradient was not finite, so the optimizer step was skipped (weights, Adam slots and the "
+                          "average are unchanged); trainer.skipped_steps counts such steps")
         return {"loss": self.loss_tracker.result()}
 
     def encode_latents(self, images):

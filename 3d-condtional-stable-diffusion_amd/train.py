@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, ConvDesc, GemmDesc, LossDesc, WgradDesc, check, lib
+from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, ConvDesc, GemmDesc, GradScaleDesc, LossDesc, WgradDesc, check, lib
 from .betas import time_embedding_table
 from .schedules import _host
 from .weights import UNetConfig, walk
@@ -49,6 +49,17 @@ def _check_ema_decay(decay) -> float:
     if not 0.0 <= decay < 1.0:                            # (a NaN fails the comparison too)
         raise ValueError(f"ema_decay must lie in [0, 1), got {decay}")
     return decay
+
+
+def _check_clipping(global_clipnorm, accum_steps):
+    """(global_clipnorm, accum_steps) as set_clipping() / compile() keep them: None or a finite float > 0, and an int >= 1."""
+    if global_clipnorm is not None:
+        global_clipnorm = float(global_clipnorm)
+        if not 0.0 < global_clipnorm < float("inf"):      # (a NaN fails the comparison too)
+            raise ValueError(f"global_clipnorm must be None or a finite number > 0, got {global_clipnorm}")
+    if isinstance(accum_steps, bool) or int(accum_steps) != accum_steps or int(accum_steps) < 1:
+        raise ValueError(f"grad_accum_steps must be an integer >= 1, got {accum_steps!r}")
+    return global_clipnorm, int(accum_steps)
 
 
 class Param:
@@ -134,6 +145,10 @@ class Trainer:
         self._cache: Dict[str, object] = {}
         self.ema, self.ema_decay, self.ema_warmup, self.ema_updates = None, None, True, 0
         self.sample_loss = None                              # [B] float64 device: the per-sample losses of the last step with an objective
+        # global-norm clipping and gradient accumulation (set_clipping): off, nothing allocated
+        self.global_clipnorm, self.accum_steps, self.cycle_steps, self.accum_pos = None, 1, 1, 0
+        self.clip_state = self.clip_partials = None          # [4] float32 / [GRADNORM_PARTIAL_BLOCKS] float64 device, made on first use
+        self.grad_norm, self.skipped_steps, self._unread_step = None, 0, None
         if ema_decay is not None:
             self.set_ema(ema_decay, ema_warmup)
 
@@ -591,8 +606,10 @@ class Trainer:
         check(lib().dm3d_fill(self.grad.data_ptr(), self.grad.numel(), 0.0, _st()), "fill")
 
     def loss_and_grad(self, latents: torch.Tensor, t: torch.Tensor, noise: torch.Tensor, ctx_ids, betas_dev, timesteps: int, global_bs: int,
-                      lc: int, update_moving: bool = True, objective=None):
-        """q_sample -> training forward -> loss -> backward.  Returns (loss [1] float64 device tensor, pred).  ``objective`` (None: the
+                      lc: int, update_moving: bool = True, objective=None, accumulate: bool = False):
+        """q_sample -> training forward -> loss -> backward.  Returns (loss [1] float64 device tensor, pred).  ``accumulate`` skips the
+        zero_grad() at the head: the backward adds into ``grad``, which then holds the sum over the calls since the last zeroing (gradient
+        accumulation; adam_step's pre_scale turns the sum into the mean).  ``objective`` (None: the
         reference's plain MSE on the noise, dm3d_mse_loss_grad) holds the [B, 4] float32 rows (a_z, a_0, w, 0) of
         schedules.objective_rows(): the loss is then w |pred - (a_z noise + a_0 latents)|^2 per sample (dm3d_objective_loss_grad),
         summed in a fixed order, and ``sample_loss`` ([B] float64 device tensor) keeps each sample's share of it."""
@@ -608,7 +625,8 @@ class Trainer:
             ids = torch.as_tensor(np.asarray(ctx_ids, dtype=np.int32).reshape(-1)).to(dev)
             if ids.numel() == 1 and B > 1:
                 ids = ids.repeat(B)
-        self.zero_grad()
+        if not accumulate:
+            self.zero_grad()
         pred = self.forward(noisy, t.cpu().numpy().astype(np.int64), ids, update_moving)
         loss = torch.zeros(1, dtype=torch.float64, device=dev)
         pred.g = torch.empty_like(pred.v)
@@ -692,18 +710,81 @@ class Trainer:
     def adam_step(self):
         """keras.optimizers.Adam.apply_gradients over the flat buffers (one launch).  With an average (set_ema) the launch is
         dm3d_adam_ema: the same step, bitwise, and ema += ema_rate * (theta_new - ema) in the same pass, ema_rate =
-        float32(1 - ema_decay_at(decay, ema_updates, warmup)) computed here in float64."""
+        float32(1 - ema_decay_at(decay, ema_updates, warmup)) computed here in float64.  With clipping or accumulation on
+        (set_clipping) dm3d_grad_scale first leaves the norm and the factor in ``clip_state`` and the launch is dm3d_adam_scaled, which
+        reads them from device memory: the host reads nothing in between (finish_step() does, afterwards; a state of an earlier step
+        that nobody has read yet is read here first, so its skip is never lost)."""
+        self.finish_step()
         self.step_count += 1
         tt = self.step_count
         lr_t = self.lr * (1.0 - ADAM_BETA2 ** tt) ** 0.5 / (1.0 - ADAM_BETA1 ** tt)
-        if self.ema is None:
+        rate = 0.0
+        if self.ema is not None:
+            rate = float(np.float32(1.0 - ema_decay_at(self.ema_decay, self.ema_updates, self.ema_warmup)))
+        if self.global_clipnorm is not None or self.cycle_steps > 1:
+            if self.clip_state is None:
+                self.clip_state = _zeros(4, device=self.device)
+                self.clip_partials = torch.empty(_lib.GRADNORM_PARTIAL_BLOCKS, dtype=torch.float64, device=self.device)
+            d = GradScaleDesc()
+            d.g, d.n, d.partials, d.state = self.grad.data_ptr(), self.total, self.clip_partials.data_ptr(), self.clip_state.data_ptr()
+            d.clip_norm = float("inf") if self.global_clipnorm is None else self.global_clipnorm
+            d.pre_scale = 1.0 / self.cycle_steps
+            check(lib().dm3d_grad_scale(C.byref(d), _st()), "grad_scale")
+            check(lib().dm3d_adam_scaled(self.theta.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                         None if self.ema is None else self.ema.data_ptr(), self.total, lr_t, ADAM_BETA1, ADAM_BETA2, ADAM_EPS,
+                                         rate, self.clip_state.data_ptr(), _st()), "adam_scaled")
+            self._unread_step = self.ema is not None         # finish_step() has a state to read; whether ema_updates advanced with it
+        elif self.ema is None:
             check(lib().dm3d_adam(self.theta.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.total, lr_t,
                                   ADAM_BETA1, ADAM_BETA2, ADAM_EPS, _st()), "adam")
-            return
-        rate = float(np.float32(1.0 - ema_decay_at(self.ema_decay, self.ema_updates, self.ema_warmup)))
-        check(lib().dm3d_adam_ema(self.theta.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.ema.data_ptr(),
-                                  self.total, lr_t, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, rate, _st()), "adam_ema")
-        self.ema_updates += 1
+        else:
+            check(lib().dm3d_adam_ema(self.theta.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.ema.data_ptr(),
+                                      self.total, lr_t, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, rate, _st()), "adam_ema")
+        if self.ema is not None:
+            self.ema_updates += 1
+
+    # ---- global-norm clipping and gradient accumulation ---------------------------------------------------------------------------------
+    def set_clipping(self, global_clipnorm: Optional[float] = None, accum_steps: int = 1):
+        """``global_clipnorm`` (None: off): adam_step scales the gradient by min(1, clipnorm / |g|), |g| the L2 norm over the whole flat
+        buffer, and skips the step when the buffer holds an inf or a NaN (theta, m, v and the average stay as they are).
+        ``accum_steps`` = k: the buffer holds the sum over k loss_and_grad calls (``accumulate``) and adam_step applies their mean;
+        a change while a cycle of micro_step() is under way takes effect when the next one starts.  With None and 1 nothing is
+        allocated and adam_step is the plain dm3d_adam / dm3d_adam_ema launch.
+        Data-parallel training: allreduce_grads runs BEFORE adam_step, so every rank computes the same norm from the same summed
+        buffer, applies the same factor and skips together; no collective is added."""
+        self.global_clipnorm, self.accum_steps = _check_clipping(global_clipnorm, accum_steps)
+        if self.accum_pos == 0:
+            self.cycle_steps = self.accum_steps
+
+    def micro_step(self):
+        """train_step's place in the accumulation cycle: (accumulate, last) for the call about to run — whether loss_and_grad adds
+        to what the buffer holds, and whether this call ends the cycle (all-reduce, adam_step, finish_step).  Nothing advances until
+        micro_step_done(): a call that raised before its backward finished is simply taken again."""
+        if self.accum_pos == 0:
+            self.cycle_steps = self.accum_steps
+        return self.accum_pos > 0, self.accum_pos + 1 >= self.cycle_steps
+
+    def micro_step_done(self):
+        """The call micro_step() described has added its gradient to the buffer."""
+        self.accum_pos = 0 if self.accum_pos + 1 >= self.cycle_steps else self.accum_pos + 1
+
+    def finish_step(self) -> bool:
+        """After adam_step, once the caller is ready to wait for the stream: reads the 16 bytes of ``clip_state``, sets ``grad_norm``
+        (the norm of the gradient the step applied, before clipping) and, if the gradient was not finite and the device skipped the step,
+        takes the step_count / ema_updates increments back — the next step's bias correction is that of a step that never happened — and
+        counts it in ``skipped_steps``.  Returns whether the step was skipped.  Without clipping or accumulation there is nothing to read."""
+        if self._unread_step is None:
+            return False
+        had_ema, self._unread_step = self._unread_step, None
+        st = self.clip_state.cpu().numpy()
+        self.grad_norm = float(st[0])
+        if st[2] == 0.0:
+            return False
+        self.step_count -= 1
+        if had_ema:
+            self.ema_updates -= 1
+        self.skipped_steps += 1
+        return True
 
     # ---- exponential moving average of the weights (what diffusion models are sampled from) -------------------------------------------
     def set_ema(self, decay: Optional[float], warmup: bool = True):

@@ -159,7 +159,9 @@ class WeightSets:
     def ensure_trainer(self, lr, ema_decay, ema_warmup, *, step=False):
         """The training engine (train.py), built on first use from the live weights, with the waiting optimizer slots.  A new one, and
         one about to take a train step (``step``), gets compile()'s settings: the learning rate and the average's decay and warm-up
-        (None: no average is kept); a loaded average continues in it."""
+        (None: no average is kept); a loaded average continues in it.  (compile()'s clipping and accumulation settings go to the
+        Trainer from train_step itself, Trainer.set_clipping: they own no weights and need no rule here.  A Trainer dropped by load()
+        takes its half-filled accumulation cycle with it.)"""
         tr, new = self.trainer, self.trainer is None
         if new:
             tr = self.trainer = self._make_trainer(self.live(), lr)

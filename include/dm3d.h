@@ -27,7 +27,7 @@ extern "C" {
                                      dm3d_pack_weights_h3f8 are gone; the Winograd-x image pairs its taps differently; dm3d_mlp_fused; conv skip_wpk_frag, gn_stats; dm3d_groupnorm_finalize2), 110 (dm3d_attn_front), 111 (conv split_counters: the Cin split
                                      meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc, dm3d_edit_update / dm3d_edit_desc,
                                      dm3d_guide_update / dm3d_guide_desc, dm3d_dpm_update / dm3d_dpm_desc and dm3d_x0_threshold / dm3d_thresh_desc were added within 111 (no existing entry changed; dm3d_ddim_desc and dm3d_dpm_desc grew by one trailing optional pointer, x0_bound, which a zeroed descriptor leaves NULL; dm3d_thresh_desc then by one, frame, likewise, and dm3d_ddim_update_frame / dm3d_dpm_update_frame are new entries),
-                                     and dm3d_pred_to_eps / dm3d_pred_desc, dm3d_objective_loss_grad / dm3d_loss_desc and dm3d_dpm_sde_update(_frame) / dm3d_dpm_sde_desc likewise (new entries and structs only): a host built against an older header must be rebuilt */
+                                     and dm3d_pred_to_eps / dm3d_pred_desc, dm3d_objective_loss_grad / dm3d_loss_desc and dm3d_dpm_sde_update(_frame) / dm3d_dpm_sde_desc and dm3d_grad_scale / dm3d_gradscale_desc / dm3d_adam_scaled likewise (new entries and structs only): a host built against an older header must be rebuilt */
 
 #define DM3D_OK            0
 #define DM3D_EINVAL       -1      /* bad argument (shape, alignment, null pointer) */
@@ -832,6 +832,42 @@ int dm3d_adam(float* w, const float* g, float* m, float* v, int64_t n, float lr_
  * n % 4 == 0 (float4 accesses), ema_rate finite in [0, 1], ema overlapping none of w, g, m, v. */
 int dm3d_adam_ema(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, float beta1, float beta2, float eps,
                   float ema_rate, void* stream);
+
+/* Global-norm gradient clipping and gradient accumulation, as two device scalars the optimizer's launch reads: no host read sits between
+ * the norm and the step.  dm3d_grad_scale makes two launches on `stream`:
+ *   grad_sqnorm_kernel          min(ceil(n/4/256), DM3D_GRADNORM_PARTIAL_BLOCKS) blocks (a function of n alone) stride over g as float4;
+ *                               every block leaves the float64 sum of (double)g*g (exact products) of its share in partials[block] and
+ *                               the slots past the grid are written as 0: nothing a previous launch left in partials is read
+ *   grad_scale_finalize_kernel  one block adds the slots in one fixed tree (thread t its slots 4t..4t+3 in index order, then a fixed
+ *                               wave and block reduction; no atomics: the result repeats bitwise whatever order the blocks ran in)
+ *                               and writes
+ *     state[0] = (float)(pre_scale * sqrt(sum))                                  the norm of the gradient the step will apply
+ *     state[1] = (float)(pre_scale * (norm > clip_norm ? clip_norm / norm : 1))  in float64, rounded once
+ *     state[2] = 1 if sum is not finite (an inf or a NaN in g), else 0
+ *     state[3] = 0
+ * pre_scale is the 1/k of k accumulated micro-batches; clip_norm = +inf clips nothing.  With nothing to clip and pre_scale = 1 the
+ * factor is exactly 1.0f, so the step is bitwise the unclipped one.  tf.clip_by_global_norm computes clip * min(1/norm, 1/clip)
+ * instead, which is not exactly 1 under the threshold; the rule here differs from it by at most an ulp of the factor.
+ * HBM-bound: 4 B per element read once.  Checked before any launch (DM3D_EINVAL): d and every pointer non-NULL, g and state 16-byte and
+ * partials 8-byte aligned, n > 0 and n % 4 == 0, clip_norm > 0 (not NaN), pre_scale finite and > 0. */
+#define DM3D_GRADNORM_PARTIAL_BLOCKS 1024  /* partials holds [DM3D_GRADNORM_PARTIAL_BLOCKS] doubles */
+typedef struct dm3d_gradscale_desc {
+    const float* g;             /* [n] the gradient buffer (read only) */
+    int64_t n;                  /* > 0, n % 4 == 0 */
+    double* partials;           /* [DM3D_GRADNORM_PARTIAL_BLOCKS] device scratch, written in full by every call */
+    float* state;               /* [4] device, 16-byte aligned */
+    float clip_norm;            /* > 0; +inf: no clipping */
+    float pre_scale;            /* finite, > 0 */
+} dm3d_gradscale_desc;
+int dm3d_grad_scale(const dm3d_gradscale_desc* d, void* stream);
+/* dm3d_adam_ema (ema NULL: dm3d_adam) on the gradient state[1] * g[i], one float32 multiply per element; g itself is not modified.
+ * Every thread reads state[1] and state[2] (dm3d_grad_scale's) from device memory.  state[2] != 0 skips the step: nothing is stored, and
+ * w, m, v and ema stay bitwise as they were.  The element update and the lerp are the functions dm3d_adam and dm3d_adam_ema run, so with
+ * state[1] = 1 the results are bitwise theirs, and with state[1] = s bitwise theirs on the buffer float32(s) * g.  Checked before
+ * the launch (DM3D_EINVAL): w, g, m, v, state non-NULL; every pointer 16-byte aligned; n > 0 and n % 4 == 0; ema_rate in [0, 1]; ema,
+ * when given, overlapping none of w, g, m, v; state overlapping none of the buffers the step writes (w, m, v, ema). */
+int dm3d_adam_scaled(float* w, const float* g, float* m, float* v, float* ema /* NULL: none */, int64_t n, float lr_t, float beta1,
+                     float beta2, float eps, float ema_rate, const float* state, void* stream);
 
 /* ---- HIP graph capture of one denoising step (replaces the eager per-op Python loop of generate, :559-573) -- */
 int dm3d_graph_begin(void* stream);
