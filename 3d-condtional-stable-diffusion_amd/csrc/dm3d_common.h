@@ -29,6 +29,11 @@ static inline int dm3d_launch_check(const char* what) {
     return DM3D_OK;
 }
 static inline bool dm3d_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// Whether the byte ranges [p, p + p_bytes) and [q, q + q_bytes) share a byte (a null pointer is no range).
+static inline bool dm3d_ranges_overlap(const void* p, uint64_t p_bytes, const void* q, uint64_t q_bytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return p && q && a < b + q_bytes && b < a + p_bytes;
+}
 static inline int64_t dm3d_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 // The grid of a stream kernel over [batch][per4] float4 (ddpm_kernel's): at most 256 blocks of 256 lanes a sample, which stride over it.
 static inline dim3 dm3d_stream_grid(long per4, int batch) {
@@ -70,6 +75,27 @@ __device__ __forceinline__ float dm3d_act(float v, int act) {
     if (act == DM3D_ACT_RELU) return fmaxf(v, 0.0f);
     if (act == DM3D_ACT_SILU) return dm3d_silu(v);
     return v;
+}
+
+// The fixed-order float64 sum of v[0..K-1] over a block of 256 lanes, the one tree behind every "runs repeat bitwise" of include/dm3d.h:
+// a wave adds lane l and lane l ^ off for off = 32, 16, .. 1, lane 0 of each wave leaves its K totals in red[wave], and after the one
+// barrier every lane returns ((red[0] + red[1]) + red[2]) + red[3].  Only lane 0's wave total is ever stored, and at every step lane 0
+// and the lanes it will still read (l < off) add their own value and that of lane l + off = l ^ off, in that order: the pairs and their
+// order are those of a __shfl_down tree, so which of the two shuffles is written here moves no bit.  Every lane of the block must
+// arrive; one call per kernel (red is not reused); red takes 8 K bytes of LDS per wave, 32 K per block.
+template <int K>
+__device__ __forceinline__ void dm3d_block_sum_f64(double (&v)[K], double (*red)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[threadIdx.x >> 6][k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
 }
 
 // One (tap, Cin-chunk) step of the implicit GEMM for a wave owning MR x NR tiles of 32x32 outputs.

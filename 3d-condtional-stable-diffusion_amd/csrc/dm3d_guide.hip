@@ -2,8 +2,8 @@
 // the combine eps_neg + w (eps_pos - eps_neg) with per-sample w, the guidance rescale of Lin et al. 2023 (section 3.4) from per-sample
 // standard deviations, and the mirror that hands the updated first half of a 2B plan to its second half.  Three pure HBM streams
 // like ddim_kernel, 16 B per lane.  The standard deviations come from float64 sums (a float32 product is exact in float64, so a
-// volume with |mean| >> std keeps its variance), reduced in a fixed order: lanes by shuffles, waves through LDS in wave order, blocks
-// through a partials buffer in block order by a second launch (no atomics, no grid-wide barrier).
+// volume with |mean| >> std keeps its variance), reduced in a fixed order: the block by dm3d_block_sum_f64, blocks through a partials
+// buffer in block order by a second launch (no atomics, no grid-wide barrier).
 #include "dm3d_common.h"
 
 namespace {
@@ -16,22 +16,6 @@ struct GuideArgs {
     const float* scale; const float* rescale; double* partials;
     float* x; int* t_idx; int batch;
 };
-
-// Sum of v[0..3] over the block's 256 lanes, in a fixed order; every lane returns the totals.  One call per kernel (red is not reused).
-__device__ __forceinline__ void block_sum4(double (&v)[4], double (*red)[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) red[wave][k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-}
 
 __global__ __launch_bounds__(256) void guide_combine_kernel(const GuideArgs p) {
     __shared__ double red[4][4];
@@ -63,7 +47,7 @@ __global__ __launch_bounds__(256) void guide_combine_kernel(const GuideArgs p) {
         }
     }
     if (!stats) return;                                                      // uniform over the block
-    block_sum4(acc, red);
+    dm3d_block_sum_f64(acc, red);
     if (threadIdx.x == 0) {
         double* dst = p.partials + ((long)b * PARTS + blockIdx.x) * 4;
 #pragma unroll
@@ -84,7 +68,7 @@ __global__ __launch_bounds__(256) void guide_rescale_kernel(const GuideArgs p) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = src[k];
     }
-    block_sum4(v, red);
+    dm3d_block_sum_f64(v, red);
     if (threadIdx.x == 0) {
         const double n = (double)(p.per4 * 4);
         const double mp = v[0] / n, mg = v[2] / n;

@@ -1,8 +1,8 @@
 // dm3d_objective.hip — what the network's output means (include/dm3d.h, dm3d_pred_desc / dm3d_loss_desc): the conversion of a v- or
 // x0-prediction to the eps every solver reads, and the training loss against the matching target with a per-sample weight (min-SNR).
 // Two pure HBM streams like q_sample_kernel, 16 B per lane, every float32 operation rounded on its own.  The loss is summed in float64
-// in a fixed order: lanes by shuffles, waves through LDS in wave order, blocks through a partials buffer in block order by a second
-// one-block launch (no atomics): runs repeat bitwise, and the caller gets one loss per sample.
+// in a fixed order: the block by dm3d_block_sum_f64, blocks through a partials buffer in block order by a second one-block launch (no
+// atomics): runs repeat bitwise, and the caller gets one loss per sample.
 #include "dm3d_common.h"
 
 namespace {
@@ -30,12 +30,12 @@ __global__ __launch_bounds__(256) void pred_to_eps_kernel(const float* pred, con
 __global__ __launch_bounds__(256) void objective_loss_kernel(const float* __restrict__ pred, const float* __restrict__ noise,
                                                              const float* __restrict__ x0, const float* __restrict__ coef, double inv,
                                                              float* __restrict__ dpred, double* __restrict__ partials, long per4) {
-    __shared__ double red[4];
+    __shared__ double red[4][1];
     const int b = blockIdx.y;
     const float az = coef[4 * b], a0 = coef[4 * b + 1];
     const float scale = (float)(2.0 * inv * (double)coef[4 * b + 2]);
     const long base = (long)b * per4;
-    double s = 0.0;
+    double s[1] = {0.0};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < per4; i += (long)gridDim.x * 256) {
         const f32x4 p = reinterpret_cast<const f32x4*>(pred)[base + i], z = reinterpret_cast<const f32x4*>(noise)[base + i];
         const f32x4 c = reinterpret_cast<const f32x4*>(x0)[base + i];
@@ -43,16 +43,13 @@ __global__ __launch_bounds__(256) void objective_loss_kernel(const float* __rest
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float d = __fsub_rn(p[e], __fadd_rn(__fmul_rn(az, z[e]), __fmul_rn(a0, c[e])));
-            s += (double)d * (double)d;
+            s[0] += (double)d * (double)d;
             g[e] = __fmul_rn(d, scale);
         }
         if (dpred) reinterpret_cast<f32x4*>(dpred)[base + i] = g;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[(long)b * PARTS + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    dm3d_block_sum_f64(s, red);
+    if (threadIdx.x == 0) partials[(long)b * PARTS + blockIdx.x] = s[0];
 }
 
 // One block: loss_rows[b] = w*inv*(partials[b][0] + ... + partials[b][nblocks-1]), then loss[0] = loss_rows[0] + ... in index order.
@@ -71,12 +68,9 @@ __global__ __launch_bounds__(256) void objective_sum_kernel(const double* __rest
     }
 }
 
-// Two byte ranges of `bytes` each that share bytes without being the same range.
-bool partial_overlap(const void* a, const void* b, uint64_t bytes) {
-    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-    return p != q && p < q + bytes && q < p + bytes;
-}
-bool overlap(const void* a, const void* b, uint64_t bytes) { return a == b || partial_overlap(a, b, bytes); }
+// Two byte ranges of `bytes` each that share bytes: at all, or without being the same range (in place is allowed).
+bool overlap(const void* a, const void* b, uint64_t bytes) { return dm3d_ranges_overlap(a, bytes, b, bytes); }
+bool partial_overlap(const void* a, const void* b, uint64_t bytes) { return a != b && overlap(a, b, bytes); }
 
 }  // namespace
 

@@ -598,7 +598,7 @@ __global__ __launch_bounds__(256) void mse_loss_grad_kernel(const float* __restr
 
 // keras.optimizers.Adam (beta_1, beta_2, epsilon; main_conditional_dm.py:153): m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
 // w -= lr_t * m / (sqrt(v) + eps), lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t) computed by the host
-// (one element; adam_kernel, adam_ema_kernel and adam_scaled_kernel share it, so turning the average or the clipping on cannot move the
+// (one element; adam_kernel and every form of adam_step_kernel share it, so turning the average or the clipping on cannot move the
 // training trajectory by more than the factor says)
 __device__ __forceinline__ void adam_element(float& wi, float gi, float& m_io, float& v_io, float lr_t, float b1, float b2, float eps) {
     const float mi = b1 * m_io + (1.0f - b1) * gi;
@@ -607,7 +607,7 @@ __device__ __forceinline__ void adam_element(float& wi, float gi, float& m_io, f
     wi -= lr_t * mi / (sqrtf(vi) + eps);
 }
 
-// ema + rate * (w_new - ema) as sub, mul, add (adam_ema_kernel and adam_scaled_kernel share it)
+// ema + rate * (w_new - ema) as sub, mul, add, so rate 0 leaves ema as it is; rate 1 stores w_new itself
 __device__ __forceinline__ float ema_lerp(float e, float wi, float rate) {
     const float lerp = e + rate * (wi - e);
     return rate == 1.0f ? wi : lerp;                         // (e + (w - e) can miss w by an ulp where the two differ in magnitude)
@@ -623,36 +623,47 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
     }
 }
 
-// The Adam step and the exponential moving average of the weights in one pass over the five buffers (36 B per element against 28 for
-// Adam alone and 40 for Adam and a separate averaging pass): ema += rate * (w_new - ema) as sub, mul, add, so rate 0 leaves ema as it
-// is; rate 1 stores w_new itself.  HBM-bound: one float4 per buffer and thread, grid-stride.
-__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, float* __restrict__ ema, long n4, float lr_t, float b1,
-                                                       float b2, float eps, float rate) {
+// The float4 Adam step of dm3d_adam_ema and dm3d_adam_scaled, one body for all their forms.  HBM-bound: one float4 per buffer and
+// thread, grid-stride.
+//   EMA: the exponential moving average of the weights in the same pass over the five buffers (36 B per element against 28 for Adam alone
+//        and 40 for Adam and a separate averaging pass).
+//   SCALED: g is multiplied by the device scalar state[1], one float32 multiply in front of adam_element, so with state[1] = 1 the
+//        results are bitwise the unscaled form's; state[2] != 0 (a non-finite gradient) skips the step: nothing is stored.
+struct NoState {};
+template <bool EMA, bool SCALED>
+__global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, float* __restrict__ ema, long n4, float lr_t, float b1,
+                                                        float b2, float eps, float rate,
+                                                        std::conditional_t<SCALED, const float* __restrict__, NoState> state) {
+    float s = 1.0f;
+    if constexpr (SCALED) {
+        s = state[1];
+        if (state[2] != 0.0f) return;
+    }
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         f32x4 wv = reinterpret_cast<f32x4*>(w)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
-        f32x4 ev = reinterpret_cast<f32x4*>(ema)[i];
+        f32x4 ev;
+        if (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
         const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float wi = wv[e], mi = mv[e], vi = vv[e];
-            adam_element(wi, gv[e], mi, vi, lr_t, b1, b2, eps);
+            adam_element(wi, SCALED ? __fmul_rn(s, gv[e]) : gv[e], mi, vi, lr_t, b1, b2, eps);
             wv[e] = wi; mv[e] = mi; vv[e] = vi;
-            ev[e] = ema_lerp(ev[e], wi, rate);
+            if (EMA) ev[e] = ema_lerp(ev[e], wi, rate);
         }
         reinterpret_cast<f32x4*>(m)[i] = mv;
         reinterpret_cast<f32x4*>(v)[i] = vv;
         reinterpret_cast<f32x4*>(w)[i] = wv;
-        reinterpret_cast<f32x4*>(ema)[i] = ev;
+        if (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
     }
 }
 
 // ---- global-norm clipping and gradient accumulation (include/dm3d.h, dm3d_gradscale_desc) ---------------------------------------------
 // Pass 1: each block leaves the float64 sum of g^2 over its grid-stride share in partials[blockIdx.x].  (double)g * g is exact, the
-// thread's sum runs in a fixed order, the wave's through an xor butterfly (every lane ends with the same bits), the block's over its
-// four wave slots in index order: a slot is a function of g, n and the grid alone, and the grid is a function of n alone.  The slots
-// past the grid are written as 0, so nothing a previous launch left in partials is ever read.  HBM-bound: 4 B per element, read once;
-// four independent float4 loads per lane and round keep enough of them in flight.
+// thread's sum runs in a fixed order and the block's through dm3d_block_sum_f64: a slot is a function of g, n and the grid alone, and
+// the grid is a function of n alone.  The slots past the grid are written as 0, so nothing a previous launch left in partials is ever
+// read.  HBM-bound: 4 B per element, read once; four independent float4 loads per lane and round keep enough of them in flight.
 constexpr int GN_PARTS = DM3D_GRADNORM_PARTIAL_BLOCKS;
 
 __device__ __forceinline__ double sq4(const f32x4 q) {
@@ -660,6 +671,7 @@ __device__ __forceinline__ double sq4(const f32x4 q) {
 }
 
 __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* __restrict__ g, long n4, double* __restrict__ partials) {
+    __shared__ double red[4][1];
     const long stride = (long)gridDim.x * 256;
     const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g);
     double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
@@ -669,32 +681,24 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* __restric
         s0 += sq4(a); s1 += sq4(b); s2 += sq4(c); s3 += sq4(d);
     }
     for (; i < n4; i += stride) s0 += sq4(g4[i]);
-    double s = (s0 + s1) + (s2 + s3);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    __shared__ double red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    double s[1] = {(s0 + s1) + (s2 + s3)};
+    dm3d_block_sum_f64(s, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s[0];
     for (long slot = (long)gridDim.x + (long)blockIdx.x * 256 + threadIdx.x; slot < GN_PARTS; slot += stride) partials[slot] = 0.0;
 }
 
-// Pass 2: one block of 256 threads adds the 1024 slots in one fixed tree: thread t adds slots 4t .. 4t+3 in index order, a wave
-// reduces through the xor butterfly, the four wave slots (32 B of LDS) are added in index order.  The tree is a function of nothing, so
-// the sum does not depend on the order the blocks of pass 1 ran in.  state = (norm of pre_scale * g, the factor the optimizer multiplies
-// g by, 1 if the sum is not finite, 0).
+// Pass 2: one block of 256 threads adds the 1024 slots in one fixed tree: thread t adds slots 4t .. 4t+3 in index order, then
+// dm3d_block_sum_f64.  The tree is a function of nothing, so the sum does not depend on the order the blocks of pass 1 ran in.
+// state = (norm of pre_scale * g, the factor the optimizer multiplies g by, 1 if the sum is not finite, 0).
 static_assert(GN_PARTS == 4 * 256, "grad_scale_finalize_kernel reads four slots per thread");
 __global__ __launch_bounds__(256) void grad_scale_finalize_kernel(const double* __restrict__ partials, float clip_norm, float pre_scale,
                                                                   float* __restrict__ state) {
+    __shared__ double red[4][1];
     const double* p = partials + 4 * threadIdx.x;
-    double s = ((p[0] + p[1]) + p[2]) + p[3];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    __shared__ double red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    double s[1] = {((p[0] + p[1]) + p[2]) + p[3]};
+    dm3d_block_sum_f64(s, red);
     if (threadIdx.x != 0) return;
-    const double sum = ((red[0] + red[1]) + red[2]) + red[3];
+    const double sum = s[0];
     const double norm = (double)pre_scale * sqrt(sum);
     const double factor = norm > (double)clip_norm ? (double)clip_norm / norm : 1.0;       // (a NaN norm compares false: the flag below skips the step)
     f32x4 st;
@@ -703,34 +707,6 @@ __global__ __launch_bounds__(256) void grad_scale_finalize_kernel(const double* 
     st[2] = isfinite(sum) ? 0.0f : 1.0f;
     st[3] = 0.0f;
     *reinterpret_cast<f32x4*>(state) = st;
-}
-
-// dm3d_adam_ema (EMA) / dm3d_adam (not EMA) on g scaled by the device scalar state[1]; state[2] != 0 (a non-finite gradient) skips the
-// step: nothing is stored.  s * g is one float32 multiply and the rest is adam_element and ema_lerp, so with s = 1 the results are
-// bitwise those of the unscaled kernels.
-template <bool EMA>
-__global__ __launch_bounds__(256) void adam_scaled_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, float* __restrict__ ema, long n4, float lr_t, float b1,
-                                                          float b2, float eps, float rate, const float* __restrict__ state) {
-    const float s = state[1];
-    if (state[2] != 0.0f) return;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        f32x4 wv = reinterpret_cast<f32x4*>(w)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
-        f32x4 ev;
-        if (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
-        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float wi = wv[e], mi = mv[e], vi = vv[e];
-            adam_element(wi, __fmul_rn(s, gv[e]), mi, vi, lr_t, b1, b2, eps);
-            wv[e] = wi; mv[e] = mi; vv[e] = vi;
-            if (EMA) ev[e] = ema_lerp(ev[e], wi, rate);
-        }
-        reinterpret_cast<f32x4*>(m)[i] = mv;
-        reinterpret_cast<f32x4*>(v)[i] = vv;
-        reinterpret_cast<f32x4*>(w)[i] = wv;
-        if (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
-    }
 }
 
 }  // namespace
@@ -954,20 +930,26 @@ extern "C" int dm3d_adam(float* w, const float* g, float* m, float* v, int64_t n
     return dm3d_launch_check("adam_kernel");
 }
 
+// What dm3d_adam_ema and dm3d_adam_scaled ask of their common arguments (`who` names the entry in the message); ema == NULL: no average.
+static int check_adam4(const char* who, const float* w, const float* g, const float* m, const float* v, const float* ema, int64_t n,
+                       float ema_rate) {
+    DM3D_REQUIRE(w && g && m && v, "%s: null pointer", who);
+    DM3D_REQUIRE(dm3d_aligned16(w) && dm3d_aligned16(g) && dm3d_aligned16(m) && dm3d_aligned16(v) && dm3d_aligned16(ema),
+                 "%s: pointers must be 16-byte aligned", who);
+    DM3D_REQUIRE(n > 0 && n % 4 == 0, "%s: n=%lld must be a positive multiple of 4", who, (long long)n);
+    DM3D_REQUIRE(ema_rate >= 0.0f && ema_rate <= 1.0f, "%s: ema_rate %g must lie in [0, 1]", who, (double)ema_rate);      // (a NaN fails both)
+    const uint64_t bytes = (uint64_t)n * sizeof(float);
+    for (const float* p : {w, g, m, v}) DM3D_REQUIRE(!dm3d_ranges_overlap(ema, bytes, p, bytes), "%s: ema overlaps another buffer", who);
+    return DM3D_OK;
+}
+
 extern "C" int dm3d_adam_ema(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, float beta1, float beta2, float eps,
                              float ema_rate, void* stream) {
-    DM3D_REQUIRE(w && g && m && v && ema, "adam_ema: null pointer");
-    DM3D_REQUIRE(dm3d_aligned16(w) && dm3d_aligned16(g) && dm3d_aligned16(m) && dm3d_aligned16(v) && dm3d_aligned16(ema),
-                 "adam_ema: pointers must be 16-byte aligned");
-    DM3D_REQUIRE(n > 0 && n % 4 == 0, "adam_ema: n=%lld must be a positive multiple of 4", (long long)n);
-    DM3D_REQUIRE(ema_rate >= 0.0f && ema_rate <= 1.0f, "adam_ema: ema_rate %g must lie in [0, 1]", (double)ema_rate);      // (a NaN fails both)
-    const uintptr_t e0 = reinterpret_cast<uintptr_t>(ema), bytes = (uintptr_t)n * sizeof(float);
-    for (const void* p : {(const void*)w, (const void*)g, (const void*)m, (const void*)v}) {
-        const uintptr_t p0 = reinterpret_cast<uintptr_t>(p);
-        DM3D_REQUIRE(e0 + bytes <= p0 || p0 + bytes <= e0, "adam_ema: ema overlaps another buffer");
-    }
-    hipLaunchKernelGGL(adam_ema_kernel, dim3(tgrid(n / 4)), dim3(256), 0, TR_ST, w, g, m, v, ema, (long)(n / 4), lr_t, beta1, beta2, eps, ema_rate);
-    return dm3d_launch_check("adam_ema_kernel");
+    DM3D_REQUIRE(ema, "adam_ema: null pointer");
+    if (int rc = check_adam4("adam_ema", w, g, m, v, ema, n, ema_rate)) return rc;
+    hipLaunchKernelGGL((adam_step_kernel<true, false>), dim3(tgrid(n / 4)), dim3(256), 0, TR_ST, w, g, m, v, ema, (long)(n / 4), lr_t, beta1,
+                       beta2, eps, ema_rate, NoState{});
+    return dm3d_launch_check("adam_step_kernel<ema>");
 }
 
 extern "C" int dm3d_grad_scale(const dm3d_gradscale_desc* d, void* stream) {
@@ -987,26 +969,15 @@ extern "C" int dm3d_grad_scale(const dm3d_gradscale_desc* d, void* stream) {
 
 extern "C" int dm3d_adam_scaled(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr_t, float beta1, float beta2,
                                 float eps, float ema_rate, const float* state, void* stream) {
-    DM3D_REQUIRE(w && g && m && v && state, "adam_scaled: null pointer");
-    DM3D_REQUIRE(dm3d_aligned16(w) && dm3d_aligned16(g) && dm3d_aligned16(m) && dm3d_aligned16(v) && dm3d_aligned16(ema) && dm3d_aligned16(state),
-                 "adam_scaled: pointers must be 16-byte aligned");
-    DM3D_REQUIRE(n > 0 && n % 4 == 0, "adam_scaled: n=%lld must be a positive multiple of 4", (long long)n);
-    DM3D_REQUIRE(ema_rate >= 0.0f && ema_rate <= 1.0f, "adam_scaled: ema_rate %g must lie in [0, 1]", (double)ema_rate);   // (a NaN fails both)
+    DM3D_REQUIRE(state && dm3d_aligned16(state), "adam_scaled: state must be non-null and 16-byte aligned");
+    if (int rc = check_adam4("adam_scaled", w, g, m, v, ema, n, ema_rate)) return rc;
+    const uint64_t bytes = (uint64_t)n * sizeof(float);
+    for (const float* p : {(const float*)w, (const float*)m, (const float*)v, (const float*)ema})      // (the kernel stores to these while it reads state)
+        DM3D_REQUIRE(!dm3d_ranges_overlap(state, 16, p, bytes), "adam_scaled: state overlaps a buffer the step writes");
     const long n4 = (long)(n / 4);
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(state), bytes = (uintptr_t)n * sizeof(float);
-    for (const void* p : {(const void*)w, (const void*)m, (const void*)v, (const void*)ema}) {          // (the kernel stores to these while it reads state)
-        const uintptr_t p0 = reinterpret_cast<uintptr_t>(p);
-        DM3D_REQUIRE(p == nullptr || s0 + 16 <= p0 || p0 + bytes <= s0, "adam_scaled: state overlaps a buffer the step writes");
-    }
-    if (ema == nullptr) {
-        hipLaunchKernelGGL(adam_scaled_kernel<false>, dim3(tgrid(n4)), dim3(256), 0, TR_ST, w, g, m, v, ema, n4, lr_t, beta1, beta2, eps, ema_rate, state);
-        return dm3d_launch_check("adam_scaled_kernel");
-    }
-    const uintptr_t e0 = reinterpret_cast<uintptr_t>(ema);
-    for (const void* p : {(const void*)w, (const void*)g, (const void*)m, (const void*)v}) {
-        const uintptr_t p0 = reinterpret_cast<uintptr_t>(p);
-        DM3D_REQUIRE(e0 + bytes <= p0 || p0 + bytes <= e0, "adam_scaled: ema overlaps another buffer");
-    }
-    hipLaunchKernelGGL(adam_scaled_kernel<true>, dim3(tgrid(n4)), dim3(256), 0, TR_ST, w, g, m, v, ema, n4, lr_t, beta1, beta2, eps, ema_rate, state);
-    return dm3d_launch_check("adam_scaled_kernel");
+    if (ema)
+        hipLaunchKernelGGL((adam_step_kernel<true, true>), dim3(tgrid(n4)), dim3(256), 0, TR_ST, w, g, m, v, ema, n4, lr_t, beta1, beta2, eps, ema_rate, state);
+    else
+        hipLaunchKernelGGL((adam_step_kernel<false, true>), dim3(tgrid(n4)), dim3(256), 0, TR_ST, w, g, m, v, ema, n4, lr_t, beta1, beta2, eps, ema_rate, state);
+    return dm3d_launch_check("adam_step_kernel<scaled>");
 }

@@ -824,7 +824,7 @@ int dm3d_mse_loss_grad(const float* pred, const float* noise, int64_t n, double 
  * lr_t = lr*sqrt(1-b2^t)/(1-b1^t) (the host supplies it; Keras defaults b1 0.9, b2 0.999, eps 1e-7). */
 int dm3d_adam(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2, float eps, void* stream);
 /* The same step and the exponential moving average of the weights in one launch and one pass over the five buffers: w, m and v
- * become bitwise what dm3d_adam makes of them (both kernels call one element function), then
+ * become bitwise what dm3d_adam makes of them (adam_kernel and adam_step_kernel call one element function), then
  *     ema += ema_rate * (w_new - ema)          (float32: one sub, one mul, one add)
  * so ema_rate = 0 leaves ema untouched; ema_rate = 1 stores w_new itself (the three operations could miss it by an ulp).  The host supplies ema_rate = 1 - decay (Trainer: with the
  * warm-up decay_t = min(decay, (1 + n) / (10 + n)) of n earlier updates).  HBM-bound at 36 B per element (Adam alone 28, Adam and a
@@ -838,8 +838,9 @@ int dm3d_adam_ema(float* w, const float* g, float* m, float* v, float* ema, int6
  *   grad_sqnorm_kernel          min(ceil(n/4/256), DM3D_GRADNORM_PARTIAL_BLOCKS) blocks (a function of n alone) stride over g as float4;
  *                               every block leaves the float64 sum of (double)g*g (exact products) of its share in partials[block] and
  *                               the slots past the grid are written as 0: nothing a previous launch left in partials is read
- *   grad_scale_finalize_kernel  one block adds the slots in one fixed tree (thread t its slots 4t..4t+3 in index order, then a fixed
- *                               wave and block reduction; no atomics: the result repeats bitwise whatever order the blocks ran in)
+ *   grad_scale_finalize_kernel  one block adds the slots in one fixed tree (thread t its slots 4t..4t+3 in index order, then the
+ *                               block sum every fixed-order reduction here shares, dm3d_block_sum_f64; no atomics: the result
+ *                               repeats bitwise whatever order the blocks ran in)
  *                               and writes
  *     state[0] = (float)(pre_scale * sqrt(sum))                                  the norm of the gradient the step will apply
  *     state[1] = (float)(pre_scale * (norm > clip_norm ? clip_norm / norm : 1))  in float64, rounded once
@@ -862,8 +863,8 @@ typedef struct dm3d_gradscale_desc {
 int dm3d_grad_scale(const dm3d_gradscale_desc* d, void* stream);
 /* dm3d_adam_ema (ema NULL: dm3d_adam) on the gradient state[1] * g[i], one float32 multiply per element; g itself is not modified.
  * Every thread reads state[1] and state[2] (dm3d_grad_scale's) from device memory.  state[2] != 0 skips the step: nothing is stored, and
- * w, m, v and ema stay bitwise as they were.  The element update and the lerp are the functions dm3d_adam and dm3d_adam_ema run, so with
- * state[1] = 1 the results are bitwise theirs, and with state[1] = s bitwise theirs on the buffer float32(s) * g.  Checked before
+ * w, m, v and ema stay bitwise as they were.  This entry and dm3d_adam_ema launch forms of one kernel (adam_step_kernel), whose element
+ * update is the function dm3d_adam runs, so with state[1] = 1 the results are bitwise theirs, and with state[1] = s bitwise theirs on the buffer float32(s) * g.  Checked before
  * the launch (DM3D_EINVAL): w, g, m, v, state non-NULL; every pointer 16-byte aligned; n > 0 and n % 4 == 0; ema_rate in [0, 1]; ema,
  * when given, overlapping none of w, g, m, v; state overlapping none of the buffers the step writes (w, m, v, ema). */
 int dm3d_adam_scaled(float* w, const float* g, float* m, float* v, float* ema /* NULL: none */, int64_t n, float lr_t, float beta1,

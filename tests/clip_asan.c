@@ -3,7 +3,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "dm3d.h"
-/* host-side paths of dm3d_grad_scale and dm3d_adam_scaled with hostile arguments (no device needed: each must refuse before any launch).
+/* host-side paths of dm3d_grad_scale, dm3d_adam_scaled and dm3d_adam_ema with hostile arguments (no device needed: each must refuse before any launch).
  * The buffers are real heap blocks of exactly the documented sizes, so a host-side read or write past them is a sanitizer report. */
 static int refused(int rc, const char* entry) {
     return rc == DM3D_EINVAL && strstr(dm3d_last_error(), entry) != NULL;
@@ -39,6 +39,17 @@ int main(void) {
     AS(w, g, m, v, v, n, 0.1f, state); AS(w, g, m, v, w + 4, n, 0.1f, state);
     AS(w, g, m, v, e, n, 0.1f, w + 8); AS(w, g, m, v, e, n, 0.1f, m); AS(w, g, m, v, e, n, 0.1f, v + 60); AS(w, g, m, v, e, n, 0.1f, e + 4);
     AS(w, g, m, v, NULL, 6, 0.1f, state);                    /* ema = NULL passes the pointer checks: n is what is refused */
+    /* dm3d_adam_ema: the same table through the other door of the validator the two entries share */
+#define AE(w, g, m, v, e, cnt, rate) do { ++total; \
+    bad += refused(dm3d_adam_ema(w, g, m, v, e, cnt, 1e-4f, 0.9f, 0.999f, 1e-7f, rate, NULL), "adam_ema"); } while (0)
+    AE(NULL, g, m, v, e, n, 0.1f); AE(w, NULL, m, v, e, n, 0.1f); AE(w, g, NULL, v, e, n, 0.1f); AE(w, g, m, NULL, e, n, 0.1f);
+    AE(w, g, m, v, NULL, n, 0.1f);
+    AE(w + 1, g, m, v, e, n, 0.1f); AE(w, g + 1, m, v, e, n, 0.1f); AE(w, g, m + 1, v, e, n, 0.1f); AE(w, g, m, v + 1, e, n, 0.1f);
+    AE(w, g, m, v, e + 1, n, 0.1f);
+    AE(w, g, m, v, e, 0, 0.1f); AE(w, g, m, v, e, 6, 0.1f); AE(w, g, m, v, e, -4, 0.1f);
+    AE(w, g, m, v, e, n, -0.1f); AE(w, g, m, v, e, n, 1.5f); AE(w, g, m, v, e, n, NAN);
+    AE(w, g, m, v, w, n, 0.1f); AE(w, g, m, v, g, n, 0.1f); AE(w, g, m, v, m, n, 0.1f); AE(w, g, m, v, v, n, 0.1f);
+    AE(w, g, m, v, w + 4, n, 0.1f); AE(w, g, m, v, g + 60, n, 0.1f); AE(w, g, m, v, m + 32, n, 0.1f); AE(w, g, m, v, v + 8, n, 0.1f);
     printf("refused %d of %d; last error: %s\n", bad, total, dm3d_last_error());
     for (int i = 0; i < 5; ++i) free(buf[i]);
     free(parts); free(state);
