@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -487,6 +488,78 @@ def _gemm_desc(a, lda, b, ldb, out, ldo, m, n, k, batch=1, stride_a=0, stride_b=
     return d
 
 
+# the packed Dense / 1x1 conv weights of one CrossAttentionBlock (UNet._prepare_attn), and the launch forms its split-float16 body takes:
+# dm3d_attn_front; dm3d_mlp_fused, with or without the proj_out tail; dm3d_attention_group.  A form that is off runs as GEMMs.
+_CrossWeights = namedtuple("_CrossWeights", "pin pout qk val m0 m1")
+_AttnForms = namedtuple("_AttnForms", "front mlp_fused tail attn_fused")
+_ATTN_KNOBS = (("DM3D_FUSED_MIN_ROWS", str(64 * 128)), ("DM3D_ATTN_FRONT", "1"), ("DM3D_MLP_FUSED", "1"), ("DM3D_ATTN_FUSED", "1"), ("DM3D_MLP_TAIL", "1"))
+
+
+def _attn_knobs():
+    """(min_rows, front, mlp_fused, attn_fused, tail): the environment switches of the attention forms with their defaults, read
+    whenever a plan is built — the Python counterpart of csrc's conv_knobs.  A switch is off when it is "0"."""
+    rows, *on = (os.environ.get(name, default) for name, default in _ATTN_KNOBS)
+    return (int(rows), *(v != "0" for v in on))
+
+
+def _attn_forms(u: int, L: int, B: int, w) -> _AttnForms:
+    """The launch forms of a split-float16 cross block over B samples of L tokens with u units, decided once."""
+    min_rows, front_on, mlp_on, attn_on, tail_on = _attn_knobs()
+    M = B * L
+
+    def packed(image, *ws):         # the operand-fragment images _prepare_attn makes for u = 256
+        return all(getattr(x, image, None) is not None for x in ws)
+
+    # dm3d_attn_front and dm3d_mlp_fused share one shape rule: u = 256 and enough 64-row tiles to fill the chip
+    fits = u == 256 and M % 64 == 0 and M >= min_rows
+    front = fits and front_on and packed("ftiled", w.pin, w.qk, w.val)
+    mlp_fused = fits and mlp_on and packed("tiled", w.m0)
+    tail = mlp_fused and tail_on and packed("ftiled", w.pout)
+    # (the fused kernel runs one 4-wave workgroup per 128 queries: it needs >= ~128 workgroups to beat the GEMM form, i.e. B >= 16 at L = 512;
+    # measured B = 1 / 4 / 8: 2.80 / 3.85 / 5.74 ms per step fused against 2.5 / 3.5 / 5.3 with the three launches)
+    attn_fused = attn_on and u == 256 and L % 128 == 0 and 2 * B * (L // 128) >= 128
+    return _AttnForms(front, mlp_fused, tail, attn_fused)
+
+
+def _front_desc(x, w, lns, y, qkb, v_t, q2, n3, m, u) -> AttnFrontDesc:
+    """dm3d_attn_front over the rows ``x``: float32 y; q|k, v^T, q2 and norm3(y) in DM3D_FMT_H2."""
+    (g1, b1), (g2, b2), (g3, b3) = lns
+    d = AttnFrontDesc()
+    d.x, d.ldx = _ptr(x), u
+    d.w_in, d.b_in, d.w_qk, d.b_qk, d.w_v, d.b_v = (w.pin.ftiled.data_ptr(), _ptr(w.pin.bias), w.qk.ftiled.data_ptr(), _ptr(w.qk.bias),
+                                                    w.val.ftiled.data_ptr(), _ptr(w.val.bias))
+    d.g1, d.be1, d.g2, d.be2, d.g3, d.be3 = g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr(), g3.data_ptr(), b3.data_ptr()
+    d.eps = LN_EPS
+    d.y, d.ldy, d.qk, d.ldqk, d.vt, d.ldvt, d.q2, d.ldq2, d.n3, d.ldn3 = _ptr(y), u, _ptr(qkb), 2 * u, _ptr(v_t), m, _ptr(q2), u, _ptr(n3), u
+    d.m, d.units = m, u
+    return d
+
+
+def _mlp_desc(x, w, res, res2, out, m, u, block_in=None) -> MlpDesc:
+    """dm3d_mlp_fused: out = Dense(Dense(x, relu)) + res + res2 in DM3D_FMT_H2.  ``block_in``: the block's input; the launch then ends with
+    the proj_out tail and ``out`` is the block's float32 output, relu(proj_out(...)) + block_in."""
+    d = MlpDesc()
+    d.x, d.ldx, d.w0, d.b0, d.w1, d.b1 = _ptr(x), u, w.m0.tiled.data_ptr(), _ptr(w.m0.bias), w.m1.tiled.data_ptr(), _ptr(w.m1.bias)
+    d.res, d.res2, d.ldr, d.m, d.units = _ptr(res), _ptr(res2), u, m, u
+    d.out, d.ldo, d.out_fmt = _ptr(out), u, _lib.FMT_H2 if block_in is None else _lib.FMT_F32
+    if block_in is not None:
+        d.w2, d.b2, d.res3, d.ldr3 = w.pout.ftiled.data_ptr(), _ptr(w.pout.bias), _ptr(block_in), u
+    return d
+
+
+def _attention_pair(B, L, u, scale, *passes):
+    """The two descriptors of one dm3d_attention_group launch over DM3D_FMT_H2 operands.  A pass is a dict: q, ldq, k (+ k_off elements),
+    ldk, stride_k, vt, ldv, stride_vt, out and an optional float32 res."""
+    descs = (_lib.AttentionDesc * 2)()
+    for d, p in zip(descs, passes):
+        d.q, d.ldq = _ptr(p["q"]), p["ldq"]
+        d.k, d.ldk, d.stride_k = _ptr(p["k"], p.get("k_off", 0)), p["ldk"], p["stride_k"]
+        d.vt, d.ldv, d.stride_vt = _ptr(p["vt"]), p["ldv"], p["stride_vt"]
+        d.out, d.ldo, d.res = _ptr(p["out"]), u, _ptr(p.get("res"))
+        d.batch, d.lq, d.lk, d.c, d.scale, d.precision, d.fmt = B, L, L, u, scale, _lib.PREC_H3, _lib.FMT_H2
+    return descs
+
+
 class Plan:
     """All launches of one U-Net forward for a fixed batch, with fixed buffers.
 
@@ -499,6 +572,7 @@ class Plan:
         S, Cc = cfg.img_size, cfg.img_channels
         self.ops: List[tuple] = []
         self._keep: List[object] = []
+        self._guarded: List[object] = []        # every descriptor _guard pointed at range_flag
         self.x = torch.empty(batch, S, S, S, Cc, dtype=torch.float32, device=dev)
         self.eps = torch.empty_like(self.x)
         self.t_idx = torch.zeros(batch, dtype=torch.int32, device=dev)
@@ -518,10 +592,8 @@ class Plan:
             # the Winograd-x form splits sums of two activations: every producer of this plan guards half the range.  Decided per plan
             # (a plan whose grids are too small for that form keeps the whole float16 range)
             self.range_limit = net._h3_range_limit(winograd=True)
-            for d in self._keep:
-                for one in (d if isinstance(d, C.Array) else (d,)):
-                    if isinstance(one, (ConvDesc, GemmDesc, MlpDesc, AttnFrontDesc)) and one.range_flag:
-                        one.range_limit = self.range_limit
+            for d in self._guarded:
+                d.range_limit = self.range_limit
         # one workspace for every conv that can split its Cin range (dm3d_conv_scratch_bytes): launches are stream-ordered
         need = max([lib().dm3d_conv_scratch_bytes(C.byref(d)) for d in self._keep if isinstance(d, ConvDesc)] + [0])
         if need:
@@ -601,8 +673,7 @@ class Plan:
         d.x1_fmt = _lib.FMT_H2 if x1_h2 else _lib.FMT_F32
         if w.wpk_wino is not None:
             d.wpk_wino = w.wpk_wino.data_ptr()
-        if self.range_flag is not None and w.precision == _lib.PREC_H3:
-            d.range_flag, d.range_limit = self.range_flag.data_ptr(), self.range_limit
+        self._guard(d)
         if w.precision == _lib.PREC_H3:
             d.split_counters, d.split_counter_words = self.split_counters.data_ptr(), self.split_counters.numel()
         if self.net.cfg.norm == "group" and normed and not out_h2 and w.cout % 4 == 0:
@@ -651,9 +722,12 @@ class Plan:
                           "bytes": 4.0 * self.B * (edge_in ** 3 * (w.cin + (skip[2] + skip[3] if skip is not None else 0))
                                                    + eo ** 3 * w.cout)}))
 
-    def _guard(self, d: GemmDesc) -> GemmDesc:
-        if self.range_flag is not None and d.precision == _lib.PREC_H3:
+    def _guard(self, d):
+        """Points a descriptor with a ``range_flag`` at the plan's flag: a ConvDesc or GemmDesc when it runs in H3, an AttnFrontDesc or
+        MlpDesc (H3 kernels, no ``precision`` field) always.  ``_guarded`` is what ``__init__`` re-limits for the Winograd-x form."""
+        if self.range_flag is not None and getattr(d, "precision", _lib.PREC_H3) == _lib.PREC_H3:
             d.range_flag, d.range_limit = self.range_flag.data_ptr(), self.range_limit
+            self._guarded.append(d)
         return d
 
     def _gemm(self, **kw):
@@ -665,7 +739,9 @@ class Plan:
 
     def _gemm_group(self, problems):
         """Independent H3 GEMMs with identical operand formats as one launch (dm3d_gemm_tn_group)."""
-        arr = (GemmDesc * len(problems))(*[self._guard(_gemm_desc(**kw)) for kw in problems])
+        arr = (GemmDesc * len(problems))(*[_gemm_desc(**kw) for kw in problems])
+        for d in arr:                          # (the array holds copies: guard its own elements, which share its memory)
+            self._guard(d)
         self._keep.append(arr)
         fl = sum(2.0 * d.m * d.n * d.k * d.batch for d in arr)
         desc = "gemm_h3 group[" + " | ".join(f"m={d.m} n={d.n} k={d.k} b={d.batch}" for d in arr) + "]"
@@ -687,9 +763,7 @@ class Plan:
         # with the norm folded it leaves that block's conv2 already normalised, activated and split (DM3D_FMT_H2, as conv1 -> conv2 inside a
         # block), and the output conv — 8 useful columns: bound by converting its input, not by its MFMAs — stages plain copies.
         last = net.blocks[-1] if net.blocks else None
-        final_handoff = (last is not None and last.kind == "res" and net.h2_handoff and cfg.norm == "batch" and net.precision == "h3"
-                         and S % 8 == 0 and last.cout % 64 == 0 and B * (S ** 3 // 256) * (last.cout // 64) > 256
-                         and lib().dm3d_conv_weight_layout(3, 1, 0, 0, last.cout) == _lib.WL_PAIR
+        final_handoff = (last is not None and last.kind == "res" and self._handoff_ok(S, last.cout)
                          and lib().dm3d_conv_weight_layout(3, 1, 0, 0, cfg.img_channels) == _lib.WL_PAIR)
         for blk in net.blocks:
             if blk.kind == "push":
@@ -718,6 +792,15 @@ class Plan:
         pro, bs = self._norm("out.norm", cur, cur_c, edge)
         self._conv(P["out.conv"], cur, self.eps, edge, pro=pro, pro_bstride=bs, normed=False)
 
+    def _handoff_ok(self, edge: int, cout: int) -> bool:
+        """The hand-off rule: a k3 conv whose output has one consumer, folded BatchNormalization -> swish -> the next k3 conv, may leave
+        it already normalised, activated and split (DM3D_FMT_H2).  Needs the 16x16x32 kernel, whole bricks, and a grid that would not
+        rather split its Cin range (the fused output forms live in the unsplit epilogue)."""
+        net = self.net
+        return (net.h2_handoff and net.cfg.norm == "batch" and net.precision == "h3" and edge % 8 == 0
+                and cout % 64 == 0 and self.B * (edge ** 3 // 256) * (cout // 64) > 256
+                and lib().dm3d_conv_weight_layout(3, 1, 0, 0, cout) == _lib.WL_PAIR)
+
     def _res_block(self, blk, x1, c1, x2, c2, edge, final_post=None):
         """ResidualBlock (conditional_dm3d.py:238-271): three launches (two when the widths match).  ``final_post``: the folded norm of
         the block's only consumer; the block's output then leaves conv2 normalised, activated and split (DM3D_FMT_H2)."""
@@ -733,14 +816,8 @@ class Plan:
         hmid = self._buf(B, edge, edge, edge, w)
         pro, bs = self._norm(f"{n}.norm1", x1, c1, edge, x2, c2)
         out = self._buf(B, edge, edge, edge, w)
-        # conv1's output has one consumer: with folded BatchNormalization it leaves conv1 already normalised, activated and split
-        # (DM3D_FMT_H2) and conv2 stages plain copies.  Needs the 16x16x32 kernel, whole bricks, and a grid that would not
-        # rather split its Cin range (the fused output forms live in the unsplit epilogue).
-        handoff = (self.net.h2_handoff and self.net.cfg.norm == "batch" and self.net.precision == "h3" and edge % 8 == 0
-                   and w % 64 == 0 and B * (edge ** 3 // 256) * (w // 64) > 256
-                   and lib().dm3d_conv_weight_layout(3, 1, 0, 0, w) == _lib.WL_PAIR)
         tail = dict(post=final_post, out_h2=True) if final_post is not None else {}
-        if handoff:
+        if self._handoff_ok(edge, w):          # conv1's output has one consumer, norm2 -> swish -> conv2: conv2 stages plain copies
             self._conv(P[f"{n}.conv1"], x1, hmid, edge, x2=x2, c1=c1, c2=c2, pro=pro, pro_bstride=bs, vec_off=self.net.temb_off[n],
                        post=P[f"{n}.norm2"], out_h2=True)
             self._conv(P[f"{n}.conv2"], hmid, out, edge, res=res, skip=skip, x1_h2=True, **tail)
@@ -769,203 +846,168 @@ class Plan:
         self._gemm(a=scores, lda=L, stride_a=L * L, b=v_t, b_off=v_off, ldb=v_ld, stride_b=v_stride, out=out, ldo=u,
                    stride_o=L * u, m=L, n=u, k=L, batch=B, res=res, ldr=u, stride_r=L * u, h3=h2, a_h2=h2, b_h2=h2)
 
-    @staticmethod
-    def _check_tokens(L: int):
+    def _attn_shape(self, blk, edge):
+        """(name, units, tokens per sample L, rows M = B * L) of an attention block."""
+        L = edge ** 3
         if L % 4:
             raise ValueError(f"attention over {L} tokens: the P.V contraction runs on the MFMA GEMM, which needs D*H*W % 4 == 0 at "
                              "attention levels (edge 3 or 5 are not supported; the reference's latents give 4^3, 8^3, 16^3)")
+        return blk.name, blk.cout, L, self.B * L
 
-    def _cross_block(self, blk, x, edge):
-        """CrossAttentionBlock (conditional_dm3d.py:186-195).  With precision "h3" every intermediate that only feeds
-        Dense layers (LayerNorm outputs, q|k, v^T, probabilities, MLP hidden, a3) lives in DM3D_FMT_H2."""
-        P, B, n, u = self.net.P, self.B, blk.name, blk.cout
-        L = edge ** 3
-        M = B * L
-        self._check_tokens(L)
-        h2 = self.net._attn_h2(u, L)
-        if h2:
-            return self._cross_block_h2(blk, x, edge)
-        W = (lambda w: w.h2) if h2 else (lambda w: w.wpk)
-        pin, pout, qk, val = P[f"{n}.proj_in"], P[f"{n}.proj_out"], P[f"{n}.qk"], P[f"{n}.value"]
-        m0, m1 = P[f"{n}.mlp.0"], P[f"{n}.mlp.1"]
-        y = self._buf(M, u)                                                   # relu(proj_in(norm(x))), float32
-        xin = self._group_normed(n, x, u, edge) if self.net.cfg.norm == "group" else x      # BatchNorm is folded into proj_in
-        self._gemm(a=xin, lda=u, b=W(pin), ldb=pin.cin_pad, out=y, ldo=u, m=M, n=u, k=u, bias=pin.bias, act=ACT_RELU,
-                   h3=h2, b_h2=h2)
-        n1, n2, n3 = self._buf(M, u), self._buf(M, u), self._buf(M, u)
-        (g1, b1), (g2, b2), (g3, b3) = P[f"{n}.ln1"], P[f"{n}.ln2"], P[f"{n}.ln3"]
-        self._keep += [g1, b1, g2, b2, g3, b3]
-        ln = lib().dm3d_layernorm3_h2 if h2 else lib().dm3d_layernorm3
-        self.ops.append((ln, (y.data_ptr(), M, u, LN_EPS, g1.data_ptr(), b1.data_ptr(), n1.data_ptr(), g2.data_ptr(),
-                              b2.data_ptr(), n2.data_ptr(), g3.data_ptr(), b3.data_ptr(), n3.data_ptr()), "layernorm", {}))
-        # self attention on norm1(y)
-        qkb = self._buf(M, 2 * u)
-        self._gemm(a=n1, lda=u, b=W(qk), ldb=qk.cin_pad, out=qkb, ldo=2 * u, m=M, n=2 * u, k=u, bias=qk.bias,
-                   h3=h2, a_h2=h2, b_h2=h2, out_h2=h2)
-        v_t = self._buf(u, M)                                                 # value projection, transposed
-        self._gemm(a=W(val), lda=val.cin_pad, b=n1, ldb=u, out=v_t, ldo=M, m=u, n=M, k=u, bias=val.bias, bias_along_m=1,
-                   h3=h2, a_h2=h2, b_h2=h2, out_h2=h2)
-        scores = self._buf(B, L, L)
-        a1 = self._buf(M, u)
-        self._attn_core(qkb, 2 * u, 0, qkb, 2 * u, u, L * 2 * u, v_t, M, 0, L, scores, y, a1, L, u, h2)
-        # cross attention: queries from norm2(y), keys/values from the context (same key/value weights, :168-169)
-        q2 = self._buf(M, u)
-        self._gemm(a=n2, lda=u, b=W(qk), ldb=qk.cin_pad, out=q2, ldo=u, m=M, n=u, k=u, bias=qk.bias,
-                   h3=h2, a_h2=h2, b_h2=h2, out_h2=h2)
-        rows = B if self.per_sample_context else 1
+    def _cross_prologue(self, blk, x, edge):
+        """What both bodies of the cross block start from: the block's weights, the float32 buffer y for relu(proj_in(norm(x))), the rows
+        proj_in reads (the block input, BatchNorm being folded into proj_in; GroupNorm: materialised first) and the (gamma, beta) pairs of
+        the three LayerNormalizations, kept alive."""
+        P, n, u = self.net.P, blk.name, blk.cout
+        w = _CrossWeights(*(P[f"{n}.{k}"] for k in ("proj_in", "proj_out", "qk", "value", "mlp.0", "mlp.1")))
+        y = self._buf(self.B * edge ** 3, u)
+        xin = self._group_normed(n, x, u, edge) if self.net.cfg.norm == "group" else x
+        lns = tuple(P[f"{n}.{ln}"] for ln in ("ln1", "ln2", "ln3"))
+        self._keep += [t for pair in lns for t in pair]
+        return w, y, xin, lns
+
+    def _context(self, n, L, u):
+        """The block's context key / transposed-value buffers (filled by ``set_context``) and their batch strides: (kctx, vctx_t, ks, vs).
+        One row serves the whole batch unless the plan has per-sample context."""
+        rows = self.B if self.per_sample_context else 1
         kctx, vctx_t = self._buf(rows, L * u), self._buf(rows, u * L)
         self.ctx_bufs[n] = (kctx, vctx_t)
-        a2 = self._buf(M, u)
         ks, vs = (L * u, u * L) if self.per_sample_context else (0, 0)
-        self._attn_core(q2, u, 0, kctx, u, 0, ks, vctx_t, L, 0, vs, scores, a1, a2, L, u, h2)
-        # MLP on norm3(y)
-        hid = self._buf(M, 4 * u)
-        self._gemm(a=n3, lda=u, b=W(m0), ldb=m0.cin_pad, out=hid, ldo=4 * u, m=M, n=4 * u, k=u, bias=m0.bias, act=ACT_RELU,
-                   h3=h2, a_h2=h2, b_h2=h2, out_h2=h2)
-        a3 = self._buf(M, u)
-        self._gemm(a=hid, lda=4 * u, b=W(m1), ldb=m1.cin_pad, out=a3, ldo=u, m=M, n=u, k=4 * u, bias=m1.bias, res=a2, ldr=u,
-                   h3=h2, a_h2=h2, b_h2=h2, out_h2=h2)
+        return kctx, vctx_t, ks, vs
+
+    def _layernorm3(self, y, M, u, lns, outs, h2):
+        """The three LayerNormalizations of y in one launch; h2: the outputs are left in DM3D_FMT_H2."""
+        args = [y.data_ptr(), M, u, LN_EPS]
+        for (g, b), o in zip(lns, outs):
+            args += [g.data_ptr(), b.data_ptr(), o.data_ptr()]
+        self.ops.append((lib().dm3d_layernorm3_h2 if h2 else lib().dm3d_layernorm3, tuple(args), "layernorm", {}))
+
+    def _cross_block(self, blk, x, edge):
+        """CrossAttentionBlock (conditional_dm3d.py:186-195): split-float16 intermediates when ``_attn_h2(u, L)`` (precision "h3" and a
+        token count the 16-k records fit), otherwise plain float32 GEMMs."""
+        _, u, L, _ = self._attn_shape(blk, edge)
+        return (self._cross_block_h2 if self.net._attn_h2(u, L) else self._cross_block_f32)(blk, x, edge)
+
+    def _cross_block_f32(self, blk, x, edge):
+        """CrossAttentionBlock in float32: proj_in, the three LayerNormalizations, then self attention on norm1(y), cross attention of
+        norm2(y) against the context (same key / value weights, :168-169), the MLP on norm3(y) and proj_out, one GEMM each."""
+        B = self.B
+        n, u, L, M = self._attn_shape(blk, edge)
+        (pin, pout, qk, val, m0, m1), y, xin, lns = self._cross_prologue(blk, x, edge)
+        self._gemm(a=xin, lda=u, b=pin.wpk, ldb=pin.cin_pad, out=y, ldo=u, m=M, n=u, k=u, bias=pin.bias, act=ACT_RELU)
+        n1, n2, n3 = self._buf(M, u), self._buf(M, u), self._buf(M, u)
+        self._layernorm3(y, M, u, lns, (n1, n2, n3), h2=False)
+        qkb, v_t = self._buf(M, 2 * u), self._buf(u, M)                       # q|k, and the value projection transposed
+        self._gemm(a=n1, lda=u, b=qk.wpk, ldb=qk.cin_pad, out=qkb, ldo=2 * u, m=M, n=2 * u, k=u, bias=qk.bias)
+        self._gemm(a=val.wpk, lda=val.cin_pad, b=n1, ldb=u, out=v_t, ldo=M, m=u, n=M, k=u, bias=val.bias, bias_along_m=1)
+        scores, a1 = self._buf(B, L, L), self._buf(M, u)
+        self._attn_core(qkb, 2 * u, 0, qkb, 2 * u, u, L * 2 * u, v_t, M, 0, L, scores, y, a1, L, u, False)
+        q2 = self._buf(M, u)
+        self._gemm(a=n2, lda=u, b=qk.wpk, ldb=qk.cin_pad, out=q2, ldo=u, m=M, n=u, k=u, bias=qk.bias)
+        kctx, vctx_t, ks, vs = self._context(n, L, u)
+        a2 = self._buf(M, u)
+        self._attn_core(q2, u, 0, kctx, u, 0, ks, vctx_t, L, 0, vs, scores, a1, a2, L, u, False)
+        hid, a3 = self._buf(M, 4 * u), self._buf(M, u)
+        self._gemm(a=n3, lda=u, b=m0.wpk, ldb=m0.cin_pad, out=hid, ldo=4 * u, m=M, n=4 * u, k=u, bias=m0.bias, act=ACT_RELU)
+        self._gemm(a=hid, lda=4 * u, b=m1.wpk, ldb=m1.cin_pad, out=a3, ldo=u, m=M, n=u, k=4 * u, bias=m1.bias, res=a2, ldr=u)
         out = self._buf(B, edge, edge, edge, u)
-        self._gemm(a=a3, lda=u, b=W(pout), ldb=pout.cin_pad, out=out, ldo=u, m=M, n=u, k=u, bias=pout.bias, act=ACT_RELU,
-                   res=x, ldr=u, h3=h2, a_h2=h2, b_h2=h2)
+        self._gemm(a=a3, lda=u, b=pout.wpk, ldb=pout.cin_pad, out=out, ldo=u, m=M, n=u, k=u, bias=pout.bias, act=ACT_RELU, res=x, ldr=u)
         return out
 
     def _cross_block_h2(self, blk, x, edge):
-        """CrossAttentionBlock with DM3D_FMT_H2 intermediates (conditional_dm3d.py:163-195).  Large batches (u = 256, >= 128 row tiles): THREE
-        launches — dm3d_attn_front (proj_in + the three LayerNormalizations + q|k, v^T, q2), dm3d_attention_group (both passes, online softmax),
-        dm3d_mlp_fused with the proj_out tail; a3 = MLP + (attn_self + y) + attn_cross is formed inside the last.  Otherwise the GEMM form: the
-        GEMMs that depend only on the LayerNorm outputs (q|k, v^T, q2, MLP hidden) as one grouped launch, likewise the two score products and
-        the two P.V products."""
-        P, B, n, u = self.net.P, self.B, blk.name, blk.cout
-        L = edge ** 3
-        M = B * L
-        pin, pout, qk, val = P[f"{n}.proj_in"], P[f"{n}.proj_out"], P[f"{n}.qk"], P[f"{n}.value"]
-        m0, m1 = P[f"{n}.mlp.0"], P[f"{n}.mlp.1"]
+        """CrossAttentionBlock with every tensor that only feeds Dense layers (LayerNorm outputs, q|k, v^T, probabilities, MLP hidden, a3) in
+        DM3D_FMT_H2 (conditional_dm3d.py:163-195).  ``_attn_forms`` decides the launches: large batches (u = 256, >= 128 row tiles) take
+        THREE — dm3d_attn_front, dm3d_attention_group, dm3d_mlp_fused with the proj_out tail, which forms a3 = MLP + (attn_self + y) +
+        attn_cross inside —, and what a fused launch does not cover runs as H3 GEMMs, independent ones grouped into one launch."""
+        B = self.B
+        n, u, L, M = self._attn_shape(blk, edge)
+        w, y, xin, lns = self._cross_prologue(blk, x, edge)
+        forms = _attn_forms(u, L, B, w)
         hh = dict(h3=True, a_h2=True, b_h2=True)
-        y = self._buf(M, u)                                                   # relu(proj_in(norm(x))), float32
-        xin = self._group_normed(n, x, u, edge) if self.net.cfg.norm == "group" else x      # BatchNorm is folded into proj_in
-        (g1, b1), (g2, b2), (g3, b3) = P[f"{n}.ln1"], P[f"{n}.ln2"], P[f"{n}.ln3"]
-        self._keep += [g1, b1, g2, b2, g3, b3]
-        # proj_in + the three LayerNormalizations + the q|k, v^T, q2 projections as ONE launch (dm3d_attn_front, round 4): y, n1, n2 stay on the
-        # CU.  Same shape rule as the fused MLP (u = 256, enough 64-row tiles to fill the chip); otherwise the three launches below.
-        min_rows = int(os.environ.get("DM3D_FUSED_MIN_ROWS", str(64 * 128)))
-        front = (u == 256 and M % 64 == 0 and M >= min_rows and all(getattr(w, "ftiled", None) is not None for w in (pin, qk, val))
-                 and os.environ.get("DM3D_ATTN_FRONT", "1") != "0")
-        n3 = self._buf(M, u)
-        if front:
-            qkb, v_t, q2 = self._buf(M, 2 * u), self._buf(u, M), self._buf(M, u)
-            fd = AttnFrontDesc()
-            fd.x, fd.ldx = _ptr(xin), u
-            fd.w_in, fd.b_in, fd.w_qk, fd.b_qk, fd.w_v, fd.b_v = (pin.ftiled.data_ptr(), _ptr(pin.bias), qk.ftiled.data_ptr(), _ptr(qk.bias),
-                                                                  val.ftiled.data_ptr(), _ptr(val.bias))
-            fd.g1, fd.be1, fd.g2, fd.be2, fd.g3, fd.be3 = g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr(), g3.data_ptr(), b3.data_ptr()
-            fd.eps = LN_EPS
-            fd.y, fd.ldy, fd.qk, fd.ldqk, fd.vt, fd.ldvt, fd.q2, fd.ldq2, fd.n3, fd.ldn3 = _ptr(y), u, _ptr(qkb), 2 * u, _ptr(v_t), M, _ptr(q2), u, _ptr(n3), u
-            fd.m, fd.units = M, u
-            if self.range_flag is not None:
-                fd.range_flag, fd.range_limit = self.range_flag.data_ptr(), self.range_limit
+        n3, qkb, v_t, q2 = self._buf(M, u), self._buf(M, 2 * u), self._buf(u, M), self._buf(M, u)
+        hid = None if forms.mlp_fused else self._buf(M, 4 * u)
+        a1, a2, out = self._buf(M, u), self._buf(M, u), self._buf(B, edge, edge, edge, u)
+        a3 = None if forms.tail else self._buf(M, u)
+        # proj_in and the three LayerNormalizations: y, n1, n2 stay on the CU in the front launch, which also makes q|k, v^T and q2
+        if forms.front:
+            fd = self._guard(_front_desc(xin, w, lns, y, qkb, v_t, q2, n3, M, u))
             self._keep.append(fd)
             self.ops.append((lib().dm3d_attn_front, (C.byref(fd),), "attn_front",
                              {"desc": f"attn_front m={M} u={u} (proj_in + 3 LayerNorm + q|k, v^T, q2)", "flops": 2.0 * M * u * 5 * u,
                               "bufs": {"x": xin, "y": y, "qk": qkb, "v_t": v_t, "q2": q2, "n3": n3}}))
         else:
-            self._gemm(a=xin, lda=u, b=pin.h2, ldb=pin.cin_pad, out=y, ldo=u, m=M, n=u, k=u, bias=pin.bias, act=ACT_RELU,
+            self._gemm(a=xin, lda=u, b=w.pin.h2, ldb=w.pin.cin_pad, out=y, ldo=u, m=M, n=u, k=u, bias=w.pin.bias, act=ACT_RELU,
                        h3=True, b_h2=True)
             n1, n2 = self._buf(M, u), self._buf(M, u)
-            self.ops.append((lib().dm3d_layernorm3_h2, (y.data_ptr(), M, u, LN_EPS, g1.data_ptr(), b1.data_ptr(), n1.data_ptr(),
-                                                        g2.data_ptr(), b2.data_ptr(), n2.data_ptr(), g3.data_ptr(), b3.data_ptr(),
-                                                        n3.data_ptr()), "layernorm", {}))
-        # the MLP (Dense(4u, relu) -> Dense(u), :132-133) as ONE launch with the hidden activation in LDS (dm3d_mlp_fused, round 4) where the
-        # kernel's shape fits (u = 256 and enough row tiles to fill the chip); otherwise its first Dense joins the grouped launch below
-        mlp_fused = u == 256 and M % 64 == 0 and M >= min_rows and getattr(m0, "tiled", None) is not None and os.environ.get("DM3D_MLP_FUSED", "1") != "0"
-        hid = None if mlp_fused else self._buf(M, 4 * u)
+            self._layernorm3(y, M, u, lns, (n1, n2, n3), h2=True)
+        # the projections of the LayerNorm outputs that no fused launch covers, as one grouped launch
         group = []
-        if not front:
-            qkb, v_t, q2 = self._buf(M, 2 * u), self._buf(u, M), self._buf(M, u)
+        if not forms.front:
             group += [
-                dict(a=n1, lda=u, b=qk.h2, ldb=qk.cin_pad, out=qkb, ldo=2 * u, m=M, n=2 * u, k=u, bias=qk.bias, out_h2=True, **hh),
-                dict(a=val.h2, lda=val.cin_pad, b=n1, ldb=u, out=v_t, ldo=M, m=u, n=M, k=u, bias=val.bias, bias_along_m=1,
+                dict(a=n1, lda=u, b=w.qk.h2, ldb=w.qk.cin_pad, out=qkb, ldo=2 * u, m=M, n=2 * u, k=u, bias=w.qk.bias, out_h2=True, **hh),
+                dict(a=w.val.h2, lda=w.val.cin_pad, b=n1, ldb=u, out=v_t, ldo=M, m=u, n=M, k=u, bias=w.val.bias, bias_along_m=1,
                      out_h2=True, **hh),
-                dict(a=n2, lda=u, b=qk.h2, ldb=qk.cin_pad, out=q2, ldo=u, m=M, n=u, k=u, bias=qk.bias, out_h2=True, **hh)]
-        if not mlp_fused:
-            group.append(dict(a=n3, lda=u, b=m0.h2, ldb=m0.cin_pad, out=hid, ldo=4 * u, m=M, n=4 * u, k=u, bias=m0.bias, act=ACT_RELU,
-                              out_h2=True, **hh))
+                dict(a=n2, lda=u, b=w.qk.h2, ldb=w.qk.cin_pad, out=q2, ldo=u, m=M, n=u, k=u, bias=w.qk.bias, out_h2=True, **hh)]
+        if not forms.mlp_fused:
+            group.append(dict(a=n3, lda=u, b=w.m0.h2, ldb=w.m0.cin_pad, out=hid, ldo=4 * u, m=M, n=4 * u, k=u, bias=w.m0.bias,
+                              act=ACT_RELU, out_h2=True, **hh))
         if group:
             self._gemm_group(group)
-        rows = B if self.per_sample_context else 1
-        kctx, vctx_t = self._buf(rows, L * u), self._buf(rows, u * L)
-        self.ctx_bufs[n] = (kctx, vctx_t)
-        ks, vs = (L * u, u * L) if self.per_sample_context else (0, 0)
-        a1, a2 = self._buf(M, u), self._buf(M, u)
+        self._attention_h2(n, qkb, v_t, q2, y, a1, a2, L, u, forms.attn_fused)
+        # the MLP (Dense(4u, relu) -> Dense(u), :132-133) and the block's proj_out (Conv3D(units, 1, relu) + the block input, :195)
+        if forms.mlp_fused:
+            d = self._guard(_mlp_desc(n3, w, a1, a2, out if forms.tail else a3, M, u, block_in=x if forms.tail else None))
+            self._keep.append(d)
+            self.ops.append((lib().dm3d_mlp_fused, (C.byref(d),), "mlp_fused",
+                             {"desc": f"mlp_fused m={M} u={u} hidden={4 * u}" + (" + proj_out" if forms.tail else ""),
+                              "flops": 2 * 2.0 * M * u * 4 * u + (2.0 * M * u * u if forms.tail else 0.0),
+                              "bufs": {"out": out if forms.tail else a3}}))
+        else:
+            self._gemm(a=hid, lda=4 * u, b=w.m1.h2, ldb=w.m1.cin_pad, out=a3, ldo=u, m=M, n=u, k=4 * u, bias=w.m1.bias, res=a1, res2=a2,
+                       ldr=u, out_h2=True, **hh)
+        if not forms.tail:
+            self._gemm(a=a3, lda=u, b=w.pout.h2, ldb=w.pout.cin_pad, out=out, ldo=u, m=M, n=u, k=u, bias=w.pout.bias, act=ACT_RELU,
+                       res=x, ldr=u, **hh)
+        return out
+
+    def _attention_h2(self, n, qkb, v_t, q2, y, a1, a2, L, u, fused):
+        """a1 = self attention of q|k, v^T + y and a2 = cross attention of q2 against the block's context, over DM3D_FMT_H2 operands.
+        ``fused``: ONE dm3d_attention_group launch (scores, online softmax and P.V per 32-key tile in registers / LDS); else the two
+        score products, one softmax over both and the two P.V products, each pair grouped."""
+        B, M = self.B, self.B * L
+        kctx, vctx_t, ks, vs = self._context(n, L, u)
         scale = float(u) ** -0.5
-        # (the fused kernel runs one 4-wave workgroup per 128 queries: it needs >= ~128 workgroups to beat the GEMM form, i.e. B >= 16 at L = 512;
-        # measured B = 1 / 4 / 8: 2.80 / 3.85 / 5.74 ms per step fused against 2.5 / 3.5 / 5.3 with the three launches)
-        if os.environ.get("DM3D_ATTN_FUSED", "1") != "0" and u == 256 and L % 128 == 0 and 2 * B * (L // 128) >= 128:
-            # both attention passes in ONE fused launch (dm3d_attention_group -> csrc/dm3d_attn_h3.hip): scores, online softmax and
-            # P.V per 32-key tile in registers / LDS; no [B, L, L] tensor
-            descs = (_lib.AttentionDesc * 2)()
-            for d, (qt, qoff, ldq, kt, koff, ldk, sk, vt, ldv, sv, out, res) in zip(descs, (
-                    (qkb, 0, 2 * u, qkb, u, 2 * u, L * 2 * u, v_t, M, L, a1, y),
-                    (q2, 0, u, kctx, 0, u, ks, vctx_t, L, vs, a2, None))):
-                d.q, d.ldq = _ptr(qt, qoff), ldq
-                d.k, d.ldk, d.stride_k = _ptr(kt, koff), ldk, sk
-                d.vt, d.ldv, d.stride_vt = _ptr(vt), ldv, sv
-                d.out, d.ldo, d.res = _ptr(out), u, _ptr(res)
-                d.batch, d.lq, d.lk, d.c, d.scale, d.precision, d.fmt = B, L, L, u, scale, _lib.PREC_H3, _lib.FMT_H2
+        if fused:
+            descs = _attention_pair(B, L, u, scale,
+                                    dict(q=qkb, ldq=2 * u, k=qkb, k_off=u, ldk=2 * u, stride_k=L * 2 * u, vt=v_t, ldv=M, stride_vt=L, out=a1, res=y),
+                                    dict(q=q2, ldq=u, k=kctx, ldk=u, stride_k=ks, vt=vctx_t, ldv=L, stride_vt=vs, out=a2))
             self._keep.append(descs)
             self.ops.append((lib().dm3d_attention_group, (descs, 2, None), "attn_fused",
                              {"desc": f"attn_fused 2 passes B={B} L={L} c={u}", "flops": 2 * 2 * 2.0 * B * L * L * u,
                               "bufs": {"a1": a1, "a2": a2}}))
-        else:
-            scores = self._buf(2, B, L, L)
-            s2 = B * L * L                                                        # element offset of the cross-attention scores
-            self._gemm_group([
-                dict(a=qkb, lda=2 * u, stride_a=L * 2 * u, b=qkb, b_off=u, ldb=2 * u, stride_b=L * 2 * u, out=scores, ldo=L,
-                     stride_o=L * L, m=L, n=L, k=u, batch=B, alpha=scale, **hh),
-                dict(a=q2, lda=u, stride_a=L * u, b=kctx, ldb=u, stride_b=ks, out=scores, out_off=s2, ldo=L, stride_o=L * L,
-                     m=L, n=L, k=u, batch=B, alpha=scale, **hh),
-            ])
-            self.ops.append((lib().dm3d_softmax_rows_h2, (scores.data_ptr(), 2 * B * L, L, L), "softmax", {}))
-            self._gemm_group([
-                dict(a=scores, lda=L, stride_a=L * L, b=v_t, ldb=M, stride_b=L, out=a1, ldo=u, stride_o=L * u, m=L, n=u, k=L,
-                     batch=B, res=y, ldr=u, stride_r=L * u, **hh),
-                dict(a=scores, a_off=s2, lda=L, stride_a=L * L, b=vctx_t, ldb=L, stride_b=vs, out=a2, ldo=u, stride_o=L * u,
-                     m=L, n=u, k=L, batch=B, **hh),
-            ])
-        # ... and the block's proj_out (Conv3D(units, 1, relu) + the block input, :195) as a tail of the same launch: a3 never leaves the CU
-        tail = mlp_fused and getattr(pout, "ftiled", None) is not None and os.environ.get("DM3D_MLP_TAIL", "1") != "0"
-        out = self._buf(B, edge, edge, edge, u)
-        a3 = None if tail else self._buf(M, u)
-        if mlp_fused:
-            d = MlpDesc()
-            d.x, d.ldx, d.w0, d.b0, d.w1, d.b1 = _ptr(n3), u, m0.tiled.data_ptr(), _ptr(m0.bias), m1.tiled.data_ptr(), _ptr(m1.bias)
-            d.res, d.res2, d.ldr, d.m, d.units = _ptr(a1), _ptr(a2), u, M, u
-            if tail:
-                d.out, d.ldo, d.out_fmt = _ptr(out), u, _lib.FMT_F32
-                d.w2, d.b2, d.res3, d.ldr3 = pout.ftiled.data_ptr(), _ptr(pout.bias), _ptr(x), u
-            else:
-                d.out, d.ldo, d.out_fmt = _ptr(a3), u, _lib.FMT_H2
-            if self.range_flag is not None:
-                d.range_flag, d.range_limit = self.range_flag.data_ptr(), self.range_limit
-            self._keep.append(d)
-            self.ops.append((lib().dm3d_mlp_fused, (C.byref(d),), "mlp_fused",
-                             {"desc": f"mlp_fused m={M} u={u} hidden={4 * u}" + (" + proj_out" if tail else ""),
-                              "flops": 2 * 2.0 * M * u * 4 * u + (2.0 * M * u * u if tail else 0.0),
-                              "bufs": {"out": out if tail else a3}}))
-        else:
-            self._gemm(a=hid, lda=4 * u, b=m1.h2, ldb=m1.cin_pad, out=a3, ldo=u, m=M, n=u, k=4 * u, bias=m1.bias, res=a1, res2=a2,
-                       ldr=u, out_h2=True, **hh)
-        if not tail:
-            self._gemm(a=a3, lda=u, b=pout.h2, ldb=pout.cin_pad, out=out, ldo=u, m=M, n=u, k=u, bias=pout.bias, act=ACT_RELU,
-                       res=x, ldr=u, **hh)
-        return out
+            return
+        hh = dict(h3=True, a_h2=True, b_h2=True)
+        scores = self._buf(2, B, L, L)
+        s2 = B * L * L                                                        # element offset of the cross-attention scores
+        self._gemm_group([
+            dict(a=qkb, lda=2 * u, stride_a=L * 2 * u, b=qkb, b_off=u, ldb=2 * u, stride_b=L * 2 * u, out=scores, ldo=L,
+                 stride_o=L * L, m=L, n=L, k=u, batch=B, alpha=scale, **hh),
+            dict(a=q2, lda=u, stride_a=L * u, b=kctx, ldb=u, stride_b=ks, out=scores, out_off=s2, ldo=L, stride_o=L * L,
+                 m=L, n=L, k=u, batch=B, alpha=scale, **hh),
+        ])
+        self.ops.append((lib().dm3d_softmax_rows_h2, (scores.data_ptr(), 2 * B * L, L, L), "softmax", {}))
+        self._gemm_group([
+            dict(a=scores, lda=L, stride_a=L * L, b=v_t, ldb=M, stride_b=L, out=a1, ldo=u, stride_o=L * u, m=L, n=u, k=L,
+                 batch=B, res=y, ldr=u, stride_r=L * u, **hh),
+            dict(a=scores, a_off=s2, lda=L, stride_a=L * L, b=vctx_t, ldb=L, stride_b=vs, out=a2, ldo=u, stride_o=L * u,
+                 m=L, n=u, k=L, batch=B, **hh),
+        ])
 
     def _self_block(self, blk, x, edge):
-        """AttentionBlock (dm3d.py:39-63): BN(x) + proj(softmax(q k^T u^-0.5) v)."""
-        P, B, n, u = self.net.P, self.B, blk.name, blk.cout
-        L = edge ** 3
-        M = B * L
-        self._check_tokens(L)
+        """AttentionBlock (dm3d.py:39-63): xn + proj(softmax(q k^T u^-0.5) v) with xn = norm(x), four GEMMs around a row softmax.  With
+        ``_attn_h2(u, L)`` the GEMMs run in H3 and q|k, v^T and the probabilities live in DM3D_FMT_H2; otherwise plain float32."""
+        P, B = self.net.P, self.B
+        n, u, L, M = self._attn_shape(blk, edge)
         h2 = self.net._attn_h2(u, L)
         W = (lambda w: w.h2) if h2 else (lambda w: w.wpk)
         qk, val, proj = P[f"{n}.qk"], P[f"{n}.value"], P[f"{n}.proj"]
@@ -1003,16 +1045,16 @@ class Plan:
                 check(lib().dm3d_gather_rows(tab.data_ptr(), tab.shape[0], ids.data_ptr(), buf.data_ptr(), buf.shape[0],
                                              buf.shape[1], st), "gather_rows")
 
-    _RANGE_OF = {"conv_wino": "conv", "conv_wino_h2in": "conv", "conv_k3s1_td4": "conv", "conv_k1": "conv", "conv_k3s2": "conv", "conv_up": "conv", "conv_k3s1_n32": "conv", "conv_k3s1_h2in": "conv", "conv_k3s1": "conv",
-                 "gemm": "attn", "gemm_h3": "attn", "mlp_fused": "attn", "attn_front": "attn", "attn_fused": "attn", "softmax": "attn", "layernorm": "attn", "groupnorm": "norm", "affine": "norm",
-                 "range": "guard"}
+    # the roctx range of a launch kind; every conv_* kind of _conv's ladder goes under "conv"
+    _RANGE_OF = {**dict.fromkeys(("gemm", "gemm_h3", "mlp_fused", "attn_front", "attn_fused", "softmax", "layernorm"), "attn"),
+                 "groupnorm": "norm", "affine": "norm", "range": "guard"}
 
     def run(self, stream: Optional[int] = None):
         st = _stream() if stream is None else stream
         push, pop = _lib.roctx()
         cur = None
         for fn, args, what, _ in self.ops:
-            rng = self._RANGE_OF.get(what, what)
+            rng = "conv" if what.startswith("conv_") else self._RANGE_OF.get(what, what)
             if rng != cur:                              # consecutive launches of one family share a range (no-ops unless DM3D_ROCTX=1)
                 if cur is not None:
                     pop()
