@@ -118,10 +118,14 @@ class Trainer:
         nothing is allocated and adam_step is the plain dm3d_adam launch)."""
         if cfg.norm != "batch":
             raise ValueError("training is built for the BatchNormalization network the reference trains (norm='batch')")
+        self.blocks, self.spec = walk(cfg)
+        for blk in self.blocks:                               # (before anything is allocated or launched; attention() checks again)
+            if blk.kind == "attn" and blk.edge ** 3 % 4:
+                raise ValueError(f"{blk.name}: attention over {blk.edge ** 3} tokens: the contractions run on the MFMA GEMM, which needs "
+                                 "D*H*W % 4 == 0 at attention levels")
         _lib.require_device()
         self.cfg, self.device, self.lr = cfg, torch.device(device), float(lr)
         self.bn_moving_unbiased = bool(bn_moving_unbiased)
-        self.blocks, self.spec = walk(cfg)
         names = [n for n in self.spec if is_trainable(n)]
         sizes = [int(np.prod(self.spec[n])) for n in names]
         # every parameter starts on a 16-byte boundary (the kernels read rows as float4)
@@ -246,6 +250,32 @@ class Trainer:
     def _colsum(self, x: torch.Tensor, groups: int, rows: int, c: int, out_ptr: int, ld_out: int):
         check(lib().dm3d_colsum(x.data_ptr(), groups, rows, c, out_ptr, ld_out, _st()), "colsum")
 
+    def _repitch(self, src: torch.Tensor, rows: int, c: int, ld_src: int, ld_dst: int, batch: int = 1) -> torch.Tensor:
+        """[batch * rows, ld_dst] whose first ``c`` columns are those of the row-major ``src`` (leading dimension ld_src), the rest zero:
+        two dm3d_transpose launches, which take any column count (the float4 kernels do not)."""
+        t1 = _empty(batch * c * rows, device=self.device)
+        check(lib().dm3d_transpose(src.data_ptr(), rows, c, ld_src, rows * ld_src, t1.data_ptr(), rows, c * rows, batch, _st()), "transpose")
+        out = _zeros(batch * rows, ld_dst, device=self.device)
+        check(lib().dm3d_transpose(t1.data_ptr(), c, rows, rows, c * rows, out.data_ptr(), ld_dst, rows * ld_dst, batch, _st()), "transpose")
+        return out
+
+    def _pad_channels(self, x: torch.Tensor) -> torch.Tensor:
+        """[B, D, H, W, C] -> the same with C rounded up to 4, zeros behind (the conv kernels read 4 channels per load)."""
+        c = x.shape[-1]
+        if c % 4 == 0:
+            return x
+        cp = -(-c // 4) * 4
+        B = x.shape[0]
+        return self._repitch(x, x.numel() // (B * c), c, c, cp, batch=B).reshape(*x.shape[:-1], cp)
+
+    def crop_channels(self, y: torch.Tensor) -> torch.Tensor:
+        """What forward() returns, without the zero channels that pad img_channels up to a multiple of 4."""
+        c, cp = self.cfg.img_channels, y.shape[-1]
+        if cp == c:
+            return y
+        B = y.shape[0]
+        return self._repitch(y, y.numel() // (B * cp), c, cp, c, batch=B).reshape(*y.shape[:-1], c)
+
     def _act(self, x: torch.Tensor, act: int) -> torch.Tensor:
         y = torch.empty_like(x)
         c = x.shape[-1]
@@ -254,9 +284,17 @@ class Trainer:
 
     # ---- layers (forward + recorded backward) -------------------------------------------------------------------------------
     def conv(self, x: Var, name: str, ksize: int, stride: int = 1, vec: Optional[Var] = None, res: Optional[Var] = None) -> Var:
-        """Conv3D(padding="same") (+ bias, + the per-sample time-embedding vector, + residual)."""
+        """Conv3D(padding="same") (+ bias, + the per-sample time-embedding vector, + residual).
+
+        A channel count that is no multiple of 4 (img_channels at conv_in's input and out.conv's output) runs rounded up to one: ``x``
+        comes in padded with zero channels (_pad_channels), the output leaves with zero channels behind (crop_channels).  The packed
+        weight images are zero-padded to 16 x 64 channels anyway, and every parameter owns a multiple of 4 floats of the flat buffers
+        whose tail stays zero (zero gradient, zero Adam moments), so the bias and its gradient are simply taken 4 wide."""
         pk, pb = self.params[f"{name}.kernel"], self.params[f"{name}.bias"]
-        cin, cout = pk.shape[-2], pk.shape[-1]
+        kin, kout = pk.shape[-2], pk.shape[-1]
+        cin, cout = -(-kin // 4) * 4, -(-kout // 4) * 4
+        if (cin != kin and cout != kout) or ((cin != kin or cout != kout) and (vec is not None or res is not None)):
+            raise ValueError(f"{name}: {kin} -> {kout} channels: only one side of a plain Conv3D may be no multiple of 4")
         B, D, H, W_, _ = x.v.shape
         out = Var(self._conv_launch(x.v, self._packed(pk.name), cin, cout, ksize, stride, bias=pb.w,
                                     vec=vec.v if vec is not None else None, vec_ld=cout, res=res.v if res is not None else None))
@@ -277,7 +315,18 @@ class Trainer:
                 check(lib().dm3d_dilate2(g.data_ptr(), geff.data_ptr(), B, od, oh, ow, D, H, W_, offs[0], offs[1], offs[2], cout, _st()), "dilate2")
             if x.needs_grad:
                 x.add_grad(self._conv_launch(geff, self._packed(pk.name, flip=True), cout, cin, ksize, 1))
-            self._wgrad(x.v, geff, pk.g, cin, cout, ksize, B, D, H, W_)
+            if cin == kin and cout == kout:
+                self._wgrad(x.v, geff, pk.g, cin, cout, ksize, B, D, H, W_)
+            else:
+                # the padded contraction into a buffer of its own, then the [taps][kin][kout] part of its [taps][cin][cout] added to pk.g
+                taps = ksize ** 3
+                dw = _zeros(taps * cin * cout, device=self.device)
+                self._wgrad(x.v, geff, dw, cin, cout, ksize, B, D, H, W_)
+                if cout == kout:
+                    check(lib().dm3d_copy_cols(dw.data_ptr(), cin * cout, 0, pk.g.data_ptr(), kin * kout, 0, taps, kin * kout, 1, _st()), "copy_cols")
+                else:
+                    part = self._repitch(dw, taps * cin, kout, cout, kout)
+                    check(lib().dm3d_axpy(pk.g.data_ptr(), part.data_ptr(), part.numel(), 1.0, _st()), "axpy")
             self._colsum(g, 1, g.numel() // cout, cout, pb.g.data_ptr(), cout)
             if vec is not None and vec.needs_grad:
                 self._colsum(g, B, od * oh * ow, cout, vec.grad_buffer().data_ptr(), cout)
@@ -568,13 +617,14 @@ class Trainer:
 
     # ---- the network ------------------------------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, t_host: np.ndarray, ctx_ids: Optional[torch.Tensor], update_moving: bool = True) -> Var:
-        """build_model's graph (conditional_dm3d.py:348-415 / dm3d.py:318-376) with training=True; records the tape."""
+        """build_model's graph (conditional_dm3d.py:348-415 / dm3d.py:318-376) with training=True; records the tape.  With an
+        img_channels that is no multiple of 4 the returned tensor carries zero channels up to the next one (crop_channels)."""
         cfg = self.cfg
         self.tape: List = []
         self._cache = {}
         self.update_moving = update_moving
         B = x.shape[0]
-        xin = Var(x, needs_grad=False)
+        xin = Var(self._pad_channels(x), needs_grad=False)
         h = self.conv(xin, "conv_in", 3)
         emb = Var(torch.from_numpy(time_embedding_table(np.asarray(t_host), cfg.temb_dim)).to(self.device), needs_grad=False)
         temb = self.dense(self.dense(emb, "time_mlp.0", act=ACT_SILU), "time_mlp.1")
@@ -631,6 +681,10 @@ class Trainer:
         loss = torch.zeros(1, dtype=torch.float64, device=dev)
         pred.g = torch.empty_like(pred.v)
         inv = 1.0 / (float(latents.shape[-1]) * float(global_bs) * float(lc) ** 4)
+        if pred.v.shape[-1] != latents.shape[-1]:
+            # img_channels rounded up to 4: prediction and targets are all zero in the added channels, which so add nothing to the loss
+            noise = self._pad_channels(noise)
+            latents = self._pad_channels(latents) if objective is not None else latents
         if objective is None:
             self.sample_loss = None
             check(lib().dm3d_mse_loss_grad(pred.v.data_ptr(), noise.data_ptr(), pred.v.numel(), inv, loss.data_ptr(), pred.g.data_ptr(), _st()),
@@ -649,7 +703,7 @@ class Trainer:
             check(lib().dm3d_objective_loss_grad(C.byref(d), _st()), "objective_loss_grad")
         self.backward()
         self._cache = {}
-        return loss, pred.v
+        return loss, self.crop_channels(pred.v)
 
     def allreduce_grads(self, loss: Optional[torch.Tensor] = None):
         """Data-parallel training (what MirroredStrategy(cross_device_ops=ReductionToOneDevice()) does for the reference,

@@ -466,7 +466,7 @@ def _training_forward(net: "UNet", inputs) -> torch.Tensor:
         new = tr.state_dict()
         net.load_state_dict({k: (new[k] if k.endswith((".mean", ".var")) else v) for k, v in net.state_dict().items()})
     # (the model's own Trainer: it was marked dirty, the network picks the new statistics up on its next use)
-    return out.v.clone()
+    return tr.crop_channels(out.v).clone()
 
 
 def _gemm_desc(a, lda, b, ldb, out, ldo, m, n, k, batch=1, stride_a=0, stride_b=0, stride_o=0, alpha=1.0, bias=None,

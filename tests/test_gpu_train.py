@@ -1,7 +1,8 @@
 """GPU parity of DiffusionModel.train_step (reference networks/conditional_dm3d.py:471-510) against the CPU oracle
 (oracle/ref_train.py: the restated forward with training-mode BatchNormalization, torch.autograd as the gradient reference,
 Keras-default Adam).  Staged as the layers are: single layers' gradients, the training forward and loss, all gradients of the
-network, one optimizer step, the public train_step.  Tolerances are written next to each assert."""
+network, one optimizer step, the public train_step.  Tolerances are written next to each assert.
+(Other build_model arguments, under a stricter gradient metric without _compare_grads' floor: tests/test_gpu_train_configs.py.)"""
 import os
 from types import SimpleNamespace
 
