@@ -7,20 +7,14 @@
 // As separate launches this was proj_in GEMM + layernorm3 + a grouped GEMM: 98 us per block at B = 32, each a single round of 256 tiles whose
 // fixed costs nothing overlaps, with y, n1, n2 round-tripping HBM.
 //
-// Shape (the scheme of dm3d_mlp_h3.hip).  One workgroup (4 waves, one per SIMD) owns 64 rows.  Every product is computed TRANSPOSED,
-// out^T[256 x 64] = W . in^T with K = 256: the weights are the MFMA's A operand and arrive as PRE-TILED operand fragments
-// (dm3d_pack_front_weights: 1 KB per (32-row tile, 16-k record, hi | lo), lane-ordered) by plain coalesced 16-byte loads straight into
-// registers, two records ahead of their MFMAs — no wave needs another wave's weights, so they never touch LDS; the 64 input rows are the B
-// operand, read from an LDS image of DM3D_FMT_H2 records ([record][row][64 B], XOR-swizzled slots; record stride 4 KB + 32 B so that the
-// row-major stores of the staging pass spread over the banks).  Wave w owns output columns 64w .. 64w+63 (2 x 2 tiles of 32x32, 64 registers).
-// A lane then holds groups of four consecutive columns of one row: 16-byte float32 / 8 + 8-byte H2 stores, no transposes.  v^T is the same
-// product with the MFMA operands exchanged (the two fragment layouts are identical), which leaves a lane with four consecutive TOKENS of one
-// channel — the orientation v^T is stored in.
+// Shape: the transposed fragment-stream product of dm3d_frag.h (tiling, weight fragments, record layout, lane mapping), 32 or 64 rows per
+// workgroup; the LDS images have a record stride of 32 MR rows + 32 B, so that the row-major stores of the staging pass spread over the banks.
+// v^T is the same product with the MFMA operands exchanged, which leaves a lane with four consecutive TOKENS of one channel — the orientation
+// v^T is stored in.
 // LayerNormalization: the row statistics need all 256 columns of a row, i.e. all four waves: two exchanges of 64 x 4 partial sums through
 // LDS (mean, then the centred sum of squares — the two-pass form of dm3d_layernorm3).
-#include "dm3d_h3.h"
+#include "dm3d_frag.h"
 #include <cstdlib>
-#include <type_traits>
 
 namespace {
 
@@ -39,16 +33,6 @@ struct FrontArgs {
     int m;
     int* range_flag; float range_limit;
 };
-
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
-}
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // MR: 32-row tiles per workgroup.  2: 64 rows, one workgroup per CU (134 KB of LDS); 1: 32 rows, 68 KB and half the registers, up to two workgroups
 // per CU, at twice the weight traffic per row (the launcher picks by the number of rows).
@@ -69,20 +53,6 @@ __global__ __launch_bounds__(256, MR == 1 ? 2 : 1) void attn_front_h3(const Fron
     const int half = lane >> 5, l32 = lane & 31;
     const int m0 = blockIdx.x * TM;
 
-    // hi = f16(x) (RNE), lo = f16(x - hi) of two values (dm3d_h3.h split8's instruction sequence)
-    auto split2 = [](float x0, float x1, unsigned int& hi, unsigned int& lo) {
-        float r0, r1;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x0), "v"(x1));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x0));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(x1));
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(r0), "v"(r1));
-    };
-    auto clamp = [](float v) { return __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f); };
-    auto lds_barrier = [&]() {                                  // raw barrier behind this wave's own LDS traffic (weight loads stay in flight across it)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
 
     // ---- weight stream: five passes of 8 groups; the loads of a group are issued in front of the MFMAs of the group before it (two register
     // sets), those of a pass's first groups during the previous pass's last groups
@@ -96,10 +66,7 @@ __global__ __launch_bounds__(256, MR == 1 ? 2 : 1) void attn_front_h3(const Fron
     // followed by its stores, two statistics exchanges), and 100 MB of output per launch add the rest; the MFMAs (14 us) hide inside the waits)
     constexpr int WSETS = 2;
     h8 wa[WSETS][8];                                            // [set][record i of the group][column tile nr][hi | lo]
-    auto load_w = [&](const int set, const char* wp, const int g) __attribute__((always_inline)) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) wa[set][t] = *reinterpret_cast<const h8*>(wp + (size_t)g * 8192 + t * 1024);
-    };
+    auto load_w = [&](const int set, const char* wp, const int g) __attribute__((always_inline)) { dm3d_load_group(wa[set], wp + (size_t)g * 8192); };
 #pragma unroll
     for (int g = 0; g < WSETS - 1; ++g) load_w(g, w_in, g);
 
@@ -117,8 +84,8 @@ __global__ __launch_bounds__(256, MR == 1 ? 2 : 1) void attn_front_h3(const Fron
         for (int j = 0; j < RW; ++j) {
             const int r = wave * RW + j, sw = (r >> 2) & 3;
             unsigned int h0, l0, h1, l1;
-            split2(clamp(xv[j][0]), clamp(xv[j][1]), h0, l0);
-            split2(clamp(xv[j][2]), clamp(xv[j][3]), h1, l1);
+            dm3d_split2(dm3d_clamp16(xv[j][0]), dm3d_clamp16(xv[j][1]), h0, l0);
+            dm3d_split2(dm3d_clamp16(xv[j][2]), dm3d_clamp16(xv[j][3]), h1, l1);
             char* rp = reg_a + rec * RS + r * 64 + sub;
             *reinterpret_cast<u32x2*>(rp + ((slot ^ sw) << 4)) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(rp + (((2 + slot) ^ sw) << 4)) = u32x2{l0, l1};
@@ -126,19 +93,16 @@ __global__ __launch_bounds__(256, MR == 1 ? 2 : 1) void attn_front_h3(const Fron
     }
     lds_barrier();
 
-    // B-operand fragment offsets (bytes): logical slot `half` (hi; lo: ^ 32) of this lane's row, swizzled by the row
-    unsigned b_off[MR];
+    unsigned b_off[MR];                                         // B-operand fragment offsets of this lane's rows
 #pragma unroll
-    for (int t = 0; t < MR; ++t) {
-        const int ra = t * 32 + l32;
-        b_off[t] = (unsigned)(ra * 64 + ((half ^ ((ra >> 2) & 3)) << 4));
-    }
+    for (int t = 0; t < MR; ++t) b_off[t] = dm3d_frag_off(t * 32 + l32, half);
     // The MFMA as the compiler's builtin, NOT inline asm: behind an asm MFMA hipcc's hazard pass knows nothing, and it placed a VALU write to a
     // register of the last MFMA's A operand two instructions behind that MFMA (the address arithmetic of the epilogue's bias loads) — on
     // gfx950 the K = 16 MFMA reads its operands over several passes, and one launch in ~20 000 workgroups stored one wrong element of y
     // (tools/chain_trace.py: two chains of one seed differed in ONE word of y at step 10, everything downstream of that row with it).
 #define DM3D_MFMA_VV(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0)
 #define DM3D_MFMA_DRAIN() do { } while (0)
+    auto mfma = [](f32x16& c, const h8& a, const h8& b) __attribute__((always_inline)) { DM3D_MFMA_VV(c, a, b); };
     // One pass: acc[mr][nr] (+)= W[64w + 32nr ..][:] . in[32mr ..][:]^T over K = 256.  SWAP: the operands exchanged (acc^T: lane = column).
     auto pass = [&](auto SWAP_T, f32x16 (&acc)[MR][2], const char* reg, const char* wp, const char* wnext) __attribute__((always_inline)) {
         constexpr bool SWAP = decltype(SWAP_T)::value;
@@ -168,24 +132,7 @@ __global__ __launch_bounds__(256, MR == 1 ? 2 : 1) void attn_front_h3(const Fron
                 const int kk = 2 * g + i, bs = i;                       // (two records per group: the record's parity is i)
                 if (kk + 1 < KR) read_b(bs ^ 1, kk + 1);
                 __builtin_amdgcn_sched_barrier(0);
-                const h8 (&ah)[MR] = bh[bs];
-                const h8 (&al)[MR] = bl[bs];
-                // pass-major over the four tiles (a 32x32x16 that depends on the one issued just before it waits out its latency)
-                if constexpr (!SWAP) {
-#pragma unroll
-                    for (int t = 0; t < 2 * MR; ++t) DM3D_MFMA_VV(acc[t >> 1][t & 1], wa[set][4 * i + 2 * (t & 1)], al[t >> 1]);
-#pragma unroll
-                    for (int t = 0; t < 2 * MR; ++t) DM3D_MFMA_VV(acc[t >> 1][t & 1], wa[set][4 * i + 2 * (t & 1) + 1], ah[t >> 1]);
-#pragma unroll
-                    for (int t = 0; t < 2 * MR; ++t) DM3D_MFMA_VV(acc[t >> 1][t & 1], wa[set][4 * i + 2 * (t & 1)], ah[t >> 1]);
-                } else {
-#pragma unroll
-                    for (int t = 0; t < 2 * MR; ++t) DM3D_MFMA_VV(acc[t >> 1][t & 1], al[t >> 1], wa[set][4 * i + 2 * (t & 1)]);
-#pragma unroll
-                    for (int t = 0; t < 2 * MR; ++t) DM3D_MFMA_VV(acc[t >> 1][t & 1], ah[t >> 1], wa[set][4 * i + 2 * (t & 1) + 1]);
-#pragma unroll
-                    for (int t = 0; t < 2 * MR; ++t) DM3D_MFMA_VV(acc[t >> 1][t & 1], ah[t >> 1], wa[set][4 * i + 2 * (t & 1)]);
-                }
+                dm3d_kstep<MR, SWAP>(acc, &wa[set][4 * i], bh[bs], bl[bs], mfma);
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
@@ -195,16 +142,15 @@ __global__ __launch_bounds__(256, MR == 1 ? 2 : 1) void attn_front_h3(const Fron
     const std::true_type swap_t;
 
     float amax = 0.0f;
-    // lane (l32, half): row 32 mr + l32; register 4 gq + j of tile (mr, nr): column n0 + j, n0 = 64 w + 32 nr + 8 gq + 4 half
-    auto col0 = [&](int nr, int gq) { return wave * 64 + nr * 32 + 8 * gq + 4 * half; };
+    auto col0 = [&](int nr, int gq) { return dm3d_col0(wave, nr, gq, half); };
     // Four consecutive columns of one row -> 16 bytes of DM3D_FMT_H2.  This lane (half h) holds columns 8 q + 4 h .. + 3 of an 8-column group,
     // its partner lane (half h ^ 1, same row) the other four: v_permlane32_swap exchanges the halves' words so that the half-0 lane ends up
     // with the group's eight hi halves (one whole 16-byte slot of the record) and the half-1 lane with its eight lo halves (the slot 32
     // bytes further): one 16-byte store per lane instead of two 8-byte ones.
     auto pack16 = [&](const float (&v)[4]) __attribute__((always_inline)) {
         unsigned int h0, l0, h1, l1;
-        split2(clamp(v[0]), clamp(v[1]), h0, l0);
-        split2(clamp(v[2]), clamp(v[3]), h1, l1);
+        dm3d_split2(dm3d_clamp16(v[0]), dm3d_clamp16(v[1]), h0, l0);
+        dm3d_split2(dm3d_clamp16(v[2]), dm3d_clamp16(v[3]), h1, l1);
         const auto s0 = __builtin_amdgcn_permlane32_swap(h0, l0, false, false);
         const auto s1 = __builtin_amdgcn_permlane32_swap(h1, l1, false, false);
         return u32x4{s0[0], s1[0], s0[1], s1[1]};
@@ -219,7 +165,7 @@ __global__ __launch_bounds__(256, MR == 1 ? 2 : 1) void attn_front_h3(const Fron
         const int sw = (r >> 2) & 3, slot = ((n8 >> 3) & 1) + 2 * half;
         *reinterpret_cast<u32x4*>(reg + (n8 >> 4) * RS + r * 64 + ((slot ^ sw) << 4)) = pack16(v);
     };
-    auto col8 = [&](int nr, int gq) { return wave * 64 + nr * 32 + 8 * gq; };
+    auto col8 = [&](int nr, int gq) { return dm3d_col8(wave, nr, gq); };
 
     // ---- pass 0: y = relu(W_in . x + b_in), kept in registers
     f32x16 yv[MR][2];
@@ -383,30 +329,36 @@ __global__ __launch_bounds__(256, MR == 1 ? 2 : 1) void attn_front_h3(const Fron
 #undef DM3D_MFMA_DRAIN
 }
 
-// DM3D_FMT_H2 weight rows W[n][256] -> operand fragments [pass n / 256][wave][record 16][column tile nr][hi | lo][lane][16 B]: one thread per 16-byte piece
-__global__ __launch_bounds__(256) void front_tile_weights_kernel(const char* __restrict__ src, char* __restrict__ dst, int n) {
-    const long total = (long)n * 256 * 4 / 16;
+// the one weight tiler (dm3d_frag.h: dm3d_tile_weights): one thread per 16-byte piece of the image
+__global__ __launch_bounds__(256) void tile_weights_kernel(const char* __restrict__ src, char* __restrict__ dst, long total, int pitch, int nr_tiles, int recs,
+                                                           int row_step, int rec_step) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         long q = i;
         const int lane = (int)(q & 63); q >>= 6;
         const int hilo = (int)(q & 1); q >>= 1;
-        const int nr = (int)(q & 1); q >>= 1;
-        const int rec = (int)(q & 15); q >>= 4;
+        const int nr = (int)(q % nr_tiles); q /= nr_tiles;
+        const int rec = (int)(q % recs); q /= recs;
         const int wave = (int)(q & 3); q >>= 2;
-        const int ps = (int)q;
-        const long off = (long)(ps * 256 + wave * 64 + nr * 32 + (lane & 31)) * 1024 + rec * 64 + ((lane >> 5) + 2 * hilo) * 16;
+        const long blk = q;
+        const long off = (blk * row_step + (wave * nr_tiles + nr) * 32 + (lane & 31)) * pitch + (blk * rec_step + rec) * 64 + ((lane >> 5) + 2 * hilo) * 16;
         *reinterpret_cast<f32x4*>(dst + i * 16) = *reinterpret_cast<const f32x4*>(src + off);
     }
 }
 
 }  // namespace
 
+int dm3d_tile_weights(const void* w_h2, void* tiled, long total, int pitch, int nr_tiles, int recs, int row_step, int rec_step, void* stream) {
+    const long blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(tile_weights_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const char*>(w_h2), static_cast<char*>(tiled), total, pitch, nr_tiles, recs, row_step, rec_step);
+    return dm3d_launch_check("tile_weights_kernel");
+}
+
 extern "C" int dm3d_pack_front_weights(const void* w_h2, int32_t n, int32_t units, void* tiled, void* stream) {
     DM3D_REQUIRE(w_h2 && tiled && dm3d_aligned16(w_h2) && dm3d_aligned16(tiled), "pack_front_weights: null or unaligned pointer");
     DM3D_REQUIRE(units == 256 && n > 0 && n % 256 == 0, "pack_front_weights: n=%d units=%d (units must be 256, n a multiple of 256)", n, units);
-    hipLaunchKernelGGL(front_tile_weights_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const char*>(w_h2),
-                       static_cast<char*>(tiled), n);
-    return dm3d_launch_check("front_tile_weights_kernel");
+    // [pass n / 256][wave][record 16][column tile nr][hi | lo][lane]: blocks of 256 rows, all 16 records of each
+    return dm3d_tile_weights(w_h2, tiled, (long)n * 64, 1024, 2, 16, 256, 0, stream);
 }
 
 extern "C" int dm3d_attn_front(const dm3d_attn_front_desc* d, void* stream) {

@@ -31,6 +31,7 @@
 // conv is bound by what the MFMA array draws on random data, not by its schedule; this kernel is kept because it is one loop for every
 // form (k3, parity, 4 / 8 slices, 16 / 32 / 64 columns) and because its work assignment halves the HBM traffic.
 #include "dm3d_conv_h3v2_parts.h"
+#include "dm3d_frag.h"
 
 using namespace h3v2;
 
@@ -265,13 +266,6 @@ __global__ __launch_bounds__(TD * 64, 2) void conv3d_igemm_h3v3(const ConvArgs p
                              : "=&v"(lo_addr) : "v"(addr), "v"(raw0[j]), "v"(raw1[j]) : "memory");
             }
         }
-    };
-    // raw barrier behind this wave's own LDS traffic: __syncthreads() would also drain the vector-memory counter, i.e. wait for the
-    // LDS-DMA fills that are meant to stay in flight across it
-    auto lds_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
     };
 
     // ---- prologue: the first chunk's image

@@ -61,6 +61,7 @@
 // reads less (the step loop below; nine-shape kernel sum -4.7 %, step 13.34 -> 13.04 ms: profiles/wino_fold_*.{csv,log}).
 #include <cstdlib>
 #include "dm3d_conv_h3v2_parts.h"
+#include "dm3d_frag.h"
 
 using namespace h3v2;
 
@@ -82,14 +83,6 @@ extern "C" int dm3d_debug_set_stamps_wino(void* p) { return (int)hipMemcpyToSymb
 #endif
 
 namespace {
-
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
-}
 
 // the chunk's executed passes: three per step, two per pad step (s % 5 == 3) — pass A of step s is number pass_of(s) of 56
 constexpr int pass_of(int s) { return 3 * s - (s + 1) / 5; }
@@ -351,12 +344,6 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_h3w(const ConvArgs p) {
 #undef DM3D_ST
             }
         }
-    };
-    // raw barrier behind this wave's own LDS traffic (never drains the vector-memory counter: the DMA fills stay in flight across it)
-    auto lds_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
     };
 
     // ---- prologue: the first chunk's image

@@ -11,20 +11,16 @@
 //   phase 1   H^T[128 x 64] = relu(W0[slab] . x^T + b0)    K = u:    wave w owns hidden columns 32w .. 32w+31 of the slab (1 x 2 MFMA tiles)
 //             -> split and stored to LDS as H2 records (the B operand of phase 2)
 //   phase 2   acc_out^T[u x 64] += W1[:, slab] . H^T        K = 128:  wave w owns output columns 64w .. 64w+63 (2 x 2 tiles, 64 registers)
-// Both products run transposed (weights = the MFMA's A operand): a lane holds groups of four consecutive COLUMNS of one row, so the hidden
-// slab is split two values per instruction and stored 8 bytes at a time, and the output leaves in 16-byte accesses.
-// Weights are PRE-TILED into operand fragments (dm3d_pack_mlp_weights, once per weight set): the 1 KB a wave needs for one (32-row tile,
-// 16-k record, hi | lo) are contiguous, lane-ordered.  Every wave consumes weights nobody else in the workgroup needs, so they do not pass
-// through LDS at all: plain coalesced 16-byte global loads (8 cache lines per instruction) straight into the fragment registers, one group
-// of records ahead of the MFMAs that use them.  (First form of this kernel: weights as DM3D_FMT_H2 rows through a ring of LDS granules by
-// LDS-DMA — 2 048 one-KB DMA instructions per workgroup at 100+ cycles of issue each, as long as the MFMAs themselves, plus a barrier per
-// granule: 78 us per block against 98 for the two GEMMs; in-kernel stamps put a granule at 1 900 cycles for 768 of MFMA.)
+// Both products are the transposed fragment-stream product of dm3d_frag.h (weight fragments, record layout, lane mapping): the hidden slab
+// is split two values per instruction and stored 8 bytes at a time, and the output leaves in 16-byte accesses.
+// (First form of this kernel: weights as DM3D_FMT_H2 rows through a ring of LDS granules by LDS-DMA — 2 048 one-KB DMA instructions per
+// workgroup at 100+ cycles of issue each, as long as the MFMAs themselves, plus a barrier per granule: 78 us per block against 98 for the
+// two GEMMs; in-kernel stamps put a granule at 1 900 cycles for 768 of MFMA.)
 // The only workgroup-wide synchronisation left is the hand-over of the H slab: two barriers per slab.
 // Optional tail (MlpArgs.w2): the block's proj_out — relu(W2 . a3 + b2) + the block input — as one more K = 256 product in the phase-2 form, with
 // the MLP's result a3 handed over through LDS instead of HBM (conditional_dm3d.py:195).
-#include "dm3d_h3.h"
+#include "dm3d_frag.h"
 #include <cstdlib>
-#include <type_traits>
 
 // Diagnostic build only (-DDM3D_MLP_STAMPS; the product library carries none of it): thread 0 of the first 256 workgroups writes s_memtime at
 // phase boundaries into a buffer of its own (tools/mlp_time.py stamps).
@@ -38,7 +34,6 @@ extern "C" int dm3d_debug_set_stamps_mlp(void* p) { return (int)hipMemcpyToSymbo
 
 namespace {
 
-
 struct MlpArgs {
     const void* x; long ldx;                    // [m][u] DM3D_FMT_H2 (ld in elements of 4 bytes)
     const void* w0; const float* b0;            // [4u][u] H2, [4u]
@@ -50,14 +45,6 @@ struct MlpArgs {
     const void* w2; const float* b2;            // optional tail: out = relu(W2 . a3 + b2) + res3 with a3 = the MLP's result (never stored)
     const float* res3; long ldr3;
 };
-
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
-}
 
 template <int U>
 __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
@@ -129,6 +116,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
 #define DM3D_MFMA_VV(acc, a, b) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b))
 #define DM3D_MFMA_DRAIN() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
+    auto mfma = [](f32x16& c, const h8& a, const h8& b) __attribute__((always_inline)) { DM3D_MFMA_VV(c, a, b); };
     f32x16 acc_out[2][2];                                       // [row tile mr][column tile nr]: lane = row 32 mr + l32, register r = column 32 nr + (r & 3) + 8 (r >> 2) + 4 half of the wave's 64
 #pragma unroll
     for (int mr = 0; mr < 2; ++mr)
@@ -137,29 +125,10 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc_out[mr][nr][r] = 0.0f;
 
-    // H fragment offsets (bytes): logical slot `half` (hi; lo: ^ 32) of this lane's row, swizzled by the row
-    unsigned a2_off[2];
+    unsigned a2_off[2];                                         // H fragment offsets of this lane's rows
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int ra = t * 32 + l32;
-        a2_off[t] = (unsigned)(ra * 64 + ((half ^ ((ra >> 2) & 3)) << 4));
-    }
+    for (int t = 0; t < 2; ++t) a2_off[t] = dm3d_frag_off(t * 32 + l32, half);
     const char* lds_hc = reinterpret_cast<const char*>(lds_h);
-    auto lds_barrier = [&]() {                                  // raw barrier behind this wave's own LDS traffic (the weight loads stay in flight across it)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    // hi = f16(x) (RNE), lo = f16(x - hi) of two values (dm3d_h3.h split8's instruction sequence)
-    auto split2 = [](float x0, float x1, unsigned int& hi, unsigned int& lo) {
-        float r0, r1;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x0), "v"(x1));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x0));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(x1));
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(r0), "v"(r1));
-    };
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
     // Groups of records: phase 1 in four groups of four records (8 fragment loads), phase 2 in four groups of two records (8 loads); the
     // loads of group g + 1 are issued in front of the MFMAs of group g (two register sets), those of a phase's first group during the
     // previous phase's last group: the stream never stops at a phase or slab boundary.  (Two groups of lead — three live sets — spilled
@@ -167,19 +136,10 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
     constexpr int G1 = 4, R1 = KR / G1, G2 = 4, R2 = HR / G2;
     h8 wa[2][8];                                                // two sets of 8 fragments
     auto load_p1 = [&](const int set, int slab, const int g) {  // W0 records 4g .. 4g+3 of the slab: [i][hi | lo]
-        const char* src = w0_lane + (size_t)(slab < NSLAB ? slab : NSLAB - 1) * W0_SLAB + (size_t)(g * R1) * 2048;
-#pragma unroll
-        for (int i = 0; i < R1; ++i) {
-            wa[set][2 * i] = *reinterpret_cast<const h8*>(src + i * 2048);
-            wa[set][2 * i + 1] = *reinterpret_cast<const h8*>(src + i * 2048 + 1024);
-        }
+        dm3d_load_group(wa[set], w0_lane + (size_t)(slab < NSLAB ? slab : NSLAB - 1) * W0_SLAB + (size_t)(g * R1) * 2048);
     };
     auto load_p2 = [&](const int set, int slab, const int g) {  // W1 records 2g, 2g+1 of the slab: [i][nr][hi | lo]
-        const char* src = w1_lane + (size_t)slab * W1_SLAB + (size_t)(g * R2) * 4096;
-#pragma unroll
-        for (int i = 0; i < R2; ++i)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) wa[set][4 * i + t] = *reinterpret_cast<const h8*>(src + i * 4096 + t * 1024);
+        dm3d_load_group(wa[set], w1_lane + (size_t)slab * W1_SLAB + (size_t)(g * R2) * 4096);
     };
     load_p1(0, 0, 0);
     MSTAMP(1);
@@ -229,8 +189,8 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = __builtin_amdgcn_fmed3f(acc_h[mr][4 * gq + j] + b0v[gq][j], 0.0f, 65504.0f);     // relu, and the float16 range
                     unsigned int h0, l0, h1, l1;
-                    split2(v[0], v[1], h0, l0);
-                    split2(v[2], v[3], h1, l1);
+                    dm3d_split2(v[0], v[1], h0, l0);
+                    dm3d_split2(v[2], v[3], h1, l1);
                     const u32x2 hi = {h0, h1}, lo = {l0, l1};
                     char* rec = reinterpret_cast<char*>(lds_h) + ((2 * wave + (gq >> 1)) * TM + row) * 64 + 8 * half;
                     *reinterpret_cast<u32x2*>(rec + (((gq & 1) ^ sw) << 4)) = hi;
@@ -255,13 +215,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
                     ah[t] = *reinterpret_cast<const h8*>(lds_hc + kk * (TM * 64) + a2_off[t]);
                     al[t] = *reinterpret_cast<const h8*>(lds_hc + kk * (TM * 64) + (a2_off[t] ^ 32u));
                 }
-                // pass-major over the four tiles; A = the W1 fragment (column tile nr: [nr][hi | lo]), B = the H fragment (row tile mr)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) DM3D_MFMA_VV(acc_out[t >> 1][t & 1], wa[set][4 * i + 2 * (t & 1)], al[t >> 1]);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) DM3D_MFMA_VV(acc_out[t >> 1][t & 1], wa[set][4 * i + 2 * (t & 1) + 1], ah[t >> 1]);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) DM3D_MFMA_VV(acc_out[t >> 1][t & 1], wa[set][4 * i + 2 * (t & 1)], ah[t >> 1]);
+                dm3d_kstep<2, false>(acc_out, &wa[set][4 * i], ah, al, mfma);
             }
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -305,8 +259,8 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
                     // the tail's B operand: this row's four columns as H2 into the LDS image [record][row][64 B] (record stride 4 KB + 32 B,
                     // slots XOR-swizzled by the row: dm3d_attn_front_h3.hip's layout).  Rows past m hold the last row's values: never stored.
                     unsigned int h0, l0, h1, l1;
-                    split2(__builtin_amdgcn_fmed3f(o[0], -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(o[1], -65504.0f, 65504.0f), h0, l0);
-                    split2(__builtin_amdgcn_fmed3f(o[2], -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(o[3], -65504.0f, 65504.0f), h1, l1);
+                    dm3d_split2(__builtin_amdgcn_fmed3f(o[0], -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(o[1], -65504.0f, 65504.0f), h0, l0);
+                    dm3d_split2(__builtin_amdgcn_fmed3f(o[2], -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(o[3], -65504.0f, 65504.0f), h1, l1);
                     const int r = mr * 32 + l32, sw = (r >> 2) & 3, slot = (n0 >> 3) & 1;
                     char* rp = reinterpret_cast<char*>(smem_m) + (n0 >> 4) * T_RS + r * 64 + (n0 & 7) * 2;
                     *reinterpret_cast<u32x2*>(rp + ((slot ^ sw) << 4)) = u32x2{h0, h1};
@@ -314,8 +268,8 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
                 } else if (row < p.m) {
                     if (p.out_h2) {
                         unsigned int h0, l0, h1, l1;
-                        split2(__builtin_amdgcn_fmed3f(o[0], -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(o[1], -65504.0f, 65504.0f), h0, l0);
-                        split2(__builtin_amdgcn_fmed3f(o[2], -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(o[3], -65504.0f, 65504.0f), h1, l1);
+                        dm3d_split2(__builtin_amdgcn_fmed3f(o[0], -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(o[1], -65504.0f, 65504.0f), h0, l0);
+                        dm3d_split2(__builtin_amdgcn_fmed3f(o[2], -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(o[3], -65504.0f, 65504.0f), h1, l1);
                         const u32x2 hi = {h0, h1}, lo = {l0, l1};
                         char* dst = static_cast<char*>(p.out) + (size_t)row * p.ldo * 4 + (n0 >> 4) * 64 + ((n0 >> 3) & 1) * 16 + (n0 & 7) * 2;
                         *reinterpret_cast<u32x2*>(dst) = hi;
@@ -332,8 +286,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
         lds_barrier();                                          // (every wave is past its last H read; the a3 image is complete)
         const char* w2_lane = static_cast<const char*>(p.w2) + (size_t)wave * (KR * 4 * 1024) + lane * 16;
         auto load_t = [&](const int set, const int g) {
-#pragma unroll
-            for (int t = 0; t < 8; ++t) wa[set][t] = *reinterpret_cast<const h8*>(w2_lane + (size_t)(g < KR / 2 ? g : KR / 2 - 1) * 8192 + t * 1024);
+            dm3d_load_group(wa[set], w2_lane + (size_t)(g < KR / 2 ? g : KR / 2 - 1) * 8192);
         };
         load_t(0, 0);
 #pragma unroll
@@ -355,12 +308,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
                     ah[t] = *reinterpret_cast<const h8*>(lds_hc + kk * T_RS + a2_off[t]);
                     al[t] = *reinterpret_cast<const h8*>(lds_hc + kk * T_RS + (a2_off[t] ^ 32u));
                 }
-#pragma unroll
-                for (int t = 0; t < 4; ++t) DM3D_MFMA_VV(acc_out[t >> 1][t & 1], wa[set][4 * i + 2 * (t & 1)], al[t >> 1]);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) DM3D_MFMA_VV(acc_out[t >> 1][t & 1], wa[set][4 * i + 2 * (t & 1) + 1], ah[t >> 1]);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) DM3D_MFMA_VV(acc_out[t >> 1][t & 1], wa[set][4 * i + 2 * (t & 1)], ah[t >> 1]);
+                dm3d_kstep<2, false>(acc_out, &wa[set][4 * i], ah, al, mfma);
             }
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -399,39 +347,15 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_h3(const MlpArgs p) {
     MSTAMP(15);
 }
 
-// DM3D_FMT_H2 weight rows -> operand fragments: one thread per 16-byte piece of the tiled image (layouts at the top of mlp_fused_h3)
-__global__ __launch_bounds__(256) void mlp_tile_weights_kernel(const char* __restrict__ src, char* __restrict__ dst, int units, int which) {
-    const int hid = 4 * units, kr = units / 16;
-    const long total = (long)units * hid * 4 / 16;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        long q = i;
-        const int lane = (int)(q & 63); q >>= 6;
-        const int hilo = (int)(q & 1); q >>= 1;
-        long off;
-        if (which == 0) {                   // W0 [hid][units]: [slab][wave][record kk][hi | lo][lane]
-            const int kk = (int)(q % kr); q /= kr;
-            const int wave = (int)(q & 3); q >>= 2;
-            const int slab = (int)q;
-            off = (long)(slab * 128 + wave * 32 + (lane & 31)) * (units * 4) + kk * 64 + ((lane >> 5) + 2 * hilo) * 16;
-        } else {                            // W1 [units][hid]: [slab][wave][record][nr][hi | lo][lane]
-            const int nr = (int)(q & 1); q >>= 1;
-            const int rec = (int)(q & 7); q >>= 3;
-            const int wave = (int)(q & 3); q >>= 2;
-            const int slab = (int)q;
-            off = (long)(wave * 64 + nr * 32 + (lane & 31)) * (hid * 4) + (long)(slab * 8 + rec) * 64 + ((lane >> 5) + 2 * hilo) * 16;
-        }
-        *reinterpret_cast<f32x4*>(dst + i * 16) = *reinterpret_cast<const f32x4*>(src + off);
-    }
-}
-
 }  // namespace
 
 extern "C" int dm3d_pack_mlp_weights(const void* w_h2, int32_t units, int32_t which, void* tiled, void* stream) {
     DM3D_REQUIRE(w_h2 && tiled && dm3d_aligned16(w_h2) && dm3d_aligned16(tiled), "pack_mlp_weights: null or unaligned pointer");
     DM3D_REQUIRE(units == 256 && (which == 0 || which == 1), "pack_mlp_weights: units=%d which=%d (units must be 256, which 0 | 1)", units, which);
-    hipLaunchKernelGGL(mlp_tile_weights_kernel, dim3(1024), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const char*>(w_h2),
-                       static_cast<char*>(tiled), units, which);
-    return dm3d_launch_check("mlp_tile_weights_kernel");
+    const long total = (long)units * 4 * units * 4 / 16;
+    // W0 [4u][u]: [slab][wave][record kk][hi | lo][lane], slabs of 128 rows;  W1 [u][4u]: [slab][wave][record][nr][hi | lo][lane], slabs of 8 records
+    return which == 0 ? dm3d_tile_weights(w_h2, tiled, total, units * 4, 1, units / 16, 128, 0, stream)
+                      : dm3d_tile_weights(w_h2, tiled, total, units * 16, 2, 8, 0, 8, stream);
 }
 
 extern "C" int dm3d_mlp_fused(const dm3d_mlp_desc* d, void* stream) {
