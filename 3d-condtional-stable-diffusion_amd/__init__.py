@@ -7,7 +7,7 @@ from .betas import Betas, time_embedding_table
 from .weights import UNetConfig, kernel_init, keras_init_weights, param_spec, synthetic_weights
 
 __all__ = ["Betas", "time_embedding_table", "UNetConfig", "kernel_init", "keras_init_weights", "param_spec",
-           "synthetic_weights", "UNet", "DiffusionModel", "UnconditionalDiffusionModel"]
+           "synthetic_weights", "UNet", "DiffusionModel", "UnconditionalDiffusionModel", "metrics"]
 
 
 def __getattr__(name):          # torch / the HIP library are only needed by the device classes
@@ -17,4 +17,7 @@ def __getattr__(name):          # torch / the HIP library are only needed by the
     if name in ("DiffusionModel", "UnconditionalDiffusionModel"):
         from . import diffusion
         return getattr(diffusion, name)
+    if name == "metrics":
+        import importlib
+        return importlib.import_module(".metrics", __name__)
     raise AttributeError(name)

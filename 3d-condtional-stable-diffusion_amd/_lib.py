@@ -174,9 +174,20 @@ class GradScaleDesc(C.Structure):
     _fields_ = [("g", _f32p), ("n", C.c_int64), ("partials", C.c_void_p), ("state", _f32p), ("clip_norm", C.c_float), ("pre_scale", C.c_float)]
 
 
+class MetricDesc(C.Structure):
+    _fields_ = [
+        ("x", _f32p), ("y", _f32p), ("batch", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("cx", C.c_int32), ("cy", C.c_int32), ("x0c", C.c_int32), ("y0c", C.c_int32), ("nc", C.c_int32),
+        ("partials", C.c_void_p), ("partials_elems", C.c_int64), ("y_min", _f32p), ("y_max", _f32p), ("y_range", _f32p),
+        ("sse", C.c_void_p), ("max_val", _f32p), ("out", _f32p),
+    ]
+
+
 GUIDE_PARTIAL_BLOCKS = 256          # DM3D_GUIDE_PARTIAL_BLOCKS: GuideDesc.partials holds [batch][256][4] doubles
 LOSS_PARTIAL_BLOCKS = 64            # DM3D_LOSS_PARTIAL_BLOCKS: LossDesc.partials holds [batch][64] doubles
 GRADNORM_PARTIAL_BLOCKS = 1024      # DM3D_GRADNORM_PARTIAL_BLOCKS: GradScaleDesc.partials holds [1024] doubles
+PAIR_PARTIAL_BLOCKS = 64            # DM3D_PAIR_PARTIAL_BLOCKS: dm3d_pair_stats runs min(ceil(h*w / 4096), 64) blocks a slice
+SSIM_TILE = 32                      # DM3D_SSIM_TILE: dm3d_ssim leaves one partial per 32 x 32 tile of outputs
 
 # name -> (restype, argtypes): every symbol include/dm3d.h declares
 SIGNATURES = {
@@ -241,6 +252,9 @@ SIGNATURES = {
     "dm3d_guide_update": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p]),
     "dm3d_pred_to_eps": (C.c_int, [C.POINTER(PredDesc), C.c_void_p]),
     "dm3d_objective_loss_grad": (C.c_int, [C.POINTER(LossDesc), C.c_void_p]),
+    "dm3d_pair_stats": (C.c_int, [C.POINTER(MetricDesc), C.c_void_p]),
+    "dm3d_ssim": (C.c_int, [C.POINTER(MetricDesc), C.c_void_p]),
+    "dm3d_psnr_finalize": (C.c_int, [C.POINTER(MetricDesc), C.c_void_p]),
     "dm3d_range_check": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "dm3d_add_i32": (C.c_int, [_i32p, C.c_int32, C.c_int32, C.c_void_p]),
     "dm3d_randn": (C.c_int, [_f32p, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p]),

@@ -15,7 +15,8 @@ What differs from ``networks/vqvae3d_monai.py`` (the autoencoder DiffusionModel 
   Decoder level (:429-467)   n x VQVAEResidualUnit -> Conv3DTranspose k4/s2 -> BatchNormalization [-> PReLU unless last]
                              8 parity 2x2x2 convs on the input grid with the norm folded into the transposed kernel
   VQVAEResidualUnit (:257-284), VectorQuantizer (:151-216): as in vqvae3d_monai.py
-Dropout layers are the identity at inference.  The GAN half (discriminators, LPIPS, train_step) is out of scope.
+Dropout layers are the identity at inference.  The GAN half (discriminators, LPIPS, train_step) is out of scope (SURVEY.md §2 A2);
+``test_step`` / ``evaluate`` report the part of the reference's evaluation that needs neither (reconst_loss, quantize_loss, ssim, psnr).
 """
 from __future__ import annotations
 
@@ -59,6 +60,8 @@ def vqgan_param_spec(in_channels, out_channels, num_channels, num_res_layers, nu
 
 
 class VQGAN(VQVAE):
+    METRIC_KEYS = ("reconst_loss", "quantize_loss", "ssim", "psnr")
+
     def __init__(self, in_channels, out_channels, num_channels, num_res_layers, num_res_channels,
                  downsample_parameters=((2, 4, 1, 1), (2, 4, 1, 1), (2, 4, 1, 1)),
                  upsample_parameters=((2, 4, 1, 1, 0), (2, 4, 1, 1, 0), (2, 4, 1, 1, 0)),
@@ -155,6 +158,15 @@ class VQGAN(VQVAE):
         """``x = tf.concat([img, mask], axis=-1)`` (train_step, vqgan.py:726-727) -> encoder."""
         img, mask = torch.as_tensor(img, dtype=torch.float32).to(self.device), torch.as_tensor(mask, dtype=torch.float32).to(self.device)
         return self._encode(torch.cat([img, mask], dim=-1).contiguous())
+
+    def test_step(self, data):
+        """VQGAN.test_step (vqgan.py:821-919) on ``data = (img, mask, _)``, as ``VQVAE.test_step``: the running means of
+        ``reconst_loss``, ``quantize_loss``, ``ssim`` and ``psnr`` as 0-d device tensors.
+
+        Omitted keys: the reference also returns ``loss``, ``gen_loss``, ``gen_feat_loss``, ``disc_loss`` and ``perceptual_loss``.  All
+        five need the 3-D and 2-D discriminators or the LPIPS network (``loss`` sums the perceptual and adversarial terms), which this
+        project does not carry (the GAN half is out of scope), so they are left out rather than given made-up values."""
+        return self._test_step(data)
 
     def call_2(self, x):
         """vqgan.py:705-709: the quantised latents."""

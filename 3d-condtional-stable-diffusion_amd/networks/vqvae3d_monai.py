@@ -13,7 +13,9 @@ device tensors.  Every layer runs on the dm3d HIP kernels (no fallback):
   VectorQuantizer.get_code_indices + lookup (:140-177) -> float32 GEMM z.E, dm3d_vq_assign, dm3d_gather_rows
 
 Keras' ``PReLU()`` has a full-shape slope ``[D,H,W,C]``, which ties the reference model to 128^3 inputs; here the spatial size
-is the keyword ``input_size`` (default 128).  Training (``train_step``, losses, codebook replacement) is out of scope.
+is the keyword ``input_size`` (default 128).  Training (``train_step``, codebook replacement) is out of scope; evaluation is here:
+``test_step`` / ``evaluate`` report ``reconst_loss``, ``quantize_loss``, ``ssim`` and ``psnr`` as the reference's ``test_step`` (:504-544)
+does, through the fused metric kernels (``dm3d_amd.metrics``).
 """
 from __future__ import annotations
 
@@ -24,8 +26,10 @@ import numpy as np
 import torch
 
 from .. import _lib, ops
+from ..metrics import Mean
 
 BN_EPS = 1e-3
+VQ_BETA = 0.25          # VectorQuantizer(beta=0.25) (:113): the weight of the commitment term in its loss
 
 
 def vqvae_param_spec(in_channels, out_channels, num_channels, num_res_layers, num_res_channels, num_embeddings,
@@ -92,6 +96,8 @@ class _Layer:
 
 
 class VQVAE:
+    METRIC_KEYS = ("loss", "reconst_loss", "quantize_loss", "ssim", "psnr")      # what test_step returns, in the reference's order
+
     def __init__(self, in_channels, out_channels, num_channels, num_res_layers, num_res_channels,
                  downsample_parameters=((2, 4, 1, 1), (2, 4, 1, 1), (2, 4, 1, 1)),
                  upsample_parameters=((2, 4, 1, 1, 0), (2, 4, 1, 1, 0), (2, 4, 1, 1, 0)),
@@ -120,6 +126,8 @@ class VQVAE:
         self._prepared = False
         self.load_state_dict(weights if weights is not None else keras_init_vqvae_weights(self.spec, seed))
         self.encoder, self.quantizer, self.decoder = self._encode, self._quantize, self._decode
+        self._last_pair = None
+        self._trackers = {k: Mean(k) for k in self.METRIC_KEYS}
 
     # ---- weights ---------------------------------------------------------------------------------------------------
     def load_state_dict(self, sd, strict=True):
@@ -264,7 +272,20 @@ class VQVAE:
         probs = torch.bincount(idx.long(), minlength=self.num_embeddings).float() / idx.numel()
         perplexity = torch.exp(-(probs * torch.log(probs + 1e-10)).sum())
         self.last_indices = idx
+        self._last_pair = (q, z)                     # what last_loss is computed from, when somebody asks
         return q, perplexity
+
+    @property
+    def last_loss(self):
+        """The loss the reference's VectorQuantizer adds in ``call`` (:150-153), forward value, of the latest ``quantizer`` call:
+        beta*mean((sg(q) - z)^2) + mean((q - sg(z))^2) = (1 + beta) * mean((q - z)^2), a 0-d float64 device tensor.  Computed when it
+        is asked for (one pass of dm3d_pair_stats over the two latents), so a ``quantizer`` call costs what it did."""
+        if self._last_pair is None:
+            raise RuntimeError("last_loss: the quantizer has not been called yet")
+        q, z = self._last_pair
+        B, n = z.shape[0], z.numel() // z.shape[0]
+        sse = ops.pair_stats(q.reshape(B, 1, 1, n, 1), z.reshape(B, 1, 1, n, 1)).sse
+        return (1.0 + VQ_BETA) * sse.sum() / z.numel()
 
     def _decode(self, z):
         """Decoder.call (:388-391)."""
@@ -285,3 +306,56 @@ class VQVAE:
         """VQVAE.call (:453-457): (decoder(quantizer(encoder(x))), perplexity)."""
         q, perplexity = self._quantize(self._encode(x))
         return self._decode(q), perplexity
+
+    # ---- evaluation ------------------------------------------------------------------------------------------------
+    @property
+    def metrics(self):
+        """The running means behind ``test_step``'s results (keras ``Model.metrics``), in ``METRIC_KEYS`` order."""
+        return list(self._trackers.values())
+
+    def reset_metrics(self):
+        for m in self._trackers.values():
+            m.reset_state()
+
+    def _test_values(self, data):
+        """One batch through the model and the metric kernels: {key: device tensor} of everything ``test_step`` tracks (:504-536)."""
+        img, mask, _ = data
+        img = torch.as_tensor(img, dtype=torch.float32).to(self.device).contiguous()
+        mask = torch.as_tensor(mask, dtype=torch.float32).to(self.device)
+        recon, _ = self(torch.cat([img, mask], dim=-1).contiguous())
+        ci = img.shape[-1]
+        if ci > recon.shape[-1]:
+            raise ValueError(f"the image has {ci} channels, the reconstruction {recon.shape[-1]}")
+        # tf.split(reconstructions, 2, axis=-1)[0]: the leading channels of the reconstruction, read in place
+        ch = dict(x_channels=(0, ci), y_channels=(0, ci))
+        stats = ops.pair_stats(img, recon, **ch)
+        return {"reconst_loss": stats.sse.sum() / img.numel(), "quantize_loss": self.last_loss,
+                "ssim": ops.ssim(img, recon, stats=stats, **ch).double().mean(), "psnr": ops.psnr(img, recon, stats=stats, **ch)}
+
+    def _test_step(self, data):
+        values = self._test_values(data)
+        if "loss" in self.METRIC_KEYS:               # :515-516; VQGAN's loss has terms this project does not carry
+            values["loss"] = (values["reconst_loss"] + values["quantize_loss"]) / self.num_gpus
+        for k in self.METRIC_KEYS:
+            self._trackers[k].update_state(values[k])
+        return {k: self._trackers[k].result() for k in self.METRIC_KEYS}
+
+    def test_step(self, data):
+        """VQVAE.test_step (:504-544) on ``data = (img, mask, _)``: ``x = concat([img, mask], -1)`` through the model, then
+        reconst_loss = mean((img - img_recon)^2), quantize_loss = the quantizer's loss (``last_loss``), loss = their sum / num_gpus,
+        ssim = the mean of tf.image.ssim over the [B, D] slices and psnr = tf.image.psnr per slice, both with the reference's
+        max_val = max(img_recon) - min(img_recon) per volume.  Returns the running means since ``reset_metrics`` as 0-d device tensors
+        (psnr weighted by its B*D values, the others one value a batch, as keras.metrics.Mean counts); nothing synchronises."""
+        return self._test_step(data)
+
+    def evaluate(self, batches):
+        """``reset_metrics``, ``test_step`` over an iterable of ``(img, mask, _)``, then the results as Python floats: the one
+        synchronisation is the read-back at the end."""
+        self.reset_metrics()
+        out = None
+        for data in batches:
+            out = self.test_step(data)
+        if out is None:
+            return {k: 0.0 for k in self.METRIC_KEYS}
+        host = torch.stack([out[k] for k in self.METRIC_KEYS]).cpu().tolist()
+        return dict(zip(self.METRIC_KEYS, host))

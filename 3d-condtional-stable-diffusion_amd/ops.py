@@ -7,7 +7,7 @@ call the HIP kernels; there is no fallback implementation.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -412,4 +412,96 @@ def mlp_fused(x_h2: torch.Tensor, w0_t: torch.Tensor, b0: torch.Tensor, w1_t: to
         w2_t, b2, res3 = tail
         d.w2, d.b2, d.res3, d.ldr3 = w2_t.data_ptr(), b2.data_ptr(), _p(res3), units
     check(lib().dm3d_mlp_fused(C.byref(d), _st()), "mlp_fused")
+    return out
+
+
+# ---- autoencoder evaluation (include/dm3d.h, dm3d_metric_desc): per-slice squared error, SSIM and PSNR of a reconstruction -------------
+class PairStats(NamedTuple):
+    """What dm3d_pair_stats leaves on the device: per volume min, max and max - min of the compared channels of y (float32 [B]), per depth
+    slice the float64 sum of squared differences over H x W x channels ([B, D])."""
+    y_min: torch.Tensor
+    y_max: torch.Tensor
+    y_range: torch.Tensor
+    sse: torch.Tensor
+
+
+def _metric_desc(x, y, x_channels, y_channels):
+    """The descriptor of a pair of NDHWC tensors; ``*_channels = (first, count)`` selects a channel window read in place (default: all)."""
+    _f32c(x, "x"), _f32c(y, "y")
+    if x.dim() != 5 or y.dim() != 5 or x.shape[:4] != y.shape[:4]:
+        raise ValueError(f"x and y must be [B,D,H,W,C] with the same batch and spatial shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    x0c, ncx = (0, x.shape[4]) if x_channels is None else x_channels
+    y0c, ncy = (0, y.shape[4]) if y_channels is None else y_channels
+    if ncx != ncy:
+        raise ValueError(f"x contributes {ncx} channels and y {ncy}: the same number must be compared")
+    d = _lib.MetricDesc()
+    d.x, d.y = x.data_ptr(), y.data_ptr()
+    d.batch, d.d, d.h, d.w = x.shape[:4]
+    d.cx, d.cy, d.x0c, d.y0c, d.nc = x.shape[4], y.shape[4], x0c, y0c, ncx
+    return d
+
+
+def _metric_partials(d, elems: int, device) -> torch.Tensor:
+    buf = torch.empty(max(1, elems), dtype=torch.float64, device=device)       # alive until the launches are enqueued (same stream)
+    d.partials, d.partials_elems = buf.data_ptr(), buf.numel()
+    return buf
+
+
+def pair_stats(x: torch.Tensor, y: torch.Tensor, *, x_channels=None, y_channels=None) -> PairStats:
+    """One pass over the truth ``x`` and the reconstruction ``y`` (NDHWC float32, channel counts may differ): ``PairStats``.  With a
+    tensor viewed as [B, 1, 1, n, 1] the one "slice" is the flattened extent: sse / n is a plain mean squared error per sample."""
+    d = _metric_desc(x, y, x_channels, y_channels)
+    B, D = d.batch, d.d
+    blocks = min(-(-(d.h * d.w) // 4096), _lib.PAIR_PARTIAL_BLOCKS)
+    buf = _metric_partials(d, 3 * B * D * blocks, x.device)
+    mm = torch.empty(3, B, dtype=torch.float32, device=x.device)
+    sse = torch.empty(B, D, dtype=torch.float64, device=x.device)
+    d.y_min, d.y_max, d.y_range, d.sse = mm[0].data_ptr(), mm[1].data_ptr(), mm[2].data_ptr(), sse.data_ptr()
+    check(lib().dm3d_pair_stats(C.byref(d), _st()), "pair_stats")
+    del buf
+    return PairStats(mm[0], mm[1], mm[2], sse)
+
+
+def _max_val(max_val, stats, x, y, x_channels, y_channels) -> torch.Tensor:
+    """The device table of one float per volume both metrics read: the caller's value, or the reference's choice max(y) - min(y)."""
+    B = x.shape[0]
+    if max_val is None:
+        return (stats if stats is not None else pair_stats(x, y, x_channels=x_channels, y_channels=y_channels)).y_range
+    if isinstance(max_val, torch.Tensor):
+        t = max_val.to(device=x.device, dtype=torch.float32).reshape(-1)
+        t = t.expand(B) if t.numel() == 1 else t
+        if t.numel() != B:
+            raise ValueError(f"max_val must hold one value, or one per volume ({B}), got {t.numel()}")
+        return t.contiguous()
+    return torch.full((B,), float(max_val), dtype=torch.float32, device=x.device)
+
+
+def ssim(x: torch.Tensor, y: torch.Tensor, max_val=None, *, x_channels=None, y_channels=None, stats: Optional[PairStats] = None) -> torch.Tensor:
+    """tf.image.ssim(x[b], y[b], max_val) for every volume b, TensorFlow's defaults: float32 [B, D], one score per depth slice (the last
+    three axes of a volume are the image).  ``max_val``: a number, a tensor of one value or one per volume, or None for the reference's
+    max(y) - min(y) per volume (taken from ``stats``, a ``pair_stats`` of the same pair, or from a pass of its own; the value goes
+    from that kernel to this one on the device).  A volume whose max_val is 0 scores NaN, as in TensorFlow."""
+    d = _metric_desc(x, y, x_channels, y_channels)
+    if d.h < 11 or d.w < 11:
+        raise ValueError(f"ssim needs H and W of at least 11 (the 11 x 11 window), got {d.h} x {d.w}")
+    mv = _max_val(max_val, stats, x, y, x_channels, y_channels)
+    tiles = -(-(d.h - 10) // _lib.SSIM_TILE) * -(-(d.w - 10) // _lib.SSIM_TILE)
+    buf = _metric_partials(d, d.batch * d.d * d.nc * tiles, x.device)
+    out = torch.empty(d.batch, d.d, dtype=torch.float32, device=x.device)
+    d.max_val, d.out = mv.data_ptr(), out.data_ptr()
+    check(lib().dm3d_ssim(C.byref(d), _st()), "ssim")
+    del buf
+    return out
+
+
+def psnr(x: torch.Tensor, y: torch.Tensor, max_val=None, *, x_channels=None, y_channels=None, stats: Optional[PairStats] = None) -> torch.Tensor:
+    """tf.image.psnr(x[b], y[b], max_val) for every volume b: float32 [B, D], 20 log10(max_val) - 10 log10(mse) per depth slice; +inf where
+    a slice is reconstructed exactly.  ``max_val`` and ``stats`` as in ``ssim``."""
+    d = _metric_desc(x, y, x_channels, y_channels)
+    if stats is None:
+        stats = pair_stats(x, y, x_channels=x_channels, y_channels=y_channels)
+    mv = _max_val(max_val, stats, x, y, x_channels, y_channels)
+    out = torch.empty(d.batch, d.d, dtype=torch.float32, device=x.device)
+    d.sse, d.max_val, d.out = stats.sse.data_ptr(), mv.data_ptr(), out.data_ptr()
+    check(lib().dm3d_psnr_finalize(C.byref(d), _st()), "psnr_finalize")
     return out

@@ -727,6 +727,61 @@ typedef struct dm3d_loss_desc {
 } dm3d_loss_desc;
 int dm3d_objective_loss_grad(const dm3d_loss_desc* d, void* stream);
 
+/* ---- Autoencoder evaluation (VQVAE.test_step, vqvae3d_monai.py:504-544; VQGAN.test_step, vqgan.py:821-919): how well y reconstructs x.
+ * x (the truth) and y (the reconstruction) are NDHWC float32 [batch, d, h, w, cx] and [batch, d, h, w, cy]; the nc channels x0c.. of x
+ * are compared with the nc channels y0c.. of y, read in place (the image half of a 2-channel reconstruction needs no split copy).
+ * Every depth slice (b, z) is one 2-D image of nc channels, as tf.image.ssim / tf.image.psnr see a volume [d, h, w, c].  Everything
+ * stays on the device: no entry reads back or synchronises.  Sums are float64 in a fixed order (a block by the tree every fixed-order
+ * reduction here shares, blocks through `partials` in block order by a second launch, no atomics): runs repeat bitwise.
+ *
+ * dm3d_pair_stats   one streaming pass, grid (P, d, batch) with P = min(ceil(h*w / 4096), DM3D_PAIR_PARTIAL_BLOCKS):
+ *     sse[b*d + z]  = sum over h, w, nc of ((double)x - (double)y)^2          (a float32 difference is exact in float64)
+ *     y_min[b], y_max[b] = min / max of the compared channels of y over the volume (exact, order-free: bitwise), and
+ *     y_range[b] = y_max[b] - y_min[b] (float32; NULL: not wanted), the max_val the reference hands to both metrics.
+ *   With d = h = 1 and w = the flattened extent the same entry gives the quantizer's sum (q - z)^2.  A NaN in y is skipped by min and
+ *   max (fminf / fmaxf) and reaches sse.  partials: 3 * batch * d * P doubles.
+ *
+ * dm3d_ssim   tf.image.ssim with its defaults (11 x 11 Gaussian window of sigma 1.5, k1 0.01, k2 0.03), one value per slice:
+ *     g[i] = exp(-(i - 5)^2 / 4.5) / sum, rounded to float32; the window is g (x) g, applied separably, VALID: (h - 10) x (w - 10) outputs
+ *     L = max_val[b];  c1 = (0.01f L)^2;  c2 = (0.03f L)^2
+ *     mx = F(x), my = F(y), sxy = F(x*y), sq = F(x*x + y*y)       float32; F: the row pass, then the column pass, each
+ *                                                                  acc = fma(g[i], v[i], acc) from acc = 0 for i = 0..10
+ *     n0 = (mx*my)*2;  d0 = mx*mx + my*my;  lum = (n0 + c1) / (d0 + c1);  cs = ((sxy*2 - n0) + c2) / ((sq - d0) + c2)
+ *     out[b*d + z] = (float)(mean over channels of (sum over outputs of (double)(lum*cs)) / ((h - 10)(w - 10)))
+ *   A workgroup owns a DM3D_SSIM_TILE^2 tile of outputs of one (b, z, channel): it stages the (TILE + 10)^2 halo of x and y in LDS once,
+ *   runs the row pass into LDS, the column pass in registers, and leaves one float64 partial; a second launch adds each slice's
+ *   partials in (channel, tile) order.  partials: batch * d * nc * ceil((h-10)/TILE) * ceil((w-10)/TILE) doubles.
+ *   max_val[b] = 0 (a constant y under the reference's choice) yields what the formula yields, 0/0 = NaN, as TensorFlow does.
+ *
+ * dm3d_psnr_finalize   tf.image.psnr from dm3d_pair_stats' sse:  mse = (float)(sse / (h*w*nc));
+ *     out[b*d + z] = (float)(20 log10 L) - (float)(10 log10 mse)   with L = max_val[b]: each term rounded to float32 once, one float32
+ *   subtraction.  mse = 0 gives +inf.
+ *
+ * Checked before any launch (DM3D_EINVAL): the descriptor and every pointer the entry reads or writes non-NULL (y_range may be NULL);
+ * batch, d in [1, 65535], h, w >= 1 (dm3d_ssim: >= 11); nc >= 1, x0c >= 0, y0c >= 0, x0c + nc <= cx, y0c + nc <= cy;
+ * partials_elems at least what the entry needs; float64 buffers 8-byte aligned. */
+#define DM3D_PAIR_PARTIAL_BLOCKS 64
+#define DM3D_SSIM_TILE 32
+typedef struct dm3d_metric_desc {
+    const float* x;             /* [batch, d, h, w, cx] the truth */
+    const float* y;             /* [batch, d, h, w, cy] the reconstruction */
+    int32_t batch, d, h, w;
+    int32_t cx, cy;             /* channel counts of the two tensors */
+    int32_t x0c, y0c;           /* first channel read of each */
+    int32_t nc;                 /* channels compared */
+    double* partials;           /* device scratch, written before it is read by every call */
+    int64_t partials_elems;     /* doubles it holds */
+    float* y_min;               /* [batch]      pair_stats: out */
+    float* y_max;               /* [batch]      pair_stats: out */
+    float* y_range;             /* [batch]      pair_stats: out, optional */
+    double* sse;                /* [batch * d]  pair_stats: out; psnr_finalize: in */
+    const float* max_val;       /* [batch]      ssim, psnr_finalize: in */
+    float* out;                 /* [batch * d]  ssim, psnr_finalize: out */
+} dm3d_metric_desc;
+int dm3d_pair_stats(const dm3d_metric_desc* d, void* stream);
+int dm3d_ssim(const dm3d_metric_desc* d, void* stream);
+int dm3d_psnr_finalize(const dm3d_metric_desc* d, void* stream);
+
 /* p[i] = max(p[i] + delta, 0) (the loop counter of generate kept on the device so a captured step replays unchanged; it
  * saturates at 0, so a step issued past the end of a chain never indexes row -1 of a table). */
 int dm3d_add_i32(int32_t* p, int32_t n, int32_t delta, void* stream);
