@@ -287,12 +287,15 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
     }
 }
 
-// ---- GroupNormalization statistics: per-(sample, channel) sum and sum of squares, float32 partials per thread, float64 atomics
+// ---- GroupNormalization statistics: per-(sample, channel) sum and sum of squares, float64 from the first addition on (per-thread sums,
+// LDS fold, atomics).  A float32 chain of x*x loses |mean|/std squared times 2^-24 of the variance it is subtracted into:
+// this kernel feeds every BatchNormalization of a training step, whose inputs nobody centres.  It reads 16 bytes per 8 float64 operations
+// and stays memory-bound.
 __global__ __launch_bounds__(256) void groupnorm_stats_kernel(const float* __restrict__ x, long voxels, int c, double* __restrict__ acc,
                                                               int c_total, int chan_off) {
     // grid: (voxel slabs, batch).  Thread -> channel quad q = tid % (c/4) (clamped), voxel lane vl = tid / (c/4); every
     // thread owns the same 4 channels for all its voxels, so sums stay in registers; LDS reduces threads sharing a quad.
-    extern __shared__ float sred[];             // [256][8]
+    extern __shared__ double sred[];            // [256][8]
     const int c4 = c >> 2;
     const int tid = threadIdx.x, b = blockIdx.y;
     const int lanes_per_vox = c4 < 256 ? c4 : 256;            // quads handled per pass
@@ -301,12 +304,12 @@ __global__ __launch_bounds__(256) void groupnorm_stats_kernel(const float* __res
     const long slab = (voxels + gridDim.x - 1) / gridDim.x;
     const long v0 = (long)blockIdx.x * slab, v1 = v0 + slab < voxels ? v0 + slab : voxels;
     for (int q = q0; q < c4; q += lanes_per_vox) {            // c > 1024 loops
-        f32x4 s = {0.f, 0.f, 0.f, 0.f}, ss = s;
+        double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
         if (vl < vox_par) {
             for (long v = v0 + vl; v < v1; v += vox_par) {
                 const f32x4 t = *reinterpret_cast<const f32x4*>(x + ((size_t)b * voxels + v) * c + q * 4);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { s[e] += t[e]; ss[e] += t[e] * t[e]; }
+                for (int e = 0; e < 4; ++e) { const double d = (double)t[e]; s[e] += d; ss[e] = fma(d, d, ss[e]); }
             }
         }
 #pragma unroll
@@ -747,7 +750,7 @@ extern "C" int dm3d_groupnorm_stats(const float* x, int32_t batch, int64_t voxel
     const int c4 = c / 4, lanes = c4 < 256 ? c4 : 256;
     long slabs = voxels / (256 / lanes * 16);                // >= 16 voxels per thread
     slabs = slabs < 1 ? 1 : (slabs > 64 ? 64 : slabs);
-    hipLaunchKernelGGL(groupnorm_stats_kernel, dim3((unsigned)slabs, (unsigned)batch), dim3(256), 256 * 8 * sizeof(float),
+    hipLaunchKernelGGL(groupnorm_stats_kernel, dim3((unsigned)slabs, (unsigned)batch), dim3(256), 256 * 8 * sizeof(double),
                        static_cast<hipStream_t>(stream), x, (long)voxels, c, acc, c_total, chan_off);
     return dm3d_launch_check("groupnorm_stats_kernel");
 }

@@ -339,7 +339,8 @@ int dm3d_groupnorm_finalize(double* acc, int32_t batch, int64_t voxels, int32_t 
 /* the same from per-TENSOR partial statistics of up to two concatenated inputs: part [batch][slots][c][2] float32, slots = ceil(voxels / 64),
  * each slot the (sum, sum of squares) of its voxels per channel — what dm3d_conv_desc.gn_stats or dm3d_groupnorm_partials left there.
  * Float64 sums over the slots in a fixed order (no atomics anywhere on this path); nothing is cleared: a tensor with several consumers is
- * summed once. */
+ * summed once.  The slots themselves are float32: the error of scale / shift grows with (|mean| / std)^2 of a group, along the measured curve
+ * of DESIGN section 7 (dm3d_groupnorm_stats sums in float64 from the first addition on and has no such curve). */
 int64_t dm3d_groupnorm_partials_bytes(int32_t batch, int64_t voxels, int32_t c);
 int dm3d_groupnorm_partials(const float* x, int32_t batch, int64_t voxels, int32_t c, float* part, void* stream);
 int dm3d_groupnorm_finalize2(const float* part1, int32_t c1, const float* part2, int32_t c2, int32_t batch, int64_t voxels, int32_t groups,
