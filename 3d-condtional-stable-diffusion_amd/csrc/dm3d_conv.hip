@@ -478,22 +478,6 @@ extern "C" int dm3d_conv3d_ndhwc(const dm3d_conv_desc* d, void* stream) {
     return dm3d_groupnorm_partials(r.a.out, r.a.batch, (int64_t)r.a.fd * r.a.fh * r.a.fw, r.a.cout, r.a.gn_stats, stream);
 }
 
-extern "C" int64_t dm3d_packed_weight_skip_h3p_bytes(int32_t cin, int32_t cout) {
-    return (cin > 0 && cout > 0) ? dm3d_h3v2_skip_image_bytes(cin, cout) : 0;
-}
-
-extern "C" int dm3d_pack_weights_skip_h3p(const float* keras_kernel, int32_t cin, int32_t cout, int32_t w_exp, void* packed, void* stream) {
-    DM3D_REQUIRE(keras_kernel && packed && cin > 0 && cout > 0, "pack_weights_skip_h3p: bad arguments");
-    DM3D_REQUIRE(w_exp >= -100 && w_exp <= 100 && dm3d_aligned16(packed), "pack_weights_skip_h3p: w_exp out of range or packed unaligned");
-    return dm3d_pack_skip_h3v2(keras_kernel, cin, cout, w_exp, packed, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int dm3d_pack_weights_skip_h3f(const float* keras_kernel, int32_t cin, int32_t cout, int32_t w_exp, void* packed, void* stream) {
-    DM3D_REQUIRE(keras_kernel && packed && cin > 0 && cout > 0, "pack_weights_skip_h3f: bad arguments");
-    DM3D_REQUIRE(w_exp >= -100 && w_exp <= 100 && dm3d_aligned16(packed), "pack_weights_skip_h3f: w_exp out of range or packed unaligned");
-    return dm3d_pack_skip_h3f(keras_kernel, cin, cout, w_exp, packed, static_cast<hipStream_t>(stream));
-}
-
 extern "C" int32_t dm3d_conv_tile_form(const dm3d_conv_desc* d) {
     const ConvLaunch r = dm3d_conv_resolve(d);
     return r.family == DM3D_CONV_FAM_WINO ? 10 : (r.family == DM3D_CONV_FAM_V3 ? r.td : 0);
@@ -508,33 +492,6 @@ extern "C" int32_t dm3d_conv_weight_layout(int32_t ksize, int32_t stride, int32_
     if (conv_knobs().pair_off) return DM3D_WL_TAP;
     if (upsample || transpose) return DM3D_WL_PAIR;
     return (ksize == 3 && stride == 1) ? DM3D_WL_PAIR : DM3D_WL_TAP;     // (round 3: also Cout <= 32, the narrow column forms of the 16x16x32 kernel)
-}
-
-extern "C" int64_t dm3d_packed_weight_h3p_bytes(int32_t taps, int32_t cin, int32_t cout) {
-    if (taps <= 0 || cin <= 0 || cout <= 0) return 0;
-    return dm3d_h3v2_image_bytes(taps, cin, cout);
-}
-
-extern "C" int dm3d_pack_weights_h3p(const float* keras_kernel, int32_t taps, int32_t cin, int32_t cout, int32_t w_exp,
-                                     const float* in_scale, void* packed, int32_t mode, void* stream) {
-    DM3D_REQUIRE(keras_kernel && packed && taps > 0 && cin > 0 && cout > 0, "pack_weights_h3p: bad arguments");
-    DM3D_REQUIRE(mode >= 0 && mode <= 2 && (mode == 0 || taps == 8), "pack_weights_h3p: mode %d with taps %d", mode, taps);
-    DM3D_REQUIRE(w_exp >= -100 && w_exp <= 100, "pack_weights_h3p: w_exp %d out of range", w_exp);
-    DM3D_REQUIRE(dm3d_aligned16(packed), "pack_weights_h3p: packed must be 16-byte aligned");
-    return dm3d_pack_h3v2(keras_kernel, taps, cin, cout, w_exp, in_scale, packed, mode, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int64_t dm3d_packed_weight_h3w_bytes(int32_t cin, int32_t cout) {
-    if (cin <= 0 || cout <= 0) return 0;
-    return dm3d_h3v2_image_bytes(40, cin, cout);          // 5 tap pairs x 4 transform terms x 2 taps
-}
-
-extern "C" int dm3d_pack_weights_h3w(const float* keras_kernel, int32_t cin, int32_t cout, int32_t w_exp, const float* in_scale, void* packed,
-                                     void* stream) {
-    DM3D_REQUIRE(keras_kernel && packed && cin > 0 && cout > 0, "pack_weights_h3w: bad arguments");
-    DM3D_REQUIRE(w_exp >= -100 && w_exp <= 100, "pack_weights_h3w: w_exp %d out of range", w_exp);
-    DM3D_REQUIRE(dm3d_aligned16(packed), "pack_weights_h3w: packed must be 16-byte aligned");
-    return dm3d_pack_h3v2(keras_kernel, 40, cin, cout, w_exp, in_scale, packed, 3, static_cast<hipStream_t>(stream));
 }
 
 int dm3d_conv_launch_f32(ConvArgs& a, int which, hipStream_t st) {

@@ -79,9 +79,3 @@ int dm3d_conv_launch_h3w(const ConvLaunch& r, hipStream_t st);
 struct H3v2Launch { ConvArgs k; bool stats_after; };       // what pre_launch made of a ConvLaunch: the kernel's own arguments; the stand-alone statistics pass behind it
 int dm3d_h3v2_pre_launch(const ConvLaunch& r, H3v2Launch& L);
 int dm3d_h3v2_post_launch(const ConvArgs& a, const H3v2Launch& L, hipStream_t st);
-int64_t dm3d_h3v2_skip_image_bytes(int cin, int cout);
-int dm3d_pack_skip_h3v2(const float* keras_kernel, int cin, int cout, int w_exp, void* packed, hipStream_t st);
-int dm3d_pack_skip_h3f(const float* keras_kernel, int cin, int cout, int w_exp, void* packed, hipStream_t st);      // operand-fragment order
-int64_t dm3d_h3v2_image_bytes(int taps, int cin, int cout);
-int dm3d_pack_h3v2(const float* keras_kernel, int taps, int cin, int cout, int w_exp, const float* in_scale, void* packed, int mode,
-                   hipStream_t st);

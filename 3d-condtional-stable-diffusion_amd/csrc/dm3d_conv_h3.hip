@@ -377,40 +377,6 @@ int launch_h3(ConvArgs& a, hipStream_t st) {
     return dm3d_launch_check("conv3d_igemm_h3");
 }
 
-// Keras [taps][cin][cout] -> [coutpad/64][cinpad/16][taps][64][REC] halfs, scaled by 2^w_exp: the LDS image of a weight
-// group, i.e. slots (hi c0-7, hi c8-15, lo c0-7, lo c8-15) of output channel n stored at physical slot s ^ swz(n)
-__global__ __launch_bounds__(256) void pack_weights_h3_kernel(const float* __restrict__ w, int taps, int cin, int cout,
-                                                              int nchunks, int ntiles, float scale, const float* in_scale,
-                                                              _Float16* __restrict__ out, int up) {
-    // up == 1: w is the 3x3x3 kernel of an UpSample conv; up == 2: the [4,4,4,Cout,Cin] kernel of a Conv3DTranspose(k4,s2).
-    // In both cases taps == 8 and 8 parity images follow each other (dm3d_up_weight / dm3d_convt_weight)
-    const long nrec = (long)ntiles * nchunks * taps * 64;
-    for (long i0 = (long)blockIdx.x * 256 + threadIdx.x; i0 < nrec * 16 * (up ? 8 : 1); i0 += (long)gridDim.x * 256) {
-        const int par = (int)(i0 / (nrec * 16));
-        const long i = i0 % (nrec * 16);
-        const int k = (int)(i & 15);
-        long rec = i >> 4;
-        const int nn = (int)(rec % 64);
-        const int tap = (int)((rec / 64) % taps);
-        const int chunk = (int)((rec / (64L * taps)) % nchunks);
-        const int nt = (int)(rec / (64L * taps * nchunks));
-        const int ci = chunk * 16 + k, co = nt * 64 + nn;
-        float v = 0.f;
-        if (ci < cin && co < cout) {
-            v = up == 1 ? dm3d_up_weight(w, cin, cout, par, tap, ci, co)
-              : up == 2 ? dm3d_convt_weight(w, cin, cout, par, tap, ci, co) : w[((long)tap * cin + ci) * cout + co];
-            if (in_scale) v *= in_scale[ci];
-            v *= scale;
-        }
-        const _Float16 hi = (_Float16)v;
-        const _Float16 lo = (_Float16)(v - (float)hi);
-        _Float16* r = out + ((long)par * nrec + rec) * REC;
-        const int sw = (nn >> 2) & 3;
-        r[(((k >> 3) ^ sw) << 3) + (k & 7)] = hi;
-        r[(((2 + (k >> 3)) ^ sw) << 3) + (k & 7)] = lo;
-    }
-}
-
 }  // namespace
 
 int dm3d_conv_launch_h3(ConvArgs& a, int which, hipStream_t st) {
@@ -420,49 +386,4 @@ int dm3d_conv_launch_h3(ConvArgs& a, int which, hipStream_t st) {
     if (which == DM3D_CONV_K4S2) return launch_h3<2, 4, 8, 2, 4, 2, 2, 1>(a, st);
     if (a.cout <= 32) return launch_h3<4, 8, 8, 1, 3, 4, 1, 2, 1>(a, st);     // conv_in / conv_out: half the MFMAs
     return launch_h3<4, 8, 8, 1, 3, 4, 1, 2>(a, st);
-}
-
-extern "C" int64_t dm3d_packed_weight_h3_bytes(int32_t taps, int32_t cin, int32_t cout) {
-    if (taps <= 0 || cin <= 0 || cout <= 0) return 0;
-    return (int64_t)taps * dm3d_round_up(cout, 64) * (dm3d_round_up(cin, 16) / 16) * REC * (int64_t)sizeof(_Float16);
-}
-
-extern "C" int dm3d_pack_weights_h3(const float* keras_kernel, int32_t taps, int32_t cin, int32_t cout, int32_t w_exp,
-                                    const float* in_scale, void* packed, void* stream) {
-    DM3D_REQUIRE(keras_kernel && packed && taps > 0 && cin > 0 && cout > 0, "pack_weights_h3: bad arguments");
-    DM3D_REQUIRE(w_exp >= -100 && w_exp <= 100, "pack_weights_h3: w_exp %d out of range", w_exp);
-    DM3D_REQUIRE(dm3d_aligned16(packed), "pack_weights_h3: packed must be 16-byte aligned");
-    const int nchunks = (int)(dm3d_round_up(cin, 16) / 16), ntiles = (int)(dm3d_round_up(cout, 64) / 64);
-    const long n = (long)ntiles * nchunks * taps * 64 * 16;
-    long g = (n + 255) / 256;
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(pack_weights_h3_kernel, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream), keras_kernel,
-                       taps, cin, cout, nchunks, ntiles, ldexpf(1.0f, w_exp), in_scale, static_cast<_Float16*>(packed), 0);
-    return dm3d_launch_check("pack_weights_h3_kernel");
-}
-
-extern "C" int64_t dm3d_packed_weight_up_h3_bytes(int32_t cin, int32_t cout) { return 8 * dm3d_packed_weight_h3_bytes(8, cin, cout); }
-
-extern "C" int dm3d_pack_weights_up_h3(const float* keras_kernel, int32_t cin, int32_t cout, int32_t w_exp, void* packed,
-                                       void* stream) {
-    DM3D_REQUIRE(keras_kernel && packed && cin > 0 && cout > 0, "pack_weights_up_h3: bad arguments");
-    DM3D_REQUIRE(w_exp >= -100 && w_exp <= 100 && dm3d_aligned16(packed), "pack_weights_up_h3: w_exp out of range or packed unaligned");
-    if (dm3d_conv_weight_layout(3, 1, 1, 0, cout) == DM3D_WL_PAIR)
-        return dm3d_pack_h3v2(keras_kernel, 8, cin, cout, w_exp, nullptr, packed, 1, static_cast<hipStream_t>(stream));
-    const int nchunks = (int)(dm3d_round_up(cin, 16) / 16), ntiles = (int)(dm3d_round_up(cout, 64) / 64);
-    hipLaunchKernelGGL(pack_weights_h3_kernel, dim3(4096), dim3(256), 0, static_cast<hipStream_t>(stream), keras_kernel, 8, cin,
-                       cout, nchunks, ntiles, ldexpf(1.0f, w_exp), nullptr, static_cast<_Float16*>(packed), 1);
-    return dm3d_launch_check("pack_weights_h3_kernel(up)");
-}
-
-extern "C" int dm3d_pack_weights_convt_h3(const float* keras_kernel, int32_t cin, int32_t cout, int32_t w_exp, void* packed,
-                                          void* stream) {
-    DM3D_REQUIRE(keras_kernel && packed && cin > 0 && cout > 0, "pack_weights_convt_h3: bad arguments");
-    DM3D_REQUIRE(w_exp >= -100 && w_exp <= 100 && dm3d_aligned16(packed), "pack_weights_convt_h3: w_exp out of range or packed unaligned");
-    if (dm3d_conv_weight_layout(4, 2, 0, 1, cout) == DM3D_WL_PAIR)
-        return dm3d_pack_h3v2(keras_kernel, 8, cin, cout, w_exp, nullptr, packed, 2, static_cast<hipStream_t>(stream));
-    const int nchunks = (int)(dm3d_round_up(cin, 16) / 16), ntiles = (int)(dm3d_round_up(cout, 64) / 64);
-    hipLaunchKernelGGL(pack_weights_h3_kernel, dim3(4096), dim3(256), 0, static_cast<hipStream_t>(stream), keras_kernel, 8, cin,
-                       cout, nchunks, ntiles, ldexpf(1.0f, w_exp), nullptr, static_cast<_Float16*>(packed), 2);
-    return dm3d_launch_check("pack_weights_h3_kernel(convt)");
 }

@@ -16,6 +16,16 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 __host__ __device__ constexpr int pi_pos(int c) {
     return c < 4 ? (c < 2 ? c : c + 2) : (c >= 12 ? (c < 14 ? c - 4 : c - 2) : (((c - 4) >> 1) * 4 + 2 + ((c - 4) & 1)));
 }
+// its inverse: the MFMA column whose weight row sits at position p of a group of 16 (what the weight packers ask, dm3d_pack.hip)
+__host__ __device__ constexpr int pi_col(int p) {
+    const int q = (p >> 2) * 2 + (p & 1);
+    return (p & 2) ? 4 + q : (q < 4 ? q : q + 8);
+}
+constexpr bool pi_col_inverts_pi_pos() {
+    for (int c = 0; c < 16; ++c) if (pi_col(pi_pos(c)) != c) return false;
+    return true;
+}
+static_assert(pi_col_inverts_pi_pos(), "pi_col must invert pi_pos");
 // patch column of MFMA row i (rows 0-3 -> 0, 4-7 -> 2, 8-11 -> 3, 12-15 -> 1); patch row is i & 3
 __device__ __forceinline__ int dx_of_row(int i) { return (0x1320 >> ((i >> 2) * 4)) & 3; }
 

@@ -515,39 +515,6 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
     }
 }
 
-// Keras [taps][cin][cout] -> [taps][coutpad][cinpad], optional per-input-channel scale
-__global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restrict__ w, int taps, int cin, int cout,
-                                                           int cinpad, int coutpad, const float* in_scale,
-                                                           float* __restrict__ out) {
-    const long n = (long)taps * coutpad * cinpad;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int ci = (int)(i % cinpad);
-        const int co = (int)((i / cinpad) % coutpad);
-        const int tap = (int)(i / ((long)cinpad * coutpad));
-        float v = 0.f;
-        if (ci < cin && co < cout) {
-            v = w[((long)tap * cin + ci) * cout + co];
-            if (in_scale) v *= in_scale[ci];
-        }
-        out[i] = v;
-    }
-}
-
-// upsample variant: 8 parity images of a taps=8 conv (see dm3d_up_weight)
-__global__ __launch_bounds__(256) void pack_weights_up_kernel(const float* __restrict__ w, int cin, int cout, int cinpad,
-                                                              int coutpad, float* __restrict__ out, int convt) {
-    const long per = (long)8 * coutpad * cinpad;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < 8 * per; i += (long)gridDim.x * 256) {
-        const int par = (int)(i / per);
-        const long j = i % per;
-        const int ci = (int)(j % cinpad);
-        const int co = (int)((j / cinpad) % coutpad);
-        const int tap = (int)(j / ((long)cinpad * coutpad));
-        out[i] = (ci < cin && co < cout) ? (convt ? dm3d_convt_weight(w, cin, cout, par, tap, ci, co)
-                                                  : dm3d_up_weight(w, cin, cout, par, tap, ci, co)) : 0.f;
-    }
-}
-
 // ---- VectorQuantizer.get_code_indices (reference networks/vqvae3d_monai.py:164-177): distances = |z|^2 + |e_k|^2 - 2 z.e_k in
 // float32 in that order, argmin with the lowest index on ties.  sim = z.E comes from the GEMM; one wavefront per row. ----
 __global__ __launch_bounds__(256) void vq_assign_kernel(const float* __restrict__ z, long rows, int d, const float* __restrict__ sim,
@@ -671,21 +638,6 @@ extern "C" int dm3d_gather_rows(const float* table, int32_t table_rows, const in
     return dm3d_launch_check("gather_rows_kernel");
 }
 
-extern "C" int64_t dm3d_packed_weight_elems(int32_t taps, int32_t cin, int32_t cout) {
-    if (taps <= 0 || cin <= 0 || cout <= 0) return 0;
-    return (int64_t)taps * dm3d_round_up(cout, DM3D_COUT_PAD) * dm3d_round_up(cin, DM3D_CIN_PAD);
-}
-
-extern "C" int dm3d_pack_weights(const float* keras_kernel, int32_t taps, int32_t cin, int32_t cout, const float* in_scale,
-                                 float* packed, void* stream) {
-    DM3D_REQUIRE(keras_kernel && packed && taps > 0 && cin > 0 && cout > 0, "pack_weights: bad arguments");
-    const int cinpad = (int)dm3d_round_up(cin, DM3D_CIN_PAD), coutpad = (int)dm3d_round_up(cout, DM3D_COUT_PAD);
-    const long n = (long)taps * cinpad * coutpad;
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(grid_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), keras_kernel,
-                       taps, cin, cout, cinpad, coutpad, in_scale, packed);
-    return dm3d_launch_check("pack_weights_kernel");
-}
-
 extern "C" int dm3d_layernorm3_h2(const float* x, int64_t rows, int32_t c, float eps,
                                   const float* g1, const float* b1, void* o1,
                                   const float* g2, const float* b2, void* o2,
@@ -714,24 +666,6 @@ extern "C" int dm3d_softmax_rows_h2(float* s, int64_t rows, int32_t cols, int64_
     hipLaunchKernelGGL(softmax_rows_h2_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        s, (long)rows, cols, (long)ld);
     return dm3d_launch_check("softmax_rows_h2_kernel");
-}
-
-extern "C" int64_t dm3d_packed_weight_up_elems(int32_t cin, int32_t cout) { return 8 * dm3d_packed_weight_elems(8, cin, cout); }
-
-extern "C" int dm3d_pack_weights_up(const float* keras_kernel, int32_t cin, int32_t cout, float* packed, void* stream) {
-    DM3D_REQUIRE(keras_kernel && packed && cin > 0 && cout > 0, "pack_weights_up: bad arguments");
-    const int cinpad = (int)dm3d_round_up(cin, DM3D_CIN_PAD), coutpad = (int)dm3d_round_up(cout, DM3D_COUT_PAD);
-    hipLaunchKernelGGL(pack_weights_up_kernel, dim3(grid_for((long)64 * cinpad * coutpad)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), keras_kernel, cin, cout, cinpad, coutpad, packed, 0);
-    return dm3d_launch_check("pack_weights_up_kernel");
-}
-
-extern "C" int dm3d_pack_weights_convt(const float* keras_kernel, int32_t cin, int32_t cout, float* packed, void* stream) {
-    DM3D_REQUIRE(keras_kernel && packed && cin > 0 && cout > 0, "pack_weights_convt: bad arguments");
-    const int cinpad = (int)dm3d_round_up(cin, DM3D_CIN_PAD), coutpad = (int)dm3d_round_up(cout, DM3D_COUT_PAD);
-    hipLaunchKernelGGL(pack_weights_up_kernel, dim3(grid_for((long)64 * cinpad * coutpad)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), keras_kernel, cin, cout, cinpad, coutpad, packed, 1);
-    return dm3d_launch_check("pack_weights_up_kernel(convt)");
 }
 
 extern "C" int dm3d_vq_assign(const float* z, int64_t rows, int32_t d, const float* sim, int32_t k, const float* esq,

@@ -42,10 +42,13 @@ def pack_weights(kernel: torch.Tensor, in_scale: Optional[torch.Tensor] = None) 
 
 
 def h3_weight_exponent(*kernels) -> int:
-    """Power-of-two pre-scale of the H3 weight images: the largest |w| of all given kernels lands in [2^13, 2^14)."""
+    """Power-of-two pre-scale of the H3 weight images: the largest |w| of all given kernels (NumPy arrays or tensors) lands in
+    [2^13, 2^14), so that hi stays finite and lo a normal float16.  Clamped to the +-100 the packers accept."""
     import math
-    wmax = max(float(k.abs().max()) for k in kernels)
-    return 0 if wmax == 0.0 or not math.isfinite(wmax) else max(-100, min(100, int(13 - math.floor(math.log2(wmax)))))
+    wmax = max(float(abs(k).max()) for k in kernels)
+    if wmax == 0.0 or not math.isfinite(wmax):
+        return 0
+    return max(-100, min(100, 14 - math.frexp(wmax)[1]))           # frexp: wmax = m 2^e with m in [0.5, 1), i.e. floor(log2 wmax) = e - 1
 
 
 def pack_weights_skip_h3p(kernel: torch.Tensor, w_exp: int) -> torch.Tensor:
@@ -100,9 +103,9 @@ def pack_weights_h3w(kernel: torch.Tensor, w_exp: int, in_scale: Optional[torch.
     return out
 
 
-def pack_weights_up(kernel: torch.Tensor, h3: bool = False):
+def pack_weights_up(kernel: torch.Tensor, h3: bool = False, w_exp: Optional[int] = None):
     """[3,3,3,Cin,Cout] kernel of an UpSample conv -> the 8 parity images dm3d_conv3d_ndhwc(upsample=1) expects.
-    Returns wpk (fp32) or (wpk, w_exp) (h3)."""
+    Returns wpk (fp32) or (wpk, w_exp) (h3; ``w_exp`` defaults to the exponent of the parity sums)."""
     _f32c(kernel, "kernel")
     if kernel.dim() != 5 or tuple(kernel.shape[:3]) != (3, 3, 3):
         raise ValueError("kernel must be [3,3,3,cin,cout]")
@@ -111,10 +114,9 @@ def pack_weights_up(kernel: torch.Tensor, h3: bool = False):
         out = torch.empty(lib().dm3d_packed_weight_up_elems(cin, cout), dtype=torch.float32, device=kernel.device)
         check(lib().dm3d_pack_weights_up(kernel.data_ptr(), cin, cout, out.data_ptr(), _st()), "pack_weights_up")
         return out
-    import math
-    from .weights import upsample_parity_kernels
-    wmax = float(abs(upsample_parity_kernels(kernel.cpu().numpy())).max())
-    w_exp = 0 if wmax == 0.0 or not math.isfinite(wmax) else int(13 - math.floor(math.log2(wmax)))
+    if w_exp is None:
+        from .weights import upsample_parity_kernels
+        w_exp = h3_weight_exponent(upsample_parity_kernels(kernel.cpu().numpy()))
     out = torch.empty(lib().dm3d_packed_weight_up_h3_bytes(cin, cout) // 2, dtype=torch.float16, device=kernel.device)
     check(lib().dm3d_pack_weights_up_h3(kernel.data_ptr(), cin, cout, w_exp, out.data_ptr(), _st()), "pack_weights_up_h3")
     return out, w_exp
@@ -131,9 +133,7 @@ def pack_weights_convt(kernel: torch.Tensor, h3: bool = False):
         out = torch.empty(lib().dm3d_packed_weight_up_elems(cin, cout), dtype=torch.float32, device=kernel.device)
         check(lib().dm3d_pack_weights_convt(kernel.data_ptr(), cin, cout, out.data_ptr(), _st()), "pack_weights_convt")
         return out
-    import math
-    wmax = float(kernel.abs().max())
-    w_exp = 0 if wmax == 0.0 or not math.isfinite(wmax) else int(13 - math.floor(math.log2(wmax)))
+    w_exp = h3_weight_exponent(kernel)
     out = torch.empty(lib().dm3d_packed_weight_up_h3_bytes(cin, cout) // 2, dtype=torch.float16, device=kernel.device)
     check(lib().dm3d_pack_weights_convt_h3(kernel.data_ptr(), cin, cout, w_exp, out.data_ptr(), _st()), "pack_weights_convt_h3")
     return out, w_exp

@@ -18,7 +18,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, ConvDesc, GemmDesc, GradScaleDesc, LossDesc, WgradDesc, check, lib
 from .betas import time_embedding_table
 from .schedules import _host
@@ -202,9 +202,7 @@ class Trainer:
                 src = _empty(taps * cin * cout, device=self.device)
                 check(lib().dm3d_flip_transpose(p.w.data_ptr(), taps, cin, cout, src.data_ptr(), _st()), "flip_transpose")
                 cin, cout = cout, cin
-            out = _empty(lib().dm3d_packed_weight_elems(taps, cin, cout), device=self.device)
-            check(lib().dm3d_pack_weights(src.data_ptr(), taps, cin, cout, None, out.data_ptr(), _st()), "pack_weights")
-            self._cache[key] = out
+            self._cache[key] = ops.pack_weights(src.view(cin, cout) if taps == 1 else src.view(taps, 1, 1, cin, cout))     # (a view: no copy)
         return self._cache[key]
 
     def _conv_launch(self, x: torch.Tensor, wpk: torch.Tensor, cin: int, cout: int, ksize: int, stride: int = 1, bias=None,

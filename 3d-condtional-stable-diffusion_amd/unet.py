@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, AttnFrontDesc, ConvDesc, GemmDesc, MlpDesc, check, lib
 from .betas import time_embedding_table
 from .weights import UNetConfig, keras_init_weights, upsample_parity_kernels, walk
@@ -41,12 +41,6 @@ def _ptr(t: Optional[torch.Tensor], offset_elems: int = 0) -> Optional[int]:
     if t is None:
         return None
     return t.data_ptr() + 4 * offset_elems
-
-
-def _h3_exponent(*kernels) -> int:
-    """power-of-two pre-scale so that max|w| over the given kernels lands in [2^13, 2^14): hi stays finite, lo a normal float16"""
-    wmax = max(float(np.abs(k).max()) for k in kernels)
-    return 0 if wmax == 0.0 or not np.isfinite(wmax) else max(-100, min(100, int(13 - np.floor(np.log2(wmax)))))
 
 
 class _Conv:
@@ -137,37 +131,17 @@ class UNet:
         dbias = self._dev(bias) if bias is not None else None
         if up:
             if self.precision == "h3":
-                wmax = float(np.abs(upsample_parity_kernels(kernel)).max())
-                w_exp = 0 if wmax == 0.0 or not np.isfinite(wmax) else max(-100, min(100, int(13 - np.floor(np.log2(wmax)))))
-                wpk = torch.empty(lib().dm3d_packed_weight_up_h3_bytes(cin, cout) // 2, dtype=torch.float16, device=self.device)
-                check(lib().dm3d_pack_weights_up_h3(raw.data_ptr(), cin, cout, w_exp, wpk.data_ptr(), _stream()), "pack_weights_up_h3")
+                wpk, w_exp = ops.pack_weights_up(raw, h3=True, w_exp=ops.h3_weight_exponent(upsample_parity_kernels(kernel)))
                 return _Conv(wpk, dbias, taps, cin, cout, _lib.PREC_H3, w_exp)
-            wpk = torch.empty(lib().dm3d_packed_weight_up_elems(cin, cout), dtype=torch.float32, device=self.device)
-            check(lib().dm3d_pack_weights_up(raw.data_ptr(), cin, cout, wpk.data_ptr(), _stream()), "pack_weights_up")
-            return _Conv(wpk, dbias, taps, cin, cout)
+            return _Conv(ops.pack_weights_up(raw), dbias, taps, cin, cout)
         if conv and self.precision == "h3":
-            # power-of-two pre-scale so that max|w| lands in [2^13, 2^14): hi stays finite, lo stays a normal float16
-            if w_exp is None:
-                w_exp = _h3_exponent(kernel)
-            if lib().dm3d_conv_weight_layout({1: 1, 27: 3}[taps], stride, 0, 0, cout) == _lib.WL_PAIR:
-                wpk = torch.empty(lib().dm3d_packed_weight_h3p_bytes(taps, cin, cout) // 2, dtype=torch.float16, device=self.device)
-                check(lib().dm3d_pack_weights_h3p(raw.data_ptr(), taps, cin, cout, w_exp, _ptr(in_scale), wpk.data_ptr(), 0,
-                                                  _stream()), "pack_weights_h3p")
-                if self.wino and taps == 27 and stride == 1 and cout > 32 and cin >= 32:       # (the library never takes the form below 32 input channels)
-                    cv = _Conv(wpk, self._dev(bias) if bias is not None else None, taps, cin, cout, _lib.PREC_H3, w_exp)
-                    cv.wpk_wino = torch.empty(lib().dm3d_packed_weight_h3w_bytes(cin, cout) // 2, dtype=torch.float16, device=self.device)
-                    check(lib().dm3d_pack_weights_h3w(raw.data_ptr(), cin, cout, w_exp, _ptr(in_scale), cv.wpk_wino.data_ptr(), _stream()), "pack_weights_h3w")
-                    return cv
-            else:
-                wpk = torch.empty(lib().dm3d_packed_weight_h3_bytes(taps, cin, cout) // 2, dtype=torch.float16, device=self.device)
-                check(lib().dm3d_pack_weights_h3(raw.data_ptr(), taps, cin, cout, w_exp, _ptr(in_scale), wpk.data_ptr(),
-                                                 _stream()), "pack_weights_h3")
-            return _Conv(wpk, self._dev(bias) if bias is not None else None, taps, cin, cout, _lib.PREC_H3, w_exp)
-        n = lib().dm3d_packed_weight_elems(taps, cin, cout)
-        wpk = torch.empty(n, dtype=torch.float32, device=self.device)
-        check(lib().dm3d_pack_weights(raw.data_ptr(), taps, cin, cout, _ptr(in_scale), wpk.data_ptr(), _stream()),
-              "pack_weights")
-        return _Conv(wpk, self._dev(bias) if bias is not None else None, taps, cin, cout)
+            wpk, w_exp = ops.pack_weights_h3(raw, in_scale, stride=stride, w_exp=ops.h3_weight_exponent(kernel) if w_exp is None else w_exp)
+            cv = _Conv(wpk, dbias, taps, cin, cout, _lib.PREC_H3, w_exp)
+            if (self.wino and taps == 27 and stride == 1 and cout > 32 and cin >= 32       # (the library never takes the form below 32 input channels)
+                    and lib().dm3d_conv_weight_layout(3, stride, 0, 0, cout) == _lib.WL_PAIR):
+                cv.wpk_wino = ops.pack_weights_h3w(raw, w_exp, in_scale)
+            return cv
+        return _Conv(ops.pack_weights(raw, in_scale), dbias, taps, cin, cout)
 
     def _to_h2(self, t: torch.Tensor, rows: int, k: int) -> torch.Tensor:
         """float32 [rows, k] device matrix (k % 16 == 0) -> DM3D_FMT_H2 buffer of the same byte size."""
@@ -209,17 +183,12 @@ class UNet:
                         and blk.cout > 32 and lib().dm3d_conv_weight_layout(3, 1, 0, 0, blk.cout) == _lib.WL_PAIR):      # (the narrow column forms have no tail phase)
                     # the 1x1 skip conv rides in conv2's launch (dm3d_conv_desc.skip_*): both images share one exponent, the
                     # skip bias joins conv2's
-                    e = _h3_exponent(s[f"{n}.conv2.kernel"], s[f"{n}.skip.kernel"])
+                    e = ops.h3_weight_exponent(s[f"{n}.conv2.kernel"], s[f"{n}.skip.kernel"])
                     P[f"{n}.conv2"] = self._pack(s[f"{n}.conv2.kernel"], s[f"{n}.conv2.bias"] + s[f"{n}.skip.bias"], conv=True, w_exp=e)
                     ks = self._dev(s[f"{n}.skip.kernel"])
-                    cin_s, cout_s = int(ks.shape[-2]), int(ks.shape[-1])
-                    img = torch.empty(lib().dm3d_packed_weight_skip_h3p_bytes(cin_s, cout_s) // 2, dtype=torch.float16, device=self.device)
-                    check(lib().dm3d_pack_weights_skip_h3p(ks.data_ptr(), cin_s, cout_s, e, img.data_ptr(), _stream()), "pack_weights_skip_h3p")
-                    P[f"{n}.skip_fused"] = img
+                    P[f"{n}.skip_fused"] = ops.pack_weights_skip_h3p(ks, e)
                     if self.wino:           # the same kernel as operand fragments: the Winograd-x form's register-direct tail (dm3d.h, skip_wpk_frag)
-                        frag = torch.empty_like(img)
-                        check(lib().dm3d_pack_weights_skip_h3f(ks.data_ptr(), cin_s, cout_s, e, frag.data_ptr(), _stream()), "pack_weights_skip_h3f")
-                        P[f"{n}.skip_frag"] = frag
+                        P[f"{n}.skip_frag"] = ops.pack_weights_skip_h3f(ks, e)
                 else:
                     if f"{n}.skip.kernel" in s:
                         P[f"{n}.skip"] = self._pack(s[f"{n}.skip.kernel"], s[f"{n}.skip.bias"], conv=True)
