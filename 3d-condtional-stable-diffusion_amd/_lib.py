@@ -133,6 +133,14 @@ class DpmSdeDesc(C.Structure):
     _fields_ = DpmDesc._fields_ + [("noise", _f32p), ("tau", _i32p), ("seed", C.c_uint64), ("seed_dev", C.c_void_p)]
 
 
+class UniPcDesc(C.Structure):
+    _fields_ = [
+        ("x", _f32p), ("eps", _f32p), ("xc", _f32p), ("hist", _f32p * 3), ("out", _f32p), ("xc_out", _f32p), ("x0_out", _f32p),
+        ("batch", C.c_int32), ("per_sample", C.c_int64), ("coef", _f32p), ("corr", _f32p), ("rows", C.c_int32), ("pos", _i32p),
+        ("t_next", _i32p), ("t_idx", _i32p), ("mode", C.c_int32), ("x0_bound", _f32p),
+    ]
+
+
 class ThreshDesc(C.Structure):
     _fields_ = [
         ("x", _f32p), ("eps", _f32p), ("batch", C.c_int32), ("per_sample", C.c_int64),
@@ -246,6 +254,7 @@ SIGNATURES = {
     "dm3d_dpm_update_frame": (C.c_int, [C.POINTER(DpmDesc), _f32p, C.c_void_p]),
     "dm3d_dpm_sde_update": (C.c_int, [C.POINTER(DpmSdeDesc), C.c_void_p]),
     "dm3d_dpm_sde_update_frame": (C.c_int, [C.POINTER(DpmSdeDesc), _f32p, C.c_void_p]),
+    "dm3d_unipc_update": (C.c_int, [C.POINTER(UniPcDesc), C.c_void_p]),
     "dm3d_x0_threshold": (C.c_int, [C.POINTER(ThreshDesc), C.c_void_p]),
     "dm3d_x0_threshold_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "dm3d_edit_update": (C.c_int, [C.POINTER(EditDesc), C.c_void_p]),

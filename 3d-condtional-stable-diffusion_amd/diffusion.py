@@ -7,7 +7,8 @@ selects the in-kernel Philox stream, ``use_graph=`` toggles HIP-graph replay of 
 ``negative_context=`` / ``guidance_rescale=`` turn on classifier-free guidance (include/dm3d.h, dm3d_guide_desc);
 ``dynamic_threshold=`` / ``threshold_max=`` replace the static clamp of the x0 estimate by Imagen's dynamic thresholding in the DDIM
 and DPM-Solver++ chains (include/dm3d.h, dm3d_thresh_desc); ``sampler="dpmpp_sde"`` / ``sde_eta=`` is the stochastic form of the
-DPM-Solver++(2M) chain (include/dm3d.h, dm3d_dpm_sde_desc).  Training extensions, off by default: ``compile(ema_decay=)`` keeps an
+DPM-Solver++(2M) chain (include/dm3d.h, dm3d_dpm_sde_desc); ``sampler="unipc"`` / ``unipc_variant=`` is UniPC, a predictor-corrector of
+order up to 3 with one fused update launch per step (include/dm3d.h, dm3d_unipc_desc).  Training extensions, off by default: ``compile(ema_decay=)`` keeps an
 exponential moving average of the weights in the optimizer's launch (include/dm3d.h, dm3d_adam_ema) and ``use_ema()`` samples from it;
 ``compile(context_dropout=, null_context=)`` trains the unconditional branch that classifier-free guidance is defined against;
 ``compile(global_clipnorm=, grad_accum_steps=)`` clips the gradient by its global norm and applies the mean of k micro-batches, both as
@@ -40,11 +41,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DdimDesc, DdpmDesc, DpmDesc, DpmSdeDesc, EditDesc, GuideDesc, PredDesc, ThreshDesc, check, lib
+from ._lib import DdimDesc, DdpmDesc, DpmDesc, DpmSdeDesc, EditDesc, GuideDesc, PredDesc, ThreshDesc, UniPcDesc, check, lib
 from .betas import BETAS_FIELDS, Betas
-from .schedules import (FLOAT32_MAX, LOSS_WEIGHTINGS, PREDICTIONS, _check_prediction, _host, _indices, context_dropout, ddim_coefficients,
-                        ddim_timesteps, dpm_coefficients, dpm_sde_coefficients, edit_levels, edit_steps, frame_table, guide_tables, latent_mask,
-                        objective_rows, prediction_table, threshold_rank, threshold_tables)
+from .schedules import (FLOAT32_MAX, LOSS_WEIGHTINGS, PREDICTIONS, UNIPC_VARIANTS, _check_prediction, _check_unipc, _host, _indices,
+                        context_dropout, ddim_coefficients, ddim_timesteps, dpm_coefficients, dpm_sde_coefficients, edit_levels, edit_steps,
+                        frame_table, guide_tables, latent_mask, objective_rows, prediction_table, threshold_rank, threshold_tables,
+                        unipc_coefficients, unipc_corrector, unipc_orders, unipc_predictor, unipc_system)
 from .unet import UNet
 from .weight_sets import WeightSets
 from .weights import UNetConfig
@@ -595,6 +597,81 @@ class DiffusionModel:
         d.seed = int(seed) & (2 ** 64 - 1)
         return d
 
+    # -- UniPC ---------------------------------------------------------------------------------------------------------------------
+    def unipc_step(self, x_t, pred_noise, t, t_prev, hist=(), t_hist=(), x_before=None, *, solver_order=1, corrector_order=0,
+                   clip_x0=True, unipc_variant="bh2", dynamic_threshold=None, threshold_max=None):
+        """One launch of the UniPC update (include/dm3d.h, dm3d_unipc_desc, mode 0): the single-call counterpart of a sampler="unipc"
+        chain's step, as dpm_step is of a "dpmpp" chain's.  ``x_t`` is the predicted state at timestep ``t`` and ``pred_noise`` the
+        network's eps on it (predict_eps() converts a v- or x0-model's output first).  Returns (x_next, x_corr, x0): the predicted
+        state at ``t_prev`` (-1: the x0 estimate itself), the corrected state at ``t`` and this level's (clipped) x0 estimate.
+        ``hist`` / ``t_hist``: up to three x0 estimates of the levels before, newest first, and their timesteps, t < t_hist[0] <
+        t_hist[1] < ...; ``x_before``: the corrected state at t_hist[0].  ``corrector_order`` = c in 0..3 (0: no corrector, x_corr is
+        x_t): the corrector at ``t``, reached from t_hist[0], uses x_before and hist[:c].  ``solver_order`` = p in 1..3: the predictor
+        from the corrected state uses this call's estimate and hist[:p-1] (p = 1: the DDIM eta = 0 step).  ``t`` / ``t_prev`` and every
+        entry of ``t_hist``: one index or one per sample.  ``unipc_variant``, ``clip_x0``, ``dynamic_threshold`` / ``threshold_max``: as
+        generate().  The inputs are left untouched."""
+        _check_unipc(solver_order, unipc_variant)
+        if corrector_order not in (0, 1, 2, 3):
+            raise ValueError(f"corrector_order must be 0, 1, 2 or 3, got {corrector_order!r}")
+        if self.zero_terminal_snr:
+            raise ValueError("unipc_step needs a finite log-SNR at every level, which a zero_terminal_snr model's last timestep lacks: use dpm_step")
+        hist, t_hist = list(hist), list(t_hist)
+        need = max(solver_order - 1, corrector_order)
+        if len(hist) != len(t_hist) or len(hist) > 3 or len(hist) < need:
+            raise ValueError(f"hist / t_hist must hold the same number (at most 3) of estimates and timesteps, at least {need} for these orders")
+        if corrector_order and x_before is None:
+            raise ValueError("a corrector needs x_before, the corrected state at t_hist[0]")
+        host, t, tp, thr = self._step_rules(x_t, pred_noise, t, t_prev, None, None, clip_x0, dynamic_threshold, threshold_max, x_before)
+        B = host[0].shape[0]
+        levels, last = [], t
+        for k, v in enumerate(t_hist):
+            v = _indices(v, B)
+            if np.any(v <= last) or v.max() >= self.timesteps:
+                raise ValueError("t_hist must lie in (t, timesteps), strictly increasing")
+            levels.append(v)
+            last = v
+            hist[k] = torch.as_tensor(hist[k], dtype=torch.float32)
+            if hist[k].shape != host[0].shape:
+                raise ValueError("every entry of hist must have x_t's shape")
+        ab = np.asarray(self.b.alpha_bar, dtype=np.float64)
+        rows = np.zeros((B, 10), dtype=np.float64)
+        for b in range(B):
+            before = [int(v[b]) for v in levels]
+            rows[b, :4] = unipc_predictor(ab, int(t[b]), int(tp[b]), before[:solver_order - 1], unipc_variant)
+            if corrector_order:
+                rows[b, 4:9] = unipc_corrector(ab, before[0], int(t[b]), before[1:corrector_order], unipc_variant)
+        dev = self.device
+        coef, corr = (v.to(dev) for v in self._unipc_table(t, rows, clip_x0))
+        x_t, eps, _, xc = self._staged(host)
+        slots = self._staged(hist) + [None] * (3 - len(hist))
+        pos = torch.arange(B, dtype=torch.int32, device=dev)
+        out, xc_out, x0 = torch.empty_like(x_t), torch.empty_like(x_t), torch.empty_like(x_t)
+        bound = None if thr is None else self._x0_bound(x_t, eps, coef, pos, thr)
+        d = self._unipc_desc(x_t, eps, xc, slots[::-1], coef, corr, pos, 0, out=out, xc_out=xc_out, x0_out=x0, x0_bound=bound)
+        check(lib().dm3d_unipc_update(C.byref(d), torch.cuda.current_stream().cuda_stream), "unipc_update")
+        return out, xc_out, x0
+
+    def _unipc_table(self, src, rows, clip_x0):
+        """The two [n, 8] float32 tables of dm3d_unipc_desc from unipc_coefficients' float64 rows for the levels ``src``: coef =
+        (sqrt(a), sqrt(1-a), p_x, p_0, p_1, clip, p_2, rot) and corr = (k_x, k_0, k_1, k_2, k_t, 0, 0, 0), rounded once."""
+        coef, corr = np.zeros((len(src), 8), dtype=np.float64), np.zeros((len(src), 8), dtype=np.float64)
+        coef[:, :2] = ddim_coefficients(self.b.alpha_bar, src, np.full(len(src), -1, dtype=np.int64))[:, :2]
+        coef[:, 2:5], coef[:, 6], coef[:, 7] = rows[:, :3], rows[:, 3], rows[:, 9]
+        coef[:, 5] = 1.0 if clip_x0 else 0.0
+        corr[:, :5] = rows[:, 4:9]
+        return torch.from_numpy(coef.astype(np.float32)), torch.from_numpy(corr.astype(np.float32))
+
+    def _unipc_desc(self, x, eps, xc, slots, coef, corr, pos, mode, out=None, xc_out=None, x0_out=None, t_next=None, t_idx=None,
+                    x0_bound=None) -> UniPcDesc:
+        """A dm3d_unipc_desc; ``slots``: the three history slots in the descriptor's order (None: a null slot)."""
+        d = _fill(UniPcDesc(), x=x, eps=eps, xc=xc, out=out, xc_out=xc_out, x0_out=x0_out, coef=coef, corr=corr, pos=pos, t_next=t_next,
+                  t_idx=t_idx, x0_bound=x0_bound)
+        for k, s in enumerate(slots):
+            d.hist[k] = None if s is None else s.data_ptr()
+        d._keep += tuple(slots)
+        d.batch, d.per_sample, d.rows, d.mode = x.shape[0], x[0].numel(), coef.shape[0], mode
+        return d
+
     # -- dynamic thresholding of the x0 estimate ----------------------------------------------------------------------------------
     @staticmethod
     def _threshold_rules(B, per_sample, clip_x0, dynamic_threshold, threshold_max, kind=None):
@@ -604,8 +681,8 @@ class DiffusionModel:
             if threshold_max is not None:
                 raise ValueError("threshold_max needs dynamic_threshold")
             return None
-        if kind is not None and kind not in ("ddim", "dpmpp", "dpmpp_sde"):
-            raise ValueError("dynamic_threshold / threshold_max belong to sampler='ddim' and 'dpmpp'")
+        if kind is not None and kind not in ("ddim", "dpmpp", "dpmpp_sde", "unipc"):
+            raise ValueError("dynamic_threshold / threshold_max belong to sampler='ddim' and 'dpmpp' (and 'dpmpp_sde', 'unipc')")
         if not clip_x0:
             raise ValueError("dynamic_threshold needs clip_x0=True: it replaces the static clamp of the x0 estimate")
         return threshold_tables(B, per_sample, dynamic_threshold, threshold_max)
@@ -828,43 +905,63 @@ class DiffusionModel:
 
     def sampler(self, shape, context_value=None, *, seed=None, use_graph=True, kind="ddpm", num_steps=None, timesteps=None,
                 eta=0.0, clip_x0=True, guidance_scale=None, negative_context=None, guidance_rescale=0.0, solver_order=2,
-                lower_order_final=True, dynamic_threshold=None, threshold_max=None, sde_eta=None) -> "Sampler":
+                lower_order_final=True, dynamic_threshold=None, threshold_max=None, sde_eta=None, unipc_variant=None) -> "Sampler":
         """The state of one generate() call: plan, tables, context rows and the captured step graph.  There is one live
         Sampler per (batch, context mode): creating another one for the same plan retires the older (its step() raises).
         ``kind="ddim"``: a DDIM chain over ``ddim_timesteps(T, num_steps, timesteps)`` (S steps) with ``eta`` / ``clip_x0``.
         ``kind="dpmpp"``: a DPM-Solver++(2M) chain over the same schedule with ``clip_x0`` / ``solver_order`` / ``lower_order_final``.
         ``kind="dpmpp_sde"``: its stochastic form at ``sde_eta`` (None: 1.0), as generate(); step(noise=) injects a step's z.
+        ``kind="unipc"``: a UniPC chain over the same schedule with ``clip_x0`` / ``solver_order`` (1-3) / ``lower_order_final`` /
+        ``unipc_variant``, as generate().
         ``guidance_scale`` / ``negative_context`` / ``guidance_rescale``: a guided chain, as generate().
         ``dynamic_threshold`` / ``threshold_max``: a dynamically thresholded DDIM or DPM-Solver++ chain, as generate()."""
         shape = self._sampler_shape(shape)
         taus, opts = self._solver_rules(kind, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final,
-                                        dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape, sde_eta=sde_eta)
+                                        dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape, sde_eta=sde_eta,
+                                        unipc_variant=unipc_variant)
         ctx, guide = self._contexts(shape[0], context_value, guidance_scale, negative_context, guidance_rescale)
         return _chain_class(kind, False, bool(guide))(self, shape, ctx, seed, use_graph, taus, **opts, **guide)
 
     def _solver_rules(self, kind, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise=None, what="sampler kind",
-                      dynamic_threshold=None, threshold_max=None, shape=None, sde_eta=None):
+                      dynamic_threshold=None, threshold_max=None, shape=None, sde_eta=None, unipc_variant=None, edit=False):
         """The argument rules of the solvers ("dpmpp_sde": the DPM-Solver++ chain in its stochastic mode, ``sde_eta`` among its
         keywords), checked before any plan or device buffer is made.  Returns the chain's schedule
         (``kind="ddpm"``: every timestep) and the keywords its sampler class takes besides.  ``noise``: the caller's injected z.
         ``dynamic_threshold`` / ``threshold_max`` (with the chain's ``shape``) add ``threshold=`` (the host tables of
-        threshold_tables()) to those keywords; without them the keywords are what they always were."""
-        if kind not in ("ddpm", "ddim", "dpmpp", "dpmpp_sde"):
-            raise ValueError(f"{what} must be 'ddpm', 'ddim', 'dpmpp' or 'dpmpp_sde', got {kind!r}")
+        threshold_tables()) to those keywords; without them the keywords are what they always were.  ``unipc_variant`` (None: "bh2")
+        belongs to "unipc", which ``edit`` chains and zero-terminal-SNR models do not have."""
+        if kind not in ("ddpm", "ddim", "dpmpp", "dpmpp_sde", "unipc"):
+            raise ValueError(f"{what} must be 'ddpm', 'ddim', 'dpmpp', 'dpmpp_sde' or 'unipc', got {kind!r}")
         if kind == "ddpm" and self.zero_terminal_snr:
             raise ValueError("a zero_terminal_snr model has no DDPM ancestral chain (its posterior divides by alpha_bar[T-1] = 0): "
                              "use sampler='ddim', eta=1.0, or sampler='dpmpp_sde'")
-        sde = kind == "dpmpp_sde"
+        sde, unipc = kind == "dpmpp_sde", kind == "unipc"
         if sde_eta is not None and not sde:
-            raise ValueError("sde_eta belongs to sampler='dpmpp_sde'")
+            raise ValueError("sde_eta belongs to sampler='dpmpp_sde'" + (": sampler='unipc' is a deterministic solver" if unipc else ""))
+        if unipc_variant is not None and not unipc:
+            raise ValueError("unipc_variant belongs to sampler='unipc'")
+        if unipc:
+            if edit:
+                raise ValueError("edit(sampler='unipc') is not supported: where RePaint's replacement step goes between the corrector and "
+                                 "the predictor is undecided; use sampler='dpmpp'")
+            if self.zero_terminal_snr:
+                raise ValueError("sampler='unipc' needs a finite log-SNR at every level: a zero_terminal_snr model's start level has "
+                                 "lambda = -inf, which breaks the corrector's h; use sampler='dpmpp'")
+            if eta != 0:
+                raise ValueError("sampler='unipc' is a deterministic solver: eta must be 0 (sampler='ddim' takes eta, sampler='dpmpp_sde' is "
+                                 "the stochastic multistep solver)")
+            if noise is not None:
+                raise ValueError("sampler='unipc' draws no noise: noise= does not apply (x_T= sets the start; sampler='dpmpp_sde' draws)")
+            unipc_variant = "bh2" if unipc_variant is None else unipc_variant
+            _check_unipc(solver_order, unipc_variant)
         if sde:
             sde_eta = self._sde_eta_rules(1.0 if sde_eta is None else sde_eta)
         thr = None
         if dynamic_threshold is not None or threshold_max is not None:
             thr = self._threshold_rules(shape[0], int(np.prod(shape[1:])), clip_x0, dynamic_threshold, threshold_max, kind)
         thr = {} if thr is None else dict(threshold=thr)
-        if kind not in ("dpmpp", "dpmpp_sde") and (solver_order != 2 or lower_order_final is not True):
-            raise ValueError("solver_order / lower_order_final belong to sampler='dpmpp' and 'dpmpp_sde'")
+        if kind not in ("dpmpp", "dpmpp_sde", "unipc") and (solver_order != 2 or lower_order_final is not True):
+            raise ValueError("solver_order / lower_order_final belong to sampler='dpmpp' and 'dpmpp_sde' (and 'unipc')")
         if kind == "ddpm":
             if num_steps is not None or timesteps is not None or eta != 0.0 or clip_x0 is not True:
                 raise ValueError("num_steps / timesteps / eta / clip_x0 belong to sampler='ddim' and 'dpmpp'")
@@ -883,7 +980,9 @@ class DiffusionModel:
             raise ValueError("eta must be >= 0")
         if sde:
             thr = dict(thr, sde_eta=sde_eta)
-        if kind in ("dpmpp", "dpmpp_sde"):
+        if unipc:
+            thr = dict(thr, variant=unipc_variant)
+        if kind in ("dpmpp", "dpmpp_sde", "unipc"):
             return taus, dict(clip_x0=clip_x0, solver_order=solver_order, lower_order_final=lower_order_final, **thr)
         return taus, dict(eta=eta, clip_x0=clip_x0, **thr)
 
@@ -906,7 +1005,7 @@ class DiffusionModel:
     def generate(self, shape=(1, 16, 16, 16, 16), last_step=0, context_value=None, *, x_T=None, noise=None, seed=None,
                  use_graph=True, steps=None, sampler="ddpm", num_steps=None, timesteps=None, eta=0.0, clip_x0=True,
                  guidance_scale=None, negative_context=None, guidance_rescale=0.0, solver_order=2, lower_order_final=True,
-                 dynamic_threshold=None, threshold_max=None, sde_eta=None):
+                 dynamic_threshold=None, threshold_max=None, sde_eta=None, unipc_variant=None):
         """conditional_dm3d.py:550-575.  For shape[0] > 1 the single context row is broadcast to every sample.
         ``seed`` (optional): Philox key of x_T and of every step's noise; None (default) draws a fresh key per call, as the
         reference draws fresh tf.random.normal noise, an integer makes the call reproducible.
@@ -928,6 +1027,14 @@ class DiffusionModel:
         and must be 0.  ``solver_order`` / ``lower_order_final`` / ``clip_x0``, guidance and thresholding apply as for "dpmpp";
         ``noise`` is [S, *shape] with row k the z of the step from tau_k, as for DDIM (such a call runs eagerly); ``sde_eta`` with any
         other sampler is an error.  A zero_terminal_snr model runs the chain natively: its first step is alpha_t x0 + sigma_t z.
+        ``sampler="unipc"``: UniPC (Zhao et al. 2023; the data-prediction multistep form; include/dm3d.h, dm3d_unipc_desc) over the same
+        schedule, S U-Net evaluations like "dpmpp".  Each step predicts the next level at order p from the last p x0 estimates and,
+        once the U-Net has run there, corrects that level with the new estimate at no further U-Net pass: the accuracy order is p + 1.
+        ``solver_order`` = 1, 2 (default) or 3; step j of a chain (from 0) has order min(solver_order, j + 1), with ``lower_order_final``
+        (default) at most the number of steps left, and the step to the clean sample returns the x0 estimate.  ``unipc_variant`` = "bh2"
+        (None: the default) or "bh1" picks B(h) = expm1(-h) or -h; with any other sampler it is an error.  The solver is deterministic:
+        eta must be 0 and ``noise`` / ``sde_eta`` do not apply (``x_T`` / ``seed`` set the start); last_step must be 0.  ``clip_x0``,
+        guidance and thresholding apply as for "dpmpp".  edit() and zero_terminal_snr models do not have it: use "dpmpp" there.
         ``guidance_scale`` = w (None, the default: no guidance, today's path): classifier-free guidance, for either sampler.  Every
         step evaluates the U-Net under ``context_value`` and under ``negative_context`` (one id or one per volume; None stands for
         compile()'s ``null_context`` and is an error on a model without one) in one pass over a plan of 2 B rows and continues from eps_neg + w (eps_pos - eps_neg);
@@ -945,7 +1052,8 @@ class DiffusionModel:
             raise ValueError("last_step out of range")
         shape = self._sampler_shape(shape)
         taus, opts = self._solver_rules(sampler, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise,
-                                        dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape, sde_eta=sde_eta)
+                                        dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape, sde_eta=sde_eta,
+                                        unipc_variant=unipc_variant)
         if noise is not None and sampler != "ddpm" and tuple(noise.shape) != (len(taus),) + shape:      # (_run repeats it for every chain)
             raise ValueError(f"noise must be [S={len(taus)}, *shape] for sampler={sampler!r}")
         if sampler != "ddpm" and last_step != 0:
@@ -1013,11 +1121,13 @@ class DiffusionModel:
         other samplers, and the solver's history keeps the model's own x0 estimate, unblended.  ``noise`` does not apply.
         ``sampler="dpmpp_sde"`` / ``sde_eta``: the stochastic form of that chain, as generate(); ``noise`` / ``known_noise`` as for DDIM.
         ``dynamic_threshold`` / ``threshold_max``: dynamic thresholding of the chain's x0 estimate over the whole volume, as generate();
-        the blend follows the thresholded update."""
+        the blend follows the thresholded update.
+        ``sampler="unipc"`` is refused: where the replacement step goes between its corrector and predictor is undecided; use "dpmpp"."""
         x0 = torch.as_tensor(x0, dtype=torch.float32)
         shape = self._sampler_shape(x0.shape)
         sched, opts = self._solver_rules(sampler, num_steps, timesteps, eta, clip_x0, solver_order, lower_order_final, noise, what="sampler",
-                                         dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape, sde_eta=sde_eta)
+                                         dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, shape=shape, sde_eta=sde_eta,
+                                         edit=True)
         n = edit_steps(strength, len(sched))
         full, sched = n == len(sched), sched[:n]
         mask = None if mask is None else latent_mask(mask, shape)
@@ -1551,6 +1661,54 @@ class GuidedDpmEditSampler(_GuidedChain, DpmEditSampler):
     KIND = "dpmpp-edit-cfg"
 
 
+class UniPcSampler(DdimSampler):
+    """One UniPC chain over a fixed batch (Zhao et al. 2023; data prediction, multistep, "bh1" / "bh2"): S steps tau_{S-1} -> ... ->
+    tau_0 -> x0, one U-Net pass each, as a DPM-Solver++ chain.
+
+    It shares the DDIM chain's frame (plan.ddim_tau / ddim_next / ddim_pos and the row counter).  One launch of dm3d_unipc_update per
+    step, after the U-Net, the guidance and the threshold, forms the x0 estimate at the row's level, corrects that level's state with
+    it and predicts the next level from the corrected state.  plan.x carries the predicted states (what the U-Net sees), plan.unipc_xc
+    the corrected ones and plan.unipc_hist three x0 estimates (order 2 reads two of them); which slot plays which role at a row is
+    column 7 of plan.unipc_coef, so no pointer changes between replays.  reset() rewrites plan.unipc_coef and plan.unipc_corr: one
+    captured graph serves every schedule, order, variant, lower_order_final and clip.  Nothing is cleared between chains: a chain's
+    first row has no corrector and reads no history, and every later row reads only what its chain wrote."""
+
+    KIND = SOLVER = "unipc"
+    UPDATE = "unipc_update"
+    DRAWS = False
+
+    def __init__(self, model, shape, ctx_ids, seed, use_graph, taus, clip_x0=True, solver_order=2, lower_order_final=True, threshold=None,
+                 variant="bh2"):
+        _check_unipc(solver_order, variant)
+        if model.zero_terminal_snr:
+            raise ValueError("sampler='unipc' needs a finite log-SNR at every level, which a zero_terminal_snr model lacks: use sampler='dpmpp'")
+        self.solver_order, self.lower_order_final, self.variant = int(solver_order), bool(lower_order_final), variant
+        super().__init__(model, shape, ctx_ids, seed, use_graph, taus, eta=0.0, clip_x0=clip_x0, threshold=threshold)
+
+    def _desc(self, noise=None):
+        plan, T, dev = self._tables("unipc_coef"), self.model.timesteps, self.model.device
+        _plan_buffer(plan, "unipc_corr", lambda: torch.zeros(T, 8, dtype=torch.float32, device=dev))
+        _plan_buffer(plan, "unipc_xc", lambda: torch.zeros_like(plan.x))
+        _plan_buffer(plan, "unipc_hist", lambda: torch.zeros((3,) + tuple(plan.x.shape), dtype=torch.float32, device=dev))
+        h = self._head
+        return self.model._unipc_desc(self.x, h(plan.eps), h(plan.unipc_xc), [h(plan.unipc_hist[k]) for k in range(3)], plan.unipc_coef,
+                                      plan.unipc_corr, plan.ddim_pos, 1, t_next=plan.ddim_next, t_idx=plan.t_idx, x0_bound=self._bound())
+
+    def _coefficients(self, src, dst):
+        rows = unipc_coefficients(self.model.b.alpha_bar, self.taus, self.solver_order, self.lower_order_final, self.variant)
+        coef, self._corr_rows = self.model._unipc_table(src, rows, self.clip_x0)
+        return self.plan.unipc_coef, coef
+
+    def _schedule(self):
+        super()._schedule()
+        if self.n_steps > 0:
+            self.plan.unipc_corr[:self.n_steps].copy_(self._corr_rows)
+
+
+class GuidedUniPcSampler(_GuidedChain, UniPcSampler):
+    KIND = "unipc-cfg"
+
+
 # (generate()'s ``sampler=``, edit chain?, guided?) -> the chain's class: the one place that picks it ("dpmpp_sde" is the "dpmpp"
 # classes' stochastic mode, not a class: _chain_class maps the name)
 _CHAINS = {(c.SOLVER, issubclass(c, _EditChain), issubclass(c, _GuidedChain)): c
@@ -1558,6 +1716,11 @@ _CHAINS = {(c.SOLVER, issubclass(c, _EditChain), issubclass(c, _GuidedChain)): c
                      GuidedDpmSampler, GuidedEditSampler, GuidedDdimEditSampler, GuidedDpmEditSampler)}
 
 
+# UniPC's chains, in a table of their own beside the twelve the three earlier solvers share: it has no edit form
+_UNIPC_CHAINS = {(c.SOLVER, issubclass(c, _EditChain), issubclass(c, _GuidedChain)): c for c in (UniPcSampler, GuidedUniPcSampler)}
+
+
 def _chain_class(sampler, edit, guided):
     """The chain class of a public sampler name: "dpmpp_sde" runs the "dpmpp" classes (with ``sde_eta`` among their keywords)."""
-    return _CHAINS["dpmpp" if sampler == "dpmpp_sde" else sampler, edit, guided]
+    key = "dpmpp" if sampler == "dpmpp_sde" else sampler, edit, guided
+    return _UNIPC_CHAINS[key] if key in _UNIPC_CHAINS else _CHAINS[key]

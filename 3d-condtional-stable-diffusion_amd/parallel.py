@@ -73,7 +73,7 @@ def generate_sharded(model, global_shape, last_step: int = 0, context_value=None
     left out stands for the model's ``null_context`` on every rank, as in generate().  Which weights a rank samples from is the
     model's own use_ema() setting; the averages of data-parallel replicas agree as their weights do, so no collective carries them.
     ``sampler="dpmpp_sde"`` / ``sde_eta`` are forwarded like every sampler keyword: one noise level for the whole batch, each rank's
-    draws under its own key."""
+    draws under its own key.  ``sampler="unipc"`` / ``unipc_variant`` likewise: the chain is deterministic, each rank's x_T under its key."""
     shape = tuple(int(s) for s in global_shape)
     dist_on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)

@@ -122,6 +122,108 @@ def dpm_sde_coefficients(alpha_bar, src, dst, prev, order=2, eta=1.0) -> np.ndar
     return out
 
 
+UNIPC_VARIANTS = ("bh1", "bh2")
+
+
+def _check_unipc(order, variant):
+    if order not in (1, 2, 3):
+        raise ValueError(f"solver_order must be 1, 2 or 3 for sampler='unipc', got {order!r}")
+    if variant not in UNIPC_VARIANTS:
+        raise ValueError(f"unipc_variant must be 'bh1' or 'bh2', got {variant!r}")
+
+
+def unipc_orders(n: int, order=2, lower_order_final=True) -> np.ndarray:
+    """The order of every row of an n-row UniPC chain (row n-1 runs first, row 0 is the step to clean): step j = n-1-r, counted from
+    the start, has order min(``order``, j+1), and with ``lower_order_final`` at most the number of steps left, itself included.  The
+    steps counted are those between levels, r of them at row r: the step to clean returns the x0 estimate and has no order to lower.
+    So the step into the schedule's lowest level (row 1) is first order, as in the DPM-Solver++ chain and for its reason: that step
+    crosses a log-SNR gap several times the one before it."""
+    r = np.arange(int(n), dtype=np.int64)
+    p = np.minimum(int(order), n - r)
+    return np.minimum(p, np.maximum(r, 1)) if lower_order_final else p
+
+
+def unipc_system(alpha_bar, s, t, earlier, variant="bh2"):
+    """What the predictor and the corrector of one UniPC step from level ``s`` to level ``t`` share (Zhao et al. 2023; the
+    data-prediction form), in float64: (sigma_t/sigma_s, alpha_t, phi1, B, r, R, b) with h = lambda_t - lambda_s, hh = -h,
+    phi1 = expm1(hh), B = hh ("bh1") or expm1(hh) ("bh2"), r_k = (lambda_{earlier[k-1]} - lambda_s) / h for the p-1 ``earlier`` levels,
+    R the p x p matrix with rows (r_1^(i-1), ..., r_{p-1}^(i-1), 1) and b_i = g_i i! / B, g_1 = phi1/hh - 1, g_{i+1} = g_i/hh - 1/(i+1)!."""
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    lam = lambda i: 0.5 * (math.log(ab[i]) - math.log1p(-ab[i]))
+    h = lam(t) - lam(s)
+    hh = -h
+    phi1 = math.expm1(hh)
+    B = hh if variant == "bh1" else phi1
+    r = np.array([(lam(e) - lam(s)) / h for e in earlier] + [1.0])
+    p = len(r)
+    R = np.stack([r ** i for i in range(p)])
+    g, fact, b = phi1 / hh - 1.0, 1.0, []
+    for i in range(1, p + 1):
+        b.append(g * fact / B)
+        fact *= i + 1
+        g = g / hh - 1.0 / fact
+    return math.sqrt((1 - ab[t]) / (1 - ab[s])), math.sqrt(ab[t]), phi1, B, r, R, np.array(b)
+
+
+def unipc_predictor(alpha_bar, s, t, earlier=(), variant="bh2") -> np.ndarray:
+    """float64 (p_x, p_0, p_1, p_2) of the UniPC predictor of order p = 1 + len(``earlier``) from level ``s`` to level ``t`` (t < 0:
+    clean, (0, 1, 0, 0) exactly): x_t = p_x x_s + p_0 m_0 + p_1 m_1 + p_2 m_2, m_0 the x0 estimate at s and m_k that at earlier[k-1].
+    It is x_t = (sigma_t/sigma_s) x_s - alpha_t phi1 m_0 - alpha_t B sum_k rho_k (m_k - m_0) / r_k collapsed, with rho = (1/2) at
+    p = 2 and the solution of the leading 2 x 2 system of unipc_system's (R, b) at p = 3; p = 1 is the DDIM eta = 0 step."""
+    out = np.zeros(4)
+    if t < 0:
+        out[1] = 1.0
+        return out
+    if len(earlier) > 2:
+        raise ValueError("the predictor's order is at most 3")
+    c_x, a_t, phi1, B, r, R, b = unipc_system(alpha_bar, s, t, earlier, variant)
+    rho = np.zeros(0) if len(earlier) == 0 else np.array([0.5]) if len(earlier) == 1 else np.linalg.solve(R[:2, :2], b[:2])
+    w = a_t * B * rho / r[:-1]
+    out[0], out[1] = c_x, -a_t * phi1 + w.sum()
+    out[2:2 + len(w)] = -w
+    return out
+
+
+def unipc_corrector(alpha_bar, s, t, earlier=(), variant="bh2") -> np.ndarray:
+    """float64 (k_x, k_0, k_1, k_2, k_t) of the UniPC corrector of order p = 1 + len(``earlier``) at level ``t``, reached from level
+    ``s``: x_t^c = k_x x_s + k_0 m_0 + k_1 m_1 + k_2 m_2 + k_t m_t, x_s the corrected state at s, m_t the x0 estimate the network
+    gave on the predicted state at t.  It is x_t^c = (sigma_t/sigma_s) x_s - alpha_t phi1 m_0 - alpha_t B (sum_k rho_k (m_k - m_0) / r_k
+    + rho_p (m_t - m_0)) collapsed, with rho = (1/2) at p = 1 and else the solution of unipc_system's R rho = b."""
+    if len(earlier) > 2:
+        raise ValueError("the corrector's order is at most 3")
+    c_x, a_t, phi1, B, r, R, b = unipc_system(alpha_bar, s, t, earlier, variant)
+    rho = np.array([0.5]) if len(earlier) == 0 else np.linalg.solve(R, b)
+    w = a_t * B * rho / r                                        # (r_p = 1: the last entry is alpha_t B rho_p)
+    out = np.zeros(5)
+    out[0], out[1] = c_x, -a_t * phi1 + w.sum()
+    out[2:2 + len(w) - 1] = -w[:-1]
+    out[4] = -w[-1]
+    return out
+
+
+def unipc_coefficients(alpha_bar, taus, order=2, lower_order_final=True, variant="bh2") -> np.ndarray:
+    """float64 [n, 10] rows (p_x, p_0, p_1, p_2, k_x, k_0, k_1, k_2, k_t, rot) of a UniPC chain over the schedule ``taus`` = tau_0 <
+    ... < tau_{n-1} (include/dm3d.h, dm3d_unipc_desc): row r belongs to the launch after the U-Net pass at tau_r (row n-1 runs
+    first).  Columns 0-3 are unipc_predictor's for the step tau_r -> tau_{r-1} (row 0: to clean) at the order unipc_orders gives the
+    row; columns 4-8 unipc_corrector's at tau_r, reached from tau_{r+1}, at the order of the predictor that produced tau_r (row r+1's),
+    all zero (no corrector) in row n-1, which nothing precedes, and in row 0, whose result is the x0 estimate alone.  rot = (n-1-r) % 3 is
+    the history slot the row's estimate goes to.  A level with alpha_bar = 0 has no finite lambda and is an error."""
+    _check_unipc(order, variant)
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    taus = np.asarray(taus, dtype=np.int64).reshape(-1)
+    if np.any(ab[taus] <= 0):
+        raise ValueError("sampler='unipc' needs alpha_bar > 0 at every level of the schedule (lambda = -inf breaks the corrector's h)")
+    n = len(taus)
+    orders = unipc_orders(n, order, lower_order_final)
+    out = np.zeros((n, 10), dtype=np.float64)
+    for r in range(n):
+        out[r, :4] = unipc_predictor(ab, taus[r], taus[r - 1] if r > 0 else -1, taus[r + 1:r + orders[r]], variant)
+        if 0 < r < n - 1:
+            out[r, 4:9] = unipc_corrector(ab, taus[r + 1], taus[r], taus[r + 2:r + 1 + orders[r + 1]], variant)
+        out[r, 9] = (n - 1 - r) % 3
+    return out
+
+
 def threshold_rank(per_sample: int, ratio) -> tuple:
     """(i, f) of the dynamic threshold's quantile (include/dm3d.h, dm3d_thresh_desc): q = ratio (N-1) in float64, i = floor(q) and
     f = float32(q - i), the weight of v_{i+1} in the interpolation between the order statistics v_i and v_{i+1} of N = per_sample

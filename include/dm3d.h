@@ -27,7 +27,7 @@ extern "C" {
                                      dm3d_pack_weights_h3f8 are gone; the Winograd-x image pairs its taps differently; dm3d_mlp_fused; conv skip_wpk_frag, gn_stats; dm3d_groupnorm_finalize2), 110 (dm3d_attn_front), 111 (conv split_counters: the Cin split
                                      meets inside the launch; dm3d_conv_split_counter_words); dm3d_ddim_update / dm3d_ddim_desc, dm3d_edit_update / dm3d_edit_desc,
                                      dm3d_guide_update / dm3d_guide_desc, dm3d_dpm_update / dm3d_dpm_desc and dm3d_x0_threshold / dm3d_thresh_desc were added within 111 (no existing entry changed; dm3d_ddim_desc and dm3d_dpm_desc grew by one trailing optional pointer, x0_bound, which a zeroed descriptor leaves NULL; dm3d_thresh_desc then by one, frame, likewise, and dm3d_ddim_update_frame / dm3d_dpm_update_frame are new entries),
-                                     and dm3d_pred_to_eps / dm3d_pred_desc, dm3d_objective_loss_grad / dm3d_loss_desc and dm3d_dpm_sde_update(_frame) / dm3d_dpm_sde_desc and dm3d_grad_scale / dm3d_gradscale_desc / dm3d_adam_scaled likewise (new entries and structs only): a host built against an older header must be rebuilt */
+                                     and dm3d_pred_to_eps / dm3d_pred_desc, dm3d_objective_loss_grad / dm3d_loss_desc and dm3d_dpm_sde_update(_frame) / dm3d_dpm_sde_desc and dm3d_grad_scale / dm3d_gradscale_desc / dm3d_adam_scaled and dm3d_unipc_update / dm3d_unipc_desc likewise (new entries and structs only): a host built against an older header must be rebuilt */
 
 #define DM3D_OK            0
 #define DM3D_EINVAL       -1      /* bad argument (shape, alignment, null pointer) */
@@ -572,6 +572,50 @@ typedef struct dm3d_dpm_sde_desc {
 
 int dm3d_dpm_sde_update(const dm3d_dpm_sde_desc* d, void* stream);
 int dm3d_dpm_sde_update_frame(const dm3d_dpm_sde_desc* d, const float* frame, void* stream);
+
+/* ---- UniPC step over a timestep schedule (Zhao et al. 2023, "UniPC"): corrector and predictor in one launch ------------------------
+ * The data-prediction, multistep form ("bh1" / "bh2").  After the U-Net has run on the predicted state x at the row's level s, one
+ * launch forms the x0 estimate m there (dm3d_dpm_update's: the float32 order, the clamp, x0_bound), corrects the state at s with it
+ * (the corrector reuses the evaluation the next step needs anyway) and predicts the state at the next level t from the corrected one.
+ * Both updates are linear in their inputs; the host folds each into coefficients, in float64 from the float32 alpha_bar table, rounded
+ * once to float32 (schedules.py, unipc_coefficients).  With h0, h1, h2 the x0 estimates of the one, two and three levels before s
+ * and xc the corrected state of the level before:
+ *   m    = clip ? bounded((x - sigma_s*eps) / alpha_s) : (x - sigma_s*eps) / alpha_s
+ *   xc'  = (((k_x*xc + k_0*h0) + k_1*h1) + k_2*h2) + k_t*m       the corrector; k_t == 0: there is none and xc' = x bitwise
+ *   res  = ((p_x*xc' + p_0*m) + p_1*h0) + p_2*h1                 the predictor; to "clean" (0, 1, 0, 0): res = m
+ * in float32, in that order, each operation rounded.  A term whose coefficient is 0 is skipped and its buffer is not read: k_x for xc,
+ * k_0 and p_1 for h0, k_1 and p_2 for h1, k_2 for h2 (dm3d_dpm_update's rule for c_1: stale history and a NaN in it never reach a
+ * chain, whose first row has none of these).
+ * The history is three slots hist[0..2]; column 7 of the row, rot in {0, 1, 2} (clamped), says which slot plays which role: h0 is
+ * hist[(rot+2)%3], h1 hist[(rot+1)%3], h2 hist[rot], and m goes to hist[rot] (a lane reads its 16 bytes of every slot before it
+ * stores).  A chain advances rot by one per row, so no host pointer swap happens between replays of a captured step.
+ *   mode 0 (DiffusionModel.unipc_step): out = res and, where set, xc_out = xc', x0_out = m; x, xc and hist are left untouched.
+ *   mode 1 (generate):                  x <- res, xc <- xc', hist[rot] <- m; xc and all three slots are required.
+ * Graph-capturable without host reads, as dm3d_dpm_desc: the row comes from device memory and, with t_idx set, the kernel writes
+ * t_idx[b] = t_next[pos[b]] (the kernel does not read t_idx).  There is no noise term and no frame form.
+ * Checked before the launch (DM3D_EINVAL): x, eps, coef, corr, pos non-NULL; every tensor and both tables 16-byte aligned; per_sample
+ * a positive multiple of 4; batch in [1, 65535]; rows > 0; the mode's required pointers; no two of x, eps, xc, the slots and the outputs
+ * sharing a byte. */
+typedef struct dm3d_unipc_desc {
+    float* x;                   /* [batch, per_sample] the predicted state at the row's level (mode 1: becomes the next level's) */
+    const float* eps;           /* predicted noise on x */
+    float* xc;                  /* the corrected state of the level before, same shape (mode 1: required, replaced by this level's) */
+    float* hist[3];             /* the x0 estimates of the three levels before, same shape each (mode 0: those a row reads; mode 1: all) */
+    float* out;                 /* mode 0: the predicted state at the next level, same shape */
+    float* xc_out;              /* mode 0, optional: the corrected state at this level */
+    float* x0_out;              /* mode 0, optional: this level's x0 estimate */
+    int32_t batch; int64_t per_sample;     /* batch <= 65535, per_sample % 4 == 0 */
+    const float* coef;          /* [rows][8] device: sqrt(a), sqrt(1-a), p_x, p_0, p_1, clip (nonzero: clamp x0), p_2, rot */
+    const float* corr;          /* [rows][8] device: k_x, k_0, k_1, k_2, k_t, 0, 0, 0 */
+    int32_t rows;               /* pos[b] is clamped to [0, rows) before any table is indexed */
+    const int32_t* pos;         /* [batch] device: the row of each sample */
+    const int32_t* t_next;      /* [rows] device, optional: the timestep the step after row r evaluates */
+    int32_t* t_idx;             /* [batch] device, optional: receives t_next[pos[b]] */
+    int32_t mode;
+    const float* x0_bound;      /* optional [batch] device: the dynamic threshold s, as dm3d_dpm_desc.x0_bound.  NULL: the static clamp. */
+} dm3d_unipc_desc;
+
+int dm3d_unipc_update(const dm3d_unipc_desc* d, void* stream);
 
 /* ---- Dynamic thresholding of the x0 estimate (Saharia et al. 2022, "Imagen", section 2.3) ------------------------------------------
  * Between the U-Net (or the guidance) and dm3d_ddim_update / dm3d_dpm_update: the bound s the update clamps and divides the x0
