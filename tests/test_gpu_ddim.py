@@ -1,15 +1,15 @@
 """GPU tier of the DDIM sampler (dm3d_ddim_update, DiffusionModel.generate(sampler="ddim"), invert, ddim_step).
 
-The float64 reference is this file's own restatement of the DDIM update (Song et al., eq. 12) with eps from the CPU oracle
+The float64 reference is tests/chain_reference.py's restatement of the DDIM update (Song et al., eq. 12) with eps from the CPU oracle
 (oracle.ref_torch.unet_forward) and alpha_bar from the oracle's float32 Betas table, the table the kernels read.
 """
-import math
 import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
+
+import chain_reference as cr
 
 pytestmark = pytest.mark.gpu
 CHAIN_BAR = 2e-3        # the existing chain tests' bar (values in [-1, 1] + noise)
@@ -24,65 +24,20 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _args(T, bs=1):
-    return SimpleNamespace(timesteps=T, num_gpus=1, kernel_resize=False, bs=bs)
-
-
-def _schedule(T, S):
-    return [T - 1] if S == 1 else [int(math.floor(i * (T - 1) / (S - 1) + 0.5)) for i in range(S)]
-
-
-def _ddim64(x, eps, a, ap, eta=0.0, z=None, clip=True):
-    """One DDIM step in float64: x at alpha_bar a -> alpha_bar ap (1: the x0 estimate)."""
-    x, eps = x.double(), eps.double()
-    x0 = (x - math.sqrt(1 - a) * eps) / math.sqrt(a)
-    if clip:
-        x0 = x0.clamp(-1, 1)
-    sigma = eta * math.sqrt((1 - ap) / (1 - a)) * math.sqrt(1 - a / ap) if eta else 0.0
-    out = math.sqrt(ap) * x0 + math.sqrt(max(1 - ap - sigma * sigma, 0.0)) * eps
-    return out + sigma * z.double() if sigma else out
-
-
-def _cond_model(T, B, size=8, C=4, **kw):
-    import dm3d_amd
-    from dm3d_amd.networks import conditional_dm3d as cdm
-    cfg = dm3d_amd.UNetConfig(img_size=size, img_channels=C)
-    W = dm3d_amd.synthetic_weights(cfg, seed=0)
-    return cdm.DiffusionModel(size, 1024, C, None, _args(T, B), weights=W, **kw), W
-
-
-def _oracle(W, size, C, conditional=True):
-    from oracle import ref_torch as rt
-    ocfg = rt.UNetConfig(img_size=size, img_channels=C, conditional=conditional)
-    Wt = {k: torch.from_numpy(v) for k, v in W.items()}
-    return lambda x, t, ctx=None: rt.unet_forward(Wt, ocfg, x.float(), torch.full((x.shape[0],), int(t), dtype=torch.int64), ctx)
-
-
-def _chain64(eps_fn, ab, taus, x_T, eta=0.0, noise=None, clip=True, steps=None):
-    x = x_T.double()
-    for n, k in enumerate(range(len(taus) - 1, -1, -1)):
-        if steps is not None and n == steps:
-            break
-        a, ap = float(ab[taus[k]]), (float(ab[taus[k - 1]]) if k > 0 else 1.0)
-        x = _ddim64(x, eps_fn(x, taus[k]), a, ap, eta, None if noise is None else noise[k], clip)
-    return x
-
-
 @pytest.mark.parametrize("B", [1, 3])
 @pytest.mark.parametrize("clip", [True, False])
 @pytest.mark.parametrize("eta", [0.0, 0.5, 1.0])
 def test_kernel_matches_float64_restatement(dev, eta, clip, B):
     """ddim_step (mode 0) on random x / eps / injected z: interior steps and the k = 0 step (t_prev = -1), per-sample t."""
-    from oracle import ref_torch as rt
     T = 1000
-    m, _ = _cond_model(T, B)
-    ab = rt.Betas(T).alpha_bar.double()
+    m, _ = cr.cond_model(T, B)
+    ab = cr.oracle_alpha_bar(T).double()
     g = torch.Generator().manual_seed(17 + B)
     shape = (B, 8, 8, 8, 4)
     x, e, z = (torch.randn(shape, generator=g) for _ in range(3))
     for t, tp in (([500, 999, 20][:B], [480, 979, -1][:B]), ([5, 0, 1][:B], [-1, -1, 0][:B])):
         got = m.ddim_step(x, e, torch.tensor(t), torch.tensor(tp), eta, noise=z, clip_x0=clip).cpu()
-        ref = torch.stack([_ddim64(x[b], e[b], float(ab[t[b]]), float(ab[tp[b]]) if tp[b] >= 0 else 1.0, eta, z[b], clip)
+        ref = torch.stack([cr.ddim64(x[b], e[b], float(ab[t[b]]), float(ab[tp[b]]) if tp[b] >= 0 else 1.0, eta, z[b], clip)
                            for b in range(B)])
         assert float(ref.abs().max()) < 20                              # O(1) values: the bar is absolute
         err = float((got.double() - ref).abs().max())
@@ -99,7 +54,7 @@ def test_eta_one_full_schedule_equals_sample(dev):
     with each other: 1 - alpha_bar_t / alpha_bar_{t-1} in float32 holds beta_t to ~1e-3 relative at t = 1, so the identity is checked
     where they resolve beta, t >= 250 of T = 1000.)"""
     T, B = 1000, 2
-    m, _ = _cond_model(T, B)
+    m, _ = cr.cond_model(T, B)
     g = torch.Generator().manual_seed(3)
     shape = (B, 8, 8, 8, 4)
     x, e, z = (torch.randn(shape, generator=g) for _ in range(3))
@@ -114,7 +69,7 @@ def test_philox_draws(dev):
     """x = eps = 0 leaves out = sigma z: the in-kernel draws repeat per seed, differ across seeds and timesteps, and are N(0, 1)."""
     from dm3d_amd.diffusion import ddim_coefficients
     T = 1000
-    m, _ = _cond_model(T, 4)
+    m, _ = cr.cond_model(T, 4)
     shape = (4, 32, 32, 32, 8)                                              # 1 048 576 draws
     zero = torch.zeros(shape, device=dev)
     a = m.ddim_step(zero, zero, 500, 480, 1.0, seed=11)
@@ -134,17 +89,16 @@ def test_philox_draws(dev):
 @pytest.mark.parametrize("eta", [0.0, 0.5])
 def test_conditional_chain_matches_float64(dev, eta):
     """8^3 x 4ch, T = 20, S = 5, B = 2 with both context ids (one per volume); eta = 0.5 with injected noise."""
-    from oracle import ref_torch as rt
     T, S, B = 20, 5, 2
-    m, W = _cond_model(T, B)
+    m, W = cr.cond_model(T, B)
     g = torch.Generator().manual_seed(21)
     shape = (B, 8, 8, 8, 4)
     x_T = torch.randn(shape, generator=g)
     noise = torch.randn((S,) + shape, generator=g) if eta else None
     ids = torch.tensor([[[1]], [[0]]])
     got = m.generate(shape, context_value=ids, x_T=x_T, noise=noise, sampler="ddim", num_steps=S, eta=eta).cpu()
-    f = _oracle(W, 8, 4)
-    ref = _chain64(lambda x, t: f(x, t, ids), rt.Betas(T).alpha_bar.double(), _schedule(T, S), x_T, eta, noise)
+    f = cr.oracle(W)
+    ref = cr.chain64(lambda x, t: f(x, t, ids), cr.oracle_alpha_bar(T).double(), cr.schedule(T, S), x_T, "ddim", eta=eta, noise=noise)
     err = float((got.double() - ref).abs().max())
     print(f"DDIM chain eta={eta}: max abs difference {err:.2e}")
     assert err < CHAIN_BAR
@@ -155,32 +109,26 @@ def test_conditional_chain_matches_float64(dev, eta):
 
 def test_unconditional_config1_chain(dev):
     """BASELINE config 1 (dm3d.py U-Net, 16^3 x 4ch, B = 1), T = 50, S = 10, eta = 0: the whole chain against float64."""
-    import dm3d_amd
-    from dm3d_amd.networks import dm3d
-    from oracle import ref_torch as rt
     T, S = 50, 10
-    cfg = dm3d_amd.UNetConfig(img_size=16, img_channels=4, conditional=False)
-    W = dm3d_amd.synthetic_weights(cfg, seed=0)
-    m = dm3d.DiffusionModel(16, 1024, 4, None, _args(T), weights=W)
+    m, W = cr.uncond_model(T, size=16)
     x_T = torch.randn((1, 16, 16, 16, 4), generator=torch.Generator().manual_seed(4))
     got = m.generate((1, 16, 16, 16, 4), x_T=x_T, sampler="ddim", num_steps=S).cpu()
-    f = _oracle(W, 16, 4, conditional=False)
-    ref = _chain64(f, rt.Betas(T).alpha_bar.double(), _schedule(T, S), x_T)
+    f = cr.oracle(W, 16, conditional=False)
+    ref = cr.chain64(f, cr.oracle_alpha_bar(T).double(), cr.schedule(T, S), x_T, "ddim")
     assert float((got.double() - ref).abs().max()) < CHAIN_BAR
 
 
 def test_inversion_matches_float64(dev):
     """invert(): S - 1 deterministic steps tau_0 -> tau_{S-1} (sigma = 0, no clip), 8^3 x 4ch conditional, S = 5."""
-    from oracle import ref_torch as rt
     T, S, B = 20, 5, 2
-    m, W = _cond_model(T, B)
+    m, W = cr.cond_model(T, B)
     x0 = torch.rand((B, 8, 8, 8, 4), generator=torch.Generator().manual_seed(5)) * 2 - 1
     got = m.invert(x0, 1, num_steps=S).cpu()
-    ab, taus, f = rt.Betas(T).alpha_bar.double(), _schedule(T, S), _oracle(W, 8, 4)
+    ab, taus, f = cr.oracle_alpha_bar(T).double(), cr.schedule(T, S), cr.oracle(W)
     ctx = torch.tensor([[[1]]])
     x = x0.double()
     for i in range(S - 1):
-        x = _ddim64(x, f(x, taus[i], ctx), float(ab[taus[i]]), float(ab[taus[i + 1]]), clip=False)
+        x = cr.ddim64(x, f(x, taus[i], ctx), float(ab[taus[i]]), float(ab[taus[i + 1]]), clip=False)
     assert float((got.double() - x).abs().max()) < CHAIN_BAR
     assert torch.equal(m.invert(x0, 1, num_steps=1).cpu(), x0)             # S = 1: no step
     eager = m.invert(x0, 1, num_steps=S, use_graph=False).cpu()
@@ -191,7 +139,7 @@ def test_graph_equals_eager_and_kinds_do_not_leak(dev):
     """A seeded DDIM chain is bitwise equal through the graph and eagerly, for two schedules through the one cached graph; a DDPM
     generate() on the same model afterwards equals one on a fresh model (graph cache and plan state are kept apart)."""
     T, B = 20, 2
-    m, _ = _cond_model(T, B)
+    m, _ = cr.cond_model(T, B)
     shape = (B, 8, 8, 8, 4)
     for kw in (dict(num_steps=5, eta=0.5), dict(timesteps=[0, 3, 11, 19], eta=1.0, clip_x0=False), dict(num_steps=20)):
         a = m.generate(shape, context_value=0, seed=5, sampler="ddim", use_graph=True, **kw)
@@ -202,7 +150,7 @@ def test_graph_equals_eager_and_kinds_do_not_leak(dev):
     d = m.generate(shape, context_value=0, seed=6, sampler="ddim", num_steps=5, eta=0.5)
     assert not torch.equal(d, m.generate(shape, context_value=0, seed=5, sampler="ddim", num_steps=5, eta=0.5))
     ddpm = m.generate(shape, context_value=0, seed=5)
-    fresh, _ = _cond_model(T, B)
+    fresh, _ = cr.cond_model(T, B)
     torch.cuda.synchronize()
     assert torch.equal(ddpm, fresh.generate(shape, context_value=0, seed=5))
     # and a DDIM chain after the DDPM one still replays its own graph
@@ -225,7 +173,7 @@ def test_shards_equal_the_whole_batch(dev):
     U-Net evaluations and is held to 1e-4."""
     from dm3d_amd import parallel
     T = 50
-    m, _ = _cond_model(T, 4, size=16, C=8)
+    m, _ = cr.cond_model(T, 4, size=16, C=8)
     shape = (4, 16, 16, 16, 8)
     x_T = torch.randn(shape, generator=torch.Generator().manual_seed(8))
     for steps, bar in ((1, 2e-6), (None, 1e-4)):
@@ -239,15 +187,14 @@ def test_shards_equal_the_whole_batch(dev):
 def test_full_size_steps_match_oracle_and_b32_chain(dev):
     """32^3 x 8ch (h3): three DDIM steps of the S = 50 schedule at B = 2 against the oracle; a whole S = 50 chain of B = 32 through the
     graph is finite with the range guard quiet."""
-    from oracle import ref_torch as rt
     T, S, B, C = 1000, 50, 2, 8
-    m, W = _cond_model(T, B, size=32, C=C, precision="h3")
+    m, W = cr.cond_model(T, B, size=32, C=C, precision="h3")
     shape = (B, 32, 32, 32, C)
     x_T = torch.randn(shape, generator=torch.Generator().manual_seed(12))
     ids = torch.tensor([[[1]], [[0]]])
     got = m.generate(shape, context_value=ids, x_T=x_T, sampler="ddim", num_steps=S, steps=3).cpu()
-    f = _oracle(W, 32, C)
-    ref = _chain64(lambda x, t: f(x, t, ids), rt.Betas(T).alpha_bar.double(), _schedule(T, S), x_T, steps=3)
+    f = cr.oracle(W, 32, C)
+    ref = cr.chain64(lambda x, t: f(x, t, ids), cr.oracle_alpha_bar(T).double(), cr.schedule(T, S), x_T, "ddim", steps=3)
     err = float((got.double() - ref).abs().max())
     print(f"3 full-size DDIM steps: max abs difference {err:.2e}, max |x| {float(ref.abs().max()):.3f}")
     # near t = T-1 the x0 estimate is clipped almost everywhere and a step hands eps on to x with weight a_eps ~ 1 (the DDPM posterior
@@ -256,10 +203,7 @@ def test_full_size_steps_match_oracle_and_b32_chain(dev):
     # an untrained network is no denoiser: near t = T-1 a DDIM step hands eps on to x at weight ~1, and these synthetic weights have an
     # eps gain of ~3.5 per step (max |x| 4.5 -> 200 in the three steps above), so the chain would grow geometrically (the DDPM chain is
     # held by its clipped mean).  With the output conv scaled by 0.1 the gain stays below 1, as a trained eps-network's does.
-    Wb = dict(W, **{k: W[k] * np.float32(0.1) for k in ("out.conv.kernel", "out.conv.bias")})
-    import dm3d_amd
-    from dm3d_amd.networks import conditional_dm3d as cdm
-    big = cdm.DiffusionModel(32, 1024, C, None, _args(T, 32), weights=Wb, precision="h3")
+    big, _ = cr.cond_model(T, 32, size=32, C=C, W=cr.weights(32, C, scale=0.1), precision="h3")
     out = big.generate((32, 32, 32, 32, C), context_value=1, seed=7, sampler="ddim", num_steps=S)   # check_range raises if flagged
     torch.cuda.synchronize()
     assert torch.isfinite(out).all() and float(out.abs().max()) <= 1.0 + 1e-6

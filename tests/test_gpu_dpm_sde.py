@@ -1,17 +1,18 @@
 """GPU tier of the stochastic DPM-Solver++(2M) sampler (dm3d_dpm_sde_update, DiffusionModel.dpm_step(sde_eta=), generate / edit /
 sampler with "dpmpp_sde").
 
-The float64 reference is this file's own restatement of the update (Lu et al. 2022, the SDE form of DPM-Solver++(2M) in the midpoint
-form) with the network from the CPU oracle (oracle.ref_torch.unet_forward) and alpha_bar from the float32 table
-the kernels read.
+The float64 reference is tests/chain_reference.py's restatement of the update (Lu et al. 2022, the SDE form of DPM-Solver++(2M) in the
+midpoint form) with the network from the CPU oracle (oracle.ref_torch.unet_forward) and alpha_bar from the
+float32 table the kernels read.
 """
 import math
 import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
+
+import chain_reference as cr
 
 pytestmark = pytest.mark.gpu
 CHAIN_BAR = 2e-3        # the existing chain tests' bar (values in [-1, 1] + noise)
@@ -32,131 +33,6 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _args(T, bs=1):
-    return SimpleNamespace(timesteps=T, num_gpus=1, kernel_resize=False, bs=bs)
-
-
-def _schedule(T, S):
-    return [T - 1] if S == 1 else [int(math.floor(i * (T - 1) / (S - 1) + 0.5)) for i in range(S)]
-
-
-def _weights(scale=1.0):
-    import dm3d_amd
-    W = dm3d_amd.synthetic_weights(dm3d_amd.UNetConfig(img_size=8, img_channels=4), seed=0)
-    if scale != 1.0:
-        W = dict(W, **{k: W[k] * np.float32(scale) for k in ("out.conv.kernel", "out.conv.bias")})
-    return W
-
-
-def _cond_model(T, B, W=None, **kw):
-    from dm3d_amd.networks import conditional_dm3d as cdm
-    return cdm.DiffusionModel(8, 1024, 4, None, _args(T, B), weights=_weights() if W is None else W, **kw)
-
-
-_ORACLES = {}
-
-
-def _oracle(W, key, conditional=True):
-    """The oracle network on ``W`` (built once per weight set): net(x, t, context) in float64."""
-    from oracle import ref_torch as rt
-    if key not in _ORACLES:
-        ocfg = rt.UNetConfig(img_size=8, img_channels=4, conditional=conditional)
-        Wt = {k: torch.from_numpy(v) for k, v in W.items()}
-        _ORACLES[key] = lambda x, t, ctx=None: rt.unet_forward(Wt, ocfg, x.float(), torch.full((x.shape[0],), int(t), dtype=torch.int64), ctx).double()
-    return _ORACLES[key]
-
-
-def _alpha_bar64(T, ztsnr=False):
-    """The linear schedule's alpha_bar (with Algorithm 1 of Lin et al. 2023 for ``ztsnr``), rounded to the float32 the kernels read."""
-    r = np.sqrt(np.cumprod(1 - np.linspace(0.0001, 0.02, T), 0))
-    if ztsnr:
-        r = (r - r[-1]) * (r[0] / (r[0] - r[-1]))
-    return (r ** 2).astype(F).astype(np.float64)
-
-
-def _row64(ab, s, t, p, eta):
-    """(c_x, c_0, c_1, c_z) of the step from timestep s to t (t < 0: clean) in float64; p: the timestep the step before started from
-    (p < 0: first order).  alpha = sqrt(ab), sigma = sqrt(1 - ab), lambda = log(alpha / sigma), h = lambda_t - lambda_s; from a level
-    with ab = 0 the limits h = inf are written out, and a history level with ab = 0 has g = 0."""
-    if t < 0:
-        return 0.0, 1.0, 0.0, 0.0
-    al = lambda i: math.sqrt(float(ab[i]))
-    sg = lambda i: math.sqrt(1.0 - float(ab[i]))
-    if ab[s] == 0.0:
-        return (sg(t), al(t), 0.0, 0.0) if eta == 0 else (0.0, al(t), 0.0, sg(t))
-    lam = lambda i: math.log(al(i) / sg(i))
-    h = lam(t) - lam(s)
-    A = al(t) * (1.0 - math.exp(-(1.0 + eta) * h))
-    g = 0.0 if p < 0 or ab[p] == 0.0 else h / (2.0 * (lam(s) - lam(p)))
-    return sg(t) / sg(s) * math.exp(-eta * h), A * (1.0 + g), -A * g, sg(t) * math.sqrt(1.0 - math.exp(-2.0 * eta * h))
-
-
-def _step64(x, eps, z, ab, s, t, p, eta, hist=None, clip=True):
-    """One step on eps in float64: (x at t, the x0 estimate)."""
-    x, eps, a = x.double(), eps.double(), float(ab[s])
-    x0 = (x - math.sqrt(1 - a) * eps) / math.sqrt(a)
-    if clip:
-        x0 = x0.clamp(-1, 1)
-    c_x, c_0, c_1, c_z = _row64(ab, s, t, p, eta)
-    out = c_x * x + c_0 * x0
-    if c_1 != 0:
-        out = out + c_1 * hist.double()
-    if c_z != 0:
-        out = out + c_z * z.double()
-    return out, x0
-
-
-def _prev(sched, order=2, lower_order_final=True):
-    n = len(sched)
-    prev = list(sched[1:]) + [-1]
-    if order == 1:
-        prev = [-1] * n
-    if lower_order_final and n > 1:
-        prev[1] = -1
-    return prev
-
-
-def _chain64(net, ab, sched, x_start, eta, noise, order=2, clip=True, kind="eps", blend=None, thr=None, states=None):
-    """The whole chain with float64 bookkeeping: steps from sched[-1] down to sched[0], then clean.  ``net(x, t)`` is the network's
-    output (guided already, where the chain is), read as ``kind``; ``noise[i]`` the z of the step from sched[i]; ``thr`` = (p, cap,
-    list) thresholds the estimate dynamically and records the bounds; ``blend(i, x)`` (edit chains) follows the step from sched[i].
-    The history is the model's own x0 estimate, before any blend."""
-    x, hist, prev = x_start.double(), None, _prev(sched, order)
-    for i in range(len(sched) - 1, -1, -1):
-        t = sched[i]
-        a, s = math.sqrt(ab[t]), math.sqrt(1 - ab[t])
-        pred = net(x, t)
-        x0 = {"eps": lambda: (x - s * pred) / a, "v": lambda: a * x - s * pred, "x0": lambda: pred}[kind]()
-        if thr is not None:
-            outs = []
-            for b in range(x0.shape[0]):
-                sb = min(max(float(np.quantile(x0[b].abs().numpy().reshape(-1), thr[0])), 1.0), thr[1])
-                thr[2].append(sb)
-                outs.append(x0[b].clamp(-sb, sb) / sb)
-            x0 = torch.stack(outs)
-        elif clip:
-            x0 = x0.clamp(-1, 1)
-        c_x, c_0, c_1, c_z = _row64(ab, t, sched[i - 1] if i > 0 else -1, prev[i], eta)
-        x = c_x * x + c_0 * x0 + (c_1 * hist if c_1 != 0 else 0.0) + (c_z * noise[i].double() if c_z != 0 else 0.0)
-        hist = x0
-        if blend is not None:
-            x = blend(i, x)
-        if states is not None:
-            states.append(x)
-    return x
-
-
-def _guide64(pp, pn, w, phi):
-    out = []
-    for b in range(pp.shape[0]):
-        g = pn[b] + w * (pp[b] - pn[b])
-        if phi != 0:
-            sg = float(g.std(unbiased=False))
-            g = (phi * float(pp[b].std(unbiased=False)) / sg + (1 - phi) if sg > 0 else 1.0) * g
-        out.append(g)
-    return torch.stack(out)
-
-
 # ---- 1. the kernel against the float64 restatement -----------------------------------------------------------------------------------
 CASES = [  # (t, t_prev, t_before or None), one entry per sample: tests/test_gpu_dpm.py's
     ([400, 300, 20], [380, 150, -1], None),                      # first order; sample 2 steps to clean
@@ -174,8 +50,8 @@ def test_kernel_matches_float64_restatement(dev, clip, B, eta):
     """dpm_step(sde_eta=, noise=z) (mode 0) on random x / eps / x0_prev / z with per-sample t.  The bar of x_next is KERNEL_BAR times the
     row's coefficient mass max(1, |c_x| + |c_0| + |c_1| + |c_z| max|z|); the x0 estimate is the plain dpm_step's bitwise."""
     T = 1000
-    m = _cond_model(T, B)
-    ab = _alpha_bar64(T)
+    m, _ = cr.cond_model(T, B)
+    ab = cr.alpha_bar64(T)
     g = torch.Generator().manual_seed(131 + B)
     for shape in [(B, 8, 8, 8, 4), (B, 4, 4, 4, 4)] + ([FLAT] if B == 1 else []):
         x, e, h, z = (torch.randn(shape, generator=g) for _ in range(4))
@@ -193,9 +69,9 @@ def test_kernel_matches_float64_restatement(dev, clip, B, eta):
             got = got.cpu()
             for b in range(B):
                 p = -1 if tb is None else tb[b]
-                ref, ref0 = _step64(x[b], e[b], z[b], ab, t[b], tp[b], p, eta, h[b], clip)
+                ref, ref0 = cr.dpm64(x[b], e[b], ab, t[b], tp[b], p, h[b], clip, eta, z[b])
                 assert float(ref.abs().max()) < 20 and float(ref0.abs().max()) < 20               # O(1) values: the bar is absolute
-                c = _row64(ab, t[b], tp[b], p, eta)
+                c = cr.dpm_row64(ab, t[b], tp[b], p, eta)
                 assert (c[3] != 0) == (tp[b] >= 0) and (c[2] != 0) == (p >= 0 and tp[b] >= 0)
                 bar = KERNEL_BAR * max(1.0, abs(c[0]) + abs(c[1]) + abs(c[2]) + abs(c[3]) * zmax)
                 err = float((got[b].double() - ref).abs().max())
@@ -209,7 +85,7 @@ def test_kernel_matches_float64_restatement(dev, clip, B, eta):
 # ---- 2. eta = 0 is the ODE solver bitwise ---------------------------------------------------------------------------------------------
 def test_eta_zero_is_the_ode_solver_bitwise(dev):
     T, B = 1000, 3
-    m = _cond_model(T, B)
+    m, _ = cr.cond_model(T, B)
     g = torch.Generator().manual_seed(17)
     x, e, h = (torch.randn((B, 8, 8, 8, 4), generator=g).cuda() for _ in range(3))
     nan = torch.full_like(x, float("nan"))
@@ -220,7 +96,7 @@ def test_eta_zero_is_the_ode_solver_bitwise(dev):
             for kw in (dict(), dict(seed=3), dict(noise=nan)):                                 # c_z = 0: nothing is drawn, noise is not read
                 got = m.dpm_step(x, e, torch.tensor(t), torch.tensor(tp), *hist, clip_x0=clip, sde_eta=0.0, **kw)
                 assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), (clip, t, kw)
-    m = _cond_model(T_C, 2)
+    m, _ = cr.cond_model(T_C, 2)
     x_T = torch.randn(SHAPE, generator=g)
     for kw in (dict(num_steps=S_C), dict(num_steps=7, solver_order=1, clip_x0=False), dict(num_steps=6, lower_order_final=False)):
         for use_graph in (True, False):
@@ -236,7 +112,7 @@ def test_philox_draws(dev):
     ddim_step's draws at the same seed and timestep (the stream constant is this kernel's own), and are N(0, 1)."""
     from dm3d_amd.diffusion import ddim_coefficients, dpm_sde_coefficients
     T = 1000
-    m = _cond_model(T, 4)
+    m, _ = cr.cond_model(T, 4)
     zero = torch.zeros((4, 32, 32, 32, 8), device=dev)                      # 1 048 576 draws
     step = lambda t, tp, seed: m.dpm_step(zero, zero, t, tp, clip_x0=False, sde_eta=1.0, seed=seed)[0]
     a, b, c, d = step(500, 480, 11), step(500, 480, 11), step(500, 480, 12), step(520, 500, 11)
@@ -263,25 +139,21 @@ def test_philox_draws(dev):
 @pytest.mark.parametrize("conditional", [True, False])
 def test_chain_matches_float64(dev, conditional, clip, order):
     """8^3 x 4ch, T = 20, S = 5, B = 2 (conditional: one context id per volume), eta = 1 with injected x_T and noise."""
-    import dm3d_amd
-    from dm3d_amd.networks import dm3d
     g = torch.Generator().manual_seed(51)
     x_T = torch.randn(SHAPE, generator=g)
     noise = torch.randn((S_C,) + SHAPE, generator=g)
     kw = dict(x_T=x_T, noise=noise, sampler="dpmpp_sde", num_steps=S_C, clip_x0=clip, solver_order=order)
     if conditional:
-        W = _weights()
-        m = _cond_model(T_C, 2, W)
+        m, W = cr.cond_model(T_C, 2)
         ckw = dict(context_value=IDS)
-        f = _oracle(W, "cond")
+        f = cr.oracle(W)
         net = lambda x, t: f(x, t, IDS)
     else:
-        W = dm3d_amd.synthetic_weights(dm3d_amd.UNetConfig(img_size=8, img_channels=4, conditional=False), seed=0)
-        m = dm3d.DiffusionModel(8, 1024, 4, None, _args(T_C, 2), weights=W)
+        m, W = cr.uncond_model(T_C, 2)
         ckw = {}
-        net = _oracle(W, "uncond", conditional=False)
+        net = cr.oracle(W, conditional=False)
     got = m.generate(SHAPE, **ckw, **kw).cpu()
-    ref = _chain64(net, _alpha_bar64(T_C), _schedule(T_C, S_C), x_T, 1.0, noise, order, clip)
+    ref = cr.chain64(net, cr.alpha_bar64(T_C), cr.schedule(T_C, S_C), x_T, eta=1.0, noise=noise, order=order, clip=clip)
     err = float((got.double() - ref).abs().max())
     print(f"dpmpp_sde chain conditional={conditional} clip={clip} order={order}: max abs difference {err:.2e}, max |x| {float(ref.abs().max()):.3f}")
     assert torch.isfinite(got).all() and err < CHAIN_BAR
@@ -292,26 +164,10 @@ def test_chain_matches_float64(dev, conditional, clip, order):
         assert not torch.equal(got, m.generate(SHAPE, **ckw, **dict(kw, solver_order=1)).cpu())
     # another eta, the same z: its own float64 chain
     got = m.generate(SHAPE, sde_eta=0.5, **ckw, **kw).cpu()
-    ref = _chain64(net, _alpha_bar64(T_C), _schedule(T_C, S_C), x_T, 0.5, noise, order, clip)
+    ref = cr.chain64(net, cr.alpha_bar64(T_C), cr.schedule(T_C, S_C), x_T, eta=0.5, noise=noise, order=order, clip=clip)
     err = float((got.double() - ref).abs().max())
     print(f"  sde_eta=0.5: max abs difference {err:.2e}")
     assert err < CHAIN_BAR
-
-
-def _half_mask(B):
-    """Regenerate the lower half of D, keep the upper half, with a fractional slab at the boundary (a 16^3 mask over 8^3 latents)."""
-    m = torch.zeros((B, 16, 16, 16))
-    m[:, :8] = 1.0
-    m[:, 8:10] = 0.3
-    m[:, 8:10, :, :4] = 0.8
-    return m
-
-
-def _known64(x0, ab, level, z):
-    if level < 0:
-        return x0.double()
-    a = float(ab[level])
-    return math.sqrt(a) * x0.double() + math.sqrt(1 - a) * z.double()
 
 
 @pytest.mark.parametrize("strength", [1.0, 0.6])
@@ -319,27 +175,27 @@ def test_edit_chain_matches_float64(dev, strength):
     """edit(sampler="dpmpp_sde") with a half mask, injected noise and known_noise: the blend follows every update, the history stays
     unblended, kept voxels are x0 bitwise; strength 0.6 keeps 3 steps and starts first order from q_sample(x0, sched[2])."""
     from dm3d_amd.diffusion import edit_steps, latent_mask
-    W = _weights()
-    m = _cond_model(T_C, 2, W)
+    m, W = cr.cond_model(T_C, 2)
     g = torch.Generator().manual_seed(61)
     x0 = torch.rand(SHAPE, generator=g) * 2 - 1
     n = edit_steps(strength, S_C)
-    sched = _schedule(T_C, S_C)[:n]
+    sched = cr.schedule(T_C, S_C)[:n]
     assert n == (5 if strength == 1.0 else 3)
     noise = torch.randn((n,) + SHAPE, generator=g)
     known_noise = torch.randn((n + 1,) + SHAPE, generator=g)
-    mask = _half_mask(2)
-    ab = _alpha_bar64(T_C)
+    mask = cr.half_mask(2, 16, slab=True)
+    ab = cr.alpha_bar64(T_C)
     kw = dict(mask=mask, strength=strength, seed=13, sampler="dpmpp_sde", num_steps=S_C)
     if n == S_C:
         x_start = m.edit(x0, IDS, steps=0, **kw).cpu()                    # generate()'s x_T under the seed
     else:
-        x_start = _known64(x0, ab, sched[-1], known_noise[n])
+        x_start = cr.known64(x0, ab, sched[-1], known_noise[n])
     got = m.edit(x0, IDS, noise=noise, known_noise=known_noise, **kw).cpu()
-    f = _oracle(W, "cond")
-    w = (1 - latent_mask(mask, SHAPE)).double().unsqueeze(-1)
-    blend = lambda i, x: w * _known64(x0, ab, sched[i - 1] if i > 0 else -1, known_noise[i]) + (1 - w) * x
-    ref = _chain64(lambda x, t: f(x, t, IDS), ab, sched, x_start, 1.0, noise, blend=blend)
+    f = cr.oracle(W)
+    keep = 1 - latent_mask(mask, SHAPE)
+    w = keep.double().unsqueeze(-1)
+    blend = cr.edit_blend64(x0, ab, sched, keep, known_noise)
+    ref = cr.chain64(lambda x, t: f(x, t, IDS), ab, sched, x_start, eta=1.0, noise=noise, blend=blend)
     err = float((got.double() - ref).abs().max())
     print(f"dpmpp_sde edit chain strength={strength}: max abs difference {err:.2e}")
     assert err < CHAIN_BAR
@@ -359,16 +215,16 @@ def test_edit_chain_matches_float64(dev, strength):
 @pytest.mark.parametrize("phi", [0.0, 0.7])
 def test_guided_chain_matches_float64(dev, phi):
     """w = 3 with per-volume contexts; the draws are those of the unguided chain of the same volumes."""
-    W = _weights()
-    m = _cond_model(T_C, 2, W)
+    m, W = cr.cond_model(T_C, 2)
     g = torch.Generator().manual_seed(71)
     x_T = torch.randn(SHAPE, generator=g)
     noise = torch.randn((S_C,) + SHAPE, generator=g)
-    f, w = _oracle(W, "cond"), 3.0
+    f, w = cr.oracle(W), 3.0
     kw = dict(context_value=IDS, x_T=x_T, sampler="dpmpp_sde", num_steps=S_C)
     gkw = dict(guidance_scale=w, negative_context=NEG, guidance_rescale=phi)
     got = m.generate(SHAPE, noise=noise, **gkw, **kw).cpu()
-    ref = _chain64(lambda x, t: _guide64(f(x, t, IDS), f(x, t, NEG), w, phi), _alpha_bar64(T_C), _schedule(T_C, S_C), x_T, 1.0, noise)
+    ref = cr.chain64(lambda x, t: cr.guide64(f(x, t, IDS), f(x, t, NEG), w, phi), cr.alpha_bar64(T_C), cr.schedule(T_C, S_C), x_T,
+                     eta=1.0, noise=noise)
     err = float((got.double() - ref).abs().max())
     print(f"guided dpmpp_sde phi={phi} chain: max abs difference {err:.2e}")
     assert err < CHAIN_BAR
@@ -380,16 +236,16 @@ def test_guided_chain_matches_float64(dev, phi):
 
 def test_thresholded_chain_matches_float64(dev):
     """The output conv scaled by 3 (tests/test_gpu_threshold.py's weights): the float64 chain's bound exceeds 1 at some step."""
-    W = _weights(3.0)
-    m = _cond_model(T_C, 2, W)
+    m, W = cr.cond_model(T_C, 2, W=cr.weights(scale=3.0))
     g = torch.Generator().manual_seed(81)
     x_T = torch.randn(SHAPE, generator=g) * 1.5
     noise = torch.randn((S_C,) + SHAPE, generator=g)
-    f, bounds = _oracle(W, "cond-x3"), []
+    f, bounds = cr.oracle(W), []
     kw = dict(context_value=IDS, x_T=x_T, sampler="dpmpp_sde", num_steps=S_C)
     tkw = dict(dynamic_threshold=0.9, threshold_max=4.0)
     got = m.generate(SHAPE, noise=noise, **tkw, **kw).cpu()
-    ref = _chain64(lambda x, t: f(x, t, IDS), _alpha_bar64(T_C), _schedule(T_C, S_C), x_T, 1.0, noise, thr=(0.9, 4.0, bounds))
+    ref = cr.chain64(lambda x, t: f(x, t, IDS), cr.alpha_bar64(T_C), cr.schedule(T_C, S_C), x_T, eta=1.0, noise=noise,
+                     thr=(0.9, 4.0, bounds))
     err = float((got.double() - ref).abs().max())
     print(f"thresholded dpmpp_sde chain: max abs difference {err:.2e}; s per step {[round(s, 3) for s in bounds]}")
     assert len(bounds) == 2 * S_C and max(bounds) > 1.0
@@ -406,8 +262,8 @@ def test_zero_terminal_snr_first_step(dev, kind):
     """dpm_step(prediction=, sde_eta=) from alpha_bar = 0: the row is (0, alpha_t, 0, sigma_t), so the result is alpha_t x0 + sigma_t z
     with x0 the clipped estimate of the raw prediction, whatever x holds."""
     T = 1000
-    m = _cond_model(T, 2, prediction=kind, zero_terminal_snr=True)
-    ab = _alpha_bar64(T, True)
+    m, _ = cr.cond_model(T, 2, prediction=kind, zero_terminal_snr=True)
+    ab = cr.alpha_bar64(T, True)
     assert ab[T - 1] == 0.0 and m.b.alpha_bar[T - 1] == 0.0
     g = torch.Generator().manual_seed(91)
     x, p, z = (torch.randn(SHAPE, generator=g) for _ in range(3))
@@ -430,16 +286,15 @@ def test_zero_terminal_snr_first_step(dev, kind):
 def test_zero_terminal_snr_chains(dev, kind):
     """The native chain against float64 with injected x_T and noise; every intermediate state finite; seeded graph and eager chains
     bitwise equal, plain, guided, thresholded and edit."""
-    W = _weights()
-    m = _cond_model(T_C, 2, W, prediction=kind, zero_terminal_snr=True)
+    m, W = cr.cond_model(T_C, 2, prediction=kind, zero_terminal_snr=True)
     g = torch.Generator().manual_seed(101)
     x_T = torch.randn(SHAPE, generator=g)
     noise = torch.randn((S_C,) + SHAPE, generator=g)
-    sched, ab = _schedule(T_C, S_C), _alpha_bar64(T_C, True)
+    sched, ab = cr.schedule(T_C, S_C), cr.alpha_bar64(T_C, True)
     assert ab[sched[-1]] == 0.0
-    f = _oracle(W, "cond")
+    f = cr.oracle(W)
     got = m.generate(SHAPE, context_value=IDS, x_T=x_T, noise=noise, sampler="dpmpp_sde", num_steps=S_C).cpu()
-    ref = _chain64(lambda x, t: f(x, t, IDS), ab, sched, x_T, 1.0, noise, kind=kind)
+    ref = cr.chain64(lambda x, t: f(x, t, IDS), ab, sched, x_T, kind=kind, eta=1.0, noise=noise)
     err = float((got.double() - ref).abs().max())
     print(f"zero-terminal-SNR {kind} model, dpmpp_sde: max abs difference {err:.2e}")
     assert torch.isfinite(got).all() and err < CHAIN_BAR
@@ -456,21 +311,20 @@ def test_zero_terminal_snr_chains(dev, kind):
         a = m.generate(SHAPE, context_value=IDS, use_graph=True, **kw, **extra)
         b = m.generate(SHAPE, context_value=IDS, use_graph=False, **kw, **extra)
         assert torch.equal(a, b) and torch.isfinite(a).all(), extra
-    a, b = (m.edit(x0, IDS, mask=_half_mask(2), use_graph=ug, **kw) for ug in (True, False))
+    a, b = (m.edit(x0, IDS, mask=cr.half_mask(2, 16, slab=True), use_graph=ug, **kw) for ug in (True, False))
     assert torch.equal(a, b) and torch.isfinite(a).all() and torch.equal(a.cpu()[:, 5:], x0[:, 5:])
     assert {"dpmpp+sde+frame", "dpmpp-cfg+sde+frame", "dpmpp+sde+thr+frame", "dpmpp-edit+sde+frame"} <= {k[1] for k in m._graphs}
 
 
 def test_plain_schedule_v_model_converts_first(dev):
     """A v-model on the plain schedule converts to eps after the U-Net, as every chain of it does: its graph kind says so."""
-    W = _weights()
-    m = _cond_model(T_C, 2, W, prediction="v")
+    m, W = cr.cond_model(T_C, 2, prediction="v")
     g = torch.Generator().manual_seed(111)
     x_T = torch.randn(SHAPE, generator=g)
     noise = torch.randn((S_C,) + SHAPE, generator=g)
-    f = _oracle(W, "cond")
+    f = cr.oracle(W)
     got = m.generate(SHAPE, context_value=IDS, x_T=x_T, noise=noise, sampler="dpmpp_sde", num_steps=S_C).cpu()
-    ref = _chain64(lambda x, t: f(x, t, IDS), _alpha_bar64(T_C), _schedule(T_C, S_C), x_T, 1.0, noise, kind="v")
+    ref = cr.chain64(lambda x, t: f(x, t, IDS), cr.alpha_bar64(T_C), cr.schedule(T_C, S_C), x_T, kind="v", eta=1.0, noise=noise)
     err = float((got.double() - ref).abs().max())
     print(f"plain-schedule v model, dpmpp_sde: max abs difference {err:.2e}")
     assert err < CHAIN_BAR
@@ -480,7 +334,7 @@ def test_plain_schedule_v_model_converts_first(dev):
 
 # ---- 6. graphs --------------------------------------------------------------------------------------------------------------------------
 def test_graph_equals_eager_repeats_and_serves_every_schedule_and_eta(dev):
-    m = _cond_model(T_C, 2)
+    m, _ = cr.cond_model(T_C, 2)
     counts = []
     runs = [dict(num_steps=5), dict(num_steps=8, sde_eta=0.5), dict(timesteps=[0, 3, 11, 19], clip_x0=False), dict(num_steps=20, sde_eta=2.0),
             dict(num_steps=7, lower_order_final=False), dict(num_steps=6, solver_order=1, sde_eta=0.5)]
@@ -503,9 +357,9 @@ def test_sde_and_ode_chains_never_replay_each_other(dev):
     """An SDE chain and an ODE chain (and a DDIM chain) alternated on one plan: each is bitwise what it is alone on a fresh model."""
     calls = {"sde": dict(sampler="dpmpp_sde", num_steps=5), "ode": dict(sampler="dpmpp", num_steps=5),
              "ddim": dict(sampler="ddim", num_steps=5, eta=1.0)}
-    alone = {k: _cond_model(T_C, 2).generate(SHAPE, context_value=0, seed=5, **kw) for k, kw in calls.items()}
+    alone = {k: cr.cond_model(T_C, 2)[0].generate(SHAPE, context_value=0, seed=5, **kw) for k, kw in calls.items()}
     assert not torch.equal(alone["sde"], alone["ode"]) and not torch.equal(alone["sde"], alone["ddim"])
-    m = _cond_model(T_C, 2)
+    m, _ = cr.cond_model(T_C, 2)
     for k in ("ode", "sde", "ode", "ddim", "sde", "sde", "ode", "ddim"):
         got = m.generate(SHAPE, context_value=0, seed=5, **calls[k])
         torch.cuda.synchronize()
@@ -514,7 +368,7 @@ def test_sde_and_ode_chains_never_replay_each_other(dev):
 
 
 def test_nan_reaches_its_element_only(dev):
-    m = _cond_model(1000, 2)
+    m, _ = cr.cond_model(1000, 2)
     g = torch.Generator().manual_seed(8)
     x, e, h, z = (torch.randn(SHAPE, generator=g) for _ in range(4))
     e_nan = e.clone()

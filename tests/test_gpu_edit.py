@@ -1,18 +1,19 @@
 """GPU tier of latent editing (dm3d_edit_update, DiffusionModel.q_sample, DiffusionModel.edit): inpainting with RePaint's
 replacement step and image-to-image (SDEdit) starts, for the DDPM and DDIM chains.
 
-The float64 reference is this file's own restatement of the known-latent step and of the DDIM update, the oracle's DDPM step
-(oracle.ref_torch.ddpm_step, in float64) and eps from the CPU oracle (oracle.ref_torch.unet_forward), with alpha_bar from the oracle's
-float32 Betas table, the table the kernels read.
+The float64 reference is tests/chain_reference.py's restatement of the known-latent step and of the DDIM update, the oracle's DDPM
+step (oracle.ref_torch.ddpm_step, in float64) and eps from the CPU oracle (oracle.ref_torch.unet_forward), with alpha_bar from the
+oracle's float32 Betas table, the table the kernels read.
 """
 import ctypes
 import math
 import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
+
+import chain_reference as cr
 
 pytestmark = pytest.mark.gpu
 CHAIN_BAR = 2e-3        # the existing chain tests' bar (values in [-1, 1] + noise)
@@ -27,74 +28,12 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _args(T, bs=1):
-    return SimpleNamespace(timesteps=T, num_gpus=1, kernel_resize=False, bs=bs)
-
-
-def _schedule(T, S):
-    return [T - 1] if S == 1 else [int(math.floor(i * (T - 1) / (S - 1) + 0.5)) for i in range(S)]
-
-
-def _cond_model(T, B, size=8, C=4, **kw):
-    import dm3d_amd
-    from dm3d_amd.networks import conditional_dm3d as cdm
-    cfg = dm3d_amd.UNetConfig(img_size=size, img_channels=C)
-    W = dm3d_amd.synthetic_weights(cfg, seed=0)
-    return cdm.DiffusionModel(size, 1024, C, None, _args(T, B), weights=W, **kw), W
-
-
-def _oracle(W, size, C, conditional=True):
-    from oracle import ref_torch as rt
-    ocfg = rt.UNetConfig(img_size=size, img_channels=C, conditional=conditional)
-    Wt = {k: torch.from_numpy(v) for k, v in W.items()}
-    return lambda x, t, ctx=None: rt.unet_forward(Wt, ocfg, x.float(), torch.full((x.shape[0],), int(t), dtype=torch.int64), ctx)
-
-
-def _known64(x0, ab, level, z):
-    """The known latent at ``level`` in float64 (-1: x0)."""
-    if level < 0:
-        return x0.double()
-    a = float(ab[level])
-    return math.sqrt(a) * x0.double() + math.sqrt(1 - a) * z.double()
-
-
-def _ddim64(x, eps, a, ap, eta=0.0, z=None, clip=True):
-    x, eps = x.double(), eps.double()
-    x0 = (x - math.sqrt(1 - a) * eps) / math.sqrt(a)
-    if clip:
-        x0 = x0.clamp(-1, 1)
-    sigma = eta * math.sqrt((1 - ap) / (1 - a)) * math.sqrt(1 - a / ap) if eta else 0.0
-    out = math.sqrt(ap) * x0 + math.sqrt(max(1 - ap - sigma * sigma, 0.0)) * eps
-    return out + sigma * z.double() if sigma else out
-
-
-def _edit_chain64(eps_fn, b, kind, sched, x_start, x0, keep, noise, known_noise, eta=0.0):
-    """The whole edit chain in float64: steps from sched[n-1] down to sched[0], each followed by the blend towards the level the step
-    reached (row i of known_noise for the step from sched[i]; row 0 clean)."""
-    from oracle import ref_torch as rt
-    ab = b.alpha_bar.double()
-    w = keep.double().unsqueeze(-1)
-    x = x_start.double()
-    n = len(sched)
-    for i in range(n - 1, -1, -1):
-        t = sched[i]
-        eps = eps_fn(x, t).double()
-        if kind == "ddpm":
-            z = noise[i] if t > 0 else torch.zeros_like(x)
-            x = rt.ddpm_step(b, x, eps, torch.full((x.shape[0],), t, dtype=torch.int64), z.double())
-        else:
-            x = _ddim64(x, eps, float(ab[t]), float(ab[sched[i - 1]]) if i > 0 else 1.0, eta, noise[i])
-        known = _known64(x0, ab, sched[i - 1] if i > 0 else -1, known_noise[i])
-        x = w * known + (1 - w) * x
-    return x
-
-
 def test_kernel_matches_float64_restatement(dev):
     """q_sample (mode 0) and the blend (mode 1) on random x / x0 / fractional w / injected z, per-sample rows and the clean row."""
     from oracle import ref_torch as rt
     T, B = 1000, 3
-    m, _ = _cond_model(T, B)
-    ab = rt.Betas(T).alpha_bar.double()
+    m, _ = cr.cond_model(T, B)
+    ab = cr.oracle_alpha_bar(T).double()
     g = torch.Generator().manual_seed(31)
     for shape in ((B, 8, 8, 8, 4), (B, 4, 4, 4, 8), (B, 4, 4, 4, 2), (B, 4, 4, 4, 1)):        # C % 4 != 0: one lane, several voxels
         x, x0, z = (torch.randn(shape, generator=g) for _ in range(3))
@@ -105,7 +44,7 @@ def test_kernel_matches_float64_restatement(dev):
             q = m.q_sample(x0, torch.tensor(t), noise=z).cpu()
             got = m._edit_call(x0, torch.tensor(t), 1, x=x, keep=keep, noise=z).cpu()
             for bb in range(B):
-                kn = _known64(x0[bb], ab, t[bb], z[bb])
+                kn = cr.known64(x0[bb], ab, t[bb], z[bb])
                 err = float((q[bb].double() - kn).abs().max())
                 assert err < 2e-6, (shape, t, err)
                 if t[bb] < 0:
@@ -155,7 +94,7 @@ def test_philox_draws(dev):
     """x0 = 0 leaves q_sample = sqrt(1-a) z: the draws repeat per seed, differ across seeds and levels, are N(0, 1), and are not the
     DDPM or DDIM update's draws under the same key and timestep."""
     T = 1000
-    m, _ = _cond_model(T, 4)
+    m, _ = cr.cond_model(T, 4)
     shape = (4, 32, 32, 32, 8)                                              # 1 048 576 draws
     a = _draws(m, dev, 11, 500, "edit", shape)
     b = _draws(m, dev, 11, 500, "edit", shape)
@@ -179,7 +118,7 @@ def test_philox_draws(dev):
 @pytest.mark.parametrize("kind,kw", [("ddpm", {}), ("ddim", dict(num_steps=5)), ("ddim", dict(num_steps=5, eta=0.5))])
 def test_all_regenerate_at_strength_one_equals_generate(dev, kind, kw):
     T, B = 20, 2
-    m, _ = _cond_model(T, B)
+    m, _ = cr.cond_model(T, B)
     shape = (B, 8, 8, 8, 4)
     x0 = torch.rand(shape, generator=torch.Generator().manual_seed(2)) * 2 - 1
     ids = torch.tensor([[[1]], [[0]]])
@@ -195,7 +134,7 @@ def test_all_regenerate_at_strength_one_equals_generate(dev, kind, kw):
 @pytest.mark.parametrize("strength", [1.0, 0.45])
 def test_all_keep_returns_x0(dev, kind, kw, strength):
     T, B = 20, 2
-    m, _ = _cond_model(T, B)
+    m, _ = cr.cond_model(T, B)
     shape = (B, 8, 8, 8, 4)
     x0 = torch.rand(shape, generator=torch.Generator().manual_seed(3)) * 2 - 1
     x0[0, 0, 0, 0, 0] = -0.0
@@ -204,44 +143,37 @@ def test_all_keep_returns_x0(dev, kind, kw, strength):
     assert torch.equal(got.cpu(), x0) and torch.equal(got.cpu().view(torch.int32), x0.view(torch.int32))
 
 
-def _half_mask(B):
-    """Regenerate the lower half of D, keep the upper half, with a fractional slab at the boundary (a 16^3 mask over 8^3 latents)."""
-    m = torch.zeros((B, 16, 16, 16))
-    m[:, :8] = 1.0
-    m[:, 8:10] = 0.3
-    m[:, 8:10, :, :4] = 0.8
-    return m
-
-
 @pytest.mark.parametrize("kind,eta", [("ddpm", 0.0), ("ddim", 0.0), ("ddim", 0.5)])
 @pytest.mark.parametrize("strength", [1.0, 0.5])
 def test_conditional_half_mask_chain_matches_float64(dev, kind, eta, strength):
     """8^3 x 4ch, T = 20 (DDIM: S = 5), B = 2 with both context ids, injected noise and known_noise."""
     from dm3d_amd.diffusion import edit_steps, latent_mask
-    from oracle import ref_torch as rt
     T, S, B = 20, 5, 2
-    m, W = _cond_model(T, B)
+    m, W = cr.cond_model(T, B)
     shape = (B, 8, 8, 8, 4)
     g = torch.Generator().manual_seed(41)
     x0 = torch.rand(shape, generator=g) * 2 - 1
-    full = list(range(T)) if kind == "ddpm" else _schedule(T, S)
+    full = list(range(T)) if kind == "ddpm" else cr.schedule(T, S)
     n = edit_steps(strength, len(full))
     sched = full[:n]
     noise = torch.randn((n,) + shape, generator=g)
     known_noise = torch.randn((n + 1,) + shape, generator=g)
     x_T = torch.randn(shape, generator=g)
     ids = torch.tensor([[[1]], [[0]]])
-    mask = _half_mask(B)
+    mask = cr.half_mask(B, 16, slab=True)
+    b = cr.oracle_betas(T)
+    ab = b.alpha_bar.double()
     kw = dict(sampler=kind) if kind == "ddpm" else dict(sampler=kind, num_steps=S, eta=eta)
     if n == len(full):
         # the start is generate()'s x_T under the seed: take it from a zero-step chain
         x_start = m.edit(x0, ids, mask=mask, seed=13, steps=0, **kw).cpu()
     else:
-        x_start = _known64(x0, rt.Betas(T).alpha_bar.double(), sched[-1], known_noise[n])
+        x_start = cr.known64(x0, ab, sched[-1], known_noise[n])
     got = m.edit(x0, ids, mask=mask, strength=strength, seed=13, noise=noise, known_noise=known_noise, **kw).cpu()
-    f = _oracle(W, 8, 4)
+    f = cr.oracle(W)
     keep = 1 - latent_mask(mask, shape)
-    ref = _edit_chain64(lambda x, t: f(x, t, ids), rt.Betas(T), kind, sched, x_start, x0, keep, noise, known_noise, eta)
+    ref = cr.chain64(lambda x, t: f(x, t, ids), ab, sched, x_start, kind, eta=eta, noise=noise,
+                     blend=cr.edit_blend64(x0, ab, sched, keep, known_noise), betas=b)
     err = float((got.double() - ref).abs().max())
     print(f"{kind} eta={eta} strength={strength} edit chain: max abs difference {err:.2e}")
     assert err < CHAIN_BAR
@@ -260,10 +192,10 @@ def test_graph_equals_eager_and_kinds_do_not_leak(dev):
     """Seeded edits are bitwise equal through the graph and eagerly, across masks, strengths and schedules through the one cached
     graph per kind; edit and generate interleaved on one plan give the bytes of fresh runs."""
     T, B = 20, 2
-    m, _ = _cond_model(T, B)
+    m, _ = cr.cond_model(T, B)
     shape = (B, 8, 8, 8, 4)
     x0 = torch.rand(shape, generator=torch.Generator().manual_seed(6)) * 2 - 1
-    mask = _half_mask(B)
+    mask = cr.half_mask(B, 16, slab=True)
     runs = [dict(sampler="ddpm", mask=mask, strength=0.6), dict(sampler="ddpm", mask=mask[:1].flip(2)),
             dict(sampler="ddim", num_steps=5, eta=0.5, mask=mask, strength=0.7), dict(sampler="ddim", num_steps=10, clip_x0=False)]
     results = []
@@ -276,12 +208,12 @@ def test_graph_equals_eager_and_kinds_do_not_leak(dev):
     gen = {k: m.generate(shape, context_value=0, seed=5, **kw) for k, kw in (("ddpm", {}), ("ddim", dict(sampler="ddim", num_steps=5)))}
     # interleaved on the same plan, against fresh models
     again = [m.edit(x0, 0, seed=5, **kw) for kw in runs]
-    fresh, _ = _cond_model(T, B)
+    fresh, _ = cr.cond_model(T, B)
     for kw, r, a in zip(runs, results, again):
         f = fresh.edit(x0, 0, seed=5, **kw)
         torch.cuda.synchronize()
         assert torch.equal(r, a) and torch.equal(r, f), kw
-    fresh2, _ = _cond_model(T, B)
+    fresh2, _ = cr.cond_model(T, B)
     assert torch.equal(gen["ddpm"], fresh2.generate(shape, context_value=0, seed=5))
     assert torch.equal(gen["ddim"], fresh2.generate(shape, context_value=0, seed=5, sampler="ddim", num_steps=5))
     assert torch.equal(m.generate(shape, context_value=0, seed=5), gen["ddpm"])
@@ -289,28 +221,20 @@ def test_graph_equals_eager_and_kinds_do_not_leak(dev):
 
 def test_unconditional_edit(dev):
     """The unconditional model edits without a context: kept voxels are x0, and mask=None at strength 1 is generate()."""
-    import dm3d_amd
-    from dm3d_amd.networks import dm3d
     T = 10
-    cfg = dm3d_amd.UNetConfig(img_size=8, img_channels=4, conditional=False)
-    m = dm3d.DiffusionModel(8, 1024, 4, None, _args(T), weights=dm3d_amd.synthetic_weights(cfg, seed=0))
+    m, _ = cr.uncond_model(T)
     x0 = torch.rand((1, 8, 8, 8, 4), generator=torch.Generator().manual_seed(7)) * 2 - 1
     assert torch.equal(m.edit(x0, seed=3), m.generate((1, 8, 8, 8, 4), seed=3))
-    got = m.edit(x0, mask=_half_mask(1), strength=0.5, seed=3, sampler="ddim", num_steps=4).cpu()
+    got = m.edit(x0, mask=cr.half_mask(1, 16, slab=True), strength=0.5, seed=3, sampler="ddim", num_steps=4).cpu()
     assert torch.equal(got[:, 5:], x0[:, 5:]) and not torch.equal(got[:, :4], x0[:, :4])
 
 
 def test_full_size_ddim_edit_chain(dev):
     """32^3 x 8ch (h3), B = 32: a whole S = 50 DDIM edit chain through the graph with a mask given at 128^3: finite, the range guard
     quiet, kept voxels x0.  The output conv is scaled by 0.1 (untrained weights amplify eps along a DDIM chain)."""
-    import dm3d_amd
     from dm3d_amd.diffusion import latent_mask
-    from dm3d_amd.networks import conditional_dm3d as cdm
     T, S, B, C = 1000, 50, 32, 8
-    cfg = dm3d_amd.UNetConfig(img_size=32, img_channels=C)
-    W = dm3d_amd.synthetic_weights(cfg, seed=0)
-    Wb = dict(W, **{k: W[k] * np.float32(0.1) for k in ("out.conv.kernel", "out.conv.bias")})
-    m = cdm.DiffusionModel(32, 1024, C, None, _args(T, B), weights=Wb, precision="h3")
+    m, _ = cr.cond_model(T, B, size=32, C=C, W=cr.weights(32, C, scale=0.1), precision="h3")
     shape = (B, 32, 32, 32, C)
     g = torch.Generator().manual_seed(12)
     x0 = (torch.rand(shape, generator=g) * 2 - 1).to(dev)

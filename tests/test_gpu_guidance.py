@@ -1,9 +1,9 @@
 """GPU tier of classifier-free guidance (dm3d_guide_update, guide_eps, generate / edit / sampler with guidance_scale=).
 
-The float64 reference is this file's own restatement: eps_pos and eps_neg from the CPU oracle (oracle.ref_torch.unet_forward) under
-the wanted and the negative context, eps_g = eps_neg + w (eps_pos - eps_neg), the guidance rescale of Lin et al. 2023 (section 3.4)
-from population standard deviations per volume, then the DDPM posterior step (the oracle's) or the DDIM update (restated here), with
-alpha_bar from the oracle's float32 Betas table, the table the kernels read.
+The float64 reference is tests/chain_reference.py's restatement: eps_pos and eps_neg from the CPU oracle (oracle.ref_torch.unet_forward)
+under the wanted and the negative context, eps_g = eps_neg + w (eps_pos - eps_neg), the guidance rescale of Lin et al. 2023 (section 3.4)
+from population standard deviations per volume, then the DDPM posterior step (the oracle's) or the DDIM update (restated there), with
+alpha_bar from the oracle's float32 Betas table, the table the kernels read.  w and phi enter as the float32 the kernel's tables hold.
 
 Measured on an MI355X (profiles/guidance_gpu_run.log), maximum absolute difference to the float64 chain at 8^3 x 4ch, T = 20, B = 2,
 w = 3 (bar 1e-2):
@@ -14,13 +14,13 @@ three full-size guided DDIM steps (32^3 x 8ch, h3): 6.60e-03 at max |ref| 202.5 
 float64: 3.5e-06 (bar 8.9e-06) without and 1.7e-06 (bar 2.3e-05) with the rescale, 7.6e-06 (3.3e-05) and 1.3e-05 (8.5e-05) in the
 |mean| / std = 100 case.
 """
-import math
 import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
+
+import chain_reference as cr
 
 pytestmark = pytest.mark.gpu
 CHAIN_BAR = 2e-3        # the existing chain tests' bar (values in [-1, 1] + noise)
@@ -35,76 +35,14 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _args(T, bs=1):
-    return SimpleNamespace(timesteps=T, num_gpus=1, kernel_resize=False, bs=bs)
-
-
-def _schedule(T, S):
-    return [T - 1] if S == 1 else [int(math.floor(i * (T - 1) / (S - 1) + 0.5)) for i in range(S)]
-
-
-def _cond_model(T, B, size=8, C=4, W=None, **kw):
-    import dm3d_amd
-    from dm3d_amd.networks import conditional_dm3d as cdm
-    cfg = dm3d_amd.UNetConfig(img_size=size, img_channels=C)
-    W = dm3d_amd.synthetic_weights(cfg, seed=0) if W is None else W
-    return cdm.DiffusionModel(size, 1024, C, None, _args(T, B), weights=W, **kw), W
-
-
-def _oracle(W, size, C):
-    from oracle import ref_torch as rt
-    ocfg = rt.UNetConfig(img_size=size, img_channels=C, conditional=True)
-    Wt = {k: torch.from_numpy(v) for k, v in W.items()}
-    return lambda x, t, ctx: rt.unet_forward(Wt, ocfg, x.float(), torch.full((x.shape[0],), int(t), dtype=torch.int64), ctx)
-
-
 def _per_volume(v, B):
     return [float(np.float32(u)) for u in np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1), (B,))]    # the tables are float32
 
 
-def _guide64(ep, en, w, phi=0.0):
-    """eps_out in float64, volume by volume; also returns max(f, 1) over the volumes."""
-    ep, en = ep.double(), en.double()
-    B = ep.shape[0]
-    out, fmax = [], 1.0
-    for b, (wb, pb) in enumerate(zip(_per_volume(w, B), _per_volume(phi, B))):
-        g = en[b] + wb * (ep[b] - en[b])
-        if pb != 0:
-            sg = float(g.std(unbiased=False))
-            f = pb * float(ep[b].std(unbiased=False)) / sg + (1 - pb) if sg > 0 else 1.0
-            fmax = max(fmax, f)
-            g = f * g
-        out.append(g)
-    return torch.stack(out), fmax
-
-
-def _ddim64(x, eps, a, ap, eta=0.0, z=None, clip=True):
-    x, eps = x.double(), eps.double()
-    x0 = (x - math.sqrt(1 - a) * eps) / math.sqrt(a)
-    if clip:
-        x0 = x0.clamp(-1, 1)
-    sigma = eta * math.sqrt((1 - ap) / (1 - a)) * math.sqrt(1 - a / ap) if eta else 0.0
-    out = math.sqrt(ap) * x0 + math.sqrt(max(1 - ap - sigma * sigma, 0.0)) * eps
-    return out + sigma * z.double() if sigma else out
-
-
-def _guided_chain64(f, b, kind, sched, x_T, c, n, w, phi, eta=0.0, noise=None, steps=None):
-    """The whole guided chain with float64 bookkeeping: steps from sched[-1] down to sched[0]; noise row i is the z of the step from
-    sched[i] (DDPM: z = 0 at t = 0, as the reference's loop)."""
-    from oracle import ref_torch as rt
-    ab = b.alpha_bar.double()
-    x = x_T.double()
-    for k, i in enumerate(range(len(sched) - 1, -1, -1)):
-        if steps is not None and k == steps:
-            break
-        t = sched[i]
-        eps, _ = _guide64(f(x, t, c), f(x, t, n), w, phi)
-        if kind == "ddpm":
-            z = noise[i].double() if t > 0 else torch.zeros_like(x)
-            x = rt.ddpm_step(b, x, eps, torch.full((x.shape[0],), t, dtype=torch.int64), z)
-        else:
-            x = _ddim64(x, eps, float(ab[t]), float(ab[sched[i - 1]]) if i > 0 else 1.0, eta, None if noise is None else noise[i])
-    return x
+def _guide_as_tables(ep, en, w, phi=0.0):
+    """cr.guide64 on w and phi as the tables hold them; also returns max(f, 1) over the volumes."""
+    B, factors = ep.shape[0], []
+    return cr.guide64(ep, en, _per_volume(w, B), _per_volume(phi, B), factors), max([1.0] + factors)
 
 
 W3, PHI3 = (7.5, -1.0, 0.3), (0.7, 0.0, 1.0)
@@ -115,30 +53,30 @@ def test_kernel_matches_float64_restatement(dev, offset):
     """guide_eps on random predictions with per-volume w, without and with a per-volume rescale; offset 100: |mean| / std = 100, the
     cancellation case of the standard deviations.  The bars are derived (three float32 roundings in the combine, two more with the
     rescale), absolute in M = max(|eps_neg| + |w| |eps_pos - eps_neg|)."""
-    m, _ = _cond_model(20, 3)
+    m, _ = cr.cond_model(20, 3)
     g = torch.Generator().manual_seed(41)
     shape = (3, 8, 8, 8, 4)
     ep, en = torch.randn(shape, generator=g) + offset, torch.randn(shape, generator=g) + offset
     wv = torch.tensor(_per_volume(W3, 3), dtype=torch.float64).reshape(3, 1, 1, 1, 1)
     M = float((en.double().abs() + wv.abs() * (ep.double() - en.double()).abs()).max())
-    ref, _ = _guide64(ep, en, W3)
+    ref, _ = _guide_as_tables(ep, en, W3)
     got = m.guide_eps(ep, en, W3).cpu()
     err = float((got.double() - ref).abs().max())
     print(f"guide_eps offset={offset}: phi=0 err {err:.3e} (bar {2.0 ** -22 * M:.3e})")
     assert err <= 2.0 ** -22 * M
-    ref, fmax = _guide64(ep, en, W3, PHI3)
+    ref, fmax = _guide_as_tables(ep, en, W3, PHI3)
     got = m.guide_eps(ep, en, W3, PHI3).cpu()
     err = float((got.double() - ref).abs().max())
     print(f"guide_eps offset={offset}: per-volume phi err {err:.3e} (bar {2.0 ** -21 * M * fmax:.3e}, max f {fmax:.4f})")
     assert err <= 2.0 ** -21 * M * fmax
     # one scalar for every volume, too
-    ref, fmax = _guide64(ep, en, 3.0, 0.7)
+    ref, fmax = _guide_as_tables(ep, en, 3.0, 0.7)
     assert float((m.guide_eps(ep, en, 3.0, 0.7).cpu().double() - ref).abs().max()) <= 2.0 ** -21 * fmax * float(
         (en.double().abs() + 3.0 * (ep.double() - en.double()).abs()).max())
 
 
 def test_constant_volume_and_nan(dev):
-    m, _ = _cond_model(20, 3)
+    m, _ = cr.cond_model(20, 3)
     g = torch.Generator().manual_seed(42)
     shape = (3, 8, 8, 8, 4)
     ep, en = torch.randn(shape, generator=g), torch.randn(shape, generator=g)
@@ -161,7 +99,7 @@ def test_constant_volume_and_nan(dev):
 
 
 def test_bitwise_identities_of_the_combine(dev):
-    m, _ = _cond_model(20, 3)
+    m, _ = cr.cond_model(20, 3)
     g = torch.Generator().manual_seed(43)
     shape = (3, 8, 8, 8, 4)
     ep, en = torch.randn(shape, generator=g).cuda(), torch.randn(shape, generator=g).cuda()
@@ -187,7 +125,7 @@ def test_guided_chain_is_the_plain_2b_chain_at_w_one(dev):
     """8^3 x 4ch, T = 20, B = 2, c = (1, 0), n = (0, 1): the guided chain drives the plan of the plain 4-row chain with contexts
     (1, 0, 0, 1), the same U-Net launches, update kernel and Philox counters for rows 0-1."""
     T, B = 20, 2
-    m, _ = _cond_model(T, 2 * B)
+    m, _ = cr.cond_model(T, 2 * B)
     shape, shape2 = (B, 8, 8, 8, 4), (2 * B, 8, 8, 8, 4)
     c, n = [1, 0], [0, 1]
     x_T = torch.randn(shape, generator=torch.Generator().manual_seed(5))
@@ -219,23 +157,24 @@ def test_guided_chain_is_the_plain_2b_chain_at_w_one(dev):
 def test_guided_chain_matches_float64(dev, kind, eta, phi):
     """8^3 x 4ch, T = 20, B = 2, per-volume contexts, w = 3: DDPM with injected noise; DDIM S = 5 at eta = 0 and at eta = 0.5 with
     injected noise.  Bar: the chain bar times |w| + |1 - w| = 5, the absolute coefficient sum of the two branch predictions."""
-    from oracle import ref_torch as rt
     T, S, B, w = 20, 5, 2, 3.0
-    m, W = _cond_model(T, B)
+    m, W = cr.cond_model(T, B)
     g = torch.Generator().manual_seed(23)
     shape = (B, 8, 8, 8, 4)
     x_T = torch.randn(shape, generator=g)
     c, n = torch.tensor([[[1]], [[0]]]), torch.tensor([[[0]], [[1]]])
-    f, b = _oracle(W, 8, 4), rt.Betas(T)
+    f, b = cr.oracle(W), cr.oracle_betas(T)
+    ab = b.alpha_bar.double()
+    net = lambda x, t: _guide_as_tables(f(x, t, c), f(x, t, n), w, phi)[0]
     if kind == "ddpm":
         noise = torch.randn((T,) + shape, generator=g)
         got = m.generate(shape, context_value=c, x_T=x_T, noise=noise, guidance_scale=w, negative_context=n, guidance_rescale=phi)
-        ref = _guided_chain64(f, b, "ddpm", list(range(T)), x_T, c, n, w, phi, noise=noise)
+        ref = cr.chain64(net, ab, list(range(T)), x_T, "ddpm", noise=noise, betas=b)
     else:
         noise = torch.randn((S,) + shape, generator=g) if eta else None
         got = m.generate(shape, context_value=c, x_T=x_T, noise=noise, sampler="ddim", num_steps=S, eta=eta, guidance_scale=w,
                          negative_context=n, guidance_rescale=phi)
-        ref = _guided_chain64(f, b, "ddim", _schedule(T, S), x_T, c, n, w, phi, eta, noise)
+        ref = cr.chain64(net, ab, cr.schedule(T, S), x_T, "ddim", eta=eta, noise=noise)
     err = float((got.cpu().double() - ref).abs().max())
     print(f"guided {kind} eta={eta} phi={phi} chain: max abs difference {err:.2e}")
     assert err < CHAIN_BAR * (abs(w) + abs(1 - w))
@@ -244,20 +183,14 @@ def test_guided_chain_matches_float64(dev, kind, eta, phi):
     assert not torch.equal(plain, got)
 
 
-def _half_mask(B, size=8):
-    mask = torch.zeros((B, size, size, size))
-    mask[:, : size // 2] = 1.0
-    return mask
-
-
 def test_graph_equals_eager_and_kinds_do_not_leak(dev):
     """Seeded guided chains of the four kinds are bitwise equal through the graph and eagerly; two scales and a phi = 0 / phi != 0 pair
     go through the one cached graph of their kind; the plain chain of the same 2 B-row plan is untouched by it, and the reverse."""
     T, B = 20, 2
-    m, _ = _cond_model(T, 2 * B)
+    m, _ = cr.cond_model(T, 2 * B)
     shape, shape2 = (B, 8, 8, 8, 4), (2 * B, 8, 8, 8, 4)
     x0 = torch.rand(shape, generator=torch.Generator().manual_seed(6)) * 2 - 1
-    mask = _half_mask(B)
+    mask = cr.half_mask(B)
     gkw = dict(guidance_scale=3.0, negative_context=[0, 1])
     ddim = dict(sampler="ddim", num_steps=5, eta=0.5)
     calls = {
@@ -281,7 +214,7 @@ def test_graph_equals_eager_and_kinds_do_not_leak(dev):
         assert sum(1 for k in m._graphs if k[1] == kind) == 1, kind            # one graph served them all
     assert {k[1] for k in m._graphs} == set(calls)
     # the plain chains of the 2 B-row plan the guided chains drove: as on a fresh model
-    fresh, _ = _cond_model(T, 2 * B)
+    fresh, _ = cr.cond_model(T, 2 * B)
     for kw in (dict(), ddim):
         plain = m.generate(shape2, context_value=[1, 0, 0, 1], seed=5, **kw)
         torch.cuda.synchronize()
@@ -304,11 +237,11 @@ def test_guided_edit(dev):
     """A half-volume mask keeps x0 bitwise under guidance; at w = 1 the guided edit is the first half of the plain 2 B edit with x0,
     mask and known_noise duplicated."""
     T, B = 20, 2
-    m, _ = _cond_model(T, 2 * B)
+    m, _ = cr.cond_model(T, 2 * B)
     g = torch.Generator().manual_seed(7)
     shape = (B, 8, 8, 8, 4)
     x0 = torch.rand(shape, generator=g) * 2 - 1
-    mask = _half_mask(B)
+    mask = cr.half_mask(B)
     c, n = [1, 0], [0, 1]
     ddim = dict(sampler="ddim", num_steps=5, eta=0.5)
     for kw in (dict(), dict(strength=0.5), ddim, dict(ddim, strength=0.6)):
@@ -332,7 +265,7 @@ def test_guided_edit(dev):
 def test_per_volume_scales(dev):
     """B = 3 with w = (1, 3, 0) in one call equals, volume by volume, the three calls with one scalar each (the same plan)."""
     T, B = 20, 3
-    m, _ = _cond_model(T, 2 * B)
+    m, _ = cr.cond_model(T, 2 * B)
     shape = (B, 8, 8, 8, 4)
     c, n, ws = [1, 0, 1], [0, 1, 0], (1.0, 3.0, 0.0)
     for kw in (dict(), dict(sampler="ddim", num_steps=5, eta=0.5), dict(guidance_rescale=0.5),
@@ -348,19 +281,19 @@ def test_full_size_steps_match_oracle_and_b32_chain(dev):
     """32^3 x 8ch (h3), T = 1000: three guided DDIM steps of the S = 50 schedule at B = 2, w = 3, against the oracle under the eps
     contract (1e-3 of max |ref|) times |w| + |1 - w| = 5; one whole guided S = 50 chain of B = 32, a 64-row plan, through the graph
     (output conv scaled by 0.1, as the unguided full-size chain test) is finite, within [-1, 1], and leaves the range guard quiet."""
-    from oracle import ref_torch as rt
     T, S, B, C, w = 1000, 50, 2, 8, 3.0
-    m, W = _cond_model(T, B, size=32, C=C, precision="h3")
+    m, W = cr.cond_model(T, B, size=32, C=C, precision="h3")
     shape = (B, 32, 32, 32, C)
     x_T = torch.randn(shape, generator=torch.Generator().manual_seed(12))
     c, n = torch.tensor([[[1]], [[0]]]), torch.tensor([[[0]], [[1]]])
     got = m.generate(shape, context_value=c, x_T=x_T, sampler="ddim", num_steps=S, steps=3, guidance_scale=w, negative_context=n).cpu()
-    ref = _guided_chain64(_oracle(W, 32, C), rt.Betas(T), "ddim", _schedule(T, S), x_T, c, n, w, 0.0, steps=3)
+    f = cr.oracle(W, 32, C)
+    ref = cr.chain64(lambda x, t: _guide_as_tables(f(x, t, c), f(x, t, n), w)[0], cr.oracle_alpha_bar(T).double(), cr.schedule(T, S), x_T,
+                     "ddim", steps=3)
     err = float((got.double() - ref).abs().max())
     print(f"3 full-size guided DDIM steps: max abs difference {err:.2e}, max |x| {float(ref.abs().max()):.3f}")
     assert err / float(ref.abs().max()) < 1e-3 * (abs(w) + abs(1 - w))
-    Wb = dict(W, **{k: W[k] * np.float32(0.1) for k in ("out.conv.kernel", "out.conv.bias")})
-    big, _ = _cond_model(T, 32, size=32, C=C, W=Wb, precision="h3")
+    big, _ = cr.cond_model(T, 32, size=32, C=C, W=cr.weights(32, C, scale=0.1), precision="h3")
     out = big.generate((32, 32, 32, 32, C), context_value=1, seed=7, sampler="ddim", num_steps=S, guidance_scale=w, negative_context=0,
                        guidance_rescale=0.7)                                # check_range raises if flagged
     torch.cuda.synchronize()

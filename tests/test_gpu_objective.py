@@ -1,17 +1,18 @@
 """GPU tier of v- / x0-prediction and min-SNR loss weighting: dm3d_pred_to_eps and dm3d_objective_loss_grad bitwise against numpy
-float32 restatements, the chains of a v- and an x0-model against float64 chains that read the CPU oracle's output as v or as x0, the
-single-call predict_eps, and training against torch.autograd with the loss written out here in float64.
+float32 restatements, the chains of a v- and an x0-model against the float64 chains of tests/chain_reference.py on the CPU oracle's
+output read as v or as x0 and converted to eps (where the chain is guided, before the guidance), the single-call predict_eps, and training against torch.autograd with the loss written out here in float64.
 
 The network is the oracle's (oracle.ref_torch.unet_forward on synthetic weights): what its output "means" is up to the chain, so the
 same weights serve as an eps-, a v- and an x0-model."""
 import ctypes as C
-import math
 import os
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
+
+import chain_reference as cr
 
 pytestmark = pytest.mark.gpu
 CHAIN_BAR = 2e-3        # the project's chain bar (tests/test_gpu_ddim.py)
@@ -26,25 +27,6 @@ def dev():
     torch.cuda.set_device(0)
     torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
     return torch.device("cuda:0")
-
-
-def _args(T, bs=1):
-    return SimpleNamespace(timesteps=T, num_gpus=1, kernel_resize=False, bs=bs)
-
-
-def _cond_model(T, B, W=None, seed=0, **kw):
-    import dm3d_amd
-    from dm3d_amd.networks import conditional_dm3d as cdm
-    cfg = dm3d_amd.UNetConfig(img_size=8, img_channels=4)
-    W = dm3d_amd.synthetic_weights(cfg, seed=seed) if W is None else W
-    return cdm.DiffusionModel(8, 1024, 4, None, _args(T, B), weights=W, **kw), W
-
-
-def _oracle(W):
-    from oracle import ref_torch as rt
-    ocfg = rt.UNetConfig(img_size=8, img_channels=4)
-    Wt = {k: torch.from_numpy(v) for k, v in W.items()}
-    return lambda x, t, ctx: rt.unet_forward(Wt, ocfg, x.float(), torch.full((x.shape[0],), int(t), dtype=torch.int64), ctx)
 
 
 def _st():
@@ -164,81 +146,9 @@ def test_objective_loss_grad_against_restatements(dev, per):
 
 
 # ---- chains -------------------------------------------------------------------------------------------------------------------------
-def _schedule(T, S):
-    return [T - 1] if S == 1 else [int(math.floor(i * (T - 1) / (S - 1) + 0.5)) for i in range(S)]
-
-
-def _eps64(kind, pred, x, a):
-    """The network's output read as ``kind`` at alpha_bar a, as eps, in float64."""
-    pred, x = pred.double(), x.double()
-    if kind == "v":
-        return math.sqrt(a) * pred + math.sqrt(1 - a) * x
-    if kind == "x0":
-        return (x - math.sqrt(a) * pred) / math.sqrt(1 - a)
-    return pred
-
-
-def _ddim64(x, eps, a, ap, clip=True):
-    x0 = (x.double() - math.sqrt(1 - a) * eps) / math.sqrt(a)
-    if clip:
-        x0 = x0.clamp(-1, 1)
-    return math.sqrt(ap) * x0 + math.sqrt(1 - ap) * eps
-
-
-def _dpm_row64(ab, s, t, p):
-    """(c_x, c_0, c_1) of the DPM-Solver++(2M) step from timestep s to t (t < 0: clean); p < 0: first order."""
-    if t < 0:
-        return 0.0, 1.0, 0.0
-    al = lambda i: math.sqrt(float(ab[i]))
-    sg = lambda i: math.sqrt(1.0 - float(ab[i]))
-    lam = lambda i: math.log(al(i) / sg(i))
-    h = lam(t) - lam(s)
-    A = al(t) * (1.0 - math.exp(-h))
-    if p < 0:
-        return sg(t) / sg(s), A, 0.0
-    r = (lam(s) - lam(p)) / h
-    return sg(t) / sg(s), A * (1.0 + 1.0 / (2.0 * r)), -A / (2.0 * r)
-
-
-def _guide64(ep, en, w, phi):
-    out = []
-    for b in range(ep.shape[0]):
-        g = en[b] + w * (ep[b] - en[b])
-        sg = float(g.std(unbiased=False))
-        f = phi * float(ep[b].std(unbiased=False)) / sg + (1 - phi) if sg > 0 else 1.0
-        out.append(f * g)
-    return torch.stack(out)
-
-
-def _chain64(kind, sampler, f, b, sched, x_T, ids, noise=None, neg=None, w=None, phi=0.0, steps=None):
-    """The chain in float64 with the oracle network's output read as ``kind``: converted to eps, guided (where ``neg`` is given), then
-    the solver's step.  sampler="ddpm": ``sched`` holds every timestep and ``noise`` row t is the z of the step from t."""
-    from oracle import ref_torch as rt
-    ab = b.alpha_bar.double()
-    x, hist = x_T.double(), None
-    n = len(sched)
-    prev = list(sched[1:]) + [-1]                 # DPM-Solver++(2M), lower_order_final: the first step, the step into sched[0] and the
-    if n > 1:                                     # step to clean are first order
-        prev[1] = -1
-    for k, i in enumerate(range(n - 1, -1, -1)):
-        if steps is not None and k == steps:
-            break
-        t = sched[i]
-        a = float(ab[t])
-        eps = _eps64(kind, f(x, t, ids), x, a)
-        if neg is not None:
-            eps = _guide64(eps, _eps64(kind, f(x, t, neg), x, a), w, phi)
-        if sampler == "ddpm":
-            z = noise[t].double() if t > 0 else torch.zeros_like(x)
-            x = rt.ddpm_step(b, x, eps, torch.full((x.shape[0],), t, dtype=torch.int64), z)
-        elif sampler == "ddim":
-            x = _ddim64(x, eps, a, float(ab[sched[i - 1]]) if i > 0 else 1.0)
-        else:
-            x0 = ((x - math.sqrt(1 - a) * eps) / math.sqrt(a)).clamp(-1, 1)
-            c_x, c_0, c_1 = _dpm_row64(ab, t, sched[i - 1] if i > 0 else -1, prev[i])
-            x = c_x * x + c_0 * x0 + (c_1 * hist if c_1 != 0 else 0.0)
-            hist = x0
-    return x
+def _as_eps(kind, f, ab, ctx):
+    """The oracle network's output under ``ctx`` read as ``kind`` and converted to eps, as the converting chain does."""
+    return lambda x, t: cr.eps64(kind, x, f(x, t, ctx), float(ab[t]))
 
 
 IDS = torch.tensor([[[1]], [[0]]])
@@ -250,20 +160,21 @@ SHAPE = (2, 8, 8, 8, 4)
 def test_chain_matches_float64(dev, kind, sampler):
     """8^3 x 4ch, T = 20, S = 5, B = 2 with one context id per volume (the DDPM chain: all 20 steps, injected noise).  At T = 20
     alpha_bar stays above 0.8: the x0 estimate divides by no small sqrt(alpha_bar)."""
-    from oracle import ref_torch as rt
     T, S = 20, 5
-    m, W = _cond_model(T, 2, prediction=kind)
+    m, W = cr.cond_model(T, 2, prediction=kind)
     g = torch.Generator().manual_seed(21)
     x_T = torch.randn(SHAPE, generator=g)
-    b = rt.Betas(T)
+    b = cr.oracle_betas(T)
+    ab = b.alpha_bar.double()
+    net = _as_eps(kind, cr.oracle(W), ab, IDS)
     assert float(b.alpha_bar.min()) > 0.8
     if sampler == "ddpm":
         noise = torch.randn((T,) + SHAPE, generator=g)
         got = m.generate(SHAPE, context_value=IDS, x_T=x_T, noise=noise).cpu()
-        ref = _chain64(kind, "ddpm", _oracle(W), b, list(range(T)), x_T, IDS, noise=noise)
+        ref = cr.chain64(net, ab, list(range(T)), x_T, "ddpm", noise=noise, betas=b)
     else:
         got = m.generate(SHAPE, context_value=IDS, x_T=x_T, sampler=sampler, num_steps=S).cpu()
-        ref = _chain64(kind, sampler, _oracle(W), b, _schedule(T, S), x_T, IDS)
+        ref = cr.chain64(net, ab, cr.schedule(T, S), x_T, sampler)
     err = float((got.double() - ref).abs().max())
     print(f"{kind} model, {sampler} chain: max abs difference {err:.2e} (max |x| {float(ref.abs().max()):.3f})")
     assert torch.isfinite(got).all() and err < CHAIN_BAR
@@ -271,14 +182,15 @@ def test_chain_matches_float64(dev, kind, sampler):
 
 def test_guided_v_chain_matches_float64(dev):
     """Guidance (w = 3, phi = 0.7) acts on the converted eps of both halves of the plan."""
-    from oracle import ref_torch as rt
     T, S = 20, 5
-    m, W = _cond_model(T, 2, prediction="v")
+    m, W = cr.cond_model(T, 2, prediction="v")
     x_T = torch.randn(SHAPE, generator=torch.Generator().manual_seed(22))
     neg = torch.tensor([[[0]], [[1]]])
     got = m.generate(SHAPE, context_value=IDS, x_T=x_T, sampler="ddim", num_steps=S, guidance_scale=3.0, guidance_rescale=0.7,
                      negative_context=neg).cpu()
-    ref = _chain64("v", "ddim", _oracle(W), rt.Betas(T), _schedule(T, S), x_T, IDS, neg=neg, w=3.0, phi=0.7)
+    f, ab = cr.oracle(W), cr.oracle_alpha_bar(T).double()
+    pos, neg_eps = _as_eps("v", f, ab, IDS), _as_eps("v", f, ab, neg)
+    ref = cr.chain64(lambda x, t: cr.guide64(pos(x, t), neg_eps(x, t), 3.0, 0.7), ab, cr.schedule(T, S), x_T, "ddim")
     err = float((got.double() - ref).abs().max())
     print(f"guided v model, ddim chain: max abs difference {err:.2e}")
     assert err < CHAIN_BAR
@@ -292,8 +204,8 @@ def test_graph_equals_eager_and_kinds_do_not_leak(dev):
     alternately, each equal their own fresh model's result bitwise; the converting step's graph has a kind of its own and the eps
     model's kinds are what they were."""
     T = 20
-    v, W = _cond_model(T, 2, prediction="v")
-    e, _ = _cond_model(T, 2, W=W)
+    v, W = cr.cond_model(T, 2, prediction="v")
+    e, _ = cr.cond_model(T, 2, W=W)
     calls = [dict(sampler="ddim", num_steps=5, eta=0.5), dict(sampler="dpmpp", num_steps=5), dict()]
     for kw in calls:
         a = v.generate(SHAPE, context_value=IDS, seed=5, use_graph=True, **kw)
@@ -302,7 +214,7 @@ def test_graph_equals_eager_and_kinds_do_not_leak(dev):
         assert torch.equal(a, b) and torch.isfinite(a).all(), kw
     fresh = {}
     for name, kind in (("v", "v"), ("eps", "eps")):
-        fm, _ = _cond_model(T, 2, W=W, prediction=kind)
+        fm, _ = cr.cond_model(T, 2, W=W, prediction=kind)
         fresh[name] = [fm.generate(SHAPE, context_value=IDS, seed=5, **kw).clone() for kw in calls]
     for _ in range(2):
         for i, kw in enumerate(calls):
@@ -318,10 +230,9 @@ def test_graph_equals_eager_and_kinds_do_not_leak(dev):
 
 
 def test_predict_eps_then_ddim_step_is_one_step_of_the_chain(dev):
-    from oracle import ref_torch as rt
     T, S = 20, 5
-    m, W = _cond_model(T, 2, prediction="v")
-    sched = _schedule(T, S)
+    m, W = cr.cond_model(T, 2, prediction="v")
+    sched = cr.schedule(T, S)
     x_T = torch.randn(SHAPE, generator=torch.Generator().manual_seed(23))
     want = m.generate(SHAPE, context_value=IDS, x_T=x_T, sampler="ddim", num_steps=S, steps=1)
     t = torch.tensor([sched[-1]] * 2)
@@ -329,11 +240,12 @@ def test_predict_eps_then_ddim_step_is_one_step_of_the_chain(dev):
     eps = m.predict_eps(x_T, pred, sched[-1])
     got = m.ddim_step(x_T, eps, sched[-1], sched[-2])
     assert float((got - want).abs().max()) < CHAIN_BAR
-    ref = _chain64("v", "ddim", _oracle(W), rt.Betas(T), sched, x_T, IDS, steps=1)
+    ab = cr.oracle_alpha_bar(T).double()
+    ref = cr.chain64(_as_eps("v", cr.oracle(W), ab, IDS), ab, sched, x_T, "ddim", steps=1)
     assert float((got.cpu().double() - ref).abs().max()) < CHAIN_BAR
     # out of place: the inputs are left alone; per-volume t; an eps model's table is the identity
     assert torch.equal(m.predict_eps(x_T, pred, [sched[-1], sched[-1]]), eps)
-    plain, _ = _cond_model(T, 2, W=W)
+    plain, _ = cr.cond_model(T, 2, W=W)
     assert torch.equal(plain.predict_eps(x_T, pred, 7), pred)
 
 
@@ -421,7 +333,7 @@ def test_train_step_public_api(dev, kind, weighting):
     import dm3d_amd
     from oracle import ref_torch as rt, ref_train as ot
     T, B, lc, lr = 50, 2, 4, 2e-4
-    m, W = _cond_model(T, B, seed=1, prediction=kind)
+    m, W = cr.cond_model(T, B, W=cr.weights(seed=1), prediction=kind)
     m.compile(loss="mse_sum", optimizer=SimpleNamespace(learning_rate=lr), loss_weighting=weighting)
     g = torch.Generator().manual_seed(5)
     lat, noise = torch.randn(SHAPE, generator=g), torch.randn(SHAPE, generator=g)

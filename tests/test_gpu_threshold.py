@@ -1,23 +1,23 @@
 """GPU tier of dynamic thresholding (dm3d_x0_threshold; DiffusionModel.x0_threshold, ddim_step / dpm_step / generate / edit / sampler
 with dynamic_threshold / threshold_max).
 
-The bound s is exact, so it is compared bitwise with this file's np.float32 restatement of the rule (include/dm3d.h,
-dm3d_thresh_desc): x0 by the same three float32 operations, the order statistics from np.sort.  Chains are compared with float64
-chains driven by the CPU oracle (oracle.ref_torch.unet_forward), whose quantile is numpy's "linear" one in float64.
+The bound s is exact, so it is compared bitwise with the np.float32 restatement of the rule (include/dm3d.h, dm3d_thresh_desc) in
+tests/chain_reference.py: x0 by the same three float32 operations, the order statistics from np.sort.  Chains are compared with that
+module's float64 chains driven by the CPU oracle (oracle.ref_torch.unet_forward), whose quantile is numpy's "linear" one in float64.
 """
 import math
 import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+import chain_reference as cr
+
 pytestmark = pytest.mark.gpu
 CHAIN_BAR = 2e-3        # the DDIM / DPM-Solver++ chain tests' bar
 KERNEL_BAR = 2e-6       # their kernel tests' bar
 ROUND = 6e-8            # one float32 rounding of a value <= 1: the thresholded estimate the float64 formulas start from
-F32_MAX = float(np.finfo(np.float32).max)
 
 
 @pytest.fixture(scope="module")
@@ -29,58 +29,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _args(T, bs=1):
-    return SimpleNamespace(timesteps=T, num_gpus=1, kernel_resize=False, bs=bs)
-
-
-def _schedule(T, S):
-    return [T - 1] if S == 1 else [int(math.floor(i * (T - 1) / (S - 1) + 0.5)) for i in range(S)]
-
-
-def _cond_model(T, B, size=8, C=4, W=None, **kw):
-    import dm3d_amd
-    from dm3d_amd.networks import conditional_dm3d as cdm
-    cfg = dm3d_amd.UNetConfig(img_size=size, img_channels=C)
-    W = dm3d_amd.synthetic_weights(cfg, seed=0) if W is None else W
-    return cdm.DiffusionModel(size, 1024, C, None, _args(T, B), weights=W, **kw), W
-
-
-def _oracle(W, size, C):
-    from oracle import ref_torch as rt
-    ocfg = rt.UNetConfig(img_size=size, img_channels=C, conditional=True)
-    Wt = {k: torch.from_numpy(v) for k, v in W.items()}
-    return lambda x, t, ctx=None: rt.unet_forward(Wt, ocfg, x.float(), torch.full((x.shape[0],), int(t), dtype=torch.int64), ctx)
-
-
-def _alpha_bar(T):
-    from oracle import ref_torch as rt
-    return rt.Betas(T).alpha_bar                        # float32: the table the kernels read
-
-
-# ---- the rule, restated in np.float32 ----------------------------------------------------------------------------------------------
-def _x0_32(x, e, ab32, t):
-    """(x - sqrt(1-a) eps) / sqrt(a) of one volume in float32: mul, sub, div, each rounded; the coefficients are the host table's
-    (float64 square roots of the float32 alpha_bar, rounded once)."""
-    a = np.float64(np.asarray(ab32)[t])
-    sqab, sq1ab = np.float32(np.sqrt(a)), np.float32(np.sqrt(1 - a))
-    x, e = np.asarray(x, dtype=np.float32).reshape(-1), np.asarray(e, dtype=np.float32).reshape(-1)
-    with np.errstate(all="ignore"):
-        return (x - sq1ab * e) / sqab
-
-
-def _bound32(x0, p, smax=F32_MAX):
-    """(s, s_raw) of one volume's float32 x0: np.sort puts a NaN last, as the kernel's bit-pattern order does."""
-    v = np.sort(np.abs(x0))
-    N = v.size
-    q = float(p) * (N - 1)
-    i = min(int(math.floor(q)), N - 1)
-    f = np.float32(q - i)
-    with np.errstate(all="ignore"):
-        raw = np.float32(v[i] + np.float32(f * np.float32(v[min(i + 1, N - 1)] - v[i])))
-    s = raw if np.isnan(raw) else np.minimum(np.maximum(raw, np.float32(1)), np.float32(smax))
-    return np.float32(s), raw
-
-
+# ---- the rule, restated in np.float32 (cr.x0_32, cr.bound32) ------------------------------------------------------------------------
 def _apply32(x0, s):
     with np.errstate(all="ignore"):
         return np.where(np.isnan(x0), x0, np.minimum(np.maximum(x0, -s), s) / s).astype(np.float32)
@@ -89,8 +38,8 @@ def _apply32(x0, s):
 def _bounds32(x, e, ab32, t, p, smax=None):
     B = x.shape[0]
     t, p = np.broadcast_to(np.asarray(t), (B,)), np.broadcast_to(np.asarray(p, dtype=np.float64), (B,))
-    smax = np.broadcast_to(np.asarray(F32_MAX if smax is None else smax, dtype=np.float64), (B,))
-    out = [_bound32(_x0_32(x[b], e[b], ab32, t[b]), p[b], smax[b]) for b in range(B)]
+    smax = np.broadcast_to(np.asarray(cr.F32_MAX if smax is None else smax, dtype=np.float64), (B,))
+    out = [cr.bound32(cr.x0_32(x[b], e[b], ab32, t[b]), p[b], smax[b]) for b in range(B)]
     return np.array([o[0] for o in out], dtype=np.float32), np.array([o[1] for o in out], dtype=np.float32)
 
 
@@ -108,8 +57,8 @@ SHAPES = [(2, 4), (2, 500), (2, 1028), (2, 2048), (3, 8, 8, 8, 4), (2, 10240)]  
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_bound_is_bitwise(dev, shape):
     T, B = 1000, shape[0]
-    m, _ = _cond_model(T, B)
-    ab = _alpha_bar(T)
+    m, _ = cr.cond_model(T, B)
+    ab = cr.oracle_alpha_bar(T)
     g = torch.Generator().manual_seed(int(np.prod(shape)))
     x, e = (torch.randn(shape, generator=g) for _ in range(2))
     t = [400, 30, 900][:B] if len(shape) == 5 else 300                # a different row per volume at 8^3 x 4
@@ -147,8 +96,8 @@ def _x0_inputs(x0, ab32, t):
 
 def test_ties_and_specials(dev):
     T, N, t = 1000, 2048, 300
-    m, _ = _cond_model(T, 2)
-    ab = _alpha_bar(T)
+    m, _ = cr.cond_model(T, 2)
+    ab = cr.oracle_alpha_bar(T)
     rng = np.random.default_rng(5)
 
     def check(x, e, p, smax=None, t=t):
@@ -170,9 +119,9 @@ def test_ties_and_specials(dev):
     e = np.zeros_like(x)
     for p in (0.5, 0.9, 0.995, 1.0):
         check(x, e, p)
-    counts = np.cumsum(np.bincount(np.searchsorted(levels, np.sort(np.abs(_x0_32(x[0], e[0], ab, t)))), minlength=8))
+    counts = np.cumsum(np.bincount(np.searchsorted(levels, np.sort(np.abs(cr.x0_32(x[0], e[0], ab, t)))), minlength=8))
     edge = int(counts[3]) - 1                                          # the last element of a run: v_i and v_{i+1} differ
-    v = np.sort(np.abs(_x0_32(x[0], e[0], ab, t)))
+    v = np.sort(np.abs(cr.x0_32(x[0], e[0], ab, t)))
     assert v[edge] != v[edge + 1]
     check(x, e, (edge + 0.5) / (N - 1))
     # +-0, +-inf and magnitudes that differ in the lowest mantissa bit only (the last digit of the select)
@@ -183,7 +132,7 @@ def test_ties_and_specials(dev):
     x0[1] = rng.standard_normal(N)
     x0[1, :6] = [0.0, -0.0, np.inf, -np.inf, 0.0, -0.0]
     x, e = _x0_inputs(x0, ab, t)
-    got_x0 = np.stack([_x0_32(x[b], e[b], ab, t) for b in range(2)])
+    got_x0 = np.stack([cr.x0_32(x[b], e[b], ab, t) for b in range(2)])
     assert len(np.unique(np.abs(got_x0[0]))) >= 4 and np.ptp(np.abs(got_x0[0]).view(np.uint32).astype(np.int64)) <= 16
     assert np.isinf(got_x0[1]).sum() == 2 and (got_x0[1] == 0).sum() == 4
     for p in (0.25, 0.5, 0.75, 0.995, (N - 3.5) / (N - 1), 1.0, 1e-4):
@@ -211,39 +160,12 @@ def test_ties_and_specials(dev):
 
 
 # ---- 3. the update -------------------------------------------------------------------------------------------------------------------
-def _row64(ab, s, t, p):
-    """(c_x, c_0, c_1) of the DPM-Solver++ step from timestep s to t (t < 0: clean) in float64; p: the step before's (p < 0: first order)."""
-    if t < 0:
-        return 0.0, 1.0, 0.0
-    al = lambda i: math.sqrt(float(ab[i]))
-    sg = lambda i: math.sqrt(1.0 - float(ab[i]))
-    lam = lambda i: math.log(al(i) / sg(i))
-    h = lam(t) - lam(s)
-    A = al(t) * (1.0 - math.exp(-h))
-    if p < 0:
-        return sg(t) / sg(s), A, 0.0
-    r = (lam(s) - lam(p)) / h
-    return sg(t) / sg(s), A * (1.0 + 1.0 / (2.0 * r)), -A / (2.0 * r)
-
-
-def _ddim_from_x0(x0, eps, a, ap, eta=0.0, z=None):
-    sigma = eta * math.sqrt((1 - ap) / (1 - a)) * math.sqrt(1 - a / ap) if eta else 0.0
-    out = math.sqrt(ap) * x0 + math.sqrt(max(1 - ap - sigma * sigma, 0.0)) * eps
-    return out + sigma * z if sigma else out
-
-
-def _dpm_from_x0(x, x0, ab, s, t, p=-1, hist=None):
-    c_x, c_0, c_1 = _row64(ab, s, t, p)
-    out = c_x * x + c_0 * x0
-    return out + c_1 * hist if c_1 != 0 else out
-
-
 def test_update_matches_restatement(dev):
     """ddim_step / dpm_step with the keywords: the restatement's float32 clamp(x0, -s, s) / s, then the float64 step formulas.  Bars: the
     DDIM / DPM-Solver++ kernel tests' for the same outputs plus one float32 rounding of the thresholded estimate."""
     T, B = 1000, 3
-    m, _ = _cond_model(T, B)
-    ab32 = _alpha_bar(T)
+    m, _ = cr.cond_model(T, B)
+    ab32 = cr.oracle_alpha_bar(T)
     ab = ab32.double()
     g = torch.Generator().manual_seed(31)
     shape = (B, 8, 8, 8, 4)
@@ -255,11 +177,11 @@ def test_update_matches_restatement(dev):
     for t, tp, tb in (([400, 300, 20], [380, 150, -1], [420, 999, 25]), ([500, 999, 5], [480, 979, -1], [520, -1, 9])):
         s, _ = _bounds32(x.numpy(), e.numpy(), ab32, t, p, smax)
         assert np.any(s > 1) and np.all(np.isfinite(s))
-        x0 = [torch.from_numpy(_apply32(_x0_32(x[b], e[b], ab32, t[b]), s[b])).reshape(shape[1:]).double() for b in range(B)]
+        x0 = [torch.from_numpy(_apply32(cr.x0_32(x[b], e[b], ab32, t[b]), s[b])).reshape(shape[1:]).double() for b in range(B)]
         for eta in (0.0, 0.5):
             got = m.ddim_step(xd, ed, torch.tensor(t), torch.tensor(tp), eta, noise=z, dynamic_threshold=p, threshold_max=smax).cpu()
             for b in range(B):
-                ref = _ddim_from_x0(x0[b], e[b].double(), float(ab[t[b]]), float(ab[tp[b]]) if tp[b] >= 0 else 1.0, eta, z[b].double())
+                ref = cr.ddim_update64(x0[b], e[b].double(), float(ab[t[b]]), float(ab[tp[b]]) if tp[b] >= 0 else 1.0, eta, z[b])
                 err = float((got[b].double() - ref).abs().max())
                 print(f"ddim_step eta={eta} t={t[b]} -> {tp[b]} s={s[b]:.4f}: err {err:.2e}")
                 assert float(ref.abs().max()) < 20 and err < KERNEL_BAR + ROUND
@@ -269,8 +191,8 @@ def test_update_matches_restatement(dev):
         got, got0 = got.cpu(), got0.cpu()
         for b in range(B):
             pb = tb[b] if second else -1
-            ref = _dpm_from_x0(x[b].double(), x0[b], ab, t[b], tp[b], pb, h[b].double())
-            bar = KERNEL_BAR * max(1.0, sum(abs(c) for c in _row64(ab, t[b], tp[b], pb))) + ROUND
+            ref = cr.dpm_update64(x[b].double(), x0[b], ab, t[b], tp[b], pb, h[b])
+            bar = KERNEL_BAR * max(1.0, sum(abs(c) for c in cr.dpm_row64(ab, t[b], tp[b], pb))) + ROUND
             err = float((got[b].double() - ref).abs().max())
             print(f"dpm_step t={t[b]} -> {tp[b]} (before {pb}) s={s[b]:.4f}: err {err:.2e} (bar {bar:.2e})")
             assert err < bar
@@ -293,67 +215,6 @@ def test_update_matches_restatement(dev):
 
 # ---- 4. chains -----------------------------------------------------------------------------------------------------------------------
 P_CHAIN, CAP_CHAIN = 0.9, 6.0
-
-
-def _thr64(x0, bounds, p=P_CHAIN, cap=CAP_CHAIN):
-    """Dynamic thresholding of a float64 x0 estimate [B, ...]; appends each volume's s to ``bounds``."""
-    out = []
-    for b in range(x0.shape[0]):
-        s = min(max(float(np.quantile(x0[b].abs().numpy().reshape(-1), p)), 1.0), cap)
-        bounds.append(s)
-        out.append(x0[b].clamp(-s, s) / s)
-    return torch.stack(out)
-
-
-def _chain64(solver, eps_fn, ab, sched, x_start, bounds, eta=0.0, noise=None, order=2, blend=None):
-    """The thresholded chain with float64 bookkeeping: steps from sched[-1] down to sched[0], then clean; ``blend(i, x)`` (edit chains)
-    follows the step from sched[i].  DDIM carries the model's eps on; DPM-Solver++ uses the thresholded estimate and remembers it."""
-    x, hist = x_start.double(), None
-    n = len(sched)
-    prev = list(sched[1:]) + [-1]
-    if order == 1:
-        prev = [-1] * n
-    if n > 1:
-        prev[1] = -1                                                    # lower_order_final
-    for i in range(n - 1, -1, -1):
-        a = float(ab[sched[i]])
-        eps = eps_fn(x, sched[i]).double()
-        x0 = _thr64((x - math.sqrt(1 - a) * eps) / math.sqrt(a), bounds)
-        if solver == "ddim":
-            ap = float(ab[sched[i - 1]]) if i > 0 else 1.0
-            x = _ddim_from_x0(x0, eps, a, ap, eta, None if noise is None else noise[i].double())
-        else:
-            x, hist = _dpm_from_x0(x, x0, ab, sched[i], sched[i - 1] if i > 0 else -1, prev[i], hist), x0
-        if blend is not None:
-            x = blend(i, x)
-    return x
-
-
-def _guide64(ep, en, w, phi):
-    ep, en = ep.double(), en.double()
-    out = []
-    for b in range(ep.shape[0]):
-        g = en[b] + w * (ep[b] - en[b])
-        if phi != 0:
-            sg = float(g.std(unbiased=False))
-            g = (phi * float(ep[b].std(unbiased=False)) / sg + (1 - phi) if sg > 0 else 1.0) * g
-        out.append(g)
-    return torch.stack(out)
-
-
-def _known64(x0, ab, level, z):
-    if level < 0:
-        return x0.double()
-    a = float(ab[level])
-    return math.sqrt(a) * x0.double() + math.sqrt(1 - a) * z.double()
-
-
-def _half_mask(B):
-    m = torch.zeros((B, 16, 16, 16))
-    m[:, :8] = 1.0
-    return m
-
-
 SOLVERS = [("ddim", dict(eta=0.0)), ("ddim", dict(eta=0.5)), ("dpmpp", dict(solver_order=1)), ("dpmpp", dict(solver_order=2))]
 X_SCALE = 1.5           # of x_T and of the edited latent
 OUT_SCALE = 3.0         # of the output conv.  A DDIM chain at eta = 0 carries eps on, so once its estimate is thresholded the next one
@@ -362,17 +223,11 @@ OUT_SCALE = 3.0         # of the output conv.  A DDIM chain at eta = 0 carries e
                         # step of the DPM-Solver++ chains (asserted below)
 
 
-def _chain_weights():
-    import dm3d_amd
-    W = dm3d_amd.synthetic_weights(dm3d_amd.UNetConfig(img_size=8, img_channels=4), seed=0)
-    return dict(W, **{k: W[k] * np.float32(OUT_SCALE) for k in ("out.conv.kernel", "out.conv.bias")})
-
-
 @pytest.fixture(scope="module")
 def chain_model(dev):
     T, B = 20, 2
-    m, W = _cond_model(T, B, W=_chain_weights())
-    return m, _oracle(W, 8, 4), _alpha_bar(T).double(), T, B
+    m, W = cr.cond_model(T, B, W=cr.weights(scale=OUT_SCALE))
+    return m, cr.oracle(W), cr.oracle_alpha_bar(T).double(), T, B
 
 
 @pytest.mark.parametrize("solver,opts", SOLVERS, ids=lambda v: v if isinstance(v, str) else "-".join(f"{k}{x}" for k, x in v.items()))
@@ -391,30 +246,30 @@ def test_chain_matches_float64(chain_model, solver, opts, mode):
     phi = 0.7 if mode == "guided-rescaled" else 0.0
     eta = opts.get("eta", 0.0)
     order = opts.get("solver_order", 2)
-    eps_fn = (lambda x, t: _guide64(f(x, t, c), f(x, t, n), w, phi)) if guided else (lambda x, t: f(x, t, c))
+    eps_fn = (lambda x, t: cr.guide64(f(x, t, c), f(x, t, n), w, phi)) if guided else (lambda x, t: f(x, t, c))
     kw = dict(sampler=solver, num_steps=S, dynamic_threshold=P_CHAIN, threshold_max=CAP_CHAIN, **opts)
     if guided:
         kw.update(guidance_scale=w, negative_context=n, guidance_rescale=phi)
     bounds = []
     if not edit:
-        sched = _schedule(T, S)
+        sched = cr.schedule(T, S)
         noise = torch.randn((S,) + shape, generator=g) if eta else None
         got = m.generate(shape, context_value=c, x_T=x_T, noise=noise, **kw)
-        ref = _chain64(solver, eps_fn, ab, sched, x_T, bounds, eta, noise, order)
+        ref = cr.chain64(eps_fn, ab, sched, x_T, solver, eta=eta, noise=noise, order=order, thr=(P_CHAIN, CAP_CHAIN, bounds))
         plain = m.generate(shape, context_value=c, x_T=x_T, noise=noise, **{k: v for k, v in kw.items() if "threshold" not in k})
     else:
         x0 = (torch.rand(shape, generator=g) * 2 - 1) * X_SCALE
         k = edit_steps(0.6, S)
-        sched = _schedule(T, S)[:k]
+        sched = cr.schedule(T, S)[:k]
         assert k == 3
         known_noise = torch.randn((k + 1,) + shape, generator=g)
         noise = torch.randn((k,) + shape, generator=g) if eta else None
-        mask = _half_mask(B)
-        keep = (1 - latent_mask(mask, shape)).double().unsqueeze(-1)
-        blend = lambda i, x: keep * _known64(x0, ab, sched[i - 1] if i > 0 else -1, known_noise[i]) + (1 - keep) * x
+        mask = cr.half_mask(B, 16)
+        blend = cr.edit_blend64(x0, ab, sched, 1 - latent_mask(mask, shape), known_noise)
         ekw = dict(mask=mask, strength=0.6, known_noise=known_noise, noise=noise, **kw)
         got = m.edit(x0, c, **ekw)
-        ref = _chain64(solver, eps_fn, ab, sched, _known64(x0, ab, sched[-1], known_noise[k]), bounds, eta, noise, order, blend)
+        ref = cr.chain64(eps_fn, ab, sched, cr.known64(x0, ab, sched[-1], known_noise[k]), solver, eta=eta, noise=noise, order=order,
+                         thr=(P_CHAIN, CAP_CHAIN, bounds), blend=blend)
         plain = m.edit(x0, c, **{k_: v for k_, v in ekw.items() if "threshold" not in k_})
         assert torch.equal(got.cpu()[:, 4:], x0[:, 4:])                 # the kept half is x0 bitwise
     steps = len(bounds) // B
@@ -438,12 +293,12 @@ def test_graph_replay_tables_and_interleaving(dev, solver):
     thr_b = dict(num_steps=8, dynamic_threshold=[0.995, 0.5], threshold_max=[2.0, 50.0])
     plain_a = dict(num_steps=5)
     # a model that never touches the feature: the parent's path, and each chain's solo result
-    m0, W = _cond_model(T, B, W=_chain_weights())
+    m0, W = cr.cond_model(T, B, W=cr.weights(scale=OUT_SCALE))
     solo_plain = m0.generate(shape, **base, **plain_a).clone()
     solo_none = m0.generate(shape, **base, **plain_a, dynamic_threshold=None, threshold_max=None).clone()
     assert torch.equal(solo_plain, solo_none)
     assert {k[1] for k in m0._graphs} == {solver}                          # None: the same graph key as ever
-    m1, _ = _cond_model(T, B, W=W)
+    m1, _ = cr.cond_model(T, B, W=W)
     solo_a = m1.generate(shape, **base, **thr_a).clone()
     solo_b = m1.generate(shape, **base, **thr_b).clone()
     kinds = [k[1] for k in m1._graphs]
@@ -455,7 +310,7 @@ def test_graph_replay_tables_and_interleaving(dev, solver):
         assert torch.equal(m1.generate(shape, **base, **kw), want)
     # a thresholded and a plain chain on one plan, interleaved in either order
     for order in ((thr_a, plain_a, thr_b, plain_a, thr_a), (plain_a, thr_b, plain_a, thr_a)):
-        m2, _ = _cond_model(T, B, W=W)
+        m2, _ = cr.cond_model(T, B, W=W)
         for kw in order:
             want = solo_plain if kw is plain_a else solo_a if kw is thr_a else solo_b
             assert torch.equal(m2.generate(shape, **base, **kw), want)
@@ -474,16 +329,12 @@ def test_graph_replay_tables_and_interleaving(dev, solver):
 def test_full_size_bounds_are_bitwise(dev):
     """32^3 x 8ch (h3), B = 2, three steps of a thresholded DPM-Solver++ chain (S = 8 of T = 1000): each step's s, read from the chain
     and recomputed by x0_threshold on the chain's own x / eps, is the restatement's bitwise.  262 144 values a volume: 32 blocks."""
-    import dm3d_amd
     T, S, B, C, p = 1000, 8, 2, 8, 0.995
-    cfg = dm3d_amd.UNetConfig(img_size=32, img_channels=C)
-    W = dm3d_amd.synthetic_weights(cfg, seed=0)
-    Wb = dict(W, **{k: W[k] * np.float32(0.1) for k in ("out.conv.kernel", "out.conv.bias")})      # as the solvers' full-size tests
-    m, _ = _cond_model(T, B, size=32, C=C, W=Wb, precision="h3")
-    ab = _alpha_bar(T)
+    m, _ = cr.cond_model(T, B, size=32, C=C, W=cr.weights(32, C, scale=0.1), precision="h3")      # as the solvers' full-size tests
+    ab = cr.oracle_alpha_bar(T)
     shape = (B, 32, 32, 32, C)
-    sched = _schedule(T, S)
-    smp = m.sampler(shape, [1, 0], seed=7, kind="dpmpp", num_steps=S, dynamic_threshold=[p, 0.9], threshold_max=[F32_MAX, 4.0])
+    sched = cr.schedule(T, S)
+    smp = m.sampler(shape, [1, 0], seed=7, kind="dpmpp", num_steps=S, dynamic_threshold=[p, 0.9], threshold_max=[cr.F32_MAX, 4.0])
     smp.reset()
     seen = []
     for k in range(3):
@@ -492,8 +343,8 @@ def test_full_size_bounds_are_bitwise(dev):
         smp.step()
         torch.cuda.synchronize()
         eps, got = smp.plan.eps.clone(), smp.plan.thr_bound.clone()
-        want, raw = _bounds32(x_before.cpu().numpy(), eps.cpu().numpy(), ab, t, [p, 0.9], [F32_MAX, 4.0])
-        again = m.x0_threshold(x_before, eps, t, [p, 0.9], [F32_MAX, 4.0])
+        want, raw = _bounds32(x_before.cpu().numpy(), eps.cpu().numpy(), ab, t, [p, 0.9], [cr.F32_MAX, 4.0])
+        again = m.x0_threshold(x_before, eps, t, [p, 0.9], [cr.F32_MAX, 4.0])
         print(f"step from t={t}: s = {got.cpu().numpy()}, s_raw = {raw}")
         assert _same(got, want) and _same(again, want)
         seen += list(raw)

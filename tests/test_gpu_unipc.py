@@ -1,7 +1,8 @@
 """GPU tier of the UniPC sampler (dm3d_unipc_update, DiffusionModel.unipc_step, generate / sampler with "unipc").
 
 The float64 reference is tests/unipc_reference.py, a restatement from the paper's formulas that never sees the library's tables, with
-eps from the CPU oracle (oracle.ref_torch.unet_forward) and alpha_bar from the oracle's float32 Betas table, the table the kernels read.
+eps from the CPU oracle (oracle.ref_torch.unet_forward) and alpha_bar from the oracle's float32 Betas table, the table the kernels read;
+models, oracle and schedules are tests/chain_reference.py's.
 
 Kernel bar.  Measured on the CPU over this file's own kernel inputs (KERNEL_CASES x clip on / off x B = 1, 3 and the two sizes): the worst
 |f32-order restatement - float64 restatement| is 4.14e-6 (x_next), 3.9e-7 (x_corr) and 2.5e-6 (x0), on values up to some tens; test_kernel_bar_is_four_times_the_
@@ -11,12 +12,12 @@ float64 oracle carried through five steps, not the update's."""
 import ctypes as C
 import math
 import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+import chain_reference as cr
 import unipc_reference as ur
 from guarded_buffers import IN, OUT, Guarded
 
@@ -35,9 +36,8 @@ KERNEL_CASES = [
 ]
 
 
-def _ab():
-    from oracle import ref_torch as rt
-    return rt.Betas(T_K).alpha_bar.double().numpy()
+def _ab(T=T_K):
+    return cr.oracle_alpha_bar(T).double().numpy()
 
 
 def _inputs(B, per, seed):
@@ -205,36 +205,9 @@ def test_nan_reaches_its_element_only_and_zero_coefficients_read_nothing(dev):
 
 
 # ---- chains ---------------------------------------------------------------------------------------------------------------------
-def _args(T, bs=1):
-    return SimpleNamespace(timesteps=T, num_gpus=1, kernel_resize=False, bs=bs)
-
-
-def _schedule(T, S):
-    return [T - 1] if S == 1 else [int(math.floor(i * (T - 1) / (S - 1) + 0.5)) for i in range(S)]
-
-
-def _cond_model(T, B, size=8, C=4, W=None, **kw):
-    import dm3d_amd
-    from dm3d_amd.networks import conditional_dm3d as cdm
-    cfg = dm3d_amd.UNetConfig(img_size=size, img_channels=C)
-    W = dm3d_amd.synthetic_weights(cfg, seed=0) if W is None else W
-    return cdm.DiffusionModel(size, 1024, C, None, _args(T, B), weights=W, **kw), W
-
-
-def _oracle(W, size, C, conditional=True):
-    from oracle import ref_torch as rt
-    ocfg = rt.UNetConfig(img_size=size, img_channels=C, conditional=conditional)
-    Wt = {k: torch.from_numpy(v) for k, v in W.items()}
-
-    def f(x, t, ctx=None):
-        x = torch.from_numpy(np.asarray(x)).float()
-        return rt.unet_forward(Wt, ocfg, x, torch.full((x.shape[0],), int(t), dtype=torch.int64), ctx).double().numpy()
-    return f
-
-
-def _ab20(T):
-    from oracle import ref_torch as rt
-    return rt.Betas(T).alpha_bar.double().numpy()
+def _numpy(net):
+    """A torch net(x, t) as ur.chain calls it: numpy in, numpy out."""
+    return lambda x, t: net(torch.from_numpy(np.asarray(x)), t).numpy()
 
 
 T, S, B = 20, 5, 2
@@ -245,8 +218,8 @@ IDS = torch.tensor([[[1]], [[0]]])
 @pytest.fixture(scope="module")
 def cond(dev):
     """The conditional 8^3 x 4ch model of tests/test_gpu_dpm.py, its oracle and alpha_bar, built once for the chain tests."""
-    m, W = _cond_model(T, B)
-    return m, _oracle(W, 8, 4), _ab20(T)
+    m, W = cr.cond_model(T, B)
+    return m, cr.oracle(W), _ab(T)
 
 
 @pytest.mark.gpu
@@ -257,7 +230,7 @@ def test_conditional_chain_matches_float64(dev, cond, order):
     for clip, variant in ((True, "bh2"), (False, "bh1")):
         got = m.generate(SHAPE, context_value=IDS, x_T=x_T, sampler="unipc", num_steps=S, clip_x0=clip, solver_order=order,
                          unipc_variant=variant).cpu()
-        ref = ur.chain(lambda x, t: f(x, t, IDS), ab, _schedule(T, S), x_T.numpy(), order, True, variant, clip)
+        ref = ur.chain(_numpy(lambda x, t: f(x, t, IDS)), ab, cr.schedule(T, S), x_T.numpy(), order, True, variant, clip)
         err = float(np.abs(got.double().numpy() - ref).max())
         print(f"unipc chain order={order} clip={clip} {variant}: max abs difference {err:.2e}, max |x| {float(np.abs(ref).max()):.3f}")
         assert err < CHAIN_BAR
@@ -269,28 +242,20 @@ def test_conditional_chain_matches_float64(dev, cond, order):
 @pytest.mark.gpu
 @pytest.mark.parametrize("order", [1, 2, 3])
 def test_unconditional_chain_matches_float64(dev, order):
-    import dm3d_amd
-    from dm3d_amd.networks import dm3d
-    cfg = dm3d_amd.UNetConfig(img_size=8, img_channels=4, conditional=False)
-    W = dm3d_amd.synthetic_weights(cfg, seed=0)
-    m = dm3d.DiffusionModel(8, 1024, 4, None, _args(T, B), weights=W)
+    m, W = cr.uncond_model(T, B)
     x_T = torch.randn(SHAPE, generator=torch.Generator().manual_seed(22))
     got = m.generate(SHAPE, x_T=x_T, sampler="unipc", num_steps=S, solver_order=order, lower_order_final=False).cpu()
-    ref = ur.chain(_oracle(W, 8, 4, conditional=False), _ab20(T), _schedule(T, S), x_T.numpy(), order, False)
+    ref = ur.chain(_numpy(cr.oracle(W, conditional=False)), _ab(T), cr.schedule(T, S), x_T.numpy(), order, False)
     err = float(np.abs(got.double().numpy() - ref).max())
     print(f"unconditional unipc chain order={order}: max abs difference {err:.2e}")
     assert err < CHAIN_BAR
-
-
-def _guide64(ep, en, w):
-    return en + w * (ep - en)
 
 
 @pytest.mark.gpu
 def test_guided_chains(dev, cond):
     """w = 1 is the plain 2B chain bitwise; w = 3 against float64 (bar: the chain bar times |w| + |1 - w| = 5, as the guidance tests)."""
     m, f, ab = cond
-    m4, _ = _cond_model(T, 2 * B)
+    m4, _ = cr.cond_model(T, 2 * B)
     c, n = [1, 0], [0, 1]
     x_T = torch.randn(SHAPE, generator=torch.Generator().manual_seed(5))
     kw = dict(sampler="unipc", num_steps=S, solver_order=3)
@@ -302,7 +267,7 @@ def test_guided_chains(dev, cond):
     w = 3.0
     neg = torch.tensor([[[0]], [[1]]])
     got = m.generate(SHAPE, context_value=IDS, x_T=x_T, guidance_scale=w, negative_context=neg, **kw)
-    ref = ur.chain(lambda x, t: _guide64(f(x, t, IDS), f(x, t, neg), w), ab, _schedule(T, S), x_T.numpy(), 3)
+    ref = ur.chain(_numpy(lambda x, t: cr.guide64(f(x, t, IDS), f(x, t, neg), w)), ab, cr.schedule(T, S), x_T.numpy(), 3)
     err = float(np.abs(got.cpu().double().numpy() - ref).max())
     print(f"guided unipc chain: max abs difference {err:.2e}")
     assert err < CHAIN_BAR * (abs(w) + abs(1 - w))
@@ -315,7 +280,7 @@ def test_thresholded_chain(dev, cond):
     x_T = torch.randn(SHAPE, generator=torch.Generator().manual_seed(31)) * 1.5
     kw = dict(context_value=IDS, x_T=x_T, sampler="unipc", num_steps=S, dynamic_threshold=0.9, threshold_max=4.0)
     got = m.generate(SHAPE, **kw)
-    ref = ur.chain(lambda x, t: f(x, t, IDS), ab, _schedule(T, S), x_T.numpy(), 2, threshold=(0.9, 4.0))
+    ref = ur.chain(_numpy(lambda x, t: f(x, t, IDS)), ab, cr.schedule(T, S), x_T.numpy(), 2, threshold=(0.9, 4.0))
     err = float(np.abs(got.cpu().double().numpy() - ref).max())
     print(f"thresholded unipc chain: max abs difference {err:.2e}")
     assert err < CHAIN_BAR and float(got.abs().max()) <= 1.0
@@ -338,8 +303,8 @@ def test_graph_equals_eager_repeats_and_serves_every_schedule_and_order(dev, con
         torch.cuda.synchronize()
         assert torch.equal(a, b) and torch.equal(a, c) and torch.isfinite(a).all(), kw
         x_T = m.generate(SHAPE, context_value=IDS, seed=5, sampler="unipc", steps=0, **kw).cpu()
-        sched = kw.get("timesteps") or _schedule(T, kw["num_steps"])
-        ref = ur.chain(lambda x, t: f(x, t, IDS), ab, sched, x_T.numpy(), kw.get("solver_order", 2), kw.get("lower_order_final", True),
+        sched = kw.get("timesteps") or cr.schedule(T, kw["num_steps"])
+        ref = ur.chain(_numpy(lambda x, t: f(x, t, IDS)), ab, sched, x_T.numpy(), kw.get("solver_order", 2), kw.get("lower_order_final", True),
                        kw.get("unipc_variant", "bh2"), kw.get("clip_x0", True))
         err = float(np.abs(a.cpu().double().numpy() - ref).max())
         print(f"unipc {kw}: max abs difference {err:.2e}")
@@ -374,9 +339,9 @@ def test_kinds_do_not_leak(dev):
              "ddim": dict(sampler="ddim", num_steps=5, eta=0.5)}
     alone = {}
     for k, kw in calls.items():
-        fresh, _ = _cond_model(T, B)
+        fresh, _ = cr.cond_model(T, B)
         alone[k] = fresh.generate(SHAPE, context_value=0, seed=5, **kw)
-    m, _ = _cond_model(T, B)
+    m, _ = cr.cond_model(T, B)
     for k in ("dpmpp", "unipc", "dpmpp", "ddim", "unipc", "ddim"):
         got = m.generate(SHAPE, context_value=0, seed=5, **calls[k])
         torch.cuda.synchronize()
@@ -392,7 +357,7 @@ def test_unipc_step_is_the_chains_step(dev, cond):
     m, _, _ = cond
     x_T = torch.randn(SHAPE, generator=torch.Generator().manual_seed(8))
     want = m.generate(SHAPE, context_value=IDS, x_T=x_T, sampler="unipc", num_steps=S, solver_order=3)
-    taus = _schedule(T, S)
+    taus = cr.schedule(T, S)
     p = ur.orders(S, 3, True)
     x, xc, hist, levels = x_T.cuda(), None, [], []
     for r in range(S - 1, -1, -1):

@@ -1,6 +1,7 @@
 """GPU tier of the zero-terminal-SNR schedule: dm3d_ddim_update_frame, dm3d_dpm_update_frame and dm3d_x0_threshold with ``frame`` set, bitwise against
-numpy float32 restatements inside guarded buffers; the chains of a zero-terminal-SNR v- and x0-model against float64 chains written here
-from the formulas of DESIGN.md section 4.13 (the network is the CPU oracle's, its output read as v or as x0); graph against eager; a
+numpy float32 restatements inside guarded buffers; the chains of a zero-terminal-SNR v- and x0-model against the float64 chains of
+tests/chain_reference.py, written from the formulas of DESIGN.md section 4.13 (the network is the CPU oracle's, its output read as v or
+as x0; guidance combines and rescales the raw predictions); graph against eager; a
 zero-terminal-SNR model beside a plain v-model; and one train_step whose timesteps include T-1 against torch.autograd in float64."""
 import ctypes as C
 import math
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import chain_reference as cr
 from guarded_buffers import IN, OUT, Guarded
 
 pytestmark = pytest.mark.gpu
@@ -185,14 +187,6 @@ def test_dpm_update_with_frame_is_bitwise_the_restatement(dev, kind, per):
             assert np.array_equal(_bits(runs[0][0]), _bits(runs[1][0])) and np.array_equal(_bits(runs[0][1]), _bits(runs[1][1]))
 
 
-def _bound32(x0, rank, frac, smax):
-    """dm3d_thresh_desc's s of one volume's float32 x0: v_i + f*(v_{i+1} - v_i), raised to 1, capped."""
-    v = np.sort(np.abs(x0))
-    i = min(int(rank), v.size - 1)
-    raw = F(v[i] + F(F(frac) * F(v[min(i + 1, v.size - 1)] - v[i])))
-    return F(min(max(raw, F(1)), F(smax)))
-
-
 @pytest.mark.parametrize("per", SIZES)
 @pytest.mark.parametrize("kind", ["v", "x0"])
 def test_x0_threshold_with_frame_is_bitwise_the_restatement(dev, kind, per):
@@ -208,7 +202,7 @@ def test_x0_threshold_with_frame_is_bitwise_the_restatement(dev, kind, per):
         c[:, 0:2] = np.nan
         want = np.ones(3, F)
         if clip == "on":
-            want = np.array([_bound32(_lin(frame[r, 0], x[b], frame[r, 1], p[b]), rank[b], frac[b], smax[b]) for b, r in enumerate(POS)], F)
+            want = np.array([cr.bound32_at(_lin(frame[r, 0], x[b], frame[r, 1], p[b]), rank[b], frac[b], smax[b]) for b, r in enumerate(POS)], F)
             if per > 4:
                 assert want[0] > 1 and want[1] == F(1.5) and want[2] > 1      # a quantile, the cap, the maximum
         runs = []
@@ -240,125 +234,6 @@ NEG = torch.tensor([[[0]], [[1]]])
 THR_P, THR_CAP = 0.9, 4.0
 
 
-def _args(T, bs=1):
-    return SimpleNamespace(timesteps=T, num_gpus=1, kernel_resize=False, bs=bs)
-
-
-def _weights(scale=1.0, seed=0):
-    import dm3d_amd
-    W = dm3d_amd.synthetic_weights(dm3d_amd.UNetConfig(img_size=8, img_channels=4), seed=seed)
-    if scale != 1.0:
-        W = dict(W, **{k: W[k] * np.float32(scale) for k in ("out.conv.kernel", "out.conv.bias")})
-    return W
-
-
-def _cond_model(T, B, W, **kw):
-    from dm3d_amd.networks import conditional_dm3d as cdm
-    return cdm.DiffusionModel(8, 1024, 4, None, _args(T, B), weights=W, **kw)
-
-
-_ORACLES = {}
-
-
-def _oracle(W, key):
-    """The oracle network on ``W`` (built once per weight set): net(x, t, context) in float64."""
-    from oracle import ref_torch as rt
-    if key not in _ORACLES:
-        ocfg = rt.UNetConfig(img_size=8, img_channels=4)
-        Wt = {k: torch.from_numpy(v) for k, v in W.items()}
-        _ORACLES[key] = lambda x, t, ctx: rt.unet_forward(Wt, ocfg, x.float(), torch.full((x.shape[0],), int(t), dtype=torch.int64), ctx).double()
-    return _ORACLES[key]
-
-
-def _schedule(T, S):
-    return [T - 1] if S == 1 else [int(math.floor(i * (T - 1) / (S - 1) + 0.5)) for i in range(S)]
-
-
-def _alpha_bar64(T):
-    """Algorithm 1 of Lin et al. 2023 on the linear schedule, rounded to the float32 the kernels read, as float64."""
-    r = np.sqrt(np.cumprod(1 - np.linspace(0.0001, 0.02, T), 0))
-    r = (r - r[-1]) * (r[0] / (r[0] - r[-1]))
-    ab = (r ** 2).astype(F).astype(np.float64)
-    assert ab[-1] == 0.0
-    return ab
-
-
-def _guide64(pp, pn, w, phi):
-    out = []
-    for b in range(pp.shape[0]):
-        g = pn[b] + w * (pp[b] - pn[b])
-        if phi != 0:
-            sg = float(g.std(unbiased=False))
-            g = (phi * float(pp[b].std(unbiased=False)) / sg + (1 - phi) if sg > 0 else 1.0) * g
-        out.append(g)
-    return torch.stack(out)
-
-
-def _dpm_row64(ab, s, t, p):
-    """(c_x, c_0, c_1) of the step from level s to t (t < 0: clean), p the level the step before started from (< 0: first order), with
-    the limits at alpha_bar = 0: from such a level lambda = -inf, h = inf: (sigma_t, alpha_t, 0); after it r = inf: first order."""
-    if t < 0:
-        return 0.0, 1.0, 0.0
-    al = lambda i: math.sqrt(ab[i])
-    sg = lambda i: math.sqrt(1.0 - ab[i])
-    if ab[s] == 0.0:
-        return sg(t), al(t), 0.0
-    lam = lambda i: math.log(al(i) / sg(i))
-    h = lam(t) - lam(s)
-    A = al(t) * (1.0 - math.exp(-h))
-    if p < 0 or ab[p] == 0.0:
-        return sg(t) / sg(s), A, 0.0
-    r = (lam(s) - lam(p)) / h
-    return sg(t) / sg(s), A * (1.0 + 1.0 / (2.0 * r)), -A / (2.0 * r)
-
-
-def _chain64(kind, solver, f, ab, sched, x_start, ids, eta=0.0, noise=None, neg=None, w=None, phi=0.0, blend=None, thr=None, states=None):
-    """DESIGN.md section 4.13 in float64.  A step from level t (a = sqrt(ab), s = sqrt(1 - ab)): pred = net(x, t), guided where ``neg``
-    is given (the raw predictions are combined and rescaled); v: x0 = a x - s pred, eps = s x + a pred; x0: x0 = pred,
-    eps = (x - a x0) / s; x0 clamped to [-1, 1], or thresholded (``thr`` = (p, cap): s_b the p-quantile of |x0| in [1, cap],
-    clamp(x0, -s_b, s_b) / s_b); DDIM: sqrt(a') x0 + sqrt(1 - a' - sigma^2) eps + sigma z; DPM-Solver++(2M): c_x x + c_0 x0 + c_1 x0_prev
-    with lower_order_final; ``blend(i, x)`` (edit chains) follows the step from sched[i]."""
-    x, hist = x_start.double(), None
-    n = len(sched)
-    prev = list(sched[1:]) + [-1]
-    if n > 1:
-        prev[1] = -1
-    for i in range(n - 1, -1, -1):
-        t = sched[i]
-        a, s = math.sqrt(ab[t]), math.sqrt(1 - ab[t])
-        pred = f(x, t, ids)
-        if neg is not None:
-            pred = _guide64(pred, f(x, t, neg), w, phi)
-        if kind == "v":
-            x0, eps = a * x - s * pred, s * x + a * pred
-        else:
-            x0, eps = pred, (x - a * pred) / s
-        if thr is None:
-            x0 = x0.clamp(-1, 1)
-        else:
-            outs = []
-            for b in range(x0.shape[0]):
-                sb = min(max(float(np.quantile(x0[b].abs().numpy().reshape(-1), thr[0])), 1.0), thr[1])
-                thr[2].append(sb)
-                outs.append(x0[b].clamp(-sb, sb) / sb)
-            x0 = torch.stack(outs)
-        if solver == "ddim":
-            ap = ab[sched[i - 1]] if i > 0 else 1.0
-            sigma = eta * math.sqrt((1 - ap) / (1 - ab[t])) * math.sqrt(1 - ab[t] / ap) if eta else 0.0
-            x = math.sqrt(ap) * x0 + math.sqrt(max(1 - ap - sigma ** 2, 0.0)) * eps
-            if sigma:
-                x = x + sigma * noise[i].double()
-        else:
-            c_x, c_0, c_1 = _dpm_row64(ab, t, sched[i - 1] if i > 0 else -1, prev[i])
-            x = c_x * x + c_0 * x0 + (c_1 * hist if c_1 != 0 else 0.0)
-            hist = x0
-        if blend is not None:
-            x = blend(i, x)
-        if states is not None:
-            states.append(x)
-    return x
-
-
 def _intermediates(m, steps_of, **kw):
     """The latents after every step of a chain driven through the public sampler: all finite, the first step included."""
     smp = m.sampler(SHAPE, IDS, **kw)
@@ -378,16 +253,16 @@ CHAINS = [("ddim", dict(eta=0.0)), ("ddim", dict(eta=0.5)), ("dpmpp", dict())]
 @pytest.mark.parametrize("kind", ["v", "x0"])
 def test_chain_matches_float64(dev, kind, solver, opts):
     """8^3 x 4ch, T = 20, S = 5, B = 2: the first step starts from alpha_bar = 0."""
-    W = _weights()
-    m = _cond_model(T_C, 2, W, prediction=kind, zero_terminal_snr=True)
+    m, W = cr.cond_model(T_C, 2, prediction=kind, zero_terminal_snr=True)
     g = torch.Generator().manual_seed(31)
     x_T = torch.randn(SHAPE, generator=g)
     eta = opts.get("eta", 0.0)
     noise = torch.randn((S_C,) + SHAPE, generator=g) if eta else None
-    sched, ab = _schedule(T_C, S_C), _alpha_bar64(T_C)
+    sched, ab = cr.schedule(T_C, S_C), cr.alpha_bar64(T_C, True)
     assert ab[sched[-1]] == 0.0
     got = m.generate(SHAPE, context_value=IDS, x_T=x_T, noise=noise, sampler=solver, num_steps=S_C, **opts).cpu()
-    ref = _chain64(kind, solver, _oracle(W, "plain"), ab, sched, x_T, IDS, eta, noise)
+    f = cr.oracle(W)
+    ref = cr.chain64(lambda x, t: f(x, t, IDS), ab, sched, x_T, solver, kind, eta=eta, noise=noise)
     err = float((got.double() - ref).abs().max())
     print(f"zero-terminal-SNR {kind} model, {solver} {opts}: max abs difference {err:.2e} (max |x| {float(ref.abs().max()):.3f})")
     assert torch.isfinite(got).all() and err < CHAIN_BAR
@@ -408,12 +283,13 @@ def test_chain_matches_float64(dev, kind, solver, opts):
 @pytest.mark.parametrize("kind", ["v", "x0"])
 def test_guided_chain_matches_float64(dev, kind, solver):
     """w = 3, phi = 0.7 on the raw predictions of both halves of the plan (Lin et al. 2023 state the rescale for v)."""
-    W = _weights()
-    m = _cond_model(T_C, 2, W, prediction=kind, zero_terminal_snr=True)
+    m, W = cr.cond_model(T_C, 2, prediction=kind, zero_terminal_snr=True)
     x_T = torch.randn(SHAPE, generator=torch.Generator().manual_seed(32))
     kw = dict(context_value=IDS, x_T=x_T, sampler=solver, num_steps=S_C, guidance_scale=3.0, guidance_rescale=0.7, negative_context=NEG)
     got = m.generate(SHAPE, **kw).cpu()
-    ref = _chain64(kind, solver, _oracle(W, "plain"), _alpha_bar64(T_C), _schedule(T_C, S_C), x_T, IDS, neg=NEG, w=3.0, phi=0.7)
+    f = cr.oracle(W)
+    net = lambda x, t: cr.guide64(f(x, t, IDS), f(x, t, NEG), 3.0, 0.7)
+    ref = cr.chain64(net, cr.alpha_bar64(T_C, True), cr.schedule(T_C, S_C), x_T, solver, kind)
     err = float((got.double() - ref).abs().max())
     print(f"guided zero-terminal-SNR {kind} model, {solver}: max abs difference {err:.2e}")
     assert torch.isfinite(got).all() and err < GUIDED_BAR
@@ -433,26 +309,21 @@ def test_guided_chain_matches_float64(dev, kind, solver):
 def test_edit_chain_matches_float64(dev, kind, solver, guided):
     """A half mask at full strength: the chain starts from the x_T generate() draws under the seed, at alpha_bar = 0, and the known
     latent is blended back after every step (at its first level it is noised with sqrt(alpha_bar) of that level, never of T-1)."""
-    W = _weights()
-    m = _cond_model(T_C, 2, W, prediction=kind, zero_terminal_snr=True)
+    m, W = cr.cond_model(T_C, 2, prediction=kind, zero_terminal_snr=True)
     g = torch.Generator().manual_seed(33)
     x0 = torch.rand(SHAPE, generator=g) * 2 - 1
     known_noise = torch.randn((S_C + 1,) + SHAPE, generator=g)
-    mask = torch.zeros((2, 8, 8, 8))
-    mask[:, :4] = 1.0
-    keep = (1 - mask).double().unsqueeze(-1)
-    sched, ab = _schedule(T_C, S_C), _alpha_bar64(T_C)
+    mask = cr.half_mask(2)
+    sched, ab = cr.schedule(T_C, S_C), cr.alpha_bar64(T_C, True)
     gkw = dict(guidance_scale=3.0, guidance_rescale=0.7, negative_context=NEG) if guided else {}
     x_T = m.generate(SHAPE, context_value=IDS, seed=11, sampler=solver, num_steps=S_C, steps=0).cpu()       # the draw of seed 11
     assert torch.isfinite(x_T).all() and 0.8 < float(x_T.std()) < 1.2
-
-    def known(level, z):
-        return x0.double() if level < 0 else math.sqrt(ab[level]) * x0.double() + math.sqrt(1 - ab[level]) * z.double()
-
-    blend = lambda i, x: keep * known(sched[i - 1] if i > 0 else -1, known_noise[i]) + (1 - keep) * x
+    blend = cr.edit_blend64(x0, ab, sched, 1 - mask, known_noise)
     kw = dict(mask=mask, strength=1.0, sampler=solver, num_steps=S_C, seed=11, **gkw)
     got = m.edit(x0, IDS, known_noise=known_noise, **kw).cpu()
-    ref = _chain64(kind, solver, _oracle(W, "plain"), ab, sched, x_T, IDS, blend=blend, **(dict(neg=NEG, w=3.0, phi=0.7) if guided else {}))
+    f = cr.oracle(W)
+    net = (lambda x, t: cr.guide64(f(x, t, IDS), f(x, t, NEG), 3.0, 0.7)) if guided else (lambda x, t: f(x, t, IDS))
+    ref = cr.chain64(net, ab, sched, x_T, solver, kind, blend=blend)
     err = float((got.double() - ref).abs().max())
     print(f"zero-terminal-SNR {kind} model, {solver} edit, guided {guided}: max abs difference {err:.2e}")
     assert torch.isfinite(got).all() and err < (GUIDED_BAR if guided else CHAIN_BAR)
@@ -468,13 +339,14 @@ def test_edit_chain_matches_float64(dev, kind, solver, guided):
 @pytest.mark.parametrize("kind", ["v", "x0"])
 def test_thresholded_chain_matches_float64(dev, kind, solver):
     """The output conv scaled by 3 (tests/test_gpu_threshold.py's weights): the float64 chain's bound exceeds 1 at some step."""
-    W = _weights(3.0)
-    m = _cond_model(T_C, 2, W, prediction=kind, zero_terminal_snr=True)
+    m, W = cr.cond_model(T_C, 2, W=cr.weights(scale=3.0), prediction=kind, zero_terminal_snr=True)
     x_T = torch.randn(SHAPE, generator=torch.Generator().manual_seed(34)) * 1.5
     bounds = []
     kw = dict(context_value=IDS, x_T=x_T, sampler=solver, num_steps=S_C, dynamic_threshold=THR_P, threshold_max=THR_CAP)
     got = m.generate(SHAPE, **kw).cpu()
-    ref = _chain64(kind, solver, _oracle(W, "x3"), _alpha_bar64(T_C), _schedule(T_C, S_C), x_T, IDS, thr=(THR_P, THR_CAP, bounds))
+    f = cr.oracle(W)
+    ref = cr.chain64(lambda x, t: f(x, t, IDS), cr.alpha_bar64(T_C, True), cr.schedule(T_C, S_C), x_T, solver, kind,
+                     thr=(THR_P, THR_CAP, bounds))
     err = float((got.double() - ref).abs().max())
     print(f"thresholded zero-terminal-SNR {kind} model, {solver}: max abs difference {err:.2e}; s per step {[round(s, 3) for s in bounds]}")
     assert len(bounds) == 2 * S_C and max(bounds) > 1.0
@@ -492,9 +364,8 @@ def test_thresholded_chain_matches_float64(dev, kind, solver):
 def test_single_call_forms_are_one_step_of_the_chain(dev):
     """ddim_step / dpm_step / x0_threshold with prediction="v" on the raw output: the chain's first step, from alpha_bar = 0, bitwise;
     without ``prediction`` the same tensors are read as eps, which has no x0 there."""
-    W = _weights()
-    m = _cond_model(T_C, 2, W, prediction="v", zero_terminal_snr=True)
-    sched = _schedule(T_C, S_C)
+    m, W = cr.cond_model(T_C, 2, prediction="v", zero_terminal_snr=True)
+    sched = cr.schedule(T_C, S_C)
     x_T = torch.randn(SHAPE, generator=torch.Generator().manual_seed(35))
     pred = m.network([x_T.to(dev), torch.tensor([sched[-1]] * 2), IDS])
     want = m.generate(SHAPE, context_value=IDS, x_T=x_T, sampler="ddim", num_steps=S_C, steps=1)
@@ -510,14 +381,13 @@ def test_single_call_forms_are_one_step_of_the_chain(dev):
 def test_native_and_converting_chains_do_not_leak(dev):
     """A zero-terminal-SNR v-model and a plain v-model on the same weights and on plans of equal shape, run alternately: each equals a
     fresh model's result bitwise, and each keeps graphs of its own kinds."""
-    W = _weights()
-    z = _cond_model(T_C, 2, W, prediction="v", zero_terminal_snr=True)
-    v = _cond_model(T_C, 2, W, prediction="v")
+    z, _ = cr.cond_model(T_C, 2, prediction="v", zero_terminal_snr=True)
+    v, _ = cr.cond_model(T_C, 2, prediction="v")
     calls = [dict(sampler="ddim", num_steps=5, eta=0.5), dict(sampler="dpmpp", num_steps=5),
              dict(sampler="ddim", num_steps=5, dynamic_threshold=0.9)]
     fresh = {}
     for name, kw in (("z", dict(zero_terminal_snr=True)), ("v", {})):
-        fm = _cond_model(T_C, 2, W, prediction="v", **kw)
+        fm, _ = cr.cond_model(T_C, 2, prediction="v", **kw)
         fresh[name] = [fm.generate(SHAPE, context_value=IDS, seed=5, **c).clone() for c in calls]
     for _ in range(2):
         for i, c in enumerate(calls):
@@ -535,13 +405,12 @@ def test_train_step_at_the_last_timestep(dev):
     tests/test_gpu_objective.py::test_train_step_public_api (2e-5 relative; 1e-5 after one step of 2e-4)."""
     from oracle import ref_torch as rt, ref_train as ot
     T, B, lc, lr = 50, 2, 4, 2e-4
-    W = _weights(seed=1)
-    m = _cond_model(T, B, W, prediction="v", zero_terminal_snr=True)
+    m, W = cr.cond_model(T, B, W=cr.weights(seed=1), prediction="v", zero_terminal_snr=True)
     m.compile(loss="mse_sum", optimizer=SimpleNamespace(learning_rate=lr))
     g = torch.Generator().manual_seed(5)
     lat, noise = torch.randn(SHAPE, generator=g), torch.randn(SHAPE, generator=g)
     t = torch.tensor([T - 1, 3])
-    ab = torch.from_numpy(_alpha_bar64(T))[t].reshape(-1, 1, 1, 1, 1)
+    ab = torch.from_numpy(cr.alpha_bar64(T, True))[t].reshape(-1, 1, 1, 1, 1)
     a, s = ab.sqrt(), (1 - ab).sqrt()
     assert float(a[0]) == 0.0 and float(s[0]) == 1.0
     ocfg = rt.UNetConfig(img_size=8, img_channels=4)

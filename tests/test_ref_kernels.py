@@ -321,7 +321,7 @@ def _xs(seed, B, n=64, k=4):
 @pytest.mark.parametrize("clip", [True, False])
 def test_dpm_update_f64_is_the_paper_form(clip):
     from dm3d_amd import schedules
-    from test_gpu_dpm import _dpm64
+    from chain_reference import dpm64
     ab = _ab()
     src, dst, prev = _steps()
     coef = np.zeros((5, 8))
@@ -331,13 +331,13 @@ def test_dpm_update_f64_is_the_paper_form(clip):
     x, e, h, _ = _xs(1, 5)
     res, x0 = rk.dpm_update(x, e, coef, np.arange(5), h, order="f64")
     for b in range(5):
-        ref, ref0 = _dpm64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), ab, src[b], dst[b], prev[b] if dst[b] >= 0 else -1, torch.from_numpy(h[b]), clip)
+        ref, ref0 = dpm64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), ab, src[b], dst[b], prev[b] if dst[b] >= 0 else -1, torch.from_numpy(h[b]), clip)
         assert _rel(res[b], ref) < F64_TOL and _rel(x0[b], ref0) < F64_TOL, b
     assert coef[0, 4] == 0 and coef[1, 4] != 0 and coef[4, 4] == 0           # first order, second order, to clean
     # without a history the add of c_1*hist is skipped, whatever c_1 holds: the paper's first-order step on the rows that are first order
     first, _ = rk.dpm_update(x, e, coef, np.arange(5), None, order="f64")
     for b in (0, 4):
-        ref, _ = _dpm64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), ab, src[b], dst[b], -1, None, clip)
+        ref, _ = dpm64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), ab, src[b], dst[b], -1, None, clip)
         assert _rel(first[b], ref) < F64_TOL, b
     assert _rel(first, coef[:, 2:3] * x + coef[:, 3:4] * x0) < F64_TOL
 
@@ -345,7 +345,7 @@ def test_dpm_update_f64_is_the_paper_form(clip):
 @pytest.mark.parametrize("eta", [0.5, 1.0])
 def test_dpm_sde_update_f64_is_the_paper_form(eta):
     from dm3d_amd import schedules
-    from test_gpu_dpm_sde import _step64
+    from chain_reference import dpm64
     ab = _ab()
     src, dst, prev = _steps()
     coef = np.zeros((5, 8))
@@ -355,8 +355,8 @@ def test_dpm_sde_update_f64_is_the_paper_form(eta):
     x, e, h, z = _xs(2, 5)
     res, x0 = rk.dpm_sde_update(x, e, coef, np.arange(5), h, z, order="f64")
     for b in range(5):
-        ref, ref0 = _step64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), torch.from_numpy(z[b]), ab, src[b], dst[b],
-                            prev[b] if dst[b] >= 0 else -1, eta, torch.from_numpy(h[b]))
+        ref, ref0 = dpm64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), ab, src[b], dst[b], prev[b] if dst[b] >= 0 else -1,
+                          torch.from_numpy(h[b]), eta=eta, z=torch.from_numpy(z[b]))
         assert _rel(res[b], ref) < F64_TOL and _rel(x0[b], ref0) < F64_TOL, b
     assert coef[0, 6] != 0 and coef[4, 6] == 0                               # the row to clean draws nothing
     # c_z = 0 everywhere: dpm_update's result
@@ -369,7 +369,7 @@ def test_dpm_sde_update_f64_is_the_paper_form(eta):
 @pytest.mark.parametrize("eta", [0.0, 0.7])
 def test_ddim_update_f64_is_the_paper_form(eta):
     from dm3d_amd import schedules
-    from test_gpu_guidance import _ddim64
+    from chain_reference import ddim64
     ab = _ab()
     src, dst, _ = _steps()
     coef = np.zeros((5, 8))
@@ -378,7 +378,7 @@ def test_ddim_update_f64_is_the_paper_form(eta):
     x, e, z, _ = _xs(3, 5)
     res = rk.ddim_update(x, e, coef, np.arange(5), z, order="f64")
     for b in range(5):
-        ref = _ddim64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), ab[src[b]], ab[dst[b]] if dst[b] >= 0 else 1.0, eta, torch.from_numpy(z[b]))
+        ref = ddim64(torch.from_numpy(x[b]), torch.from_numpy(e[b]), ab[src[b]], ab[dst[b]] if dst[b] >= 0 else 1.0, eta, torch.from_numpy(z[b]))
         assert _rel(res[b], ref) < F64_TOL, b
 
 
