@@ -191,11 +191,22 @@ class MetricDesc(C.Structure):
     ]
 
 
+class MsSsimDesc(C.Structure):
+    _fields_ = [
+        ("x", _f32p), ("y", _f32p), ("x_index", _i32p), ("y_index", _i32p), ("pairs", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32),
+        ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cx", C.c_int32), ("cy", C.c_int32), ("x0c", C.c_int32), ("y0c", C.c_int32),
+        ("nc", C.c_int32), ("filter_size", C.c_int32), ("filter_sigma", C.c_float), ("scales", C.c_int32), ("power_factors", C.c_float * 5),
+        ("max_val", _f32p), ("out", _f32p), ("partials", C.c_void_p), ("partials_elems", C.c_int64), ("scratch", _f32p),
+        ("scratch_elems", C.c_int64),
+    ]
+
+
 GUIDE_PARTIAL_BLOCKS = 256          # DM3D_GUIDE_PARTIAL_BLOCKS: GuideDesc.partials holds [batch][256][4] doubles
 LOSS_PARTIAL_BLOCKS = 64            # DM3D_LOSS_PARTIAL_BLOCKS: LossDesc.partials holds [batch][64] doubles
 GRADNORM_PARTIAL_BLOCKS = 1024      # DM3D_GRADNORM_PARTIAL_BLOCKS: GradScaleDesc.partials holds [1024] doubles
 PAIR_PARTIAL_BLOCKS = 64            # DM3D_PAIR_PARTIAL_BLOCKS: dm3d_pair_stats runs min(ceil(h*w / 4096), 64) blocks a slice
 SSIM_TILE = 32                      # DM3D_SSIM_TILE: dm3d_ssim leaves one partial per 32 x 32 tile of outputs
+MSSSIM_TILE = (32, 16, 32)          # DM3D_MSSSIM_TD / TH / TW: dm3d_ms_ssim leaves one partial pair per tile of 32 x 16 x 32 (d, h, w) outputs
 
 # name -> (restype, argtypes): every symbol include/dm3d.h declares
 SIGNATURES = {
@@ -264,6 +275,7 @@ SIGNATURES = {
     "dm3d_pair_stats": (C.c_int, [C.POINTER(MetricDesc), C.c_void_p]),
     "dm3d_ssim": (C.c_int, [C.POINTER(MetricDesc), C.c_void_p]),
     "dm3d_psnr_finalize": (C.c_int, [C.POINTER(MetricDesc), C.c_void_p]),
+    "dm3d_ms_ssim": (C.c_int, [C.POINTER(MsSsimDesc), C.c_void_p]),
     "dm3d_range_check": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "dm3d_add_i32": (C.c_int, [_i32p, C.c_int32, C.c_int32, C.c_void_p]),
     "dm3d_randn": (C.c_int, [_f32p, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p]),

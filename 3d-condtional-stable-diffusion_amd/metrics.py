@@ -12,9 +12,9 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .ops import pair_stats, psnr, ssim
+from .ops import ms_ssim, pair_stats, psnr, ssim
 
-__all__ = ["Mean", "pair_stats", "psnr", "ssim", "volume_metrics"]
+__all__ = ["Mean", "ms_ssim", "pair_stats", "pairwise_ms_ssim", "psnr", "sample_diversity", "ssim", "volume_metrics"]
 
 
 def volume_metrics(x: torch.Tensor, y: torch.Tensor, max_val=None, *, x_channels=None, y_channels=None) -> Dict[str, torch.Tensor]:
@@ -28,6 +28,24 @@ def volume_metrics(x: torch.Tensor, y: torch.Tensor, max_val=None, *, x_channels
     return {"y_min": stats.y_min, "y_max": stats.y_max, "max_val": mv,
             "sse": stats.sse, "mse": stats.sse / float(x.shape[2] * x.shape[3] * nc),
             "ssim": ssim(x, y, mv, **kw), "psnr": psnr(x, y, mv, **kw)}
+
+
+def pairwise_ms_ssim(volumes: torch.Tensor, max_val, **kw) -> torch.Tensor:
+    """3-D multi-scale SSIM (``ops.ms_ssim``; ``kw`` goes to it) of every pair i < j of ``volumes`` [B, D, H, W, C], B >= 2: float32
+    [B (B - 1) / 2] in lexicographic order (0, 1), (0, 2), .., (B - 2, B - 1).  The volumes are read in place through a pair table, in
+    one launch sequence.  ``max_val`` is a number or a tensor of one value per pair; there is no truth whose range could stand in."""
+    if max_val is None:
+        raise ValueError("pairwise_ms_ssim needs max_val: a generated batch has no truth whose range could stand in")
+    if not isinstance(volumes, torch.Tensor) or volumes.dim() != 5 or volumes.shape[0] < 2:
+        raise ValueError(f"volumes must be [B, D, H, W, C] with B >= 2, got {tuple(getattr(volumes, 'shape', ()))}")
+    n = volumes.shape[0]
+    pairs = torch.triu_indices(n, n, 1, device=volumes.device).t().contiguous()
+    return ms_ssim(volumes, volumes, max_val, pairs=pairs, **kw)
+
+
+def sample_diversity(volumes: torch.Tensor, max_val, **kw) -> torch.Tensor:
+    """The diversity score of a generated batch: the mean of ``pairwise_ms_ssim`` as a 0-d float64 device tensor (lower is more diverse)."""
+    return pairwise_ms_ssim(volumes, max_val, **kw).double().mean()
 
 
 class Mean:

@@ -505,3 +505,93 @@ def psnr(x: torch.Tensor, y: torch.Tensor, max_val=None, *, x_channels=None, y_c
     d.sse, d.max_val, d.out = stats.sse.data_ptr(), mv.data_ptr(), out.data_ptr()
     check(lib().dm3d_psnr_finalize(C.byref(d), _st()), "psnr_finalize")
     return out
+
+
+# ---- 3-D multi-scale SSIM (include/dm3d.h, dm3d_ms_ssim_desc): fidelity of a reconstruction, diversity of a generated batch ---------
+MS_SSIM_POWER_FACTORS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)        # Wang, Simoncelli, Bovik 2003
+
+
+def ms_ssim_max_scales(spatial, filter_size: int = 11) -> int:
+    """The largest number of scales (at most 5) whose coarsest volume still holds one window: min(spatial) >> (scales - 1) >= filter_size."""
+    n = 0
+    while n < 5 and (min(spatial) >> n) >= filter_size:
+        n += 1
+    return n
+
+
+def ms_ssim(x: torch.Tensor, y: torch.Tensor, max_val=None, *, power_factors=MS_SSIM_POWER_FACTORS, filter_size: int = 11,
+            filter_sigma: float = 1.5, x_channels=None, y_channels=None, stats: Optional[PairStats] = None, pairs=None) -> torch.Tensor:
+    """Multi-scale SSIM (Wang et al. 2003) with a 3-D Gaussian window: float32 [P], one score per compared pair of volumes (the mean
+    over the compared channels).  ``x`` [Nx, D, H, W, Cx] and ``y`` [Ny, D, H, W, Cy] are NDHWC float32 device tensors;
+    ``*_channels = (first, count)`` reads a channel window in place.  ``len(power_factors)`` is the number of scales (1 to 5); between
+    scales both volumes are averaged over 2 x 2 x 2 (an odd edge drops its last plane).  ``filter_size`` is odd, 3 to 11.
+
+    ``pairs`` None compares volume p of x with volume p of y (P = Nx = Ny); an int tensor [P, 2] on the device makes row p compare
+    ``x[pairs[p, 0]]`` with ``y[pairs[p, 1]]``, read in place.  ``max_val`` is a number, or a tensor of one value or one per row; None
+    is the reference's max(y) - min(y) per volume (``stats`` as in ``ssim``) and is refused with ``pairs``, where a row's y is not one
+    volume's own.  Everything stays on the device: the buffers are allocated here and nothing is read back.
+
+    Not offered: the 2-D ``tf.image.ssim_multiscale`` form, other pooling rules, uniform windows."""
+    power = tuple(float(w) for w in power_factors)
+    if not 1 <= len(power) <= 5 or any(not w > 0.0 for w in power):
+        raise ValueError(f"power_factors must be 1 to 5 positive numbers, got {power}")
+    if filter_size % 2 == 0 or not 3 <= filter_size <= 11:
+        raise ValueError(f"filter_size must be odd and in [3, 11], got {filter_size}")
+    if pairs is not None:
+        if max_val is None:
+            raise ValueError("max_val=None (max(y) - min(y) per volume) is not defined under a pair table: pass max_val")
+        if not isinstance(pairs, torch.Tensor) or pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1 or pairs.dtype not in (
+                torch.int32, torch.int64):
+            raise ValueError(f"pairs must be an int32 or int64 tensor [P, 2] with P >= 1, got {getattr(pairs, 'dtype', type(pairs))} "
+                             f"{tuple(getattr(pairs, 'shape', ()))}")
+    _f32c(x, "x"), _f32c(y, "y")
+    if x.dim() != 5 or y.dim() != 5 or x.shape[1:4] != y.shape[1:4] or (pairs is None and x.shape[0] != y.shape[0]):
+        raise ValueError(f"x and y must be [N,D,H,W,C] with the same spatial shape (and the same N without pairs), got {tuple(x.shape)} and "
+                         f"{tuple(y.shape)}")
+    x0c, ncx = (0, x.shape[4]) if x_channels is None else x_channels
+    y0c, ncy = (0, y.shape[4]) if y_channels is None else y_channels
+    if ncx != ncy:
+        raise ValueError(f"x contributes {ncx} channels and y {ncy}: the same number must be compared")
+    D, H, W = x.shape[1:4]
+    fit = ms_ssim_max_scales((D, H, W), filter_size)
+    if len(power) > fit:
+        raise ValueError(f"ms_ssim: {len(power)} scales of a {D} x {H} x {W} volume leave an edge smaller than filter_size={filter_size}; "
+                         f"at most {fit} scales fit")
+    dev = x.device
+    if pairs is None:
+        P, idx = x.shape[0], None
+        mv = _max_val(max_val, stats, x, y, x_channels, y_channels)
+    else:
+        if pairs.device != dev:
+            raise ValueError("pairs must be on the device of x and y")
+        P = pairs.shape[0]
+        idx = pairs.to(torch.int32).t().contiguous()                            # [2, P]: the two tables
+        if isinstance(max_val, torch.Tensor):
+            mv = max_val.to(device=dev, dtype=torch.float32).reshape(-1)
+            mv = mv.expand(P) if mv.numel() == 1 else mv
+            if mv.numel() != P:
+                raise ValueError(f"max_val must hold one value, or one per pair ({P}), got {mv.numel()}")
+            mv = mv.contiguous()
+        else:
+            mv = torch.full((P,), float(max_val), dtype=torch.float32, device=dev)
+    TD, TH, TW = _lib.MSSSIM_TILE
+    tiles = sum(-(-((D >> j) - filter_size + 1) // TD) * -(-((H >> j) - filter_size + 1) // TH) * -(-((W >> j) - filter_size + 1) // TW)
+                for j in range(len(power)))
+    pooled = sum((D >> j) * (H >> j) * (W >> j) for j in range(1, len(power)))
+    partials = torch.empty(max(1, 2 * P * ncx * tiles), dtype=torch.float64, device=dev)       # alive until the launches are enqueued
+    scratch = torch.empty(max(1, (x.shape[0] + y.shape[0]) * ncx * pooled), dtype=torch.float32, device=dev)
+    out = torch.empty(P, dtype=torch.float32, device=dev)
+    d = _lib.MsSsimDesc()
+    d.x, d.y = x.data_ptr(), y.data_ptr()
+    if idx is not None:
+        d.x_index, d.y_index = idx[0].data_ptr(), idx[1].data_ptr()
+    d.pairs, d.nx, d.ny, d.d, d.h, d.w = P, x.shape[0], y.shape[0], D, H, W
+    d.cx, d.cy, d.x0c, d.y0c, d.nc = x.shape[4], y.shape[4], x0c, y0c, ncx
+    d.filter_size, d.filter_sigma, d.scales = filter_size, float(filter_sigma), len(power)
+    for j, w in enumerate(power):
+        d.power_factors[j] = w
+    d.max_val, d.out = mv.data_ptr(), out.data_ptr()
+    d.partials, d.partials_elems, d.scratch, d.scratch_elems = partials.data_ptr(), partials.numel(), scratch.data_ptr(), scratch.numel()
+    check(lib().dm3d_ms_ssim(C.byref(d), _st()), "ms_ssim")
+    del partials, scratch, idx
+    return out

@@ -827,6 +827,65 @@ int dm3d_pair_stats(const dm3d_metric_desc* d, void* stream);
 int dm3d_ssim(const dm3d_metric_desc* d, void* stream);
 int dm3d_psnr_finalize(const dm3d_metric_desc* d, void* stream);
 
+/* ---- 3-D multi-scale SSIM (Wang, Simoncelli, Bovik 2003, with a 3-D window): a fidelity score of a reconstruction against its truth
+ * and, over the pairs of a generated batch, a diversity score.  x is [nx, d, h, w, cx] and y [ny, d, h, w, cy], NDHWC float32; the nc
+ * channels x0c.. of x are compared with the nc channels y0c.. of y, read in place.  Output row p compares volume x_index[p] of x with
+ * volume y_index[p] of y (a NULL table is the identity p, and then pairs <= nx resp. ny); a table entry outside [0, nx) resp. [0, ny)
+ * reads nothing and makes out[p] NaN.  max_val and out are indexed by p.  Nothing is read back; runs repeat bitwise.
+ *
+ *     g[i] = exp(-(i - (F-1)/2)^2 / (2 sigma^2)) / sum, i = 0..F-1, F = filter_size: float64, rounded to float32.  The window is
+ *     g (x) g (x) g, applied separably along w, then h, then d, no padding: each pass acc = fma(g[i], v[i], acc) from acc = 0, i ascending.
+ *     Scale j = 0..scales-1 has edges (d >> j, h >> j, w >> j) and a valid map of (edge - (F-1)) points per axis.
+ *     L = max_val[p] at every scale;  c1 = (0.01f L)^2;  c2 = (0.03f L)^2
+ *     mx = W(x), my = W(y), sxy = W(x*y), sq = W(x*x + y*y);  n0 = (mx*my)*2;  d0 = mx*mx + my*my          all float32
+ *     lum = (n0 + c1) / (d0 + c1);  cs = ((sxy*2 - n0) + c2) / ((sq - d0) + c2)
+ *     CS_j = (sum over the valid map of (double)cs) / points;  S_j = (sum of (double)(lum*cs)) / points        per channel
+ *     between scales x and y become their 2 x 2 x 2 means, an odd edge dropping its last plane: the eight values added in float32 in
+ *     (dz, dy, dx) index order, times 0.125f
+ *     out[p] = (float)(mean over channels of  prod_{j < scales-1} max(CS_j, 0)^w_j  *  max(S_{scales-1}, 0)^w_{scales-1}),
+ *     w = power_factors (float32 values), the product and pow() in float64, scales in ascending order.
+ *
+ * One launch per scale: a workgroup owns DM3D_MSSSIM_TD x TH x TW points of the valid map of one (p, channel), walks the input planes
+ * along d (each staged in LDS once, w pass into LDS, h pass in registers, d pass as a register delay line) and leaves one float64 pair
+ * (sum cs, sum lum*cs).  Between scales one pooling launch per tensor writes every volume's compared channels to `scratch`; a final
+ * launch combines tiles, scales, powers and channels in index order.
+ *     tiles_j          = ceil(od/TD) * ceil(oh/TH) * ceil(ow/TW)  with  (od, oh, ow) = ((d >> j) - (F-1), (h >> j) - (F-1), (w >> j) - (F-1))
+ *     partials_elems  >= 2 * pairs * nc * sum_{j < scales} tiles_j                                   doubles, 8-byte aligned
+ *     scratch_elems   >= (nx + ny) * nc * sum_{1 <= j < scales} (d >> j)(h >> j)(w >> j)            floats (scales = 1: none, may be NULL)
+ *
+ * Checked before any launch (DM3D_EINVAL, the message starts "ms_ssim:"): the descriptor, x, y, max_val, out, partials (and scratch
+ * when scales > 1) non-NULL; pairs in [1, 65535] and, for a NULL table, at most the volumes of that tensor; nx, ny, d, h, w, nc >= 1;
+ * filter_size odd in [3, 11]; filter_sigma > 0; scales in [1, 5]; power_factors[j] > 0 for j < scales; x0c, y0c >= 0,
+ * x0c + nc <= cx, y0c + nc <= cy; min(d, h, w) >> (scales - 1) >= filter_size (the message names the largest number of scales that
+ * fits); both buffer sizes; the alignment of partials.
+ * Not offered: the 2-D tf.image.ssim_multiscale form, other pooling rules, uniform windows. */
+#define DM3D_MSSSIM_TD 32
+#define DM3D_MSSSIM_TH 16
+#define DM3D_MSSSIM_TW 32
+typedef struct dm3d_ms_ssim_desc {
+    const float* x;             /* [nx, d, h, w, cx] */
+    const float* y;             /* [ny, d, h, w, cy] */
+    const int32_t* x_index;     /* [pairs] device, optional: the volume of x row p reads */
+    const int32_t* y_index;     /* [pairs] device, optional: the volume of y row p reads */
+    int32_t pairs;              /* P: rows of out */
+    int32_t nx, ny;             /* volumes in x and in y */
+    int32_t d, h, w;
+    int32_t cx, cy;             /* channel counts of the two tensors */
+    int32_t x0c, y0c;           /* first channel read of each */
+    int32_t nc;                 /* channels compared */
+    int32_t filter_size;        /* F: odd, 3..11 */
+    float filter_sigma;
+    int32_t scales;             /* M: 1..5 */
+    float power_factors[5];     /* w_j, j < scales */
+    const float* max_val;       /* [pairs] */
+    float* out;                 /* [pairs] */
+    double* partials;           /* device scratch, written before it is read by every call */
+    int64_t partials_elems;     /* doubles it holds */
+    float* scratch;             /* device scratch for the pooled volumes */
+    int64_t scratch_elems;      /* floats it holds */
+} dm3d_ms_ssim_desc;
+int dm3d_ms_ssim(const dm3d_ms_ssim_desc* d, void* stream);
+
 /* p[i] = max(p[i] + delta, 0) (the loop counter of generate kept on the device so a captured step replays unchanged; it
  * saturates at 0, so a step issued past the end of a chain never indexes row -1 of a table). */
 int dm3d_add_i32(int32_t* p, int32_t n, int32_t delta, void* stream);
