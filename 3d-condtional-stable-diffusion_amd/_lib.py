@@ -201,11 +201,22 @@ class MsSsimDesc(C.Structure):
     ]
 
 
+class MaskDesc(C.Structure):
+    _fields_ = [
+        ("x", _f32p), ("y", _f32p), ("batch", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cx", C.c_int32),
+        ("cy", C.c_int32), ("x0c", C.c_int32), ("y0c", C.c_int32), ("nc", C.c_int32), ("threshold", C.c_float), ("of", C.c_int32),
+        ("percentile", C.c_double), ("counts", C.c_void_p), ("surf_x", C.c_void_p), ("surf_y", C.c_void_p), ("map", _i32p),
+        ("out", C.c_void_p), ("masks", C.c_void_p), ("masks_elems", C.c_int64), ("work", _i32p), ("work_elems", C.c_int64),
+    ]
+
+
 GUIDE_PARTIAL_BLOCKS = 256          # DM3D_GUIDE_PARTIAL_BLOCKS: GuideDesc.partials holds [batch][256][4] doubles
 LOSS_PARTIAL_BLOCKS = 64            # DM3D_LOSS_PARTIAL_BLOCKS: LossDesc.partials holds [batch][64] doubles
 GRADNORM_PARTIAL_BLOCKS = 1024      # DM3D_GRADNORM_PARTIAL_BLOCKS: GradScaleDesc.partials holds [1024] doubles
 PAIR_PARTIAL_BLOCKS = 64            # DM3D_PAIR_PARTIAL_BLOCKS: dm3d_pair_stats runs min(ceil(h*w / 4096), 64) blocks a slice
 SSIM_TILE = 32                      # DM3D_SSIM_TILE: dm3d_ssim leaves one partial per 32 x 32 tile of outputs
+EDT_MAX_EXTENT = 512                # DM3D_EDT_MAX_EXTENT: the longest axis dm3d_edt / dm3d_surface_distance stage in LDS
+EDT_SURFACE, EDT_FOREGROUND = 0, 1  # DM3D_EDT_SURFACE / DM3D_EDT_FOREGROUND: MaskDesc.of
 MSSSIM_TILE = (32, 16, 32)          # DM3D_MSSSIM_TD / TH / TW: dm3d_ms_ssim leaves one partial pair per tile of 32 x 16 x 32 (d, h, w) outputs
 
 # name -> (restype, argtypes): every symbol include/dm3d.h declares
@@ -276,6 +287,9 @@ SIGNATURES = {
     "dm3d_ssim": (C.c_int, [C.POINTER(MetricDesc), C.c_void_p]),
     "dm3d_psnr_finalize": (C.c_int, [C.POINTER(MetricDesc), C.c_void_p]),
     "dm3d_ms_ssim": (C.c_int, [C.POINTER(MsSsimDesc), C.c_void_p]),
+    "dm3d_mask_overlap": (C.c_int, [C.POINTER(MaskDesc), C.c_void_p]),
+    "dm3d_edt": (C.c_int, [C.POINTER(MaskDesc), C.c_void_p]),
+    "dm3d_surface_distance": (C.c_int, [C.POINTER(MaskDesc), C.c_void_p]),
     "dm3d_range_check": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "dm3d_add_i32": (C.c_int, [_i32p, C.c_int32, C.c_int32, C.c_void_p]),
     "dm3d_randn": (C.c_int, [_f32p, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p]),

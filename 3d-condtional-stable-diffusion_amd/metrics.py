@@ -12,9 +12,10 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .ops import ms_ssim, pair_stats, psnr, ssim
+from .ops import distance_transform, mask_overlap, ms_ssim, pair_stats, psnr, ssim, surface_distances
 
-__all__ = ["Mean", "ms_ssim", "pair_stats", "pairwise_ms_ssim", "psnr", "sample_diversity", "ssim", "volume_metrics"]
+__all__ = ["Mean", "NanMean", "dice", "distance_transform", "hausdorff", "iou", "mask_metrics", "mask_overlap", "ms_ssim", "pair_stats",
+           "pairwise_ms_ssim", "psnr", "sample_diversity", "ssim", "surface_distances", "volume_metrics"]
 
 
 def volume_metrics(x: torch.Tensor, y: torch.Tensor, max_val=None, *, x_channels=None, y_channels=None) -> Dict[str, torch.Tensor]:
@@ -48,6 +49,45 @@ def sample_diversity(volumes: torch.Tensor, max_val, **kw) -> torch.Tensor:
     return pairwise_ms_ssim(volumes, max_val, **kw).double().mean()
 
 
+# ---- the mask channels: Dice, IoU, Hausdorff, ASSD of binarised masks (MONAI's definitions; include/dm3d.h, dm3d_mask_desc) ------------
+def _dice_iou(counts: ops.MaskOverlap):
+    """float64 Dice = 2 |X and Y| / (|X| + |Y|) and IoU = |X and Y| / |X or Y| from the exact counts; NaN where the truth mask is empty
+    (MONAI's ``ignore_empty=True``)."""
+    x, y, both = counts.x.double(), counts.y.double(), counts.both.double()
+    nan = torch.full_like(x, float("nan"))
+    return torch.where(counts.x > 0, 2.0 * both / (x + y), nan), torch.where(counts.x > 0, both / (x + y - both), nan)
+
+
+def dice(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, *, x_channels=None, y_channels=None) -> torch.Tensor:
+    """Dice of the masks ``x > threshold`` (the truth) and ``y > threshold`` per volume and compared channel: float64 [B, nc], NaN where
+    the truth mask is empty.  NDHWC float32 device tensors, ``*_channels = (first, count)`` read in place (``ops.mask_overlap``)."""
+    return _dice_iou(mask_overlap(x, y, threshold, x_channels=x_channels, y_channels=y_channels))[0]
+
+
+def iou(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, *, x_channels=None, y_channels=None) -> torch.Tensor:
+    """Intersection over union of the two masks, as ``dice``: float64 [B, nc], NaN where the truth mask is empty."""
+    return _dice_iou(mask_overlap(x, y, threshold, x_channels=x_channels, y_channels=y_channels))[1]
+
+
+def hausdorff(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, percentile: Optional[float] = 95.0, *, x_channels=None,
+              y_channels=None) -> torch.Tensor:
+    """The Hausdorff distance of the two masks' surfaces per volume and compared channel, float64 [B, nc] in voxels (anisotropic spacing
+    is not offered: the caller scales): the larger of the two directed ``percentile``-th percentiles (numpy's linear rule), or with
+    ``percentile=None`` the plain maximum.  NaN where either mask is empty (``ops.surface_distances``)."""
+    dist = surface_distances(x, y, threshold, 100.0 if percentile is None else percentile, x_channels=x_channels, y_channels=y_channels)
+    return dist.hd if percentile is None else dist.hd_percentile
+
+
+def mask_metrics(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, percentile: float = 95.0, *, x_channels=None,
+                 y_channels=None) -> Dict[str, torch.Tensor]:
+    """Everything above from one launch sequence (the overlap pass of ``ops.surface_distances`` also leaves the counts): float64 [B, nc]
+    ``dice``, ``iou``, ``hd``, ``hd_percentile``, ``assd``, ``surface_x``, ``surface_y`` and the int64 ``counts`` (``ops.MaskOverlap``).
+    Distances are in voxels."""
+    dist, counts = ops._surface_distances(x, y, threshold, percentile, x_channels, y_channels, True)
+    d, i = _dice_iou(counts)
+    return {"dice": d, "iou": i, **dist._asdict(), "counts": counts}
+
+
 class Mean:
     """``keras.metrics.Mean``: the mean of every element it was shown, so an update with a [B, D] tensor counts B*D values.  The float64
     sum and the count live on the device of the values: ``update_state`` enqueues two additions and never synchronises; ``result()`` is
@@ -73,3 +113,18 @@ class Mean:
         if self.total is None:
             return torch.zeros((), dtype=torch.float64)
         return torch.where(self.count > 0, self.total / self.count.clamp(min=1), torch.zeros_like(self.total))
+
+
+class NanMean(Mean):
+    """``Mean`` over the values that are not NaN (a Dice whose truth mask is empty, a Hausdorff distance of an empty surface): they add
+    nothing to the sum or the count.  0 before any value that counts, as ``Mean``."""
+
+    def update_state(self, values) -> None:
+        v = torch.as_tensor(values)
+        if self.total is None:
+            self.total = torch.zeros((), dtype=torch.float64, device=v.device)
+            self.count = torch.zeros((), dtype=torch.int64, device=v.device)
+        v = v.to(device=self.total.device, dtype=torch.float64)
+        keep = ~torch.isnan(v)
+        self.total += torch.where(keep, v, torch.zeros_like(v)).sum()
+        self.count += keep.sum()

@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from .. import _lib, ops
-from ..metrics import Mean
+from ..metrics import Mean, NanMean
+from ..metrics import mask_metrics as mask_metrics_of
 
 BN_EPS = 1e-3
 VQ_BETA = 0.25          # VectorQuantizer(beta=0.25) (:113): the weight of the commitment term in its loss
@@ -97,6 +98,7 @@ class _Layer:
 
 class VQVAE:
     METRIC_KEYS = ("loss", "reconst_loss", "quantize_loss", "ssim", "psnr")      # what test_step returns, in the reference's order
+    MASK_METRIC_KEYS = ("mask_dice", "mask_iou", "mask_hd95", "mask_assd")       # what mask_test_step adds: the mask half, not in the reference
 
     def __init__(self, in_channels, out_channels, num_channels, num_res_layers, num_res_channels,
                  downsample_parameters=((2, 4, 1, 1), (2, 4, 1, 1), (2, 4, 1, 1)),
@@ -128,6 +130,7 @@ class VQVAE:
         self.encoder, self.quantizer, self.decoder = self._encode, self._quantize, self._decode
         self._last_pair = None
         self._trackers = {k: Mean(k) for k in self.METRIC_KEYS}
+        self._mask_trackers = {k: NanMean(k) for k in self.MASK_METRIC_KEYS}
 
     # ---- weights ---------------------------------------------------------------------------------------------------
     def load_state_dict(self, sd, strict=True):
@@ -314,11 +317,12 @@ class VQVAE:
         return list(self._trackers.values())
 
     def reset_metrics(self):
-        for m in self._trackers.values():
+        for m in list(self._trackers.values()) + list(self._mask_trackers.values()):
             m.reset_state()
 
-    def _test_values(self, data):
-        """One batch through the model and the metric kernels: {key: device tensor} of everything ``test_step`` tracks (:504-536)."""
+    def _test_values(self, data, mask_metrics=False):
+        """One batch through the model and the metric kernels: {key: device tensor} of everything ``test_step`` tracks (:504-536) and,
+        with ``mask_metrics``, of what ``mask_test_step`` adds."""
         img, mask, _ = data
         img = torch.as_tensor(img, dtype=torch.float32).to(self.device).contiguous()
         mask = torch.as_tensor(mask, dtype=torch.float32).to(self.device)
@@ -326,6 +330,20 @@ class VQVAE:
         ci = img.shape[-1]
         if ci > recon.shape[-1]:
             raise ValueError(f"the image has {ci} channels, the reconstruction {recon.shape[-1]}")
+        if mask_metrics:
+            return {**self._image_values(img, recon, ci), **self._mask_values(mask.contiguous(), recon, ci)}
+        return self._image_values(img, recon, ci)
+
+    def _mask_values(self, mask, recon, ci):
+        """The mask half of the reconstruction, channels [ci, ci + cm), against the mask at threshold 0.5: per (volume, channel) values."""
+        cm = mask.shape[-1]
+        if ci + cm > recon.shape[-1]:
+            raise ValueError(f"the reconstruction has no mask channels to score: it has {recon.shape[-1]} channels, the image takes {ci} "
+                             f"and the mask needs {cm} behind them")
+        m = mask_metrics_of(mask, recon, x_channels=(0, cm), y_channels=(ci, cm))
+        return {"mask_dice": m["dice"], "mask_iou": m["iou"], "mask_hd95": m["hd_percentile"], "mask_assd": m["assd"]}
+
+    def _image_values(self, img, recon, ci):
         # tf.split(reconstructions, 2, axis=-1)[0]: the leading channels of the reconstruction, read in place
         ch = dict(x_channels=(0, ci), y_channels=(0, ci))
         stats = ops.pair_stats(img, recon, **ch)
@@ -333,7 +351,9 @@ class VQVAE:
                 "ssim": ops.ssim(img, recon, stats=stats, **ch).double().mean(), "psnr": ops.psnr(img, recon, stats=stats, **ch)}
 
     def _test_step(self, data):
-        values = self._test_values(data)
+        return self._track(self._test_values(data))
+
+    def _track(self, values):
         if "loss" in self.METRIC_KEYS:               # :515-516; VQGAN's loss has terms this project does not carry
             values["loss"] = (values["reconst_loss"] + values["quantize_loss"]) / self.num_gpus
         for k in self.METRIC_KEYS:
@@ -348,14 +368,34 @@ class VQVAE:
         (psnr weighted by its B*D values, the others one value a batch, as keras.metrics.Mean counts); nothing synchronises."""
         return self._test_step(data)
 
+    def mask_test_step(self, data):
+        """``test_step`` plus the scores of the mask half (not in the reference, whose test_step reads the image half only): the mask
+        channels of the reconstruction, ``[ci, ci + cm)`` behind the image's, against ``mask``, both binarised at 0.5, per volume and
+        channel: ``mask_dice``, ``mask_iou`` (NaN where the truth mask is empty), ``mask_hd95`` and ``mask_assd`` (in voxels; NaN where
+        either mask is empty).  Their running means skip NaN.  One forward pass serves both halves; nothing synchronises.  A
+        reconstruction without mask channels raises a ValueError."""
+        values = self._test_values(data, mask_metrics=True)
+        out = self._track(values)
+        for k in self.MASK_METRIC_KEYS:
+            self._mask_trackers[k].update_state(values[k])
+            out[k] = self._mask_trackers[k].result()
+        return out
+
     def evaluate(self, batches):
         """``reset_metrics``, ``test_step`` over an iterable of ``(img, mask, _)``, then the results as Python floats: the one
         synchronisation is the read-back at the end."""
+        return self._evaluate(batches, self.test_step, self.METRIC_KEYS)
+
+    def mask_evaluate(self, batches):
+        """``evaluate`` with ``mask_test_step``: ``METRIC_KEYS`` and ``MASK_METRIC_KEYS``, one forward pass and one read-back."""
+        return self._evaluate(batches, self.mask_test_step, self.METRIC_KEYS + self.MASK_METRIC_KEYS)
+
+    def _evaluate(self, batches, step, keys):
         self.reset_metrics()
         out = None
         for data in batches:
-            out = self.test_step(data)
+            out = step(data)
         if out is None:
-            return {k: 0.0 for k in self.METRIC_KEYS}
-        host = torch.stack([out[k] for k in self.METRIC_KEYS]).cpu().tolist()
-        return dict(zip(self.METRIC_KEYS, host))
+            return {k: 0.0 for k in keys}
+        host = torch.stack([out[k] for k in keys]).cpu().tolist()
+        return dict(zip(keys, host))

@@ -7,6 +7,7 @@ call the HIP kernels; there is no fallback implementation.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -595,3 +596,106 @@ def ms_ssim(x: torch.Tensor, y: torch.Tensor, max_val=None, *, power_factors=MS_
     check(lib().dm3d_ms_ssim(C.byref(d), _st()), "ms_ssim")
     del partials, scratch, idx
     return out
+
+
+# ---- mask-channel scores (include/dm3d.h, dm3d_mask_desc): overlap counts, the exact squared distance transform, surface distances ----
+class MaskOverlap(NamedTuple):
+    """What dm3d_mask_overlap counts per (volume, channel): int64 [B, nc] voxels of the truth mask, of the other mask, of both."""
+    x: torch.Tensor
+    y: torch.Tensor
+    both: torch.Tensor
+
+
+class SurfaceDistances(NamedTuple):
+    """What dm3d_surface_distance leaves per (volume, channel), float64 [B, nc], in voxels: the Hausdorff distance, its percentile form,
+    the average symmetric surface distance (all three NaN where either surface is empty) and the voxel counts of the two surfaces."""
+    hd: torch.Tensor
+    hd_percentile: torch.Tensor
+    assd: torch.Tensor
+    surface_x: torch.Tensor
+    surface_y: torch.Tensor
+
+
+def _mask_desc(x, y, threshold, x_channels, y_channels):
+    """The descriptor of one NDHWC tensor (``y`` None) or of a pair; ``*_channels = (first, count)`` as in ``_metric_desc``."""
+    _f32c(x, "x")
+    if x.dim() != 5:
+        raise ValueError(f"x must be [B,D,H,W,C], got {tuple(x.shape)}")
+    x0c, nc = (0, x.shape[4]) if x_channels is None else x_channels
+    d = _lib.MaskDesc()
+    d.x = x.data_ptr()
+    d.batch, d.d, d.h, d.w = x.shape[:4]
+    d.cx, d.x0c, d.nc = x.shape[4], x0c, nc
+    if y is not None:
+        _f32c(y, "y")
+        if y.dim() != 5 or x.shape[:4] != y.shape[:4]:
+            raise ValueError(f"x and y must be [B,D,H,W,C] with the same batch and spatial shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+        y0c, ncy = (0, y.shape[4]) if y_channels is None else y_channels
+        if nc != ncy:
+            raise ValueError(f"x contributes {nc} channels and y {ncy}: the same number must be compared")
+        d.y, d.cy, d.y0c = y.data_ptr(), y.shape[4], y0c
+    if max(x.shape[1:4]) > _lib.EDT_MAX_EXTENT:
+        raise ValueError(f"a {x.shape[1]} x {x.shape[2]} x {x.shape[3]} volume exceeds {_lib.EDT_MAX_EXTENT} voxels per axis")
+    thr = float(threshold)
+    if not math.isfinite(thr):
+        raise ValueError(f"threshold must be finite, got {threshold}")
+    d.threshold = thr
+    return d
+
+
+def mask_overlap(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, *, x_channels=None, y_channels=None) -> MaskOverlap:
+    """The voxel counts behind Dice and IoU: ``MaskOverlap`` of int64 [B, nc], exact.  A mask is ``value > threshold`` (NaN is background),
+    per volume and per channel of the window ``*_channels = (first, count)``, read in place from NDHWC float32 device tensors."""
+    d = _mask_desc(x, y, threshold, x_channels, y_channels)
+    counts = torch.empty(d.batch, d.nc, 3, dtype=torch.int64, device=x.device)
+    d.counts = counts.data_ptr()
+    check(lib().dm3d_mask_overlap(C.byref(d), _st()), "mask_overlap")
+    return MaskOverlap(counts[..., 0], counts[..., 1], counts[..., 2])
+
+
+def distance_transform(x: torch.Tensor, threshold: float = 0.5, *, channels=None, of: str = "surface") -> torch.Tensor:
+    """The exact squared Euclidean distance transform of the masks ``x > threshold``: int32 [B, D, H, W, nc], at every voxel the smallest
+    dz^2 + dy^2 + dx^2 to a voxel of the mask's surface (``of="surface"``: mask voxels with a 6-neighbour in the background or outside
+    the volume) or of the mask itself (``of="foreground"``); INT32_MAX everywhere where there is none.  The result is a view of a
+    channel-planar buffer [B, nc, D, H, W].  Distances are in voxels: anisotropic spacing is not offered, scale the axes yourself."""
+    if of not in ("surface", "foreground"):
+        raise ValueError(f'of must be "surface" or "foreground", got {of!r}')
+    d = _mask_desc(x, None, threshold, channels, None)
+    d.of = _lib.EDT_FOREGROUND if of == "foreground" else _lib.EDT_SURFACE
+    B, D, H, W, nc = d.batch, d.d, d.h, d.w, d.nc
+    out = torch.empty(B, nc, D, H, W, dtype=torch.int32, device=x.device)
+    masks = torch.empty(out.numel(), dtype=torch.uint8, device=x.device)       # alive until the launches are enqueued (same stream)
+    d.map, d.masks, d.masks_elems = out.data_ptr(), masks.data_ptr(), masks.numel()
+    check(lib().dm3d_edt(C.byref(d), _st()), "edt")
+    del masks
+    return out.permute(0, 2, 3, 4, 1)
+
+
+def _surface_distances(x, y, threshold, percentile, x_channels, y_channels, want_counts):
+    pct = float(percentile)
+    if not 0.0 < pct <= 100.0:
+        raise ValueError(f"percentile must be in (0, 100], got {percentile}")
+    d = _mask_desc(x, y, threshold, x_channels, y_channels)
+    B, D, H, W, nc = d.batch, d.d, d.h, d.w, d.nc
+    vox = B * nc * D * H * W
+    bins = (D - 1) ** 2 + (H - 1) ** 2 + (W - 1) ** 2 + 1
+    masks = torch.empty(2 * vox, dtype=torch.uint8, device=x.device)           # alive until the launches are enqueued (same stream)
+    work = torch.empty(vox + 2 * B * nc * (bins + 1), dtype=torch.int32, device=x.device)
+    out = torch.empty(B, nc, 5, dtype=torch.float64, device=x.device)
+    counts = torch.empty(B, nc, 3, dtype=torch.int64, device=x.device) if want_counts else None
+    d.percentile, d.out, d.counts = pct, out.data_ptr(), _p(counts)
+    d.masks, d.masks_elems, d.work, d.work_elems = masks.data_ptr(), masks.numel(), work.data_ptr(), work.numel()
+    check(lib().dm3d_surface_distance(C.byref(d), _st()), "surface_distance")
+    del masks, work
+    dist = SurfaceDistances(*(out[..., k] for k in range(5)))
+    return dist, (MaskOverlap(counts[..., 0], counts[..., 1], counts[..., 2]) if want_counts else None)
+
+
+def surface_distances(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, percentile: float = 95.0, *, x_channels=None,
+                      y_channels=None) -> SurfaceDistances:
+    """Distances between the surfaces of the masks ``x > threshold`` and ``y > threshold`` (MONAI's definitions): ``SurfaceDistances`` of
+    float64 [B, nc].  The directed distances X -> Y are the exact distance map of Y's surface read at X's surface voxels; ``hd`` is the
+    larger of the two directed maxima, ``hd_percentile`` the larger of the two directed percentiles (numpy's linear rule,
+    ``percentile`` in (0, 100]), ``assd`` the mean over both directed sets together.  Everything stays on the device.  Distances are in
+    voxels: anisotropic spacing is not offered, the caller scales.  No axis may exceed 512 voxels."""
+    return _surface_distances(x, y, threshold, percentile, x_channels, y_channels, False)[0]

@@ -886,6 +886,70 @@ typedef struct dm3d_ms_ssim_desc {
 } dm3d_ms_ssim_desc;
 int dm3d_ms_ssim(const dm3d_ms_ssim_desc* d, void* stream);
 
+/* ---- Scores of the mask channels: overlap (Dice, IoU) and surface distances (Hausdorff, its percentile, ASSD) of binarised masks, by
+ * MONAI's definitions, through an exact 3-D squared Euclidean distance transform.  x (the truth) is [batch, d, h, w, cx] and y
+ * [batch, d, h, w, cy], NDHWC float32; the nc channels x0c.. of x are compared with the nc channels y0c.. of y, read in place.
+ * Everything the entries write that has a voxel axis is channel-planar, [batch, nc, d, h, w], so that every column of the transform
+ * is a strided run of one volume.  Distances are in voxels: anisotropic spacing is not offered, the caller scales.  Nothing is read
+ * back.  Every quantity before the last kernel is an integer (integer atomics, min-plus over int32), the last kernel forms its float64
+ * values in a fixed order: runs repeat bitwise.
+ *
+ *     mask        m = value > threshold (NaN is background), per volume and channel
+ *     counts      counts[(b * nc + c) * 3 + {0, 1, 2}] = |X|, |Y|, |X and Y|                                               int64, exact
+ *     surface     a mask voxel with one of its 6 face neighbours in the background or outside the volume                 uint8 0 / 1
+ *     map         map[v] = min over feature voxels s of |v - s|^2 = dz^2 + dy^2 + dx^2; INT32_MAX everywhere without a feature   int32, exact
+ *
+ * dm3d_mask_overlap   one pass over both tensors: counts, and (surf_x and surf_y both non-NULL) the two surface masks.
+ * dm3d_edt            map of x's surface (of = DM3D_EDT_SURFACE) or of its mask (DM3D_EDT_FOREGROUND; 0 inside it): y, cy, y0c are not
+ *     read.  One pass writes the features to `masks`; then out[i] = min_j (i - j)^2 + g[j] along w (g = 0 at a feature, "none"
+ *     elsewhere), along h and along d, in place in `map`: a workgroup stages DM3D_EDT_LANES neighbouring columns in LDS
+ *     ([n][DM3D_EDT_LANES + 1] int32, twice: the columns and the results) and evaluates the form branch-free, O(n^2) per column.
+ *         masks_elems >= batch * nc * d * h * w                                   bytes
+ * dm3d_surface_distance   the overlap pass (counts if non-NULL), the map of Y's surface, a histogram of its values at X's surface voxels,
+ *     the same with X and Y exchanged, and one kernel that reads the two histograms of a (volume, channel):
+ *         out[(b * nc + c) * 5 + {0..4}] = hd, hd_percentile, assd, |S_X|, |S_Y|                                           float64
+ *         per direction: n voxels, max = sqrt(largest k), sum = sum_k count[k] sqrt(k) (256 runs of ascending k, added in ascending
+ *         order), percentile = numpy's default (linear) rule on the sorted distances: r = (n - 1) * (percentile / 100), lo = floor(r),
+ *         t = r - lo, a = sqrt(k at rank lo), b = sqrt(k at rank min(lo + 1, n - 1)), a + (b - a) t for t < 0.5, else b - (b - a)(1 - t)
+ *         hd = the larger max, hd_percentile = the larger percentile, assd = (sum_0 + sum_1) / (n_0 + n_1); all three NaN when
+ *         either surface is empty.
+ *         bins         = (d-1)^2 + (h-1)^2 + (w-1)^2 + 1
+ *         masks_elems >= 2 * batch * nc * d * h * w                               bytes
+ *         work_elems  >= batch * nc * (d * h * w + 2 * (bins + 1))                int32, 4-byte aligned
+ *
+ * Checked before any launch (DM3D_EINVAL; the message starts "mask_overlap:", "edt:" or "surface_distance:"): the descriptor and every
+ * pointer the entry reads or writes non-NULL (counts is optional for dm3d_surface_distance; surf_x and surf_y are given or omitted
+ * together); batch, nc >= 1 and batch * nc <= 65535; d, h, w in [1, DM3D_EDT_MAX_EXTENT], a larger extent named as such; x0c >= 0,
+ * x0c + nc <= cx (and y's window where y is read); threshold finite; of one of the two constants; percentile in (0, 100]; both scratch
+ * sizes; int64 / float64 buffers 8-byte aligned, int32 buffers 4-byte aligned. */
+#define DM3D_EDT_MAX_EXTENT 512
+#define DM3D_EDT_LANES 32
+#define DM3D_EDT_SURFACE 0
+#define DM3D_EDT_FOREGROUND 1
+typedef struct dm3d_mask_desc {
+    const float* x;             /* [batch, d, h, w, cx] the truth */
+    const float* y;             /* [batch, d, h, w, cy] the reconstruction (dm3d_edt: not read) */
+    int32_t batch, d, h, w;
+    int32_t cx, cy;             /* channel counts of the two tensors */
+    int32_t x0c, y0c;           /* first channel read of each */
+    int32_t nc;                 /* channels compared */
+    float threshold;
+    int32_t of;                 /* dm3d_edt: DM3D_EDT_SURFACE or DM3D_EDT_FOREGROUND */
+    double percentile;          /* dm3d_surface_distance: in (0, 100] */
+    int64_t* counts;            /* [batch, nc, 3]        mask_overlap: out; surface_distance: out, optional */
+    uint8_t* surf_x;            /* [batch, nc, d, h, w]  mask_overlap: out, optional */
+    uint8_t* surf_y;            /* [batch, nc, d, h, w]  mask_overlap: out, optional */
+    int32_t* map;               /* [batch, nc, d, h, w]  edt: out */
+    double* out;                /* [batch, nc, 5]        surface_distance: out */
+    uint8_t* masks;             /* device scratch of edt and surface_distance */
+    int64_t masks_elems;        /* bytes it holds */
+    int32_t* work;              /* device scratch of surface_distance */
+    int64_t work_elems;         /* int32 it holds */
+} dm3d_mask_desc;
+int dm3d_mask_overlap(const dm3d_mask_desc* d, void* stream);
+int dm3d_edt(const dm3d_mask_desc* d, void* stream);
+int dm3d_surface_distance(const dm3d_mask_desc* d, void* stream);
+
 /* p[i] = max(p[i] + delta, 0) (the loop counter of generate kept on the device so a captured step replays unchanged; it
  * saturates at 0, so a step issued past the end of a chain never indexes row -1 of a table). */
 int dm3d_add_i32(int32_t* p, int32_t n, int32_t delta, void* stream);
