@@ -210,6 +210,30 @@ class MaskDesc(C.Structure):
     ]
 
 
+class SplineDesc(C.Structure):
+    _fields_ = [("x", _f32p), ("coeff", C.c_void_p), ("volumes", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+class ResampleDesc(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("table", C.c_void_p), ("out", _f32p), ("in_f64", C.c_int32), ("volumes", C.c_int32), ("id", C.c_int32),
+        ("ih", C.c_int32), ("iw", C.c_int32), ("od", C.c_int32), ("oh", C.c_int32), ("ow", C.c_int32), ("order", C.c_int32), ("cval", C.c_float),
+    ]
+
+
+class NormalizeDesc(C.Structure):
+    _fields_ = [("x", _f32p), ("out", _f32p), ("volumes", C.c_int32), ("n", C.c_int64), ("partials", _f32p), ("minmax", _f32p), ("flag", _i32p)]
+
+
+class AugmentDesc(C.Structure):
+    _fields_ = [
+        ("x", _f32p), ("out", _f32p), ("mask", _f32p), ("mask_out", _f32p), ("batch", C.c_int32), ("d", C.c_int32), ("h", C.c_int32),
+        ("w", C.c_int32), ("c", C.c_int32), ("cm", C.c_int32), ("flip", _i32p), ("brightness", _f32p), ("contrast", _f32p), ("draw", C.c_int32),
+        ("seed", C.c_uint64), ("flip_chance", C.c_float), ("brightness_lo", C.c_float), ("brightness_hi", C.c_float), ("contrast_lo", C.c_float),
+        ("contrast_hi", C.c_float), ("partials", C.c_void_p),
+    ]
+
+
 GUIDE_PARTIAL_BLOCKS = 256          # DM3D_GUIDE_PARTIAL_BLOCKS: GuideDesc.partials holds [batch][256][4] doubles
 LOSS_PARTIAL_BLOCKS = 64            # DM3D_LOSS_PARTIAL_BLOCKS: LossDesc.partials holds [batch][64] doubles
 GRADNORM_PARTIAL_BLOCKS = 1024      # DM3D_GRADNORM_PARTIAL_BLOCKS: GradScaleDesc.partials holds [1024] doubles
@@ -217,6 +241,11 @@ PAIR_PARTIAL_BLOCKS = 64            # DM3D_PAIR_PARTIAL_BLOCKS: dm3d_pair_stats 
 SSIM_TILE = 32                      # DM3D_SSIM_TILE: dm3d_ssim leaves one partial per 32 x 32 tile of outputs
 EDT_MAX_EXTENT = 512                # DM3D_EDT_MAX_EXTENT: the longest axis dm3d_edt / dm3d_surface_distance stage in LDS
 EDT_SURFACE, EDT_FOREGROUND = 0, 1  # DM3D_EDT_SURFACE / DM3D_EDT_FOREGROUND: MaskDesc.of
+SPLINE_MAX_EXTENT = 512             # DM3D_SPLINE_MAX_EXTENT: the longest axis dm3d_spline_filter stages in LDS
+RESAMPLE_F32, RESAMPLE_F64 = 0, 1   # DM3D_RESAMPLE_F32 / DM3D_RESAMPLE_F64: ResampleDesc.in_f64
+NORM_PARTIAL_BLOCKS = 256           # DM3D_NORM_PARTIAL_BLOCKS: NormalizeDesc.partials holds [volumes][256][2] floats
+AUG_PARTIAL_BLOCKS = 256            # DM3D_AUG_PARTIAL_BLOCKS: AugmentDesc.partials holds [batch][256] doubles
+STREAM_AUGMENT = 0xA063             # DM3D_STREAM_AUGMENT: word 3 of the Philox counter of dm3d_augment's draws
 MSSSIM_TILE = (32, 16, 32)          # DM3D_MSSSIM_TD / TH / TW: dm3d_ms_ssim leaves one partial pair per tile of 32 x 16 x 32 (d, h, w) outputs
 
 # name -> (restype, argtypes): every symbol include/dm3d.h declares
@@ -290,6 +319,10 @@ SIGNATURES = {
     "dm3d_mask_overlap": (C.c_int, [C.POINTER(MaskDesc), C.c_void_p]),
     "dm3d_edt": (C.c_int, [C.POINTER(MaskDesc), C.c_void_p]),
     "dm3d_surface_distance": (C.c_int, [C.POINTER(MaskDesc), C.c_void_p]),
+    "dm3d_spline_filter": (C.c_int, [C.POINTER(SplineDesc), C.c_void_p]),
+    "dm3d_affine_resample": (C.c_int, [C.POINTER(ResampleDesc), C.c_void_p]),
+    "dm3d_volume_normalize": (C.c_int, [C.POINTER(NormalizeDesc), C.c_void_p]),
+    "dm3d_augment": (C.c_int, [C.POINTER(AugmentDesc), C.c_void_p]),
     "dm3d_range_check": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "dm3d_add_i32": (C.c_int, [_i32p, C.c_int32, C.c_int32, C.c_void_p]),
     "dm3d_randn": (C.c_int, [_f32p, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p]),

@@ -699,3 +699,201 @@ def surface_distances(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, 
     ``percentile`` in (0, 100]), ``assd`` the mean over both directed sets together.  Everything stays on the device.  Distances are in
     voxels: anisotropic spacing is not offered, the caller scales.  No axis may exceed 512 voxels."""
     return _surface_distances(x, y, threshold, percentile, x_channels, y_channels, False)[0]
+
+
+# ---- volume preprocessing (include/dm3d.h, "Volume preprocessing"): spline prefilter, affine resample, normalise, augment --------------
+SPLINE_ORDERS = (0, 1, 3)
+
+
+def _volume_check(x, name="x", *, spline=False, ndhwc=False, one_channel=False, host=None):
+    """The tensor checks of the preprocessing entries, in one order on any machine: dtype, rank (``ndhwc``: five axes only), empty axes,
+    the prefilter's extent (``spline``), one channel per volume (``one_channel``), then ``host()``, the caller's checks of its host
+    arguments, whose value is returned, and the device last."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise ValueError(f"{name} must be a float32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if x.dim() not in ((5,) if ndhwc else (4, 5)):
+        raise ValueError(f"{name} must be {'' if ndhwc else '[B,D,H,W] or '}[B,D,H,W,C], got {tuple(x.shape)}")
+    if min(x.shape) < 1:
+        raise ValueError(f"{name} has an empty axis: {tuple(x.shape)}")
+    if spline and max(x.shape[1:4]) > _lib.SPLINE_MAX_EXTENT:
+        raise ValueError(f"a {x.shape[1]} x {x.shape[2]} x {x.shape[3]} volume exceeds {_lib.SPLINE_MAX_EXTENT} voxels per axis, the longest line "
+                         "the spline prefilter stages")
+    if one_channel and x.dim() == 5 and x.shape[4] != 1:
+        raise ValueError(f"{name} must hold one channel per volume, got C={x.shape[4]}")
+    checked = host() if host is not None else None
+    _f32c(x, name)
+    return checked
+
+
+def _planar(x):
+    """[B,D,H,W] as it is, [B,D,H,W,C] as the channel-planar [B*C,D,H,W] (a view for C = 1, a copy otherwise), and the way back."""
+    if x.dim() == 4:
+        return x, lambda t: t
+    B, D, H, W, Cn = x.shape
+    if Cn == 1:
+        return x.reshape(B, D, H, W), lambda t: t.unsqueeze(-1)
+    return (x.permute(0, 4, 1, 2, 3).contiguous().view(B * Cn, D, H, W),
+            lambda t: t.reshape(B, Cn, *t.shape[1:]).permute(0, 2, 3, 4, 1).contiguous())
+
+
+def _spline_coefficients(planar):
+    V, D, H, W = planar.shape
+    coeff = torch.empty(V, D, H, W, dtype=torch.float64, device=planar.device)
+    d = _lib.SplineDesc()
+    d.x, d.coeff, d.volumes, d.d, d.h, d.w = planar.data_ptr(), coeff.data_ptr(), V, D, H, W
+    check(lib().dm3d_spline_filter(C.byref(d), _st()), "spline_filter")
+    return coeff
+
+
+def spline_filter(x: torch.Tensor) -> torch.Tensor:
+    """``scipy.ndimage.spline_filter(x, order=3, mode="mirror")`` over the three spatial axes of every volume of ``x`` ([B,D,H,W], or
+    NDHWC with each channel a volume): the float64 cubic B-spline coefficients, in x's layout.  This is the prefilter scipy runs in front
+    of ``mode="constant"`` interpolation; an axis of length 1 is left unfiltered, as scipy leaves it.  No axis may exceed 512 voxels."""
+    _volume_check(x, spline=True)
+    planar, back = _planar(x)
+    return back(_spline_coefficients(planar))
+
+
+def _affine_table(matrix, offset, batch, per):
+    """The float64 host table [batch * per, 12] of (matrix row by row, offset) from what ``affine_transform`` accepts."""
+    import numpy as np
+    as_np = lambda v: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float64)
+    m, off = as_np(matrix), as_np(offset)
+    if m.shape in ((4, 4), (batch, 4, 4)):                                      # homogeneous: the offset is its last column, as in scipy
+        if not np.array_equal(m[..., 3, :], np.broadcast_to([0.0, 0.0, 0.0, 1.0], m.shape[:-2] + (4,))):
+            raise ValueError("the last row of a homogeneous matrix must be (0, 0, 0, 1)")
+        if off.any():
+            raise ValueError("offset must be left at 0 with a homogeneous matrix: its last column is the offset")
+        m, off = m[..., :3, :3], m[..., :3, 3]
+    if m.shape == (3,):
+        m = np.diag(m)
+    if m.shape == (3, 3):
+        m = np.broadcast_to(m, (batch, 3, 3))
+    if m.shape != (batch, 3, 3):
+        raise ValueError(f"matrix must be a 3-vector, [3,3], [4,4] homogeneous or [B,3,3] with B={batch}, got {tuple(as_np(matrix).shape)}")
+    if off.shape not in ((), (3,), (batch, 3)):
+        raise ValueError(f"offset must be a scalar, a 3-vector or [B,3] with B={batch}, got {tuple(off.shape)}")
+    off = np.broadcast_to(off, (batch, 3))
+    if not (np.isfinite(m).all() and np.isfinite(off).all()):
+        raise ValueError("matrix and offset must be finite")
+    table = np.concatenate([m.reshape(batch, 9), off], 1)
+    return np.ascontiguousarray(np.repeat(table, per, 0))
+
+
+def affine_transform(x: torch.Tensor, matrix, offset=0.0, output_shape=None, order: int = 3, cval: float = 0.0, prefilter: bool = True,
+                     mode: str = "constant") -> torch.Tensor:
+    """``scipy.ndimage.affine_transform(volume, matrix, offset, output_shape, order=order, mode="constant", cval=cval)`` of every volume of
+    ``x`` ([B,D,H,W], or NDHWC with each channel a volume): ``out[o] = interp(volume, matrix @ o + offset)``, float32, in x's layout with
+    the spatial shape ``output_shape`` (default: x's).  ``matrix`` is a 3-vector (a diagonal, scipy's zoom form), [3,3], [4,4] homogeneous
+    (last row (0, 0, 0, 1), its last column is the offset and ``offset`` stays 0), [B,4,4] or [B,3,3], ``offset`` a scalar, a 3-vector or [B,3]; both are host values, formed in float64.
+    ``order`` 0 is nearest (floor(c + 0.5)), 1 trilinear, 3 cubic B-spline on the prefiltered coefficients (``prefilter=False``: x already
+    holds them).  A coordinate below 0 or above n - 1 on any axis gives ``cval``; spline taps beyond the edge are mirrored.  Coordinates
+    are ((o0 m0 + o1 m1) + o2 m2) + offset in float64, the taps are summed in float64 in one fixed order, runs repeat bitwise.  Orders 2,
+    4 and 5 and the other boundary modes are not offered."""
+    if order not in SPLINE_ORDERS:
+        raise ValueError(f"order must be 0, 1 or 3, got {order!r}: orders 2, 4 and 5 are not offered")
+    if mode != "constant":
+        raise ValueError(f'mode must be "constant", got {mode!r}: the other boundary modes are not offered')
+    if not math.isfinite(float(cval)):
+        raise ValueError(f"cval must be finite, got {cval}")
+    filtered = order == 3 and prefilter
+
+    def host_arguments():
+        shape = tuple(int(s) for s in (x.shape[1:4] if output_shape is None else output_shape))
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError(f"output_shape must be three positive extents, got {output_shape!r}")
+        return _affine_table(matrix, offset, x.shape[0], 1 if x.dim() == 4 else x.shape[4]), shape
+
+    table, shape = _volume_check(x, spline=filtered, host=host_arguments)
+    planar, back = _planar(x)
+    src = _spline_coefficients(planar) if filtered else planar
+    V = planar.shape[0]
+    dev_table = torch.from_numpy(table).to(x.device)
+    out = torch.empty(V, *shape, dtype=torch.float32, device=x.device)
+    d = _lib.ResampleDesc()
+    d.src, d.table, d.out, d.in_f64 = src.data_ptr(), dev_table.data_ptr(), out.data_ptr(), (_lib.RESAMPLE_F64 if filtered else _lib.RESAMPLE_F32)
+    d.volumes, d.id, d.ih, d.iw = planar.shape
+    d.od, d.oh, d.ow = shape
+    d.order, d.cval = order, float(cval)
+    check(lib().dm3d_affine_resample(C.byref(d), _st()), "affine_resample")
+    del src, dev_table                                                          # alive until the launch is enqueued (same stream)
+    return back(out)
+
+
+class Normalized(NamedTuple):
+    """What dm3d_volume_normalize leaves: the normalised volumes, ``minmax`` float32 [B, 2] (min and max of |x| per volume, exact) and
+    ``constant`` int32 [B], 1 where max = min (that volume is written as zeros).  All on the device; nothing is read back."""
+    out: torch.Tensor
+    minmax: torch.Tensor
+    constant: torch.Tensor
+
+
+def volume_normalize(x: torch.Tensor) -> Normalized:
+    """Per volume of ``x`` ([B,D,H,W] or [B,D,H,W,1]): a = |x| (the reference's ``vol[vol < 0] *= -1``), then (a - min a) / (max a - min a),
+    evaluated in float64 and rounded once.  Lazy: the constant-volume flag stays on the device (``data.normalize`` reads it)."""
+    _volume_check(x, one_channel=True)
+    B, n = x.shape[0], x[0].numel()
+    out = torch.empty_like(x)
+    partials = torch.empty(B, _lib.NORM_PARTIAL_BLOCKS, 2, dtype=torch.float32, device=x.device)
+    minmax = torch.empty(B, 2, dtype=torch.float32, device=x.device)
+    flag = torch.empty(B, dtype=torch.int32, device=x.device)
+    d = _lib.NormalizeDesc()
+    d.x, d.out, d.volumes, d.n = x.data_ptr(), out.data_ptr(), B, n
+    d.partials, d.minmax, d.flag = partials.data_ptr(), minmax.data_ptr(), flag.data_ptr()
+    check(lib().dm3d_volume_normalize(C.byref(d), _st()), "volume_normalize")
+    del partials
+    return Normalized(out, minmax, flag)
+
+
+class Augmented(NamedTuple):
+    """What dm3d_augment leaves: the augmented images, the masks flipped with them (None without masks) and the per-sample ``flip``
+    (int32 0 / 1), ``brightness`` and ``contrast`` (float32) that were applied, drawn or given.  All on the device."""
+    images: torch.Tensor
+    masks: Optional[torch.Tensor]
+    flip: torch.Tensor
+    brightness: torch.Tensor
+    contrast: torch.Tensor
+
+
+def augment(images: torch.Tensor, masks: Optional[torch.Tensor] = None, *, seed: Optional[int] = None, flip_chance: float = 0.6,
+            brightness_range=(0.9, 1.1), contrast_range=(0.9, 1.1), flip=None, brightness=None, contrast=None) -> Augmented:
+    """dm3d_augment on NDHWC batches (``data.augment`` documents the definitions).  Each of ``flip`` (int32 [B]), ``brightness`` and
+    ``contrast`` (float32 [B]) that is not given is drawn on the device and needs ``seed``."""
+    _volume_check(images, "images", ndhwc=True)
+    if masks is not None:
+        _volume_check(masks, "masks", ndhwc=True)
+        if masks.shape[:4] != images.shape[:4]:
+            raise ValueError(f"masks must be [B,D,H,W,C] with the batch and spatial shape of images, got {tuple(masks.shape)} and {tuple(images.shape)}")
+    B, D, H, W, Cn = images.shape
+    dev = images.device
+    draw, tables = 0, []
+    for bit, given, dtype, name in ((1, flip, torch.int32, "flip"), (2, brightness, torch.float32, "brightness"), (4, contrast, torch.float32, "contrast")):
+        if given is None:
+            draw |= bit
+            tables.append(torch.empty(B, dtype=dtype, device=dev))
+        else:
+            if not isinstance(given, torch.Tensor) or given.dtype != dtype or tuple(given.shape) != (B,) or not given.is_cuda or not given.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dtype} device tensor [B] with B={B}")
+            tables.append(given)
+    if draw and seed is None:
+        raise ValueError("augment needs seed= unless flip, brightness and contrast are all given")
+    for name, (lo, hi) in (("brightness_range", brightness_range), ("contrast_range", contrast_range)):
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+            raise ValueError(f"{name} must be finite and ascending, got ({lo}, {hi})")
+    if not 0.0 <= flip_chance <= 1.0:
+        raise ValueError(f"flip_chance must be in [0, 1], got {flip_chance}")
+    out = torch.empty_like(images)
+    mask_out = None if masks is None else torch.empty_like(masks)
+    partials = torch.empty(B, _lib.AUG_PARTIAL_BLOCKS, dtype=torch.float64, device=dev)
+    d = _lib.AugmentDesc()
+    d.x, d.out, d.mask, d.mask_out = images.data_ptr(), out.data_ptr(), _p(masks), _p(mask_out)
+    d.batch, d.d, d.h, d.w, d.c, d.cm = B, D, H, W, Cn, (0 if masks is None else masks.shape[4])
+    d.flip, d.brightness, d.contrast = (t.data_ptr() for t in tables)
+    d.draw, d.seed = draw, (int(seed) & (2 ** 64 - 1) if seed is not None else 0)
+    d.flip_chance = flip_chance
+    d.brightness_lo, d.brightness_hi = brightness_range
+    d.contrast_lo, d.contrast_hi = contrast_range
+    d.partials = partials.data_ptr()
+    check(lib().dm3d_augment(C.byref(d), _st()), "augment")
+    del partials
+    return Augmented(out, mask_out, *tables)

@@ -950,6 +950,98 @@ int dm3d_mask_overlap(const dm3d_mask_desc* d, void* stream);
 int dm3d_edt(const dm3d_mask_desc* d, void* stream);
 int dm3d_surface_distance(const dm3d_mask_desc* d, void* stream);
 
+/* ---- Volume preprocessing (the reference's dataset_utils.py: reslice, the affine recentring through scipy.ndimage.affine_transform,
+ * the fold of negatives, min-max normalisation, flip / brightness / contrast): four entries, all on channel-planar volumes
+ * [volumes, d, h, w] except dm3d_augment, which reads NDHWC batches.  Coordinates, weights, coefficients and sums are float64 in one
+ * fixed order (the library builds with -ffp-contract=off), stores are float32; no kernel uses an atomic: runs repeat bitwise.
+ *
+ * dm3d_spline_filter   scipy.ndimage.spline_filter(order=3, mode="mirror"), the prefilter scipy runs in front of mode="constant"
+ *     interpolation, per axis w, h, d:   z = sqrt(3) - 2;  c[i] *= (1 - z)(1 - 1/z);
+ *         c[0] = (c[0] + z^(n-1) c[n-1] + sum_{i=1}^{n-2} z^i (c[i] + z^(n-1) c[n-1-i])) / (1 - z^(2n-2));   c[i] += z c[i-1]  (i = 1 .. n-1)
+ *         c[n-1] = (z c[n-2] + c[n-1]) z / (z^2 - 1);   c[i] = z (c[i+1] - c[i])  (i = n-2 .. 0)
+ *     in float64; an axis of length 1 is left unfiltered, as scipy leaves it.  A workgroup stages DM3D_SPLINE_LANES neighbouring lines
+ *     in LDS ([n][DM3D_SPLINE_LANES + 1] float64) and one lane walks each line.  coeff holds volumes * d * h * w float64.
+ * dm3d_affine_resample   out[v][o] = interp(src[v], M_v o + offset_v), scipy.ndimage.affine_transform(mode="constant") for a
+ *     [3, 3] matrix; table[v] = {M row by row, offset} (12 float64); a diagonal matrix is the same entry with zeros off the diagonal.
+ *         coordinate   c[h] = ((o0 M[h][0] + o1 M[h][1]) + o2 M[h][2]) + offset[h]      each product and sum rounded to float64
+ *         outside      c[h] < 0 or c[h] > n[h] - 1 on any axis (or c[h] not a number): out = cval; exactly 0 and n - 1 are inside
+ *         order 0      in[floor(c + 0.5)]
+ *         order 1      taps floor(c), floor(c) + 1 with weights w0 = 1 - x, w1 = 1 - w0, x = c - floor(c)
+ *         order 3      taps floor(c) - 1 .. floor(c) + 2 on the coefficients, y = 1 - x:  w1 = (x x (x - 2) 3 + 4) / 6,
+ *                      w2 = (y y (y - 2) 3 + 4) / 6, w0 = y y y / 6, w3 = ((1 - w0) - w1) - w2
+ *         a tap outside [0, n - 1] is mirrored (period 2n - 2, no repeated edge; n = 1: index 0)
+ *         out = (float) sum over taps, axis 0 outermost, axis 2 innermost, of ((in * w0) * w1) * w2
+ *     src is float32 (in_f64 = DM3D_RESAMPLE_F32) or float64 (DM3D_RESAMPLE_F64: dm3d_spline_filter's coefficients).  A workgroup owns
+ *     a brick of 4 x 4 x 16 (d, h, w) outputs.  Nothing bounds the table's values: whatever they are, no read leaves the volume.
+ * dm3d_volume_normalize   per volume of n elements: a = |x|; out = (a - min a) / (max a - min a), evaluated in float64 and rounded once.
+ *     A first kernel leaves exact per-block minima and maxima in partials, a second folds them, writes minmax[v] = {min, max} and
+ *     flag[v] = (max == min), and applies them; a constant volume is written as zeros.  No host read sits between the two.
+ *         partials holds volumes * DM3D_NORM_PARTIAL_BLOCKS * 2 float32
+ * dm3d_augment   per sample b of an NDHWC batch x [batch, d, h, w, c], with mask [batch, d, h, w, cm] (optional) flipped alike:
+ *         t(v)   = clip((double)x[v] * brightness[b], 0, 1)
+ *         mean   = (sum over the sample of t, float64: DM3D_AUG_PARTIAL_BLOCKS block sums by the fixed tree, added by the same tree) / (d h w c)
+ *         out[v] = (float) clip((1 + contrast[b]) * (t(v') - mean) + mean, 0, 1),   v' = v with d - 1 - z for z where flip[b] != 0
+ *     (the reference's flip_axis_0, adjust_brightness, adjust_contrast, with its literal (1 + factor)).  flip (int32), brightness and
+ *     contrast (float32) are device tables [batch]; bit 1, 2, 4 of draw fills the respective table first, from the Philox4x32-10 block
+ *     of counter (b, 0, 0, DM3D_STREAM_AUGMENT) under the key seed: u_k = (float)word_k * 2^-32,
+ *         flip = !(u_0 < flip_chance),  brightness = lo + (hi - lo) * u_1,  contrast = lo + (hi - lo) * u_2        in float32
+ *         partials holds batch * DM3D_AUG_PARTIAL_BLOCKS float64
+ *
+ * Checked before any launch (DM3D_EINVAL; the message starts "spline_filter:", "affine_resample:", "volume_normalize:" or "augment:"): the
+ * descriptor and every pointer non-NULL (mask and mask_out are given or omitted together) and aligned to its element; volumes / batch
+ * >= 1 (at most 65535 where it is a grid axis); every extent >= 1; spline_filter: d, h, w <= DM3D_SPLINE_MAX_EXTENT, a larger extent
+ * named as such; affine_resample: order 0, 1 or 3, in_f64 one of the two constants, cval finite, an input volume below 2^31 voxels;
+ * volume_normalize: n >= 1; augment: c >= 1, cm >= 1 with a mask, draw in [0, 7], neither out nor mask_out sharing a byte with x, mask or each other, and where draw != 0
+ * flip_chance in [0, 1] and both ranges finite and ascending. */
+#define DM3D_SPLINE_MAX_EXTENT 512
+#define DM3D_SPLINE_LANES 32
+#define DM3D_RESAMPLE_F32 0
+#define DM3D_RESAMPLE_F64 1
+#define DM3D_NORM_PARTIAL_BLOCKS 256
+#define DM3D_AUG_PARTIAL_BLOCKS 256
+#define DM3D_STREAM_AUGMENT 0xA063u
+typedef struct dm3d_spline_desc {
+    const float* x;             /* [volumes, d, h, w] */
+    double* coeff;              /* [volumes, d, h, w] out */
+    int32_t volumes, d, h, w;
+} dm3d_spline_desc;
+int dm3d_spline_filter(const dm3d_spline_desc* d, void* stream);
+typedef struct dm3d_resample_desc {
+    const void* src;            /* [volumes, id, ih, iw] float32 or float64 */
+    const double* table;        /* [volumes, 12] */
+    float* out;                 /* [volumes, od, oh, ow] */
+    int32_t in_f64;             /* DM3D_RESAMPLE_F32 or DM3D_RESAMPLE_F64 */
+    int32_t volumes, id, ih, iw, od, oh, ow;
+    int32_t order;              /* 0, 1 or 3 */
+    float cval;
+} dm3d_resample_desc;
+int dm3d_affine_resample(const dm3d_resample_desc* d, void* stream);
+typedef struct dm3d_normalize_desc {
+    const float* x;             /* [volumes, n] */
+    float* out;                 /* [volumes, n]; may be x itself */
+    int32_t volumes;
+    int64_t n;
+    float* partials;            /* device scratch, written before it is read by every call */
+    float* minmax;              /* [volumes, 2] out */
+    int32_t* flag;              /* [volumes] out: 1 where the volume is constant */
+} dm3d_normalize_desc;
+int dm3d_volume_normalize(const dm3d_normalize_desc* d, void* stream);
+typedef struct dm3d_augment_desc {
+    const float* x;             /* [batch, d, h, w, c] */
+    float* out;                 /* [batch, d, h, w, c] */
+    const float* mask;          /* [batch, d, h, w, cm] or NULL */
+    float* mask_out;            /* [batch, d, h, w, cm] or NULL */
+    int32_t batch, d, h, w, c, cm;
+    int32_t* flip;              /* [batch] in, or out where bit 1 of draw is set */
+    float* brightness;          /* [batch] in, or out where bit 2 of draw is set */
+    float* contrast;            /* [batch] in, or out where bit 4 of draw is set */
+    int32_t draw;
+    uint64_t seed;
+    float flip_chance, brightness_lo, brightness_hi, contrast_lo, contrast_hi;
+    double* partials;           /* device scratch, written before it is read by every call */
+} dm3d_augment_desc;
+int dm3d_augment(const dm3d_augment_desc* d, void* stream);
+
 /* p[i] = max(p[i] + delta, 0) (the loop counter of generate kept on the device so a captured step replays unchanged; it
  * saturates at 0, so a step issued past the end of a chain never indexes row -1 of a table). */
 int dm3d_add_i32(int32_t* p, int32_t n, int32_t delta, void* stream);
