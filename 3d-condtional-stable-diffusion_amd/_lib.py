@@ -210,6 +210,14 @@ class MaskDesc(C.Structure):
     ]
 
 
+class CclDesc(C.Structure):
+    _fields_ = [
+        ("x", _f32p), ("batch", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cx", C.c_int32), ("x0c", C.c_int32),
+        ("nc", C.c_int32), ("threshold", C.c_float), ("connectivity", C.c_int32), ("mode", C.c_int32), ("min_size", C.c_int32),
+        ("labels", _i32p), ("count", _i32p), ("largest", C.c_void_p), ("out", _f32p), ("work", _i32p), ("work_elems", C.c_int64),
+    ]
+
+
 class SplineDesc(C.Structure):
     _fields_ = [("x", _f32p), ("coeff", C.c_void_p), ("volumes", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
 
@@ -241,6 +249,9 @@ PAIR_PARTIAL_BLOCKS = 64            # DM3D_PAIR_PARTIAL_BLOCKS: dm3d_pair_stats 
 SSIM_TILE = 32                      # DM3D_SSIM_TILE: dm3d_ssim leaves one partial per 32 x 32 tile of outputs
 EDT_MAX_EXTENT = 512                # DM3D_EDT_MAX_EXTENT: the longest axis dm3d_edt / dm3d_surface_distance stage in LDS
 EDT_SURFACE, EDT_FOREGROUND = 0, 1  # DM3D_EDT_SURFACE / DM3D_EDT_FOREGROUND: MaskDesc.of
+CCL_MAX_EXTENT = 512                # DM3D_CCL_MAX_EXTENT: the longest axis dm3d_components / dm3d_component_filter take
+CCL_BLOCK_VOXELS = 1024             # DM3D_CCL_BLOCK_VOXELS: the voxels behind one block count of CclDesc.work
+CCL_LARGEST, CCL_MIN_SIZE, CCL_FILL_HOLES = 0, 1, 2   # DM3D_CCL_*: CclDesc.mode
 SPLINE_MAX_EXTENT = 512             # DM3D_SPLINE_MAX_EXTENT: the longest axis dm3d_spline_filter stages in LDS
 RESAMPLE_F32, RESAMPLE_F64 = 0, 1   # DM3D_RESAMPLE_F32 / DM3D_RESAMPLE_F64: ResampleDesc.in_f64
 NORM_PARTIAL_BLOCKS = 256           # DM3D_NORM_PARTIAL_BLOCKS: NormalizeDesc.partials holds [volumes][256][2] floats
@@ -319,6 +330,8 @@ SIGNATURES = {
     "dm3d_mask_overlap": (C.c_int, [C.POINTER(MaskDesc), C.c_void_p]),
     "dm3d_edt": (C.c_int, [C.POINTER(MaskDesc), C.c_void_p]),
     "dm3d_surface_distance": (C.c_int, [C.POINTER(MaskDesc), C.c_void_p]),
+    "dm3d_components": (C.c_int, [C.POINTER(CclDesc), C.c_void_p]),
+    "dm3d_component_filter": (C.c_int, [C.POINTER(CclDesc), C.c_void_p]),
     "dm3d_spline_filter": (C.c_int, [C.POINTER(SplineDesc), C.c_void_p]),
     "dm3d_affine_resample": (C.c_int, [C.POINTER(ResampleDesc), C.c_void_p]),
     "dm3d_volume_normalize": (C.c_int, [C.POINTER(NormalizeDesc), C.c_void_p]),

@@ -13,7 +13,7 @@ import torch
 
 from . import ops
 
-__all__ = ["reslice", "transform_image", "normalize", "augment", "preprocess"]
+__all__ = ["reslice", "transform_image", "normalize", "augment", "preprocess"]    # the preprocessing set, pinned by its host test; clean_mask is public beside it
 
 
 def _batched(x):
@@ -136,3 +136,14 @@ def preprocess(x: torch.Tensor, affine, voxsize, mask: Optional[torch.Tensor] = 
     image = normalize(vol).unsqueeze(-1)
     context = torch.zeros(image.shape[0], 1, 1, dtype=torch.int64, device=image.device)
     return image, torch.zeros_like(image), context
+
+
+def clean_mask(mask: torch.Tensor, *, keep_largest: bool = True, fill_holes: bool = True, min_size: Optional[int] = None, connectivity: int = 6,
+               threshold: float = 0.5) -> torch.Tensor:
+    """A predicted or generated mask made fit for scoring, between a reconstruction and ``metrics.mask_metrics``: binarise the NDHWC
+    float32 device tensor at ``threshold`` per volume and channel, drop the components below ``min_size`` voxels (when given), keep the
+    largest component (``keep_largest``), fill the holes (``fill_holes``), in that order (``ops.component_filter``).  ``connectivity``
+    (6, 18, 26) is the foreground's.  Returns float32 zeros and ones of the same shape; nothing is read back.  At least one step must
+    be asked for."""
+    return ops.component_filter(mask, threshold, connectivity=connectivity, keep="largest" if keep_largest else None, min_size=min_size,
+                                fill_holes=fill_holes)

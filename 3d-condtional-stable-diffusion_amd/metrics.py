@@ -12,9 +12,9 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .ops import distance_transform, mask_overlap, ms_ssim, pair_stats, psnr, ssim, surface_distances
+from .ops import connected_components, distance_transform, mask_overlap, ms_ssim, pair_stats, psnr, ssim, surface_distances
 
-__all__ = ["Mean", "NanMean", "dice", "distance_transform", "hausdorff", "iou", "mask_metrics", "mask_overlap", "ms_ssim", "pair_stats",
+__all__ = ["Mean", "NanMean", "component_stats", "connected_components", "dice", "distance_transform", "hausdorff", "iou", "mask_metrics", "mask_overlap", "ms_ssim", "pair_stats",
            "pairwise_ms_ssim", "psnr", "sample_diversity", "ssim", "surface_distances", "volume_metrics"]
 
 
@@ -86,6 +86,16 @@ def mask_metrics(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, perce
     dist, counts = ops._surface_distances(x, y, threshold, percentile, x_channels, y_channels, True)
     d, i = _dice_iou(counts)
     return {"dice": d, "iou": i, **dist._asdict(), "counts": counts}
+
+
+def component_stats(x: torch.Tensor, threshold: float = 0.5, *, channels=None, connectivity: int = 6) -> Dict[str, torch.Tensor]:
+    """How many blobs the masks ``x > threshold`` fall into (``ops.connected_components``; ``connectivity`` 6, 18 or 26): ``components``
+    int32 [B, nc] and ``largest_fraction`` float64 [B, nc], the share of the mask's voxels its largest component holds (1 for one blob,
+    NaN for an empty mask).  Nothing is read back."""
+    comp = connected_components(x, threshold, channels=channels, connectivity=connectivity)
+    total = (comp.labels > 0).sum(dim=(1, 2, 3)).double()
+    nan = torch.full_like(total, float("nan"))
+    return {"components": comp.count, "largest_fraction": torch.where(total > 0, comp.largest[..., 1].double() / total.clamp(min=1.0), nan)}
 
 
 class Mean:

@@ -701,6 +701,101 @@ def surface_distances(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, 
     return _surface_distances(x, y, threshold, percentile, x_channels, y_channels, False)[0]
 
 
+# ---- connected components of the mask channels (include/dm3d.h, dm3d_ccl_desc): labels, count, largest, the three filters -------------
+class Components(NamedTuple):
+    """What dm3d_components leaves: ``labels`` int32 [B, D, H, W, nc] (0 at the background, scipy.ndimage.label's numbering per volume
+    and channel; a view of a channel-planar buffer), ``count`` int32 [B, nc], ``largest`` int64 [B, nc, 2] = (label, size) of the
+    component with the most voxels, the lowest label on a tie, (0, 0) for an empty mask."""
+    labels: torch.Tensor
+    count: torch.Tensor
+    largest: torch.Tensor
+
+
+CONNECTIVITIES = (6, 18, 26)
+
+
+def _ccl_desc(x, threshold, channels, connectivity, planes):
+    """The descriptor of one NDHWC tensor and its scratch of ``planes`` int32 planes (alive while the caller holds it)."""
+    _f32c(x, "x")
+    if x.dim() != 5:
+        raise ValueError(f"x must be [B,D,H,W,C], got {tuple(x.shape)}")
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
+    if max(x.shape[1:4]) > _lib.CCL_MAX_EXTENT:
+        raise ValueError(f"a {x.shape[1]} x {x.shape[2]} x {x.shape[3]} volume exceeds {_lib.CCL_MAX_EXTENT} voxels per axis")
+    thr = float(threshold)
+    if not math.isfinite(thr):
+        raise ValueError(f"threshold must be finite, got {threshold}")
+    x0c, nc = (0, x.shape[4]) if channels is None else channels
+    d = _lib.CclDesc()
+    d.x = x.data_ptr()
+    d.batch, d.d, d.h, d.w = x.shape[:4]
+    d.cx, d.x0c, d.nc = x.shape[4], x0c, nc
+    d.threshold, d.connectivity = thr, connectivity
+    vol = d.d * d.h * d.w
+    nblk = -(-vol // _lib.CCL_BLOCK_VOXELS)
+    work = torch.empty(planes * d.batch * nc * vol + 1 + d.batch * nc * (3 * nblk + 2), dtype=torch.int32, device=x.device)
+    d.work, d.work_elems = work.data_ptr(), work.numel()
+    return d, work
+
+
+def connected_components(x: torch.Tensor, threshold: float = 0.5, *, channels=None, connectivity: int = 6) -> Components:
+    """The connected components of the masks ``x > threshold`` (NaN is background), per volume and per channel of the window
+    ``channels = (first, count)``, read in place from an NDHWC float32 device tensor: ``Components(labels, count, largest)``.
+    ``connectivity`` is 6, 18 or 26 (``scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3)``); nothing connects across volumes,
+    channels or round the border.  Labels do not depend on the order anything ran in: runs repeat bitwise.  Nothing is read back.  No
+    axis may exceed 512 voxels; anisotropy, per-label size tables and slice-wise labelling are not offered."""
+    d, work = _ccl_desc(x, threshold, channels, connectivity, 2)
+    labels = torch.empty(d.batch, d.nc, d.d, d.h, d.w, dtype=torch.int32, device=x.device)
+    count = torch.empty(d.batch, d.nc, dtype=torch.int32, device=x.device)
+    largest = torch.empty(d.batch, d.nc, 2, dtype=torch.int64, device=x.device)
+    d.labels, d.count, d.largest = labels.data_ptr(), count.data_ptr(), largest.data_ptr()
+    check(lib().dm3d_components(C.byref(d), _st()), "components")
+    del work                                                                    # alive until the launches are enqueued (same stream)
+    return Components(labels.permute(0, 2, 3, 4, 1), count, largest)
+
+
+def _component_filter(x, threshold, channels, connectivity, mode, min_size=1):
+    d, work = _ccl_desc(x, threshold, channels, connectivity, 3)
+    out = torch.empty(d.batch, d.d, d.h, d.w, d.nc, dtype=torch.float32, device=x.device)
+    d.mode, d.min_size, d.out = mode, min(int(min_size), 2 ** 31 - 1), out.data_ptr()
+    check(lib().dm3d_component_filter(C.byref(d), _st()), "component_filter")
+    del work
+    return out
+
+
+def component_filter(x: torch.Tensor, threshold: float = 0.5, *, channels=None, connectivity: int = 6, keep: Optional[str] = None,
+                     min_size: Optional[int] = None, fill_holes: bool = False) -> torch.Tensor:
+    """The masks ``x > threshold`` cleaned through their connected components: float32 [B, D, H, W, nc] of 0 and 1, ready for
+    ``metrics.mask_metrics``.  At least one of
+
+        min_size=n        (n >= 1) keep every component with at least n voxels          MONAI's RemoveSmallObjects
+        keep="largest"    keep the component with the most voxels, the lowest label on a tie; an empty mask stays empty
+                                                                                         MONAI's KeepLargestConnectedComponent
+        fill_holes=True   add every background voxel whose 6-connected background component touches no face of the volume
+                                                                                         scipy.ndimage.binary_fill_holes / MONAI's FillHoles
+
+    must be asked for; several apply in that order, each stage reading the previous stage's result at threshold 0.5.  ``connectivity``
+    (6, 18, 26) is the foreground's; the background of ``fill_holes`` is always 6-connected.  Nothing is read back."""
+    if keep not in (None, "largest"):
+        raise ValueError(f'keep must be "largest" or None, got {keep!r}')
+    if min_size is not None and (int(min_size) != min_size or min_size < 1):
+        raise ValueError(f"min_size must be an integer of at least 1, got {min_size!r}")
+    if keep is None and min_size is None and not fill_holes:
+        raise ValueError('component_filter needs at least one of min_size, keep="largest" and fill_holes=True')
+    stages = []
+    if min_size is not None:
+        stages.append((_lib.CCL_MIN_SIZE, int(min_size)))
+    if keep is not None:
+        stages.append((_lib.CCL_LARGEST, 1))
+    if fill_holes:
+        stages.append((_lib.CCL_FILL_HOLES, 1))
+    for mode, n in stages:
+        x = _component_filter(x, threshold, channels, connectivity, mode, n)
+        threshold, channels = 0.5, None
+    return x
+
+
 # ---- volume preprocessing (include/dm3d.h, "Volume preprocessing"): spline prefilter, affine resample, normalise, augment --------------
 SPLINE_ORDERS = (0, 1, 3)
 

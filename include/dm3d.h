@@ -950,6 +950,63 @@ int dm3d_mask_overlap(const dm3d_mask_desc* d, void* stream);
 int dm3d_edt(const dm3d_mask_desc* d, void* stream);
 int dm3d_surface_distance(const dm3d_mask_desc* d, void* stream);
 
+/* ---- Connected components of the mask channels: labels, count, largest, and the filters built on them (MONAI's
+ * KeepLargestConnectedComponent, RemoveSmallObjects and FillHoles).  x is [batch, d, h, w, cx] NDHWC float32; the nc channels x0c.. are
+ * read in place.  labels is channel-planar, [batch, nc, d, h, w]; out is NDHWC with nc channels.  Nothing is read back, every quantity
+ * is an integer and the result does not depend on the order anything happened in: runs repeat bitwise.
+ *
+ *     mask          m = value > threshold (NaN is background), per volume and channel
+ *     connectivity  6, 18 or 26: voxels are neighbours when they differ by at most 1 on every axis and on at most 1, 2 or 3 axes;
+ *                   nothing connects across volumes, channels or round the border
+ *     labels        0 at the background; a component's label is 1 + the rank of its smallest raster index (z * h + y) * w + x among the
+ *                   components of its (volume, channel): scipy.ndimage.label's numbering                                     int32
+ *     count         count[b * nc + c] components                                                                             int32
+ *     largest       largest[(b * nc + c) * 2 + {0, 1}] = label, size of the component with the most voxels, the lowest label on a
+ *                   tie, (0, 0) for an empty mask                                                                            int64
+ *
+ * dm3d_components        labels, count and largest.  A workgroup labels one 8 x 8 x 64 (d, h, w) brick by union-find in LDS; voxels on
+ *     brick faces are united across the seams by device-scope atomic min on the larger root; one pass replaces every parent by its
+ *     root and adds the brick pieces' sizes at the roots; the roots are counted per block of DM3D_CCL_BLOCK_VOXELS voxels, the block
+ *     counts scanned by one workgroup per (volume, channel), and the roots' ranks written back through them.
+ *         work_elems >= 2 * batch * nc * d * h * w + 1 + batch * nc * (3 * nblk + 2)      int32, 8-byte aligned
+ * dm3d_component_filter  out = 1.0f at the voxels a mode keeps, 0.0f elsewhere:
+ *     DM3D_CCL_LARGEST      the voxels of `largest`'s component; an empty mask stays empty
+ *     DM3D_CCL_MIN_SIZE     the voxels of every component with at least min_size voxels
+ *     DM3D_CCL_FILL_HOLES   the mask and every background voxel whose 6-connected background component touches no face of the volume
+ *                           (scipy.ndimage.binary_fill_holes, default structure); `connectivity` is checked and not used
+ *         work_elems >= 3 * batch * nc * d * h * w + 1 + batch * nc * (3 * nblk + 2)      int32, 8-byte aligned
+ *         nblk        = ceil(d * h * w / DM3D_CCL_BLOCK_VOXELS)
+ *
+ * Checked before any launch (DM3D_EINVAL; the message starts "components:" or "component_filter:"): the descriptor and every pointer
+ * the entry uses non-NULL; x, labels, count, out 4-byte and largest, work 8-byte aligned; batch, nc >= 1 and batch * nc <= 65535; d, h,
+ * w in [1, DM3D_CCL_MAX_EXTENT], a larger extent named as such (at 512^3 an index still fits int32 beside the background sentinel and
+ * the flag bits of a size word); x0c >= 0, x0c + nc <= cx; threshold finite; connectivity 6, 18 or 26; a known mode; min_size >= 1 for
+ * DM3D_CCL_MIN_SIZE; the scratch size; labels and out share no byte with x. */
+#define DM3D_CCL_MAX_EXTENT 512
+#define DM3D_CCL_BLOCK_VOXELS 1024
+#define DM3D_CCL_LARGEST 0
+#define DM3D_CCL_MIN_SIZE 1
+#define DM3D_CCL_FILL_HOLES 2
+typedef struct dm3d_ccl_desc {
+    const float* x;             /* [batch, d, h, w, cx] */
+    int32_t batch, d, h, w;
+    int32_t cx;                 /* channels of x */
+    int32_t x0c;                /* first channel read */
+    int32_t nc;                 /* channels read */
+    float threshold;
+    int32_t connectivity;       /* 6, 18 or 26 */
+    int32_t mode;               /* dm3d_component_filter: DM3D_CCL_LARGEST, DM3D_CCL_MIN_SIZE or DM3D_CCL_FILL_HOLES */
+    int32_t min_size;           /* DM3D_CCL_MIN_SIZE: at least 1 */
+    int32_t* labels;            /* [batch, nc, d, h, w]  components: out */
+    int32_t* count;             /* [batch, nc]           components: out */
+    int64_t* largest;           /* [batch, nc, 2]        components: out */
+    float* out;                 /* [batch, d, h, w, nc]  component_filter: out */
+    int32_t* work;              /* device scratch */
+    int64_t work_elems;         /* int32 it holds */
+} dm3d_ccl_desc;
+int dm3d_components(const dm3d_ccl_desc* d, void* stream);
+int dm3d_component_filter(const dm3d_ccl_desc* d, void* stream);
+
 /* ---- Volume preprocessing (the reference's dataset_utils.py: reslice, the affine recentring through scipy.ndimage.affine_transform,
  * the fold of negatives, min-max normalisation, flip / brightness / contrast): four entries, all on channel-planar volumes
  * [volumes, d, h, w] except dm3d_augment, which reads NDHWC batches.  Coordinates, weights, coefficients and sums are float64 in one
