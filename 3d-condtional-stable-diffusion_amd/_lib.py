@@ -218,6 +218,15 @@ class CclDesc(C.Structure):
     ]
 
 
+class DistDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("y", C.c_void_p), ("rows_x", _i32p), ("rows_y", _i32p), ("n", C.c_int32), ("m", C.c_int32), ("nx", C.c_int32),
+        ("ny", C.c_int32), ("dim", C.c_int32), ("k", C.c_int32), ("subsets", C.c_int32), ("radius_x", C.c_void_p), ("radius_y", C.c_void_p),
+        ("mean", C.c_void_p), ("cov", C.c_void_p), ("radius", C.c_void_p), ("count_y", _i32p), ("near_x", _i32p), ("cover_x", _i32p),
+        ("sums", C.c_void_p), ("work", C.c_void_p), ("work_elems", C.c_int64),
+    ]
+
+
 class SplineDesc(C.Structure):
     _fields_ = [("x", _f32p), ("coeff", C.c_void_p), ("volumes", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
 
@@ -252,6 +261,8 @@ EDT_SURFACE, EDT_FOREGROUND = 0, 1  # DM3D_EDT_SURFACE / DM3D_EDT_FOREGROUND: Ma
 CCL_MAX_EXTENT = 512                # DM3D_CCL_MAX_EXTENT: the longest axis dm3d_components / dm3d_component_filter take
 CCL_BLOCK_VOXELS = 1024             # DM3D_CCL_BLOCK_VOXELS: the voxels behind one block count of CclDesc.work
 CCL_LARGEST, CCL_MIN_SIZE, CCL_FILL_HOLES = 0, 1, 2   # DM3D_CCL_*: CclDesc.mode
+DIST_MAX_ROWS, DIST_MAX_DIM, DIST_MAX_K, DIST_MAX_SUBSETS = 65536, 4096, 16, 16384   # DM3D_DIST_MAX_*: what the DistDesc entries take
+DIST_TILE, DIST_CHUNK = 64, 32      # DM3D_DIST_TILE / DM3D_DIST_CHUNK: rows and columns of a workgroup's tile, features staged at a time
 SPLINE_MAX_EXTENT = 512             # DM3D_SPLINE_MAX_EXTENT: the longest axis dm3d_spline_filter stages in LDS
 RESAMPLE_F32, RESAMPLE_F64 = 0, 1   # DM3D_RESAMPLE_F32 / DM3D_RESAMPLE_F64: ResampleDesc.in_f64
 NORM_PARTIAL_BLOCKS = 256           # DM3D_NORM_PARTIAL_BLOCKS: NormalizeDesc.partials holds [volumes][256][2] floats
@@ -332,6 +343,10 @@ SIGNATURES = {
     "dm3d_surface_distance": (C.c_int, [C.POINTER(MaskDesc), C.c_void_p]),
     "dm3d_components": (C.c_int, [C.POINTER(CclDesc), C.c_void_p]),
     "dm3d_component_filter": (C.c_int, [C.POINTER(CclDesc), C.c_void_p]),
+    "dm3d_feature_moments": (C.c_int, [C.POINTER(DistDesc), C.c_void_p]),
+    "dm3d_knn_radius": (C.c_int, [C.POINTER(DistDesc), C.c_void_p]),
+    "dm3d_prdc_counts": (C.c_int, [C.POINTER(DistDesc), C.c_void_p]),
+    "dm3d_poly_mmd": (C.c_int, [C.POINTER(DistDesc), C.c_void_p]),
     "dm3d_spline_filter": (C.c_int, [C.POINTER(SplineDesc), C.c_void_p]),
     "dm3d_affine_resample": (C.c_int, [C.POINTER(ResampleDesc), C.c_void_p]),
     "dm3d_volume_normalize": (C.c_int, [C.POINTER(NormalizeDesc), C.c_void_p]),

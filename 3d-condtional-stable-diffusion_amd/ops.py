@@ -992,3 +992,148 @@ def augment(images: torch.Tensor, masks: Optional[torch.Tensor] = None, *, seed:
     check(lib().dm3d_augment(C.byref(d), _st()), "augment")
     del partials
     return Augmented(out, mask_out, *tables)
+
+
+# ---- distribution metrics on feature vectors (include/dm3d.h, dm3d_dist_desc): moments, k-NN radii, PRDC counts, cubic-kernel sums -----
+class FeatureMoments(NamedTuple):
+    """What dm3d_feature_moments leaves: ``mean`` float64 [D] and the unbiased ``cov`` float64 [D, D], symmetric bit for bit."""
+    mean: torch.Tensor
+    cov: torch.Tensor
+
+
+class PrdcCounts(NamedTuple):
+    """What dm3d_prdc_counts leaves, all int32: ``count_fake`` [M], the real balls a generated row lies in; ``near_real`` [N], 1 where a
+    real row lies in some generated row's ball; ``cover_real`` [N], 1 where a real row's nearest generated row lies in its ball."""
+    count_fake: torch.Tensor
+    near_real: torch.Tensor
+    cover_real: torch.Tensor
+
+
+def _features_check(t, name: str, other=None, min_rows: int = 2) -> None:
+    """What every feature matrix must be, whatever machine it is checked on: 2-D, float32 or float64, within the limits."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError(f"{name} must be a 2-D feature tensor [rows, D], got {tuple(getattr(t, 'shape', ()))}: flatten or pool the features to one vector per sample first")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{name} must be float32 or float64, got {t.dtype}: cast with .float() or .double()")
+    n, dim = t.shape
+    if n < min_rows:
+        raise ValueError(f"{name} has {n} rows, at least {min_rows} are needed")
+    if dim < 1 or dim > _lib.DIST_MAX_DIM:
+        raise ValueError(f"{name} has D={dim} features; 1 to {_lib.DIST_MAX_DIM} are taken: pool or project the features first")
+    if n > _lib.DIST_MAX_ROWS:
+        raise ValueError(f"{name} has {n} rows, at most {_lib.DIST_MAX_ROWS} are taken: score a subsample")
+    if other is not None and other.shape[1] != dim:
+        raise ValueError(f"{name} has D={dim} features, the other set has D={other.shape[1]}: both sets must come from one feature extractor")
+
+
+def _features(t, name: str, other=None, min_rows: int = 2) -> torch.Tensor:
+    """``_features_check``, then the device, then the exact widening to contiguous float64."""
+    _features_check(t, name, other, min_rows)
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be a device tensor: the distribution kernels have no CPU path")
+    return t.to(torch.float64).contiguous()
+
+
+def _feature_pair(real, fake, min_fake: int = 2):
+    """Both sets of a two-set score: every shape check of both before the first device check."""
+    _features_check(real, "real")
+    _features_check(fake, "fake", real, min_fake)
+    return _features(real, "real"), _features(fake, "fake", real, min_fake)
+
+
+def _row_table(rows, name: str, device, per_subset: bool = False):
+    """An optional int32 row table [n] (``per_subset``: [S, n]) on the device."""
+    if rows is None:
+        return None
+    if not isinstance(rows, torch.Tensor) or rows.dim() != (2 if per_subset else 1) or rows.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name} must be an int32 or int64 tensor {'[subsets, rows]' if per_subset else '[rows]'} or None")
+    return rows.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _dist_desc(x, rows_x, y=None, rows_y=None):
+    d = _lib.DistDesc()
+    d.x, d.nx, d.dim, d.rows_x = x.data_ptr(), x.shape[0], x.shape[1], _p(rows_x)
+    d.n = x.shape[0] if rows_x is None else rows_x.shape[-1]
+    if y is not None:
+        d.y, d.ny, d.rows_y = y.data_ptr(), y.shape[0], _p(rows_y)
+        d.m = y.shape[0] if rows_y is None else rows_y.shape[-1]
+    return d
+
+
+def feature_moments(x: torch.Tensor, rows: Optional[torch.Tensor] = None) -> FeatureMoments:
+    """Mean and unbiased covariance of the feature vectors ``x`` [n, D] (float32 or float64 device tensor; float32 is widened exactly),
+    or of its rows ``rows`` (int [r], read in place; repeats allowed): ``FeatureMoments(mean, cov)`` in float64, every sum sequential in
+    row order, so runs repeat bitwise.  At least 2 rows.  Nothing is read back."""
+    x = _features(x, "x", min_rows=1)
+    rows = _row_table(rows, "rows", x.device)
+    d = _dist_desc(x, rows)
+    if d.n < 2:
+        raise ValueError(f"x has {d.n} rows, at least 2 are needed for a covariance")
+    mean = torch.empty(d.dim, dtype=torch.float64, device=x.device)
+    cov = torch.empty(d.dim, d.dim, dtype=torch.float64, device=x.device)
+    d.mean, d.cov = mean.data_ptr(), cov.data_ptr()
+    check(lib().dm3d_feature_moments(C.byref(d), _st()), "feature_moments")
+    return FeatureMoments(mean, cov)
+
+
+def knn_radius(x: torch.Tensor, k: int = 5, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The squared Euclidean distance of every row of ``x`` [n, D] to its ``k``-th nearest neighbour in the same set, float64 [n], by
+    the ``prdc`` package's rule: the (k + 1)-th smallest entry of the row of the set's own distance matrix, itself included, so a
+    duplicated row is a neighbour at distance 0.  1 <= k <= 16 and k < n.  No square root is taken.  Nothing is read back."""
+    x = _features(x, "x", min_rows=1)
+    rows = _row_table(rows, "rows", x.device)
+    d = _dist_desc(x, rows)
+    if int(k) != k or not 1 <= k <= _lib.DIST_MAX_K:
+        raise ValueError(f"k must be an integer from 1 to {_lib.DIST_MAX_K}, got {k!r}")
+    if k >= d.n:
+        raise ValueError(f"k={k} needs more than k rows, the set has {d.n}: lower k or add samples")
+    radius = torch.empty(d.n, dtype=torch.float64, device=x.device)
+    d.k, d.radius = int(k), radius.data_ptr()
+    check(lib().dm3d_knn_radius(C.byref(d), _st()), "knn_radius")
+    return radius
+
+
+def prdc_counts(real: torch.Tensor, fake: torch.Tensor, radius_real: torch.Tensor, radius_fake: torch.Tensor, *, rows_real=None,
+                rows_fake=None) -> PrdcCounts:
+    """The integers behind precision, recall, density and coverage of generated features ``fake`` [M, D] against real features
+    ``real`` [N, D], given both sets' ``knn_radius`` (squared, float64 [N] and [M]): ``PrdcCounts(count_fake, near_real, cover_real)``,
+    every comparison a strict < on squared distances, as in the ``prdc`` package.  The N x M distances are never stored.  Nothing is
+    read back."""
+    real, fake = _feature_pair(real, fake, 1)
+    rows_real, rows_fake = _row_table(rows_real, "rows_real", real.device), _row_table(rows_fake, "rows_fake", real.device)
+    d = _dist_desc(real, rows_real, fake, rows_fake)
+    for t, name, n in ((radius_real, "radius_real", d.n), (radius_fake, "radius_fake", d.m)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != (n,) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float64 device tensor [{n}], what knn_radius returns for that set")
+    count = torch.empty(d.m, dtype=torch.int32, device=real.device)
+    near = torch.empty(d.n, dtype=torch.int32, device=real.device)
+    cover = torch.empty(d.n, dtype=torch.int32, device=real.device)
+    d.radius_x, d.radius_y = radius_real.data_ptr(), radius_fake.data_ptr()
+    d.count_y, d.near_x, d.cover_x = count.data_ptr(), near.data_ptr(), cover.data_ptr()
+    check(lib().dm3d_prdc_counts(C.byref(d), _st()), "prdc_counts")
+    return PrdcCounts(count, near, cover)
+
+
+def poly_mmd(real: torch.Tensor, fake: torch.Tensor, rows_real: Optional[torch.Tensor] = None, rows_fake: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The three sums the unbiased MMD^2 needs under KID's kernel k(a, b) = (a . b / D + 1)^3, for S subsets at once: float64 [S, 3] =
+    (sum_{i != j} k(x_i, x_j), sum_{i != j} k(y_i, y_j), sum_{i, j} k(x_i, y_j)).  ``rows_real`` [S, n] and ``rows_fake`` [S, m] (int,
+    read in place) pick each subset's rows; None takes the whole set, and with both None S = 1.  Dot products, row sums and their
+    sum run in index order: runs repeat bitwise.  Other kernels are not offered.  Nothing is read back."""
+    real, fake = _feature_pair(real, fake)
+    rows_real = _row_table(rows_real, "rows_real", real.device, True)
+    rows_fake = _row_table(rows_fake, "rows_fake", real.device, True)
+    subsets = {t.shape[0] for t in (rows_real, rows_fake) if t is not None}
+    if len(subsets) > 1:
+        raise ValueError(f"rows_real and rows_fake must list the same number of subsets, got {rows_real.shape[0]} and {rows_fake.shape[0]}")
+    d = _dist_desc(real, rows_real, fake, rows_fake)
+    d.subsets = subsets.pop() if subsets else 1
+    if d.subsets < 1 or d.subsets > _lib.DIST_MAX_SUBSETS:
+        raise ValueError(f"1 to {_lib.DIST_MAX_SUBSETS} subsets are taken, got {d.subsets}: split the call")
+    if d.n < 2 or d.m < 2:
+        raise ValueError(f"a subset needs at least 2 rows of each set, got {d.n} and {d.m}")
+    sums = torch.empty(d.subsets, 3, dtype=torch.float64, device=real.device)
+    work = torch.empty(d.subsets * (2 * d.n + d.m), dtype=torch.float64, device=real.device)
+    d.sums, d.work, d.work_elems = sums.data_ptr(), work.data_ptr(), work.numel()
+    check(lib().dm3d_poly_mmd(C.byref(d), _st()), "poly_mmd")
+    del work                                                                    # alive until the launches are enqueued (same stream)
+    return sums

@@ -1007,6 +1007,78 @@ typedef struct dm3d_ccl_desc {
 int dm3d_components(const dm3d_ccl_desc* d, void* stream);
 int dm3d_component_filter(const dm3d_ccl_desc* d, void* stream);
 
+/* ---- Distribution metrics on feature vectors: the all-pairs passes behind the Frechet distance, KID and precision / recall / density /
+ * coverage.  x and y are float64 row-major feature matrices [nx, dim] and [ny, dim].  An entry reads n rows of x and m rows of y: row p
+ * of the set is matrix row rows_x[p] (rows_y[p]), or row p where the table is NULL, so a subset or a resample is read in place.  A
+ * table entry outside [0, nx) is clamped into it: the caller's fault, never a read outside the matrix.  Features are taken to be
+ * finite.  Nothing is read back.
+ *
+ * Arithmetic, every entry: a pair's sum over the feature axis is float64, sequential in index order 0, 1, .., dim - 1, multiply and
+ * add rounded separately (the library builds with -ffp-contract=off); sums over rows or pairs run in the one order given below; no
+ * floating-point atomic.  Runs repeat bitwise and a restatement with the same operations in the same order agrees bit for bit.
+ *
+ *     d2(a, b)  = sum_f (a[f] - b[f]) * (a[f] - b[f])                           squared Euclidean distance, 0 between equal rows
+ *     k(a, b)   = t * t * t,  t = (sum_f a[f] * b[f]) / dim + 1                 the cubic kernel of KID; (t * t) * t
+ *
+ * dm3d_feature_moments  mean[f] = (sum over p = 0 .. n-1 of x[p][f]) / n; cov[f][g] = (sum over p of (x[p][f] - mean[f]) *
+ *     (x[p][g] - mean[g])) / (n - 1), both sums sequential in p.  The triangle f <= g is computed and mirrored.  n >= 2.
+ * dm3d_knn_radius       radius[p] = the (k + 1)-th smallest of d2(x[p], x[q]) over q = 0 .. n-1, q = p included (the prdc package's
+ *     rule: a duplicated row is a neighbour at distance 0).  Squared; no square root is taken.  1 <= k <= DM3D_DIST_MAX_K, k < n.
+ * dm3d_prdc_counts      with x the real and y the generated set, radius_x [n] and radius_y [m] their dm3d_knn_radius:
+ *     count_y[j] = the number of i with d2(x[i], y[j]) < radius_x[i]           (density; precision is count_y[j] > 0)      int32
+ *     near_x[i]  = 1 if some j has d2(x[i], y[j]) < radius_y[j], else 0         (recall)                                    int32
+ *     cover_x[i] = 1 if min over j of d2(x[i], y[j]) < radius_x[i], else 0      (coverage)                                  int32
+ *     Strict <.  count_y is zeroed on the stream and summed with integer atomics.
+ * dm3d_poly_mmd         for every subset s of `subsets`, with rows_x [subsets, n] and rows_y [subsets, m] (NULL: rows 0 .. n-1 and
+ *     0 .. m-1 for every subset):  sums[s] = { sum_{i != j} k(x_i, x_j),  sum_{i != j} k(y_i, y_j),  sum_{i, j} k(x_i, y_j) }.
+ *     i and j are positions in the subset.  A row sum runs over j in index order (j = i left out), the sum of row sums over i in
+ *     index order.
+ *         work_elems >= subsets * (2 * n + m)                                   float64
+ *
+ * A workgroup owns DM3D_DIST_TILE rows, walks the columns in tiles of DM3D_DIST_TILE and the feature axis in chunks of
+ * DM3D_DIST_CHUNK, both tiles staged in LDS, 4 x 4 pairs per lane; what a row keeps across column tiles (its k + 1 smallest, its
+ * minimum, its sum) stays in the workgroup, so no n x m intermediate reaches memory and no workgroup waits for another one.
+ *
+ * Checked before any launch (DM3D_EINVAL; the message starts "feature_moments:", "knn_radius:", "prdc_counts:" or "poly_mmd:"): the
+ * descriptor and every pointer the entry uses non-NULL; float64 pointers 8-byte, int32 pointers 4-byte aligned; 1 <= dim <=
+ * DM3D_DIST_MAX_DIM; n, m, nx, ny <= DM3D_DIST_MAX_ROWS, each limit named when exceeded; n <= nx and m <= ny without a table, nx,
+ * ny >= 1; n >= 2 (and m >= 2 for poly_mmd, m >= 1 for prdc_counts); k as above; 1 <= subsets <= DM3D_DIST_MAX_SUBSETS; the scratch
+ * size; no output shares a byte with x or y. */
+#define DM3D_DIST_MAX_ROWS 65536
+#define DM3D_DIST_MAX_DIM 4096
+#define DM3D_DIST_MAX_K 16
+#define DM3D_DIST_MAX_SUBSETS 16384
+#define DM3D_DIST_TILE 64
+#define DM3D_DIST_CHUNK 32
+typedef struct dm3d_dist_desc {
+    const double* x;            /* [nx, dim] */
+    const double* y;            /* [ny, dim]             prdc_counts, poly_mmd */
+    const int32_t* rows_x;      /* [n], poly_mmd [subsets, n]; NULL: rows 0 .. n-1 */
+    const int32_t* rows_y;      /* [m], poly_mmd [subsets, m]; NULL: rows 0 .. m-1 */
+    int32_t n;                  /* rows of x read */
+    int32_t m;                  /* rows of y read */
+    int32_t nx;                 /* rows x holds */
+    int32_t ny;                 /* rows y holds */
+    int32_t dim;
+    int32_t k;                  /* knn_radius */
+    int32_t subsets;            /* poly_mmd */
+    const double* radius_x;     /* [n]                   prdc_counts: in */
+    const double* radius_y;     /* [m]                   prdc_counts: in */
+    double* mean;               /* [dim]                 feature_moments: out */
+    double* cov;                /* [dim, dim]            feature_moments: out */
+    double* radius;             /* [n]                   knn_radius: out */
+    int32_t* count_y;           /* [m]                   prdc_counts: out */
+    int32_t* near_x;            /* [n]                   prdc_counts: out */
+    int32_t* cover_x;           /* [n]                   prdc_counts: out */
+    double* sums;               /* [subsets, 3]          poly_mmd: out */
+    double* work;               /* device scratch of poly_mmd */
+    int64_t work_elems;         /* float64 it holds */
+} dm3d_dist_desc;
+int dm3d_feature_moments(const dm3d_dist_desc* d, void* stream);
+int dm3d_knn_radius(const dm3d_dist_desc* d, void* stream);
+int dm3d_prdc_counts(const dm3d_dist_desc* d, void* stream);
+int dm3d_poly_mmd(const dm3d_dist_desc* d, void* stream);
+
 /* ---- Volume preprocessing (the reference's dataset_utils.py: reslice, the affine recentring through scipy.ndimage.affine_transform,
  * the fold of negatives, min-max normalisation, flip / brightness / contrast): four entries, all on channel-planar volumes
  * [volumes, d, h, w] except dm3d_augment, which reads NDHWC batches.  Coordinates, weights, coefficients and sums are float64 in one
