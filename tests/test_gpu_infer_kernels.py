@@ -38,7 +38,9 @@ DM3D_CONV_WIDE_WGS / DM3D_CONV_WINO_MINCHUNKS / DM3D_CONV_WINO_SPLIT_MINCHUNKS a
 128 x 128 tile form of the H3 GEMM (taken from 256 tiles of that size up) runs under the per-call knob DM3D_GEMM_MR=2, and no query names
 the tile form a GEMM launch took, so those cases rest on the knob; the grouped GEMM and the attention entries run the 64 x 64 form only.
 Without a plant case of their own: PReLU on a partial brick and PReLU behind the Winograd-x form (other instantiations of branches that
-have one).  Not covered: dm3d_conv_desc.gn_stats (normalisation statistics: tests/test_gpu_round4.py).
+have one).  Not covered: dm3d_conv_desc.gn_stats (normalisation statistics: tests/test_gpu_round4.py); the logit axis of the attention and
+softmax entries (constructed score rows, the fused kernel's lazy running maximum, the float16 floor of the probabilities:
+tests/test_gpu_attention_logits.py).
 
 Tolerances (max |err| / max |ref|), the project's: contractions 2e-5, row kernels 3e-6, elementwise 1e-6, data movement bitwise.
 The worst error per entry is printed at the end of the module (docs/EXPERIMENTS.md records a run)."""
