@@ -227,6 +227,16 @@ class DistDesc(C.Structure):
     ]
 
 
+class CodebookDesc(C.Structure):
+    _fields_ = [
+        ("z", _f32p), ("idx", _i32p), ("rows", C.c_int32), ("dim", C.c_int32), ("k", C.c_int32), ("counts", _i32p), ("sums", C.c_void_p),
+        ("invalid", _i32p), ("eps", C.c_double), ("perplexity", C.c_void_p), ("active", _i32p), ("used_accum", _i32p),
+        ("cluster_size", _f32p), ("ema_w", _f32p), ("codebook", _f32p), ("esq", _f32p), ("decay", C.c_float), ("epsilon", C.c_float),
+        ("used", _i32p), ("num_batches", C.c_int32), ("draw", C.c_int32), ("threshold", C.c_double), ("noise_scale", C.c_float),
+        ("seed", C.c_uint64), ("used_count", _i32p), ("unused_count", _i32p), ("map", _i32p),
+    ]
+
+
 class SplineDesc(C.Structure):
     _fields_ = [("x", _f32p), ("coeff", C.c_void_p), ("volumes", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
 
@@ -263,6 +273,9 @@ CCL_BLOCK_VOXELS = 1024             # DM3D_CCL_BLOCK_VOXELS: the voxels behind o
 CCL_LARGEST, CCL_MIN_SIZE, CCL_FILL_HOLES = 0, 1, 2   # DM3D_CCL_*: CclDesc.mode
 DIST_MAX_ROWS, DIST_MAX_DIM, DIST_MAX_K, DIST_MAX_SUBSETS = 65536, 4096, 16, 16384   # DM3D_DIST_MAX_*: what the DistDesc entries take
 DIST_TILE, DIST_CHUNK = 64, 32      # DM3D_DIST_TILE / DM3D_DIST_CHUNK: rows and columns of a workgroup's tile, features staged at a time
+CODEBOOK_MAX_K, CODEBOOK_MAX_DIM, CODEBOOK_MAX_ROWS = 4096, 1024, 1 << 30   # DM3D_CODEBOOK_MAX_*: what the CodebookDesc entries take
+CODEBOOK_SLICE, CODEBOOK_BATCH = 64, 16   # DM3D_CODEBOOK_SLICE / DM3D_CODEBOOK_BATCH: features of a wave of dm3d_code_stats, rows it loads together
+STREAM_CODEBOOK, STREAM_CODEBOOK_SHUFFLE = 0xC0DE, 0xC0D5   # DM3D_STREAM_CODEBOOK[_SHUFFLE]: word 3 of dm3d_codebook_replace's Philox counters
 SPLINE_MAX_EXTENT = 512             # DM3D_SPLINE_MAX_EXTENT: the longest axis dm3d_spline_filter stages in LDS
 RESAMPLE_F32, RESAMPLE_F64 = 0, 1   # DM3D_RESAMPLE_F32 / DM3D_RESAMPLE_F64: ResampleDesc.in_f64
 NORM_PARTIAL_BLOCKS = 256           # DM3D_NORM_PARTIAL_BLOCKS: NormalizeDesc.partials holds [volumes][256][2] floats
@@ -347,6 +360,10 @@ SIGNATURES = {
     "dm3d_knn_radius": (C.c_int, [C.POINTER(DistDesc), C.c_void_p]),
     "dm3d_prdc_counts": (C.c_int, [C.POINTER(DistDesc), C.c_void_p]),
     "dm3d_poly_mmd": (C.c_int, [C.POINTER(DistDesc), C.c_void_p]),
+    "dm3d_code_stats": (C.c_int, [C.POINTER(CodebookDesc), C.c_void_p]),
+    "dm3d_code_usage": (C.c_int, [C.POINTER(CodebookDesc), C.c_void_p]),
+    "dm3d_codebook_ema": (C.c_int, [C.POINTER(CodebookDesc), C.c_void_p]),
+    "dm3d_codebook_replace": (C.c_int, [C.POINTER(CodebookDesc), C.c_void_p]),
     "dm3d_spline_filter": (C.c_int, [C.POINTER(SplineDesc), C.c_void_p]),
     "dm3d_affine_resample": (C.c_int, [C.POINTER(ResampleDesc), C.c_void_p]),
     "dm3d_volume_normalize": (C.c_int, [C.POINTER(NormalizeDesc), C.c_void_p]),

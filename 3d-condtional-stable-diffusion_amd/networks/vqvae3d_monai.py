@@ -13,7 +13,8 @@ device tensors.  Every layer runs on the dm3d HIP kernels (no fallback):
   VectorQuantizer.get_code_indices + lookup (:140-177) -> float32 GEMM z.E, dm3d_vq_assign, dm3d_gather_rows
 
 Keras' ``PReLU()`` has a full-shape slope ``[D,H,W,C]``, which ties the reference model to 128^3 inputs; here the spatial size
-is the keyword ``input_size`` (default 128).  Training (``train_step``, codebook replacement) is out of scope; evaluation is here:
+is the keyword ``input_size`` (default 128).  Gradient training (``train_step``) is out of scope; the codebook of the frozen
+autoencoder can be fitted and inspected on the device (``fit_codebook``, ``codebook_usage``; ``dm3d_amd.codebook``); evaluation is here:
 ``test_step`` / ``evaluate`` report ``reconst_loss``, ``quantize_loss``, ``ssim`` and ``psnr`` as the reference's ``test_step`` (:504-544)
 does, through the fused metric kernels (``dm3d_amd.metrics``).
 """
@@ -289,6 +290,71 @@ class VQVAE:
         B, n = z.shape[0], z.numel() // z.shape[0]
         sse = ops.pair_stats(q.reshape(B, 1, 1, n, 1), z.reshape(B, 1, 1, n, 1)).sse
         return (1.0 + VQ_BETA) * sse.sum() / z.numel()
+
+    # ---- the codebook of the frozen autoencoder ----------------------------------------------------------------------------
+    def _latent_rows(self, batch):
+        """The frozen encoder on one batch, an encoder input or ``(img, mask, _)`` as ``test_step`` takes it: latents [rows, D]."""
+        if isinstance(batch, (tuple, list)):
+            img = torch.as_tensor(batch[0], dtype=torch.float32).to(self.device)
+            mask = torch.as_tensor(batch[1], dtype=torch.float32).to(self.device)
+            batch = torch.cat([img, mask], dim=-1).contiguous()
+        return self._encode(batch).reshape(-1, self.embedding_dim)
+
+    def fit_codebook(self, batches, decay=0.99, epsilon=1e-5, replace_every=None, discarding_threshold=0.01, seed=0):
+        """Fits the codebook to the latents of ``batches`` with the encoder frozen: per batch, encoder -> nearest code -> per-code
+        counts and float64 sums -> the reference's moving-average update (VectorQuantizerEMA, emavqvae.py:213-222), and every
+        ``replace_every`` batches NSVQ's dead-code replacement (nsvqvae.py:193-230) with ``discarding_threshold``.  All of it acts on
+        the model's own device codebook and ``esq``; the moving averages start from the codebook with cluster sizes of 1.  Nothing
+        synchronises in the loop; per-batch ``perplexity``, ``active_codes`` and ``quantize_loss`` (``last_loss``'s rule, before
+        the batch's update) come back in one read at the end together with the codebook, which becomes ``state["vq.embeddings"]``:
+        ``quantizer`` / ``test_step`` use it, and a model loaded from the state picks the same codes.  Sums run in a fixed order with
+        no floating-point atomic, so a fit repeats bitwise."""
+        if replace_every is not None and (int(replace_every) != replace_every or replace_every < 1):
+            raise ValueError(f"replace_every must be None or an integer of at least 1, got {replace_every!r}")
+        self.prepare()
+        k, dim = self.num_embeddings, self.embedding_dim
+        book, esq = self.P["vq.codebook_t"], self.P["vq.esq"]
+        size, ema_w = torch.ones(k, dtype=torch.float32, device=self.device), book.clone()
+        used = torch.zeros(k, dtype=torch.int32, device=self.device)
+        kept, replacements = [], 0
+        for i, batch in enumerate(batches):
+            flat = self._latent_rows(batch)
+            idx = ops.vq_assign(flat, book, esq)
+            q = ops.gather_rows(book, idx)
+            sse = ops.pair_stats(q.reshape(1, 1, 1, -1, 1), flat.reshape(1, 1, 1, -1, 1)).sse
+            stats = ops.code_stats(flat, idx, k)
+            usage = ops.code_usage(stats.counts, flat.shape[0], 1e-10, used_accum=used)
+            ops.codebook_ema(book, esq, size, ema_w, stats.counts, stats.sums, decay, epsilon)
+            kept.append(torch.stack([usage.perplexity, usage.active.double(), (1.0 + VQ_BETA) * sse.sum() / flat.numel()]))
+            if replace_every is not None and (i + 1) % replace_every == 0:
+                ops.codebook_replace(book, esq, used, int(replace_every), discarding_threshold, seed=seed, draw=replacements,
+                                     cluster_size=size, ema_w=ema_w)
+                replacements += 1
+        host = torch.cat([book.double().reshape(-1)] + [v for v in kept]).cpu().numpy()      # the one read-back; float32 -> float64 is exact
+        self.state["vq.embeddings"] = np.ascontiguousarray(host[:k * dim].reshape(k, dim).T.astype(np.float32))
+        per = host[k * dim:].reshape(-1, 3)
+        return {"batches": len(kept), "replacements": replacements, "perplexity": per[:, 0].tolist(),
+                "active_codes": [int(v) for v in per[:, 1]], "quantize_loss": per[:, 2].tolist()}
+
+    def codebook_usage(self, batches):
+        """How the codebook is used on ``batches`` (encoder inputs or ``(img, mask, _)``), with one read-back: ``counts`` (numpy int64
+        [K], rows per code), ``rows``, ``perplexity`` (over all rows), ``active_codes`` and ``dead_codes`` (the indices with no row)."""
+        self.prepare()
+        k = self.num_embeddings
+        total = torch.zeros(k, dtype=torch.int32, device=self.device)
+        rows = 0
+        for batch in batches:
+            flat = self._latent_rows(batch)
+            idx = ops.vq_assign(flat, self.P["vq.codebook_t"], self.P["vq.esq"])
+            ops.code_usage(ops.code_stats(flat, idx, k).counts, flat.shape[0], 1e-10, used_accum=total)
+            rows += flat.shape[0]
+        if rows == 0:
+            raise ValueError("codebook_usage: no batch was given")
+        usage = ops.code_usage(total, rows, 1e-10)
+        host = torch.cat([total.double(), usage.perplexity.reshape(1), usage.active.double().reshape(1)]).cpu().numpy()
+        counts = host[:k].astype(np.int64)
+        return {"counts": counts, "rows": rows, "perplexity": float(host[k]), "active_codes": int(host[k + 1]),
+                "dead_codes": np.flatnonzero(counts == 0).tolist()}
 
     def _decode(self, z):
         """Decoder.call (:388-391)."""

@@ -1137,3 +1137,149 @@ def poly_mmd(real: torch.Tensor, fake: torch.Tensor, rows_real: Optional[torch.T
     check(lib().dm3d_poly_mmd(C.byref(d), _st()), "poly_mmd")
     del work                                                                    # alive until the launches are enqueued (same stream)
     return sums
+
+
+# ---- fitting the VQ codebook (include/dm3d.h, dm3d_codebook_desc): per-code statistics, usage, EMA update, dead-code replacement ---------
+class CodeStats(NamedTuple):
+    """What dm3d_code_stats leaves: ``counts`` int32 [K]; ``sums`` float64 [K, D], each code's member rows added in ascending row order;
+    ``invalid`` int32 [1], the rows whose index lies outside [0, K)."""
+    counts: torch.Tensor
+    sums: torch.Tensor
+    invalid: torch.Tensor
+
+
+class CodeUsage(NamedTuple):
+    """What dm3d_code_usage leaves: ``perplexity`` 0-d float64 and ``active`` 0-d int32, the number of codes with a member."""
+    perplexity: torch.Tensor
+    active: torch.Tensor
+
+
+class Replaced(NamedTuple):
+    """What dm3d_codebook_replace reports, both 0-d int32 device tensors."""
+    used_count: torch.Tensor
+    unused_count: torch.Tensor
+
+
+def _dev_tensor(t, name: str, dtype, shape, device: bool = True) -> torch.Tensor:
+    words = {torch.float32: "float32", torch.float64: "float64", torch.int32: "int32"}[dtype]
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a {words} tensor {list(shape)}, got {getattr(t, 'dtype', type(t).__name__)} {list(getattr(t, 'shape', ()))}")
+    if device and (not t.is_cuda or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous device tensor: the codebook kernels have no CPU path")
+    return t
+
+
+def _codebook_shape(k, dim) -> None:
+    if not 1 <= k <= _lib.CODEBOOK_MAX_K:
+        raise ValueError(f"K={k} codes; 1 to {_lib.CODEBOOK_MAX_K} are taken")
+    if not 4 <= dim <= _lib.CODEBOOK_MAX_DIM or dim % 4:
+        raise ValueError(f"D={dim}; a multiple of 4 from 4 to {_lib.CODEBOOK_MAX_DIM} is taken")
+
+
+def code_stats(z: torch.Tensor, idx: torch.Tensor, num_codes: int) -> CodeStats:
+    """Per-code member count and float64 member sum of the latent rows ``z`` [rows, D] (float32) under the assignment ``idx`` [rows]
+    (int32, what ``vq_assign`` returns): ``CodeStats(counts, sums, invalid)``.  A code's sum adds its member rows in ascending row
+    order, one at a time, with no atomic, so it depends on ``z`` and ``idx`` alone and runs repeat bitwise (``index_add_`` does not
+    promise that).  An index outside [0, num_codes) counts in ``invalid`` and nowhere else.  Nothing is read back."""
+    if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.dtype != torch.float32:
+        raise ValueError(f"z must be a float32 tensor [rows, D], got {getattr(z, 'dtype', type(z).__name__)} {list(getattr(z, 'shape', ()))}")
+    rows, dim = z.shape
+    _codebook_shape(int(num_codes), dim)
+    if not 1 <= rows <= _lib.CODEBOOK_MAX_ROWS:
+        raise ValueError(f"z has {rows} rows; 1 to {_lib.CODEBOOK_MAX_ROWS} are taken")
+    _dev_tensor(z, "z", torch.float32, (rows, dim))
+    _dev_tensor(idx, "idx", torch.int32, (rows,))
+    d = _lib.CodebookDesc()
+    counts = torch.empty(num_codes, dtype=torch.int32, device=z.device)
+    sums = torch.empty(num_codes, dim, dtype=torch.float64, device=z.device)
+    invalid = torch.empty(1, dtype=torch.int32, device=z.device)
+    d.z, d.idx, d.rows, d.dim, d.k = z.data_ptr(), idx.data_ptr(), rows, dim, int(num_codes)
+    d.counts, d.sums, d.invalid = counts.data_ptr(), sums.data_ptr(), invalid.data_ptr()
+    check(lib().dm3d_code_stats(C.byref(d), _st()), "code_stats")
+    return CodeStats(counts, sums, invalid)
+
+
+def code_usage(counts: torch.Tensor, rows: int, eps: float = 1e-10, used_accum: Optional[torch.Tensor] = None) -> CodeUsage:
+    """Perplexity ``exp(-sum p log(p + eps))``, ``p = counts / rows``, summed in float64 over ascending code, and the number of codes
+    with a member: ``CodeUsage(perplexity, active)``.  ``used_accum`` (int32 [K]), when given, is incremented by ``counts`` in place
+    (NSVQ's ``codebooks_used``).  log and exp are the library's own stated operations, so the value repeats bitwise.  Nothing is read back."""
+    if not isinstance(counts, torch.Tensor) or counts.dim() != 1:
+        raise ValueError("counts must be an int32 tensor [K]")
+    k = counts.shape[0]
+    _codebook_shape(k, 4)
+    if int(rows) != rows or not 1 <= rows <= _lib.CODEBOOK_MAX_ROWS:
+        raise ValueError(f"rows must be an integer from 1 to {_lib.CODEBOOK_MAX_ROWS}, got {rows!r}")
+    if not eps >= 0:
+        raise ValueError(f"eps must be at least 0, got {eps!r}")
+    _dev_tensor(counts, "counts", torch.int32, (k,))
+    if used_accum is not None:
+        _dev_tensor(used_accum, "used_accum", torch.int32, (k,))
+    out = torch.empty(1, dtype=torch.float64, device=counts.device)
+    active = torch.empty(1, dtype=torch.int32, device=counts.device)
+    d = _lib.CodebookDesc()
+    d.counts, d.rows, d.k, d.eps = counts.data_ptr(), int(rows), k, float(eps)
+    d.perplexity, d.active, d.used_accum = out.data_ptr(), active.data_ptr(), _p(used_accum)
+    check(lib().dm3d_code_usage(C.byref(d), _st()), "code_usage")
+    return CodeUsage(out[0], active[0])
+
+
+def _codebook_state(d, codebook, esq, cluster_size, ema_w, optional=False):
+    if not isinstance(codebook, torch.Tensor) or codebook.dim() != 2:
+        raise ValueError("codebook must be a float32 tensor [K, D] (rows are codes, the layout vq_assign reads)")
+    k, dim = codebook.shape
+    _codebook_shape(k, dim)
+    both = not optional or cluster_size is not None or ema_w is not None
+    if both and (cluster_size is None or ema_w is None):
+        raise ValueError("cluster_size and ema_w are given together or not at all")
+    for device in (False, True):                                       # every shape before the first device check
+        _dev_tensor(codebook, "codebook", torch.float32, (k, dim), device)
+        _dev_tensor(esq, "esq", torch.float32, (k,), device)
+        if both:
+            _dev_tensor(cluster_size, "cluster_size", torch.float32, (k,), device)
+            _dev_tensor(ema_w, "ema_w", torch.float32, (k, dim), device)
+    d.k, d.dim, d.codebook, d.esq, d.cluster_size, d.ema_w = k, dim, codebook.data_ptr(), esq.data_ptr(), _p(cluster_size), _p(ema_w)
+    return k, dim
+
+
+def codebook_ema(codebook: torch.Tensor, esq: torch.Tensor, cluster_size: torch.Tensor, ema_w: torch.Tensor, counts: torch.Tensor,
+                 sums: torch.Tensor, decay: float = 0.99, epsilon: float = 1e-5) -> None:
+    """The reference's VectorQuantizerEMA update (emavqvae.py:213-222) in one launch, in place on ``cluster_size`` [K], ``ema_w`` [K, D],
+    ``codebook`` [K, D] and ``esq`` [K] (float32), from ``code_stats``' ``counts`` and ``sums``: N' = N decay + (1 - decay) count,
+    W' = W decay + (1 - decay) sum, codebook = W' / N' * n / (n + epsilon) with n = sum N'.  A code whose N' is exactly 0 keeps its row
+    and its esq (the literal rule divides by zero there).  Nothing is read back."""
+    d = _lib.CodebookDesc()
+    k, dim = _codebook_state(d, codebook, esq, cluster_size, ema_w)
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f"decay must lie in [0, 1], got {decay!r}")
+    if not epsilon >= 0:
+        raise ValueError(f"epsilon must be at least 0, got {epsilon!r}")
+    _dev_tensor(counts, "counts", torch.int32, (k,))
+    _dev_tensor(sums, "sums", torch.float64, (k, dim))
+    d.counts, d.sums, d.decay, d.epsilon = counts.data_ptr(), sums.data_ptr(), float(decay), float(epsilon)
+    check(lib().dm3d_codebook_ema(C.byref(d), _st()), "codebook_ema")
+
+
+def codebook_replace(codebook: torch.Tensor, esq: torch.Tensor, used: torch.Tensor, num_batches: int, threshold: float = 0.01, *,
+                     seed: int = 0, draw: int = 0, noise_scale: float = 1e-12, cluster_size: Optional[torch.Tensor] = None,
+                     ema_w: Optional[torch.Tensor] = None) -> Replaced:
+    """NSVQ.replace_unused_codebooks (nsvqvae.py:193-230) with no host read, in place: a code is unused where
+    ``used / num_batches < threshold``; the j-th unused code takes the row of the j-th used code (of the j-th entry of the tiled and
+    shuffled used list where fewer codes are used than unused) plus ``noise_scale`` * N(0,1); with no used code every row gets the
+    noise alone.  ``esq`` of the rewritten rows is recomputed, ``used`` is zeroed, and ``cluster_size`` / ``ema_w``, when given, copy
+    the source's entries.  Shuffle and noise are Philox draws keyed by ``seed`` and ``draw`` (count the replacements in ``draw``), so a
+    call repeats bitwise.  Returns ``Replaced(used_count, unused_count)`` on the device."""
+    d = _lib.CodebookDesc()
+    k, dim = _codebook_state(d, codebook, esq, cluster_size, ema_w, optional=True)
+    _dev_tensor(used, "used", torch.int32, (k,))
+    if int(num_batches) != num_batches or num_batches < 1:
+        raise ValueError(f"num_batches must be an integer of at least 1, got {num_batches!r}")
+    if not math.isfinite(noise_scale) or math.isnan(threshold):
+        raise ValueError("noise_scale must be finite and threshold a number")
+    out = torch.empty(2, dtype=torch.int32, device=codebook.device)
+    work = torch.empty(k, dtype=torch.int32, device=codebook.device)
+    d.used, d.num_batches, d.threshold, d.noise_scale = used.data_ptr(), int(num_batches), float(threshold), float(noise_scale)
+    d.seed, d.draw = int(seed) & (2 ** 64 - 1), int(draw) & 0x7FFFFFFF
+    d.used_count, d.unused_count, d.map = out.data_ptr(), out.data_ptr() + 4, work.data_ptr()
+    check(lib().dm3d_codebook_replace(C.byref(d), _st()), "codebook_replace")
+    del work                                                                    # alive until the launches are enqueued (same stream)
+    return Replaced(out[0], out[1])

@@ -1314,6 +1314,103 @@ int dm3d_grad_scale(const dm3d_gradscale_desc* d, void* stream);
 int dm3d_adam_scaled(float* w, const float* g, float* m, float* v, float* ema /* NULL: none */, int64_t n, float lr_t, float beta1,
                      float beta2, float eps, float ema_rate, const float* state, void* stream);
 
+/* ---- Fitting the VQ codebook on the device: per-code statistics, usage, the exponential-moving-average update of the reference's
+ * VectorQuantizerEMA (networks/emavqvae.py:213-222) and the dead-code replacement of NSVQ.replace_unused_codebooks
+ * (networks/nsvqvae.py:193-230).  The codebook is [k, dim] float32, rows = codes: the layout dm3d_vq_assign and dm3d_gather_rows read.
+ * No entry reads anything back, no kernel uses a floating-point atomic, no workgroup waits for another one, and every sum runs in the
+ * one order stated here (the library builds with -ffp-contract=off): runs repeat bitwise and a restatement with the same operations
+ * in the same order agrees bit for bit.
+ *
+ * dm3d_code_stats       z [rows, dim] float32, idx [rows] int32 ->
+ *     counts[c]  = the number of rows r with idx[r] == c                                                            int32
+ *     sums[c][f] = (double)z[r0][f] + (double)z[r1][f] + ..  over the rows r0 < r1 < .. with idx[r] == c, one add at a time,
+ *                  starting from 0.0; a code without a member gets 0 and 0.0                                        float64
+ *     invalid[0] = the number of rows with idx[r] outside [0, k); such a row counts nowhere and adds nowhere          int32
+ *     A wave owns one code and DM3D_CODEBOOK_SLICE neighbouring features: it streams idx 64 rows at a time, ballots the members,
+ *     queues their row numbers in ascending order, loads up to DM3D_CODEBOOK_BATCH queued rows at once and adds them in queue
+ *     order, so a code that owns every row pays one load latency per batch, not per row.  No atomic of any kind.
+ * dm3d_code_usage       counts [k], rows ->
+ *     perplexity[0] = dexp(-(t[0] + t[1] + .. + t[k-1])),  t[c] = p * dlog(p + eps),  p = (double)counts[c] / (double)rows  float64
+ *     active[0]     = the number of codes with counts[c] > 0                                                        int32
+ *     used_accum[c] += counts[c] when used_accum is non-NULL (NSVQ's codebooks_used.assign_add, :186)               int32
+ *     The sum runs over ascending c from 0.0.  dlog and dexp are the library's own, built from +, -, *, / alone so that their bits
+ *     are stated, not a math library's:
+ *         dlog(x), x > 0:  x = m * 2^e with m in [0.5, 1) (frexp); if m < 0.70710678118654757 then m = m * 2, e = e - 1;
+ *             s = (m - 1) / (m + 1);  w = s * s;  P = 1/25;  for j = 23, 21, .., 3: P = P * w + 1/j;  P = P * w + 1;
+ *             dlog = e * 0.69314718055994529 + (2 * s) * P       (1/j is the double nearest to it: the constant 1.0 / j)
+ *         dexp(y):  n = rint(y * 1.4426950408889634);  r = (y - n * 0.693147180369123816490) - n * 1.90821492927058770002e-10;
+ *             Q = 1/14!;  for j = 13, 12, .., 1: Q = Q * r + 1/j!;  Q = Q * r + 1;  dexp = ldexp(Q, n)   (1/j! = 1.0 / (double)j!)
+ *     Both agree with a correctly rounded log and exp within 1e-15 relative on what this entry feeds them (tests/test_codebook_host.py).
+ * dm3d_codebook_ema     counts [k], sums [k, dim] -> cluster_size [k], ema_w [k, dim], codebook [k, dim], esq [k], all in place, float32:
+ *     om = 1.0f - decay;  N'[c] = N[c] * decay + om * (float)counts[c];  W'[c][f] = W[c][f] * decay + om * (float)sums[c][f]
+ *     (every multiply and add rounded on its own, the float64 sum rounded to float32 once);
+ *     n = N'[0] + N'[1] + .. in float64 over ascending c from 0.0;  g = (float)(n / (n + (double)epsilon));
+ *     codebook[c][f] = (W'[c][f] / N'[c]) * g;  esq[c] = codebook[c][0]^2 + codebook[c][1]^2 + ..  in float32, sequential in f from
+ *     0.0f, multiply and add rounded separately (numpy's (emb ** 2).sum(axis=0, dtype=float32) on [dim, k]).
+ *     One departure from the reference: a code whose N' is exactly 0 (it has never had a member) keeps its codebook row and its esq;
+ *     the literal rule divides by zero there.  One launch of one workgroup, since n needs every N' before any row is written.
+ * dm3d_codebook_replace  used [k] int32 (NSVQ's codebooks_used), num_batches, threshold -> codebook, esq (and cluster_size, ema_w when
+ *     given) in place, used zeroed, used_count[0] and unused_count[0] int32:
+ *     code c is unused where (double)used[c] / (double)num_batches < threshold.  U = the used codes, V = the unused codes, both ascending.
+ *       |U| == 0:          every row c becomes codebook[c] + noise; cluster_size and ema_w stay.
+ *       |U| >= |V|:        V[j] takes the row of U[j].
+ *       0 < |U| < |V|:     the list L[i] = U[i % |U|], i < |U| * (|V| / |U| + 1) (integer division; at most k entries), is sorted
+ *                          ascending by (key[i], i), key[i] = word 0 of Philox4x32-10 on the counter (i, 0, draw,
+ *                          DM3D_STREAM_CODEBOOK_SHUFFLE) under the key seed; V[j] takes the row of the j-th entry.
+ *     A row c that takes the row of source s becomes codebook[s][f] + noise_scale * z[c][f] (float32, multiply and add rounded
+ *     separately), z the N(0,1) stream of "What seeded means": float4 c * (dim / 4) + f / 4 has the counter (that index, draw,
+ *     DM3D_STREAM_CODEBOOK) under the key seed; it also copies cluster_size[s] and ema_w[s] when those are given, so that an EMA step
+ *     afterwards does not pull it straight back.  esq of every rewritten row is recomputed by dm3d_codebook_ema's rule.  Sources are
+ *     used codes and are never written, so every source row is read as it was.  Two launches on the stream: one workgroup builds
+ *     map[c] (the source of c, c itself where only noise is added, -1 where the row stays), then a workgroup per code applies it.
+ *
+ * Checked before any launch (DM3D_EINVAL; the message starts "code_stats:", "code_usage:", "codebook_ema:" or "codebook_replace:"):
+ * the descriptor and every pointer the entry uses non-NULL (used_accum, and cluster_size with ema_w for codebook_replace, are
+ * optional); float64 pointers 8-byte, all others 4-byte aligned, codebook and ema_w 16-byte; 1 <= k <= DM3D_CODEBOOK_MAX_K;
+ * 4 <= dim <= DM3D_CODEBOOK_MAX_DIM and dim % 4 == 0; 1 <= rows <= DM3D_CODEBOOK_MAX_ROWS, each limit named when exceeded; eps >= 0;
+ * 0 <= decay <= 1, epsilon >= 0; num_batches >= 1, noise_scale finite; no buffer an entry writes shares a byte with another buffer
+ * it uses. */
+#define DM3D_CODEBOOK_MAX_K 4096
+#define DM3D_CODEBOOK_MAX_DIM 1024
+#define DM3D_CODEBOOK_MAX_ROWS 1073741824
+#define DM3D_CODEBOOK_SLICE 64
+#define DM3D_CODEBOOK_BATCH 16
+#define DM3D_STREAM_CODEBOOK 0xC0DE
+#define DM3D_STREAM_CODEBOOK_SHUFFLE 0xC0D5
+typedef struct dm3d_codebook_desc {
+    const float* z;             /* [rows, dim]           code_stats: in */
+    const int32_t* idx;         /* [rows]                code_stats: in */
+    int32_t rows;               /* code_stats, code_usage */
+    int32_t dim;
+    int32_t k;
+    int32_t* counts;            /* [k]                   code_stats: out; code_usage, codebook_ema: in */
+    double* sums;               /* [k, dim]              code_stats: out; codebook_ema: in */
+    int32_t* invalid;           /* [1]                   code_stats: out */
+    double eps;                 /* code_usage */
+    double* perplexity;         /* [1]                   code_usage: out */
+    int32_t* active;            /* [1]                   code_usage: out */
+    int32_t* used_accum;        /* [k]                   code_usage: in place, optional */
+    float* cluster_size;        /* [k]                   codebook_ema: in place; codebook_replace: in place, optional */
+    float* ema_w;               /* [k, dim]              codebook_ema: in place; codebook_replace: in place, optional */
+    float* codebook;            /* [k, dim]              codebook_ema, codebook_replace: in place */
+    float* esq;                 /* [k]                   codebook_ema, codebook_replace: in place */
+    float decay;                /* codebook_ema */
+    float epsilon;              /* codebook_ema */
+    int32_t* used;              /* [k]                   codebook_replace: in, zeroed */
+    int32_t num_batches;        /* codebook_replace */
+    int32_t draw;               /* codebook_replace: word of both Philox counters; a caller counts its replacements here */
+    double threshold;           /* codebook_replace */
+    float noise_scale;          /* codebook_replace */
+    uint64_t seed;              /* codebook_replace */
+    int32_t* used_count;        /* [1]                   codebook_replace: out */
+    int32_t* unused_count;      /* [1]                   codebook_replace: out */
+    int32_t* map;               /* [k]                   codebook_replace: device scratch */
+} dm3d_codebook_desc;
+int dm3d_code_stats(const dm3d_codebook_desc* d, void* stream);
+int dm3d_code_usage(const dm3d_codebook_desc* d, void* stream);
+int dm3d_codebook_ema(const dm3d_codebook_desc* d, void* stream);
+int dm3d_codebook_replace(const dm3d_codebook_desc* d, void* stream);
+
 /* ---- HIP graph capture of one denoising step (replaces the eager per-op Python loop of generate, :559-573) -- */
 int dm3d_graph_begin(void* stream);
 int dm3d_graph_end(void* stream, void** graph_exec_out);
