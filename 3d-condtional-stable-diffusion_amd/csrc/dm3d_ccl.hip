@@ -6,7 +6,8 @@
 // brick faces with device-scope atomic min, and every later pass is a plain stream.  No workgroup waits for another one; every loop walks
 // strictly falling indices or has a fixed trip count.  The root of a finished component is its smallest raster index, whatever order
 // the unions arrived in, and sizes are integer sums, so the results are canonical: runs repeat bitwise.  Plain HIP, integer atomics only.
-#include "dm3d_common.h"
+// The window and volume checks are dm3d_volume.h's.
+#include "dm3d_volume.h"
 #include <math.h>
 
 namespace {
@@ -357,19 +358,13 @@ int64_t small_words(int64_t bc, int64_t nblk) { return bc * (3 * nblk + 2); }
 int check_common(const dm3d_ccl_desc* d, const char* who) {
     DM3D_REQUIRE(d != nullptr, "%s: null descriptor", who);
     DM3D_REQUIRE(d->x != nullptr, "%s: x must be non-null", who);
-    DM3D_REQUIRE((reinterpret_cast<uintptr_t>(d->x) & 3u) == 0, "%s: x must be 4-byte aligned", who);
-    DM3D_REQUIRE(d->batch >= 1, "%s: batch=%d (at least 1)", who, d->batch);
-    DM3D_REQUIRE(d->d >= 1 && d->h >= 1 && d->w >= 1, "%s: d=%d h=%d w=%d (all at least 1)", who, d->d, d->h, d->w);
-    DM3D_REQUIRE(d->d <= DM3D_CCL_MAX_EXTENT && d->h <= DM3D_CCL_MAX_EXTENT && d->w <= DM3D_CCL_MAX_EXTENT,
-                 "%s: d=%d h=%d w=%d exceeds DM3D_CCL_MAX_EXTENT=%d per axis", who, d->d, d->h, d->w, DM3D_CCL_MAX_EXTENT);
-    DM3D_REQUIRE(d->nc >= 1, "%s: nc=%d (at least 1)", who, d->nc);
-    DM3D_REQUIRE((int64_t)d->batch * d->nc <= 65535, "%s: batch * nc = %lld (at most 65535)", who, (long long)d->batch * d->nc);
-    DM3D_REQUIRE(d->x0c >= 0 && d->cx >= 1 && (int64_t)d->x0c + d->nc <= d->cx, "%s: channels [%d, %d + %d) are outside x's cx=%d", who, d->x0c,
-                 d->x0c, d->nc, d->cx);
+    DM3D_REQUIRE(dm3d_aligned(d->x, 4), "%s: x must be 4-byte aligned", who);
+    int rc = dm3d_check_volume(who, d->batch, d->d, d->h, d->w, d->nc, DM3D_CCL_MAX_EXTENT, "DM3D_CCL_MAX_EXTENT");
+    if (rc != DM3D_OK || (rc = dm3d_check_window(who, "x", d->x0c, d->nc, d->cx)) != DM3D_OK) return rc;
     DM3D_REQUIRE(isfinite(d->threshold), "%s: threshold=%g (finite)", who, (double)d->threshold);
     DM3D_REQUIRE(d->connectivity == 6 || d->connectivity == 18 || d->connectivity == 26, "%s: connectivity=%d (6, 18 or 26)", who, d->connectivity);
     DM3D_REQUIRE(d->work != nullptr, "%s: work must be non-null", who);
-    DM3D_REQUIRE((reinterpret_cast<uintptr_t>(d->work) & 7u) == 0, "%s: work must be 8-byte aligned", who);
+    DM3D_REQUIRE(dm3d_aligned(d->work, 8), "%s: work must be 8-byte aligned", who);
     return DM3D_OK;
 }
 
@@ -428,9 +423,9 @@ extern "C" int dm3d_components(const dm3d_ccl_desc* d, void* stream) {
     int rc = check_common(d, "components");
     if (rc != DM3D_OK) return rc;
     DM3D_REQUIRE(d->labels != nullptr && d->count != nullptr && d->largest != nullptr, "components: labels, count and largest must be non-null");
-    DM3D_REQUIRE((reinterpret_cast<uintptr_t>(d->labels) & 3u) == 0 && (reinterpret_cast<uintptr_t>(d->count) & 3u) == 0,
+    DM3D_REQUIRE(dm3d_aligned(d->labels, 4) && dm3d_aligned(d->count, 4),
                  "components: labels and count must be 4-byte aligned");
-    DM3D_REQUIRE((reinterpret_cast<uintptr_t>(d->largest) & 7u) == 0, "components: largest must be 8-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->largest, 8), "components: largest must be 8-byte aligned");
     Plan pl{};
     if ((rc = make_plan(d, "components", 2, d->labels, &pl)) != DM3D_OK) return rc;
     DM3D_REQUIRE(!dm3d_ranges_overlap(d->labels, (uint64_t)pl.V * 4, d->x, (uint64_t)d->batch * pl.vol * d->cx * 4), "components: labels overlaps x");
@@ -450,7 +445,7 @@ extern "C" int dm3d_component_filter(const dm3d_ccl_desc* d, void* stream) {
                  "component_filter: mode=%d (DM3D_CCL_LARGEST, DM3D_CCL_MIN_SIZE or DM3D_CCL_FILL_HOLES)", d->mode);
     DM3D_REQUIRE(d->mode != DM3D_CCL_MIN_SIZE || d->min_size >= 1, "component_filter: min_size=%d (at least 1)", d->min_size);
     DM3D_REQUIRE(d->out != nullptr, "component_filter: out must be non-null");
-    DM3D_REQUIRE((reinterpret_cast<uintptr_t>(d->out) & 3u) == 0, "component_filter: out must be 4-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->out, 4), "component_filter: out must be 4-byte aligned");
     Plan pl{};
     if ((rc = make_plan(d, "component_filter", 3, nullptr, &pl)) != DM3D_OK) return rc;
     DM3D_REQUIRE(!dm3d_ranges_overlap(d->out, (uint64_t)pl.V * 4, d->x, (uint64_t)d->batch * pl.vol * d->cx * 4), "component_filter: out overlaps x");

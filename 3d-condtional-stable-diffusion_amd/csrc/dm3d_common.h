@@ -28,7 +28,8 @@ static inline int dm3d_launch_check(const char* what) {
     if (e != hipSuccess) return dm3d_fail(DM3D_EHIP, "launch of %s failed: %s", what, hipGetErrorString(e));
     return DM3D_OK;
 }
-static inline bool dm3d_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool dm3d_aligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }   // bytes: a power of two
+static inline bool dm3d_aligned16(const void* p) { return dm3d_aligned(p, 16); }
 // Whether the byte ranges [p, p + p_bytes) and [q, q + q_bytes) share a byte (a null pointer is no range).
 static inline bool dm3d_ranges_overlap(const void* p, uint64_t p_bytes, const void* q, uint64_t q_bytes) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);

@@ -3,15 +3,15 @@
 // read in place through their channel windows; every quantity up to the last kernel is an integer (counts by integer atomics, squared
 // distances by min-plus over int32, a histogram of them by integer atomics), so no result depends on the order blocks run in, and the
 // last kernel forms its float64 values from the histogram in a fixed order: runs repeat bitwise.  Plain HIP: no MFMA, no float atomics.
-#include "dm3d_common.h"
+// The window and volume checks and the tiling of the three transform passes are dm3d_volume.h's.
+#include "dm3d_volume.h"
 #include <limits.h>
 #include <math.h>
 
 namespace {
 
 constexpr int MAXE = DM3D_EDT_MAX_EXTENT;          // longest column staged in LDS
-constexpr int LANES = DM3D_EDT_LANES;              // columns a block stages side by side
-constexpr int LDT = LANES + 1;                     // LDS row of one column position: the pad keeps the transposed W-pass stores off one bank
+constexpr int LANES = DM3D_LINE_LANES, LDT = DM3D_LINE_LDT;   // columns a block stages side by side; LDS row of one column position
 constexpr int BIG = 0x3fffffff;                    // "no feature yet": BIG + 511^2 stays below INT32_MAX
 constexpr int VOX = 1024;                          // voxels a block of the streaming kernels walks (4 per lane)
 
@@ -77,35 +77,25 @@ __global__ __launch_bounds__(256) void mask_feature_kernel(const FeatArgs p) {
 struct PassArgs {
     const uint8_t* feat;                           // first pass: the features (a column position holds 0 where feat, BIG elsewhere)
     int* map;                                      // in place (first pass: out only)
-    long gs, ls, cs;                               // strides of a group of columns, of neighbouring columns, along a column
-    long lanes;                                    // columns of a group
-    int tiles;                                     // blocks of a group: ceil(lanes / LANES)
-    int n;                                         // column length, 1 .. MAXE
+    dm3d_line_pass line;                           // a line is a column here, of length 1 .. MAXE
     int first, last;                               // last: values of BIG and above leave as INT32_MAX
 };
 
-// out[i] = min_j (i - j)^2 + g[j] for LANES neighbouring columns of one group, in place.  The columns are staged in LDS as [n][LDT]; a
-// 32-lane half of a wave owns the 32 columns at one j, so its LDS reads are 32 consecutive banks, and each lane carries 4 outputs of
-// its column per read.  The results go through a second LDS image so that the stores run in the order of the loads: ALONG (the W pass,
-// a column is contiguous in memory) walks a column with consecutive lanes, the H and D passes walk the LANES neighbours.
+// out[i] = min_j (i - j)^2 + g[j] for LANES neighbouring columns of one group, in place.  The columns are staged in LDS as [n][LDT]
+// (dm3d_line_walk); a 32-lane half of a wave owns the 32 columns at one j, so its LDS reads are 32 consecutive banks, and each lane
+// carries 4 outputs of its column per read.  The results go through a second LDS image so that the stores run in the order of the loads.
 template <bool ALONG>
 __global__ __launch_bounds__(256) void edt_pass_kernel(const PassArgs p) {
     extern __shared__ int lds[];
-    const int n = p.n;
+    const int n = p.line.n;
     int* col = lds;
     int* res = lds + n * LDT;
-    const long group = blockIdx.x / p.tiles, lane0 = (long)(blockIdx.x % p.tiles) * LANES;
-    const int nl = p.lanes - lane0 < LANES ? (int)(p.lanes - lane0) : LANES;
-    const long base = group * p.gs + lane0 * p.ls;
-    for (int i = threadIdx.x; i < n * LANES; i += 256) {
-        const int j = ALONG ? i % n : i / LANES, l = ALONG ? i / n : i % LANES;
+    const dm3d_line_block blk = dm3d_line_block_of(p.line);
+    dm3d_line_walk<ALONG>(p.line, blk, [&](int at, long off, bool live) {
         int v = BIG;
-        if (l < nl) {
-            const long off = base + l * p.ls + j * p.cs;
-            v = p.first ? (p.feat[off] ? 0 : BIG) : p.map[off];
-        }
-        col[j * LDT + l] = v;
-    }
+        if (live) v = p.first ? (p.feat[off] ? 0 : BIG) : p.map[off];
+        col[at] = v;
+    });
     __syncthreads();
     const int xl = threadIdx.x & (LANES - 1), rg = threadIdx.x / LANES;
     for (int i0 = rg * 4; i0 < n; i0 += 4 * (256 / LANES)) {
@@ -124,10 +114,9 @@ __global__ __launch_bounds__(256) void edt_pass_kernel(const PassArgs p) {
             if (i0 + r < n) res[(i0 + r) * LDT + xl] = o[r] >= BIG ? (p.last ? INT_MAX : BIG) : o[r];
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < n * LANES; i += 256) {
-        const int j = ALONG ? i % n : i / LANES, l = ALONG ? i / n : i % LANES;
-        if (l < nl) p.map[base + l * p.ls + j * p.cs] = res[j * LDT + l];
-    }
+    dm3d_line_walk<ALONG>(p.line, blk, [&](int at, long off, bool live) {
+        if (live) p.map[off] = res[at];
+    });
 }
 
 // Grid (ceil(dhw / VOX), batch * nc): hist[bc][dir][k] += 1 for every voxel of `surf` whose squared distance is k; a distance of `bins`
@@ -251,16 +240,9 @@ int check_common(const dm3d_mask_desc* d, const char* who, bool pair) {
     DM3D_REQUIRE(d != nullptr, "%s: null descriptor", who);
     DM3D_REQUIRE(d->x != nullptr, "%s: x must be non-null", who);
     DM3D_REQUIRE(!pair || d->y != nullptr, "%s: y must be non-null", who);
-    DM3D_REQUIRE(d->batch >= 1, "%s: batch=%d (at least 1)", who, d->batch);
-    DM3D_REQUIRE(d->d >= 1 && d->h >= 1 && d->w >= 1, "%s: d=%d h=%d w=%d (all at least 1)", who, d->d, d->h, d->w);
-    DM3D_REQUIRE(d->d <= MAXE && d->h <= MAXE && d->w <= MAXE, "%s: d=%d h=%d w=%d exceeds DM3D_EDT_MAX_EXTENT=%d per axis", who, d->d, d->h, d->w,
-                 MAXE);
-    DM3D_REQUIRE(d->nc >= 1, "%s: nc=%d (at least 1)", who, d->nc);
-    DM3D_REQUIRE((int64_t)d->batch * d->nc <= 65535, "%s: batch * nc = %lld (at most 65535)", who, (long long)d->batch * d->nc);
-    DM3D_REQUIRE(d->x0c >= 0 && d->cx >= 1 && (int64_t)d->x0c + d->nc <= d->cx, "%s: channels [%d, %d + %d) are outside x's cx=%d", who, d->x0c,
-                 d->x0c, d->nc, d->cx);
-    DM3D_REQUIRE(!pair || (d->y0c >= 0 && d->cy >= 1 && (int64_t)d->y0c + d->nc <= d->cy), "%s: channels [%d, %d + %d) are outside y's cy=%d", who,
-                 d->y0c, d->y0c, d->nc, d->cy);
+    int rc = dm3d_check_volume(who, d->batch, d->d, d->h, d->w, d->nc, MAXE, "DM3D_EDT_MAX_EXTENT");
+    if (rc != DM3D_OK || (rc = dm3d_check_window(who, "x", d->x0c, d->nc, d->cx)) != DM3D_OK) return rc;
+    if (pair && (rc = dm3d_check_window(who, "y", d->y0c, d->nc, d->cy)) != DM3D_OK) return rc;
     DM3D_REQUIRE(isfinite(d->threshold), "%s: threshold=%g (finite)", who, (double)d->threshold);
     return DM3D_OK;
 }
@@ -293,29 +275,24 @@ int launch_edt(const dm3d_mask_desc* d, const uint8_t* feat, int* map, hipStream
     const size_t lds_max = (size_t)2 * MAXE * LDT * sizeof(int);
     const int dev = dm3d_dyn_lds(lds_max, lds_set, "edt", edt_pass_kernel<true>, edt_pass_kernel<false>);
     if (dev < 0) return dev;
-    const int64_t bc = (int64_t)d->batch * d->nc, D = d->d, H = d->h, W = d->w;
+    static const char* const names[3] = {"edt_pass_kernel (w)", "edt_pass_kernel (h)", "edt_pass_kernel (d)"};
     PassArgs a{};
     a.feat = feat; a.map = map;
-    int rc;
-    // w: every row of the tensor is a column; 32 neighbouring rows a block
-    a.gs = 0; a.ls = W; a.cs = 1; a.lanes = bc * D * H; a.tiles = (int)((a.lanes + LANES - 1) / LANES); a.n = (int)W; a.first = 1; a.last = 0;
-    hipLaunchKernelGGL(edt_pass_kernel<true>, dim3((unsigned)a.tiles), dim3(256), (size_t)2 * a.n * LDT * sizeof(int), st, a);
-    if ((rc = dm3d_launch_check("edt_pass_kernel (w)")) != DM3D_OK) return rc;
-    // h: a group is one plane, its columns the w positions
-    a.gs = H * W; a.ls = 1; a.cs = W; a.lanes = W; a.tiles = (int)((W + LANES - 1) / LANES); a.n = (int)H; a.first = 0;
-    hipLaunchKernelGGL(edt_pass_kernel<false>, dim3((unsigned)(bc * D * a.tiles)), dim3(256), (size_t)2 * a.n * LDT * sizeof(int), st, a);
-    if ((rc = dm3d_launch_check("edt_pass_kernel (h)")) != DM3D_OK) return rc;
-    // d: a group is one volume of one channel, its columns the h * w positions of a plane
-    a.gs = D * H * W; a.ls = 1; a.cs = H * W; a.lanes = H * W; a.tiles = (int)((H * W + LANES - 1) / LANES); a.n = (int)D; a.last = 1;
-    hipLaunchKernelGGL(edt_pass_kernel<false>, dim3((unsigned)(bc * a.tiles)), dim3(256), (size_t)2 * a.n * LDT * sizeof(int), st, a);
-    return dm3d_launch_check("edt_pass_kernel (d)");
+    for (int axis = 0; axis < 3; ++axis) {
+        const int64_t blocks = dm3d_line_pass_fill(&a.line, axis, (int64_t)d->batch * d->nc, d->d, d->h, d->w);
+        a.first = axis == 0; a.last = axis == 2;
+        hipLaunchKernelGGL(axis == 0 ? edt_pass_kernel<true> : edt_pass_kernel<false>, dim3((unsigned)blocks), dim3(256),
+                           (size_t)2 * a.line.n * LDT * sizeof(int), st, a);
+        const int rc = dm3d_launch_check(names[axis]);
+        if (rc != DM3D_OK) return rc;
+    }
+    return DM3D_OK;
 }
 
-int check_edt_grid(const dm3d_mask_desc* d, const char* who) {
-    const int64_t bc = (int64_t)d->batch * d->nc, D = d->d, H = d->h, W = d->w;
-    const int64_t blocks[3] = {(bc * D * H + LANES - 1) / LANES, bc * D * ((W + LANES - 1) / LANES), bc * ((H * W + LANES - 1) / LANES)};
-    for (int k = 0; k < 3; ++k)                                                  // cannot fail under the limits above; kept beside the launches
-        DM3D_REQUIRE(blocks[k] <= 0x7fffffffLL, "%s: %lld blocks of the %s pass exceed the grid", who, (long long)blocks[k], k == 0 ? "w" : k == 1 ? "h" : "d");
+int check_edt_grid(const dm3d_mask_desc* d, const char* who) {                  // cannot fail under the limits above; kept beside the launches
+    int64_t blocks = 0;
+    const int axis = dm3d_line_grid_fault((int64_t)d->batch * d->nc, d->d, d->h, d->w, &blocks);
+    DM3D_REQUIRE(axis < 0, "%s: %lld blocks of the %s pass exceed the grid", who, (long long)blocks, dm3d_line_axis[axis < 0 ? 0 : axis]);
     return DM3D_OK;
 }
 
@@ -325,7 +302,7 @@ extern "C" int dm3d_mask_overlap(const dm3d_mask_desc* d, void* stream) {
     int rc = check_common(d, "mask_overlap", true);
     if (rc != DM3D_OK) return rc;
     DM3D_REQUIRE(d->counts != nullptr, "mask_overlap: counts must be non-null");
-    DM3D_REQUIRE((reinterpret_cast<uintptr_t>(d->counts) & 7u) == 0, "mask_overlap: counts must be 8-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->counts, 8), "mask_overlap: counts must be 8-byte aligned");
     DM3D_REQUIRE((d->surf_x == nullptr) == (d->surf_y == nullptr), "mask_overlap: surf_x and surf_y must be both given or both null");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = launch_zero(d->counts, 6 * (int64_t)d->batch * d->nc, st)) != DM3D_OK) return rc;
@@ -337,7 +314,7 @@ extern "C" int dm3d_edt(const dm3d_mask_desc* d, void* stream) {
     if (rc != DM3D_OK) return rc;
     DM3D_REQUIRE(d->map != nullptr && d->masks != nullptr, "edt: map and masks must be non-null");
     DM3D_REQUIRE(d->of == DM3D_EDT_SURFACE || d->of == DM3D_EDT_FOREGROUND, "edt: of=%d (DM3D_EDT_SURFACE or DM3D_EDT_FOREGROUND)", d->of);
-    DM3D_REQUIRE((reinterpret_cast<uintptr_t>(d->map) & 3u) == 0, "edt: map must be 4-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->map, 4), "edt: map must be 4-byte aligned");
     const int64_t V = voxels(d);
     DM3D_REQUIRE(d->masks_elems >= V, "edt: masks holds %lld bytes, %lld are needed (batch * nc * d * h * w)", (long long)d->masks_elems, (long long)V);
     if ((rc = check_edt_grid(d, "edt")) != DM3D_OK) return rc;
@@ -351,9 +328,8 @@ extern "C" int dm3d_surface_distance(const dm3d_mask_desc* d, void* stream) {
     if (rc != DM3D_OK) return rc;
     DM3D_REQUIRE(d->out != nullptr && d->masks != nullptr && d->work != nullptr, "surface_distance: out, masks and work must be non-null");
     DM3D_REQUIRE(d->percentile > 0.0 && d->percentile <= 100.0, "surface_distance: percentile=%g (in (0, 100])", d->percentile);
-    DM3D_REQUIRE((reinterpret_cast<uintptr_t>(d->out) & 7u) == 0 && (reinterpret_cast<uintptr_t>(d->counts) & 7u) == 0,
-                 "surface_distance: out and counts must be 8-byte aligned");
-    DM3D_REQUIRE((reinterpret_cast<uintptr_t>(d->work) & 3u) == 0, "surface_distance: work must be 4-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->out, 8) && dm3d_aligned(d->counts, 8), "surface_distance: out and counts must be 8-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->work, 4), "surface_distance: work must be 4-byte aligned");
     const int64_t V = voxels(d), bc = (int64_t)d->batch * d->nc, bins = bins_of(d);
     DM3D_REQUIRE(d->masks_elems >= 2 * V, "surface_distance: masks holds %lld bytes, %lld are needed (2 * batch * nc * d * h * w)",
                  (long long)d->masks_elems, (long long)(2 * V));

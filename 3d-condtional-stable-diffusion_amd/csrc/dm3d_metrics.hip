@@ -3,7 +3,8 @@
 // the 11-tap row pass into LDS, the column pass in registers, the formula, one float64 partial per tile), and tf.image.psnr from the
 // squared error.  Plain HIP: no MFMA, no atomics.  Every sum is float64 in a fixed order: a thread over its elements in index order, the
 // block by dm3d_block_sum_f64, blocks through a partials buffer in block order by a second launch: runs repeat bitwise.
-#include "dm3d_common.h"
+// The channel-window check and the block min / max are dm3d_volume.h's.
+#include "dm3d_volume.h"
 
 namespace {
 
@@ -48,18 +49,12 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(const MetricArgs p) {
             mx = fmaxf(mx, yv);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = fminf(mn, __shfl_xor(mn, off, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) { mm[threadIdx.x >> 6][0] = mn; mm[threadIdx.x >> 6][1] = mx; }
+    dm3d_block_minmax_put(mn, mx, mm);
     dm3d_block_sum_f64(s, red);                                               // its barrier also publishes mm
     if (threadIdx.x == 0) {
         double* dst = p.partials + (slice * gridDim.x + blockIdx.x) * 3;
-        dst[0] = s[0];
-        dst[1] = (double)fminf(fminf(mm[0][0], mm[1][0]), fminf(mm[2][0], mm[3][0]));
-        dst[2] = (double)fmaxf(fmaxf(mm[0][1], mm[1][1]), fmaxf(mm[2][1], mm[3][1]));
+        dm3d_block_minmax_get(mn, mx, mm);
+        dst[0] = s[0]; dst[1] = (double)mn; dst[2] = (double)mx;
     }
 }
 
@@ -80,16 +75,8 @@ __global__ __launch_bounds__(256) void pair_stats_sum_kernel(const MetricArgs p)
         }
         p.sse[slice] = s;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = fminf(mn, __shfl_xor(mn, off, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) { mm[threadIdx.x >> 6][0] = mn; mm[threadIdx.x >> 6][1] = mx; }
-    __syncthreads();
+    dm3d_block_minmax(mn, mx, mm);
     if (threadIdx.x == 0) {
-        mn = fminf(fminf(mm[0][0], mm[1][0]), fminf(mm[2][0], mm[3][0]));
-        mx = fmaxf(fmaxf(mm[0][1], mm[1][1]), fmaxf(mm[2][1], mm[3][1]));
         p.y_min[b] = mn;
         p.y_max[b] = mx;
         if (p.y_range) p.y_range[b] = __fsub_rn(mx, mn);
@@ -200,8 +187,6 @@ __global__ __launch_bounds__(256) void psnr_kernel(const MetricArgs p, long slic
     p.out[slice] = __fsub_rn((float)(20.0 * log10((double)L)), (float)(10.0 * log10((double)mse)));
 }
 
-bool aligned8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7u) == 0; }
-
 // The checks the three entries share; `who` names the entry in the message.
 int check_common(const dm3d_metric_desc* d, const char* who, int min_edge) {
     DM3D_REQUIRE(d != nullptr, "%s: null descriptor", who);
@@ -214,11 +199,8 @@ int check_common(const dm3d_metric_desc* d, const char* who, int min_edge) {
 }
 
 int check_channels(const dm3d_metric_desc* d, const char* who) {
-    DM3D_REQUIRE(d->x0c >= 0 && d->cx >= 1 && (int64_t)d->x0c + d->nc <= d->cx, "%s: channels [%d, %d + %d) are outside x's cx=%d", who, d->x0c,
-                 d->x0c, d->nc, d->cx);
-    DM3D_REQUIRE(d->y0c >= 0 && d->cy >= 1 && (int64_t)d->y0c + d->nc <= d->cy, "%s: channels [%d, %d + %d) are outside y's cy=%d", who, d->y0c,
-                 d->y0c, d->nc, d->cy);
-    return DM3D_OK;
+    const int rc = dm3d_check_window(who, "x", d->x0c, d->nc, d->cx);
+    return rc != DM3D_OK ? rc : dm3d_check_window(who, "y", d->y0c, d->nc, d->cy);
 }
 
 MetricArgs make_args(const dm3d_metric_desc* d) {
@@ -236,7 +218,7 @@ extern "C" int dm3d_pair_stats(const dm3d_metric_desc* d, void* stream) {
     if (rc != DM3D_OK) return rc;
     DM3D_REQUIRE(d->x && d->y && d->partials && d->y_min && d->y_max && d->sse, "pair_stats: x/y/partials/y_min/y_max/sse must be non-null");
     if ((rc = check_channels(d, "pair_stats")) != DM3D_OK) return rc;
-    DM3D_REQUIRE(aligned8(d->partials) && aligned8(d->sse), "pair_stats: partials/sse must be 8-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->partials, 8) && dm3d_aligned(d->sse, 8), "pair_stats: partials/sse must be 8-byte aligned");
     const int64_t npix = (int64_t)d->h * d->w, want = (npix + PAIR_PIXELS - 1) / PAIR_PIXELS;
     const int blocks = (int)(want > PARTS ? PARTS : want);
     const int64_t need = 3 * (int64_t)d->batch * d->d * blocks;
@@ -256,7 +238,7 @@ extern "C" int dm3d_ssim(const dm3d_metric_desc* d, void* stream) {
     if (rc != DM3D_OK) return rc;
     DM3D_REQUIRE(d->x && d->y && d->partials && d->max_val && d->out, "ssim: x/y/partials/max_val/out must be non-null");
     if ((rc = check_channels(d, "ssim")) != DM3D_OK) return rc;
-    DM3D_REQUIRE(aligned8(d->partials), "ssim: partials must be 8-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->partials, 8), "ssim: partials must be 8-byte aligned");
     const int64_t tiles_y = (d->h - (TAPS - 1) + TILE - 1) / TILE, tiles_x = (d->w - (TAPS - 1) + TILE - 1) / TILE;
     const int64_t tiles = tiles_y * tiles_x, need = (int64_t)d->batch * d->d * d->nc * tiles;
     DM3D_REQUIRE(tiles * d->nc <= 0x7fffffffLL, "ssim: %lld tiles x %d channels exceed the grid", (long long)tiles, d->nc);
@@ -277,7 +259,7 @@ extern "C" int dm3d_psnr_finalize(const dm3d_metric_desc* d, void* stream) {
     int rc = check_common(d, "psnr_finalize", 1);
     if (rc != DM3D_OK) return rc;
     DM3D_REQUIRE(d->sse && d->max_val && d->out, "psnr_finalize: sse/max_val/out must be non-null");
-    DM3D_REQUIRE(aligned8(d->sse), "psnr_finalize: sse must be 8-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->sse, 8), "psnr_finalize: sse must be 8-byte aligned");
     MetricArgs a = make_args(d);
     const long slices = (long)d->batch * d->d;
     hipLaunchKernelGGL(psnr_kernel, dim3((unsigned)((slices + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a, slices);

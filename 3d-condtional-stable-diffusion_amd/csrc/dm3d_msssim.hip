@@ -4,7 +4,8 @@
 // and point in registers, so no filtered map ever reaches memory.  A pooling launch per tensor makes the next scale's volumes; a last
 // launch combines tiles, scales, powers and channels.  Plain HIP: no MFMA, no atomics.  Every sum is float64 in a fixed order (a thread
 // over its points in plane order, the block by dm3d_block_sum_f64, tiles in index order): runs repeat bitwise.
-#include "dm3d_common.h"
+// The channel-window check is dm3d_volume.h's.
+#include "dm3d_volume.h"
 #include <math.h>
 
 namespace {
@@ -229,10 +230,8 @@ extern "C" int dm3d_ms_ssim(const dm3d_ms_ssim_desc* d, void* stream) {
     DM3D_REQUIRE(d->y_index || d->pairs <= d->ny, "ms_ssim: pairs=%d exceeds ny=%d and no y_index is given", d->pairs, d->ny);
     DM3D_REQUIRE(d->d >= 1 && d->h >= 1 && d->w >= 1, "ms_ssim: d=%d h=%d w=%d (all at least 1)", d->d, d->h, d->w);
     DM3D_REQUIRE(d->nc >= 1 && d->nc <= 65535, "ms_ssim: nc=%d (in [1, 65535])", d->nc);
-    DM3D_REQUIRE(d->x0c >= 0 && d->cx >= 1 && (int64_t)d->x0c + d->nc <= d->cx, "ms_ssim: channels [%d, %d + %d) are outside x's cx=%d", d->x0c,
-                 d->x0c, d->nc, d->cx);
-    DM3D_REQUIRE(d->y0c >= 0 && d->cy >= 1 && (int64_t)d->y0c + d->nc <= d->cy, "ms_ssim: channels [%d, %d + %d) are outside y's cy=%d", d->y0c,
-                 d->y0c, d->nc, d->cy);
+    int rc = dm3d_check_window("ms_ssim", "x", d->x0c, d->nc, d->cx);
+    if (rc != DM3D_OK || (rc = dm3d_check_window("ms_ssim", "y", d->y0c, d->nc, d->cy)) != DM3D_OK) return rc;
     const int F = d->filter_size;
     DM3D_REQUIRE(F >= 3 && F <= MAXF && (F & 1), "ms_ssim: filter_size=%d (odd, in [3, %d])", F, MAXF);
     DM3D_REQUIRE(d->filter_sigma > 0.f, "ms_ssim: filter_sigma=%g (positive)", (double)d->filter_sigma);
@@ -243,7 +242,7 @@ extern "C" int dm3d_ms_ssim(const dm3d_ms_ssim_desc* d, void* stream) {
     while (fit < MAXS && (edge >> fit) >= F) ++fit;
     DM3D_REQUIRE(d->scales <= fit, "ms_ssim: %d scales of a %d x %d x %d volume leave an edge smaller than filter_size=%d; at most %d scales fit",
                  d->scales, d->d, d->h, d->w, F, fit);
-    DM3D_REQUIRE((reinterpret_cast<uintptr_t>(d->partials) & 7u) == 0, "ms_ssim: partials must be 8-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->partials, 8), "ms_ssim: partials must be 8-byte aligned");
 
     SumArgs sa{};
     int64_t tiles[MAXS], tiles_all = 0, pooled = 0;
@@ -293,7 +292,7 @@ extern "C" int dm3d_ms_ssim(const dm3d_ms_ssim_desc* d, void* stream) {
             case 9: launch_tile<9>(a, grid, st); break;
             default: launch_tile<11>(a, grid, st); break;
         }
-        int rc = dm3d_launch_check("msssim_tile_kernel");
+        rc = dm3d_launch_check("msssim_tile_kernel");
         if (rc != DM3D_OK) return rc;
         if (j + 1 == d->scales) break;
         // the next scale's volumes: every volume of x, then every volume of y, the compared channels only

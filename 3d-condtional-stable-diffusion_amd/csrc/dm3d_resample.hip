@@ -2,15 +2,15 @@
 // resample at orders 0, 1 and 3 by scipy.ndimage's rules, fold-and-min-max normalisation and the flip / brightness / contrast
 // augmentation.  Coordinates, weights, coefficients and every sum are float64 in one fixed order, the stores float32 (float64 for the
 // coefficients); no kernel here uses an atomic, so runs repeat bitwise.  Plain HIP: no MFMA, no inline assembly.
-#include "dm3d_common.h"
+// The tiling of the three prefilter passes and the block min / max are dm3d_volume.h's.
+#include "dm3d_volume.h"
 #include "dm3d_philox.h"
 #include <math.h>
 
 namespace {
 
 constexpr int MAXE = DM3D_SPLINE_MAX_EXTENT;       // longest line staged in LDS
-constexpr int LANES = DM3D_SPLINE_LANES;           // lines a block stages side by side
-constexpr int LDT = LANES + 1;                     // LDS row of one line position: the pad keeps the transposed W-pass stores apart
+constexpr int LDT = DM3D_LINE_LDT;                 // LDS row of one line position
 constexpr int BX = 16, BY = 4, BZ = 4;             // the output brick of a resample block (x, y, z): 256 lanes
 constexpr int NORM_BLOCKS = DM3D_NORM_PARTIAL_BLOCKS;
 constexpr int AUG_BLOCKS = DM3D_AUG_PARTIAL_BLOCKS;
@@ -20,35 +20,26 @@ constexpr uint32_t STREAM_AUGMENT = DM3D_STREAM_AUGMENT;
 struct FilterArgs {
     const float* x;                                // first pass: the float32 input
     double* c;                                     // in place (first pass: out only)
-    long gs, ls, cs;                               // strides of a group of lines, of neighbouring lines, along a line
-    long lanes;                                    // lines of a group
-    int tiles;                                     // blocks of a group: ceil(lanes / LANES)
-    int n;                                         // line length, 1 .. MAXE; 1: the pass only copies
+    dm3d_line_pass line;                           // length 1 .. MAXE; 1: the pass only copies
     int first;
     double z, gain, zn1;                           // the pole sqrt(3) - 2, (1 - z)(1 - 1/z), z^(n-1) by n - 1 products: the host's values
 };
 
 // One causal and one anti-causal recursion over each of LANES neighbouring lines of one group, in place: scipy.ndimage.spline_filter1d
 // (order 3, mode "mirror") operation by operation.  The lines are staged in LDS as [n][LDT] float64 by all 256 lanes, in the order of
-// memory: ALONG (the W pass, a line is contiguous) walks a line with consecutive lanes, the H and D passes walk the LANES neighbours.
-// Lane l < LANES then owns line l; its LDS reads and writes are LANES consecutive float64.  A line of length 1 is left as it is.
+// memory (dm3d_line_walk).  Lane l < LANES then owns line l; its LDS reads and writes are LANES consecutive float64.  A line of length
+// 1 is left as it is.
 template <bool ALONG>
 __global__ __launch_bounds__(256) void spline_pass_kernel(const FilterArgs p) {
     extern __shared__ double col[];
-    const int n = p.n;
-    const long group = blockIdx.x / p.tiles, lane0 = (long)(blockIdx.x % p.tiles) * LANES;
-    const int nl = p.lanes - lane0 < LANES ? (int)(p.lanes - lane0) : LANES;
-    const long base = group * p.gs + lane0 * p.ls;
+    const int n = p.line.n;
+    const dm3d_line_block blk = dm3d_line_block_of(p.line);
     const double gain = n > 1 ? p.gain : 1.0;
-    for (int i = threadIdx.x; i < n * LANES; i += 256) {
-        const int j = ALONG ? i % n : i / LANES, l = ALONG ? i / n : i % LANES;
-        if (l < nl) {
-            const long off = base + l * p.ls + j * p.cs;
-            col[j * LDT + l] = (p.first ? (double)p.x[off] : p.c[off]) * gain;
-        }
-    }
+    dm3d_line_walk<ALONG>(p.line, blk, [&](int at, long off, bool live) {
+        if (live) col[at] = (p.first ? (double)p.x[off] : p.c[off]) * gain;
+    });
     __syncthreads();
-    if ((int)threadIdx.x < nl && n > 1) {
+    if ((int)threadIdx.x < blk.nl && n > 1) {
         double* c = col + threadIdx.x;
         const double z = p.z, zn1 = p.zn1;
         double c0 = c[0] + zn1 * c[(n - 1) * LDT], zi = z;
@@ -71,10 +62,9 @@ __global__ __launch_bounds__(256) void spline_pass_kernel(const FilterArgs p) {
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < n * LANES; i += 256) {
-        const int j = ALONG ? i % n : i / LANES, l = ALONG ? i / n : i % LANES;
-        if (l < nl) p.c[base + l * p.ls + j * p.cs] = col[j * LDT + l];
-    }
+    dm3d_line_walk<ALONG>(p.line, blk, [&](int at, long off, bool live) {
+        if (live) p.c[off] = col[at];
+    });
 }
 
 // ---- the resample --------------------------------------------------------------------------------------------------------------------
@@ -172,19 +162,6 @@ struct NormArgs {
     int* flag;                                     // [volumes]
 };
 
-// min and max of a block of 256 lanes: exact whatever the order
-__device__ __forceinline__ void block_minmax(float& mn, float& mx, float (*red)[2]) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = fminf(mn, __shfl_xor(mn, off, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = mn; red[threadIdx.x >> 6][1] = mx; }
-    __syncthreads();
-    mn = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
-    mx = fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1]));
-}
-
 // Grid (blocks, volumes): partials[v][block] = min and max of |x| over the block's share.
 __global__ __launch_bounds__(256) void norm_minmax_kernel(const NormArgs p) {
     __shared__ float red[4][2];
@@ -195,7 +172,7 @@ __global__ __launch_bounds__(256) void norm_minmax_kernel(const NormArgs p) {
         mn = fminf(mn, a);
         mx = fmaxf(mx, a);
     }
-    block_minmax(mn, mx, red);
+    dm3d_block_minmax(mn, mx, red);
     if (threadIdx.x == 0) {
         float* o = p.partials + ((long)blockIdx.y * NORM_BLOCKS + blockIdx.x) * 2;
         o[0] = mn; o[1] = mx;
@@ -212,7 +189,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const NormArgs p) {
         const float* q = p.partials + ((long)v * NORM_BLOCKS + threadIdx.x) * 2;
         mn = q[0]; mx = q[1];
     }
-    block_minmax(mn, mx, red);
+    dm3d_block_minmax(mn, mx, red);
     const bool constant = !(mx > mn);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         p.minmax[2 * v] = mn; p.minmax[2 * v + 1] = mx;
@@ -294,8 +271,6 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const AugArgs p) {
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
-bool aligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 int check_extents(const char* who, const char* what, int d, int h, int w) {
     DM3D_REQUIRE(d >= 1 && h >= 1 && w >= 1, "%s: %s d=%d h=%d w=%d (all at least 1)", who, what, d, h, w);
     return DM3D_OK;
@@ -313,38 +288,32 @@ int launch_resample(const dm3d_resample_desc* d, const ResArgs& a, dim3 grid, hi
 extern "C" int dm3d_spline_filter(const dm3d_spline_desc* d, void* stream) {
     DM3D_REQUIRE(d != nullptr, "spline_filter: null descriptor");
     DM3D_REQUIRE(d->x != nullptr && d->coeff != nullptr, "spline_filter: x and coeff must be non-null");
-    DM3D_REQUIRE(aligned(d->x, 4) && aligned(d->coeff, 8), "spline_filter: x must be 4-byte and coeff 8-byte aligned");
+    DM3D_REQUIRE(dm3d_aligned(d->x, 4) && dm3d_aligned(d->coeff, 8), "spline_filter: x must be 4-byte and coeff 8-byte aligned");
     DM3D_REQUIRE(d->volumes >= 1, "spline_filter: volumes=%d (at least 1)", d->volumes);
     int rc = check_extents("spline_filter", "extent", d->d, d->h, d->w);
     if (rc != DM3D_OK) return rc;
     DM3D_REQUIRE(d->d <= MAXE && d->h <= MAXE && d->w <= MAXE, "spline_filter: d=%d h=%d w=%d exceeds DM3D_SPLINE_MAX_EXTENT=%d per axis", d->d, d->h,
                  d->w, MAXE);
-    const int64_t V = d->volumes, D = d->d, H = d->h, W = d->w;
-    DM3D_REQUIRE(V * D * H <= 0x7fffffffLL * LANES && V * D * ((W + LANES - 1) / LANES) <= 0x7fffffffLL, "spline_filter: %lld volumes exceed the grid",
-                 (long long)V);
+    int64_t blocks = 0;
+    DM3D_REQUIRE(dm3d_line_grid_fault(d->volumes, d->d, d->h, d->w, &blocks) < 0, "spline_filter: %lld volumes exceed the grid", (long long)d->volumes);
     static std::atomic<bool> lds_set[64];
     const int dev = dm3d_dyn_lds((size_t)MAXE * LDT * sizeof(double), lds_set, "spline_filter", spline_pass_kernel<true>, spline_pass_kernel<false>);
     if (dev < 0) return dev;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    static const char* const names[3] = {"spline_pass_kernel (w)", "spline_pass_kernel (h)", "spline_pass_kernel (d)"};
     FilterArgs a{};
     a.x = d->x; a.c = d->coeff;
     a.z = sqrt(3.0) - 2.0;
     a.gain = (1.0 - a.z) * (1.0 - 1.0 / a.z);
-    auto power = [&](int n) { double p = 1.0; for (int i = 0; i < n - 1; ++i) p *= a.z; return p; };
-    // w: every row of the tensor is a line; LANES neighbouring rows a block
-    a.gs = 0; a.ls = W; a.cs = 1; a.lanes = V * D * H; a.tiles = (int)((a.lanes + LANES - 1) / LANES); a.n = (int)W; a.first = 1; a.zn1 = power(a.n);
-    hipLaunchKernelGGL(spline_pass_kernel<true>, dim3((unsigned)a.tiles), dim3(256), (size_t)a.n * LDT * sizeof(double), st, a);
-    if ((rc = dm3d_launch_check("spline_pass_kernel (w)")) != DM3D_OK) return rc;
-    a.first = 0;
-    if (H > 1) {                                                                // h: a group is one plane, its lines the w positions
-        a.gs = H * W; a.ls = 1; a.cs = W; a.lanes = W; a.tiles = (int)((W + LANES - 1) / LANES); a.n = (int)H; a.zn1 = power(a.n);
-        hipLaunchKernelGGL(spline_pass_kernel<false>, dim3((unsigned)(V * D * a.tiles)), dim3(256), (size_t)a.n * LDT * sizeof(double), st, a);
-        if ((rc = dm3d_launch_check("spline_pass_kernel (h)")) != DM3D_OK) return rc;
-    }
-    if (D > 1) {                                                                // d: a group is one volume, its lines the h * w positions of a plane
-        a.gs = D * H * W; a.ls = 1; a.cs = H * W; a.lanes = H * W; a.tiles = (int)((H * W + LANES - 1) / LANES); a.n = (int)D; a.zn1 = power(a.n);
-        hipLaunchKernelGGL(spline_pass_kernel<false>, dim3((unsigned)(V * a.tiles)), dim3(256), (size_t)a.n * LDT * sizeof(double), st, a);
-        if ((rc = dm3d_launch_check("spline_pass_kernel (d)")) != DM3D_OK) return rc;
+    for (int axis = 0; axis < 3; ++axis) {                                      // w always (it makes the float64 copy); h and d where they filter
+        blocks = dm3d_line_pass_fill(&a.line, axis, d->volumes, d->d, d->h, d->w);
+        if (axis > 0 && a.line.n == 1) continue;
+        a.first = axis == 0;
+        a.zn1 = 1.0;
+        for (int i = 0; i < a.line.n - 1; ++i) a.zn1 *= a.z;
+        hipLaunchKernelGGL(axis == 0 ? spline_pass_kernel<true> : spline_pass_kernel<false>, dim3((unsigned)blocks), dim3(256),
+                           (size_t)a.line.n * LDT * sizeof(double), st, a);
+        if ((rc = dm3d_launch_check(names[axis])) != DM3D_OK) return rc;
     }
     return DM3D_OK;
 }
@@ -354,7 +323,7 @@ extern "C" int dm3d_affine_resample(const dm3d_resample_desc* d, void* stream) {
     DM3D_REQUIRE(d->src != nullptr && d->table != nullptr && d->out != nullptr, "affine_resample: src, table and out must be non-null");
     DM3D_REQUIRE(d->in_f64 == DM3D_RESAMPLE_F32 || d->in_f64 == DM3D_RESAMPLE_F64, "affine_resample: in_f64=%d (DM3D_RESAMPLE_F32 or DM3D_RESAMPLE_F64)",
                  d->in_f64);
-    DM3D_REQUIRE(aligned(d->src, d->in_f64 ? 8 : 4) && aligned(d->table, 8) && aligned(d->out, 4),
+    DM3D_REQUIRE(dm3d_aligned(d->src, d->in_f64 ? 8 : 4) && dm3d_aligned(d->table, 8) && dm3d_aligned(d->out, 4),
                  "affine_resample: src must be aligned to its element, table 8-byte and out 4-byte aligned");
     DM3D_REQUIRE(d->order == 0 || d->order == 1 || d->order == 3, "affine_resample: order=%d (0, 1 or 3; orders 2, 4 and 5 are not offered)", d->order);
     DM3D_REQUIRE(d->volumes >= 1 && d->volumes <= 65535, "affine_resample: volumes=%d (1 to 65535)", d->volumes);
@@ -382,7 +351,7 @@ extern "C" int dm3d_volume_normalize(const dm3d_normalize_desc* d, void* stream)
     DM3D_REQUIRE(d != nullptr, "volume_normalize: null descriptor");
     DM3D_REQUIRE(d->x != nullptr && d->out != nullptr && d->partials != nullptr && d->minmax != nullptr && d->flag != nullptr,
                  "volume_normalize: x, out, partials, minmax and flag must be non-null");
-    DM3D_REQUIRE(aligned(d->x, 4) && aligned(d->out, 4) && aligned(d->partials, 4) && aligned(d->minmax, 4) && aligned(d->flag, 4),
+    DM3D_REQUIRE(dm3d_aligned(d->x, 4) && dm3d_aligned(d->out, 4) && dm3d_aligned(d->partials, 4) && dm3d_aligned(d->minmax, 4) && dm3d_aligned(d->flag, 4),
                  "volume_normalize: every buffer must be 4-byte aligned");
     DM3D_REQUIRE(d->volumes >= 1 && d->volumes <= 65535, "volume_normalize: volumes=%d (1 to 65535)", d->volumes);
     DM3D_REQUIRE(d->n >= 1, "volume_normalize: n=%lld (at least 1)", (long long)d->n);
@@ -404,8 +373,8 @@ extern "C" int dm3d_augment(const dm3d_augment_desc* d, void* stream) {
     DM3D_REQUIRE(d->x != nullptr && d->out != nullptr && d->flip != nullptr && d->brightness != nullptr && d->contrast != nullptr && d->partials != nullptr,
                  "augment: x, out, flip, brightness, contrast and partials must be non-null");
     DM3D_REQUIRE((d->mask == nullptr) == (d->mask_out == nullptr), "augment: mask and mask_out must be both given or both null");
-    DM3D_REQUIRE(aligned(d->x, 4) && aligned(d->out, 4) && aligned(d->mask, 4) && aligned(d->mask_out, 4) && aligned(d->flip, 4) &&
-                     aligned(d->brightness, 4) && aligned(d->contrast, 4) && aligned(d->partials, 8),
+    DM3D_REQUIRE(dm3d_aligned(d->x, 4) && dm3d_aligned(d->out, 4) && dm3d_aligned(d->mask, 4) && dm3d_aligned(d->mask_out, 4) && dm3d_aligned(d->flip, 4) &&
+                     dm3d_aligned(d->brightness, 4) && dm3d_aligned(d->contrast, 4) && dm3d_aligned(d->partials, 8),
                  "augment: partials must be 8-byte and every other buffer 4-byte aligned");
     DM3D_REQUIRE(d->batch >= 1 && d->batch <= 65535, "augment: batch=%d (1 to 65535)", d->batch);
     int rc = check_extents("augment", "extent", d->d, d->h, d->w);

@@ -426,20 +426,49 @@ class PairStats(NamedTuple):
     sse: torch.Tensor
 
 
+def _window(t, channels):
+    """``channels = (first, count)`` selects a channel window of the NDHWC tensor ``t``, read in place (default: all)."""
+    return (0, t.shape[4]) if channels is None else channels
+
+
+def _volume_desc(d, x, y=None, x_channels=None, y_channels=None, *, alone=False, same=slice(0, 4),
+                 same_text="x and y must be [B,D,H,W,C] with the same batch and spatial shape"):
+    """Fills what the volume descriptors share by name, for one NDHWC tensor (``y`` None) or a pair: x, cx, x0c, nc, d, h, w (y, cy, y0c),
+    and batch where ``d`` has one.  ``alone``: x is checked on its own before y is looked at; ``same``: the axes on which a pair must agree."""
+    _f32c(x, "x")
+    if alone and x.dim() != 5:
+        raise ValueError(f"x must be [B,D,H,W,C], got {tuple(x.shape)}")
+    if y is not None:
+        _f32c(y, "y")
+        if x.dim() != 5 or y.dim() != 5 or x.shape[same] != y.shape[same]:
+            raise ValueError(f"{same_text}, got {tuple(x.shape)} and {tuple(y.shape)}")
+    x0c, nc = _window(x, x_channels)
+    if y is not None:
+        y0c, ncy = _window(y, y_channels)
+        if nc != ncy:
+            raise ValueError(f"x contributes {nc} channels and y {ncy}: the same number must be compared")
+        d.y, d.cy, d.y0c = y.data_ptr(), y.shape[4], y0c
+    d.x, d.cx, d.x0c, d.nc = x.data_ptr(), x.shape[4], x0c, nc
+    d.d, d.h, d.w = x.shape[1:4]
+    if hasattr(d, "batch"):
+        d.batch = x.shape[0]
+    return d
+
+
+def _mask_limits(d, x, threshold, max_extent):
+    """The two refusals of the mask entries (distance transform, components): an axis longer than ``max_extent``, a threshold not finite."""
+    if max(x.shape[1:4]) > max_extent:
+        raise ValueError(f"a {x.shape[1]} x {x.shape[2]} x {x.shape[3]} volume exceeds {max_extent} voxels per axis")
+    thr = float(threshold)
+    if not math.isfinite(thr):
+        raise ValueError(f"threshold must be finite, got {threshold}")
+    d.threshold = thr
+    return d
+
+
 def _metric_desc(x, y, x_channels, y_channels):
     """The descriptor of a pair of NDHWC tensors; ``*_channels = (first, count)`` selects a channel window read in place (default: all)."""
-    _f32c(x, "x"), _f32c(y, "y")
-    if x.dim() != 5 or y.dim() != 5 or x.shape[:4] != y.shape[:4]:
-        raise ValueError(f"x and y must be [B,D,H,W,C] with the same batch and spatial shape, got {tuple(x.shape)} and {tuple(y.shape)}")
-    x0c, ncx = (0, x.shape[4]) if x_channels is None else x_channels
-    y0c, ncy = (0, y.shape[4]) if y_channels is None else y_channels
-    if ncx != ncy:
-        raise ValueError(f"x contributes {ncx} channels and y {ncy}: the same number must be compared")
-    d = _lib.MetricDesc()
-    d.x, d.y = x.data_ptr(), y.data_ptr()
-    d.batch, d.d, d.h, d.w = x.shape[:4]
-    d.cx, d.cy, d.x0c, d.y0c, d.nc = x.shape[4], y.shape[4], x0c, y0c, ncx
-    return d
+    return _volume_desc(_lib.MetricDesc(), x, y, x_channels, y_channels)
 
 
 def _metric_partials(d, elems: int, device) -> torch.Tensor:
@@ -465,16 +494,20 @@ def pair_stats(x: torch.Tensor, y: torch.Tensor, *, x_channels=None, y_channels=
 
 def _max_val(max_val, stats, x, y, x_channels, y_channels) -> torch.Tensor:
     """The device table of one float per volume both metrics read: the caller's value, or the reference's choice max(y) - min(y)."""
-    B = x.shape[0]
     if max_val is None:
         return (stats if stats is not None else pair_stats(x, y, x_channels=x_channels, y_channels=y_channels)).y_range
+    return _max_val_table(max_val, x.shape[0], "volume", x.device)
+
+
+def _max_val_table(max_val, rows: int, noun: str, device) -> torch.Tensor:
+    """float32 [rows] on the device from a number, or from a tensor of one value or one per row (``noun`` names a row in the refusal)."""
     if isinstance(max_val, torch.Tensor):
-        t = max_val.to(device=x.device, dtype=torch.float32).reshape(-1)
-        t = t.expand(B) if t.numel() == 1 else t
-        if t.numel() != B:
-            raise ValueError(f"max_val must hold one value, or one per volume ({B}), got {t.numel()}")
+        t = max_val.to(device=device, dtype=torch.float32).reshape(-1)
+        t = t.expand(rows) if t.numel() == 1 else t
+        if t.numel() != rows:
+            raise ValueError(f"max_val must hold one value, or one per {noun} ({rows}), got {t.numel()}")
         return t.contiguous()
-    return torch.full((B,), float(max_val), dtype=torch.float32, device=x.device)
+    return torch.full((rows,), float(max_val), dtype=torch.float32, device=device)
 
 
 def ssim(x: torch.Tensor, y: torch.Tensor, max_val=None, *, x_channels=None, y_channels=None, stats: Optional[PairStats] = None) -> torch.Tensor:
@@ -545,15 +578,9 @@ def ms_ssim(x: torch.Tensor, y: torch.Tensor, max_val=None, *, power_factors=MS_
                 torch.int32, torch.int64):
             raise ValueError(f"pairs must be an int32 or int64 tensor [P, 2] with P >= 1, got {getattr(pairs, 'dtype', type(pairs))} "
                              f"{tuple(getattr(pairs, 'shape', ()))}")
-    _f32c(x, "x"), _f32c(y, "y")
-    if x.dim() != 5 or y.dim() != 5 or x.shape[1:4] != y.shape[1:4] or (pairs is None and x.shape[0] != y.shape[0]):
-        raise ValueError(f"x and y must be [N,D,H,W,C] with the same spatial shape (and the same N without pairs), got {tuple(x.shape)} and "
-                         f"{tuple(y.shape)}")
-    x0c, ncx = (0, x.shape[4]) if x_channels is None else x_channels
-    y0c, ncy = (0, y.shape[4]) if y_channels is None else y_channels
-    if ncx != ncy:
-        raise ValueError(f"x contributes {ncx} channels and y {ncy}: the same number must be compared")
-    D, H, W = x.shape[1:4]
+    d = _volume_desc(_lib.MsSsimDesc(), x, y, x_channels, y_channels, same=slice(0 if pairs is None else 1, 4),
+                     same_text="x and y must be [N,D,H,W,C] with the same spatial shape (and the same N without pairs)")
+    D, H, W, ncx = d.d, d.h, d.w, d.nc
     fit = ms_ssim_max_scales((D, H, W), filter_size)
     if len(power) > fit:
         raise ValueError(f"ms_ssim: {len(power)} scales of a {D} x {H} x {W} volume leave an edge smaller than filter_size={filter_size}; "
@@ -567,14 +594,7 @@ def ms_ssim(x: torch.Tensor, y: torch.Tensor, max_val=None, *, power_factors=MS_
             raise ValueError("pairs must be on the device of x and y")
         P = pairs.shape[0]
         idx = pairs.to(torch.int32).t().contiguous()                            # [2, P]: the two tables
-        if isinstance(max_val, torch.Tensor):
-            mv = max_val.to(device=dev, dtype=torch.float32).reshape(-1)
-            mv = mv.expand(P) if mv.numel() == 1 else mv
-            if mv.numel() != P:
-                raise ValueError(f"max_val must hold one value, or one per pair ({P}), got {mv.numel()}")
-            mv = mv.contiguous()
-        else:
-            mv = torch.full((P,), float(max_val), dtype=torch.float32, device=dev)
+        mv = _max_val_table(max_val, P, "pair", dev)
     TD, TH, TW = _lib.MSSSIM_TILE
     tiles = sum(-(-((D >> j) - filter_size + 1) // TD) * -(-((H >> j) - filter_size + 1) // TH) * -(-((W >> j) - filter_size + 1) // TW)
                 for j in range(len(power)))
@@ -582,12 +602,9 @@ def ms_ssim(x: torch.Tensor, y: torch.Tensor, max_val=None, *, power_factors=MS_
     partials = torch.empty(max(1, 2 * P * ncx * tiles), dtype=torch.float64, device=dev)       # alive until the launches are enqueued
     scratch = torch.empty(max(1, (x.shape[0] + y.shape[0]) * ncx * pooled), dtype=torch.float32, device=dev)
     out = torch.empty(P, dtype=torch.float32, device=dev)
-    d = _lib.MsSsimDesc()
-    d.x, d.y = x.data_ptr(), y.data_ptr()
     if idx is not None:
         d.x_index, d.y_index = idx[0].data_ptr(), idx[1].data_ptr()
-    d.pairs, d.nx, d.ny, d.d, d.h, d.w = P, x.shape[0], y.shape[0], D, H, W
-    d.cx, d.cy, d.x0c, d.y0c, d.nc = x.shape[4], y.shape[4], x0c, y0c, ncx
+    d.pairs, d.nx, d.ny = P, x.shape[0], y.shape[0]
     d.filter_size, d.filter_sigma, d.scales = filter_size, float(filter_sigma), len(power)
     for j, w in enumerate(power):
         d.power_factors[j] = w
@@ -618,29 +635,8 @@ class SurfaceDistances(NamedTuple):
 
 def _mask_desc(x, y, threshold, x_channels, y_channels):
     """The descriptor of one NDHWC tensor (``y`` None) or of a pair; ``*_channels = (first, count)`` as in ``_metric_desc``."""
-    _f32c(x, "x")
-    if x.dim() != 5:
-        raise ValueError(f"x must be [B,D,H,W,C], got {tuple(x.shape)}")
-    x0c, nc = (0, x.shape[4]) if x_channels is None else x_channels
-    d = _lib.MaskDesc()
-    d.x = x.data_ptr()
-    d.batch, d.d, d.h, d.w = x.shape[:4]
-    d.cx, d.x0c, d.nc = x.shape[4], x0c, nc
-    if y is not None:
-        _f32c(y, "y")
-        if y.dim() != 5 or x.shape[:4] != y.shape[:4]:
-            raise ValueError(f"x and y must be [B,D,H,W,C] with the same batch and spatial shape, got {tuple(x.shape)} and {tuple(y.shape)}")
-        y0c, ncy = (0, y.shape[4]) if y_channels is None else y_channels
-        if nc != ncy:
-            raise ValueError(f"x contributes {nc} channels and y {ncy}: the same number must be compared")
-        d.y, d.cy, d.y0c = y.data_ptr(), y.shape[4], y0c
-    if max(x.shape[1:4]) > _lib.EDT_MAX_EXTENT:
-        raise ValueError(f"a {x.shape[1]} x {x.shape[2]} x {x.shape[3]} volume exceeds {_lib.EDT_MAX_EXTENT} voxels per axis")
-    thr = float(threshold)
-    if not math.isfinite(thr):
-        raise ValueError(f"threshold must be finite, got {threshold}")
-    d.threshold = thr
-    return d
+    d = _volume_desc(_lib.MaskDesc(), x, y, x_channels, y_channels, alone=True)
+    return _mask_limits(d, x, threshold, _lib.EDT_MAX_EXTENT)
 
 
 def mask_overlap(x: torch.Tensor, y: torch.Tensor, threshold: float = 0.5, *, x_channels=None, y_channels=None) -> MaskOverlap:
@@ -716,25 +712,13 @@ CONNECTIVITIES = (6, 18, 26)
 
 def _ccl_desc(x, threshold, channels, connectivity, planes):
     """The descriptor of one NDHWC tensor and its scratch of ``planes`` int32 planes (alive while the caller holds it)."""
-    _f32c(x, "x")
-    if x.dim() != 5:
-        raise ValueError(f"x must be [B,D,H,W,C], got {tuple(x.shape)}")
+    d = _volume_desc(_lib.CclDesc(), x, None, channels, alone=True)
     if connectivity not in CONNECTIVITIES:
         raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
-    if max(x.shape[1:4]) > _lib.CCL_MAX_EXTENT:
-        raise ValueError(f"a {x.shape[1]} x {x.shape[2]} x {x.shape[3]} volume exceeds {_lib.CCL_MAX_EXTENT} voxels per axis")
-    thr = float(threshold)
-    if not math.isfinite(thr):
-        raise ValueError(f"threshold must be finite, got {threshold}")
-    x0c, nc = (0, x.shape[4]) if channels is None else channels
-    d = _lib.CclDesc()
-    d.x = x.data_ptr()
-    d.batch, d.d, d.h, d.w = x.shape[:4]
-    d.cx, d.x0c, d.nc = x.shape[4], x0c, nc
-    d.threshold, d.connectivity = thr, connectivity
+    _mask_limits(d, x, threshold, _lib.CCL_MAX_EXTENT).connectivity = connectivity
     vol = d.d * d.h * d.w
     nblk = -(-vol // _lib.CCL_BLOCK_VOXELS)
-    work = torch.empty(planes * d.batch * nc * vol + 1 + d.batch * nc * (3 * nblk + 2), dtype=torch.int32, device=x.device)
+    work = torch.empty(planes * d.batch * d.nc * vol + 1 + d.batch * d.nc * (3 * nblk + 2), dtype=torch.int32, device=x.device)
     d.work, d.work_elems = work.data_ptr(), work.numel()
     return d, work
 

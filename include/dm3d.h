@@ -904,6 +904,7 @@ int dm3d_ms_ssim(const dm3d_ms_ssim_desc* d, void* stream);
  *     read.  One pass writes the features to `masks`; then out[i] = min_j (i - j)^2 + g[j] along w (g = 0 at a feature, "none"
  *     elsewhere), along h and along d, in place in `map`: a workgroup stages DM3D_EDT_LANES neighbouring columns in LDS
  *     ([n][DM3D_EDT_LANES + 1] int32, twice: the columns and the results) and evaluates the form branch-free, O(n^2) per column.
+ *     The staging is the line-pass tiler of csrc/dm3d_volume.h, shared with dm3d_spline_filter.
  *         masks_elems >= batch * nc * d * h * w                                   bytes
  * dm3d_surface_distance   the overlap pass (counts if non-NULL), the map of Y's surface, a histogram of its values at X's surface voxels,
  *     the same with X and Y exchanged, and one kernel that reads the two histograms of a (volume, channel):
@@ -1089,7 +1090,8 @@ int dm3d_poly_mmd(const dm3d_dist_desc* d, void* stream);
  *         c[0] = (c[0] + z^(n-1) c[n-1] + sum_{i=1}^{n-2} z^i (c[i] + z^(n-1) c[n-1-i])) / (1 - z^(2n-2));   c[i] += z c[i-1]  (i = 1 .. n-1)
  *         c[n-1] = (z c[n-2] + c[n-1]) z / (z^2 - 1);   c[i] = z (c[i+1] - c[i])  (i = n-2 .. 0)
  *     in float64; an axis of length 1 is left unfiltered, as scipy leaves it.  A workgroup stages DM3D_SPLINE_LANES neighbouring lines
- *     in LDS ([n][DM3D_SPLINE_LANES + 1] float64) and one lane walks each line.  coeff holds volumes * d * h * w float64.
+ *     in LDS ([n][DM3D_SPLINE_LANES + 1] float64; the line-pass tiler of csrc/dm3d_volume.h, shared with dm3d_edt) and one lane walks
+ *     each line.  coeff holds volumes * d * h * w float64.
  * dm3d_affine_resample   out[v][o] = interp(src[v], M_v o + offset_v), scipy.ndimage.affine_transform(mode="constant") for a
  *     [3, 3] matrix; table[v] = {M row by row, offset} (12 float64); a diagonal matrix is the same entry with zeros off the diagonal.
  *         coordinate   c[h] = ((o0 M[h][0] + o1 M[h][1]) + o2 M[h][2]) + offset[h]      each product and sum rounded to float64

@@ -151,6 +151,25 @@ def test_surface_distances_meet_the_restatement_and_repeat_bitwise(dev, case):
         assert again.tobytes() == got.tobytes() and counts2.tobytes() == counts.tobytes()
 
 
+@pytest.mark.parametrize("shape", [(33, 1, 70), (1, 70, 33), (70, 33, 1)], ids=lambda s: "x".join(map(str, s)))
+def test_distance_transform_line_tiler(dev, shape):
+    """What the shared line-pass tiler (csrc/dm3d_volume.h) can get wrong, through ops.distance_transform on two volumes of two channels
+    with a window of one: column counts that are no multiple of 32 (33, 70), more than one tile per group (70 > 64), an axis of extent
+    1 (its pass still runs: the d pass writes INT32_MAX) and a group stride (batch * nc = 2).  Exact: int32 against the brute force."""
+    from dm3d_amd import ops
+    rng = np.random.default_rng([11] + list(shape))
+    x = rng.random((2,) + shape + (2,)).astype(np.float32)
+    x[..., 1] = np.stack([mk.values_of(mk.mask_of("balls", shape, seed=b), rng) for b in range(2)])
+    m = mk.masks(x, 1, 1)
+    t = torch.from_numpy(x).to(dev)
+    for of, feat in (("surface", mk.surface), ("foreground", lambda v: v)):
+        got = ops.distance_transform(t, mk.THRESHOLD, channels=(1, 1), of=of)
+        again = ops.distance_transform(t, mk.THRESHOLD, channels=(1, 1), of=of)
+        want = np.stack([mk.sq_distance_map(feat(m[b, 0])) for b in range(2)])[..., None]
+        assert got.dtype == torch.int32 and got.shape == (2,) + shape + (1,) and torch.equal(got, again)
+        assert np.array_equal(got.cpu().numpy(), want), f"{of}: {int((got.cpu().numpy() != want).sum())} of {want.size} voxels differ"
+
+
 def test_the_interpolation_is_exercised():
     """About the inputs, on the CPU side: at both percentiles some (volume, channel) has its two ranks on different squared distances."""
     for p in mk.PERCENTILES:

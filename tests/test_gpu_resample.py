@@ -97,6 +97,19 @@ def test_prefilter(dev, shape):
     assert np.isfinite(got).all() and err <= COEFF_BOUND
 
 
+@pytest.mark.parametrize("shape", [(33, 1, 70), (1, 70, 33), (70, 33, 1)], ids=lambda s: "x".join(map(str, s)))
+def test_prefilter_line_tiler(dev, shape):
+    """What the shared line-pass tiler (csrc/dm3d_volume.h) can get wrong, through ops.spline_filter on two volumes: line counts that are no
+    multiple of 32 (33, 70), more than one tile per group (70 > 64), an axis of extent 1 (its h or d pass is skipped, its w pass copies)
+    and a group stride (two volumes)."""
+    from dm3d_amd import ops
+    x = rr.volumes(shape, 2)
+    got = _twice(lambda: ops.spline_filter(torch.from_numpy(x).to(dev)).cpu().numpy())
+    err = float(np.abs(got - rr.spline_filter(x)).max())
+    print(f"prefilter tiler {shape}: worst |gpu - restatement| {err:.3e}")
+    assert got.shape == x.shape and got.dtype == np.float64 and np.isfinite(got).all() and err <= COEFF_BOUND
+
+
 def test_prefilter_wrapper_layouts(dev):
     from dm3d_amd import ops
     x = rr.volumes((5, 4, 6, 2), 2)                                             # NDHWC, C = 2: each channel a volume
