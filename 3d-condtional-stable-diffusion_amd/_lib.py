@@ -261,7 +261,27 @@ class AugmentDesc(C.Structure):
     ]
 
 
-GUIDE_PARTIAL_BLOCKS = 256          # DM3D_GUIDE_PARTIAL_BLOCKS: GuideDesc.partials holds [batch][256][4] doubles
+class GaussDesc(C.Structure):
+    _fields_ = [
+        ("x", _f32p), ("out", _f32p), ("weights", C.c_void_p), ("volumes", C.c_int32), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("rd", C.c_int32), ("rh", C.c_int32), ("rw", C.c_int32), ("mode", C.c_int32), ("cval", C.c_double), ("gains", C.c_int32),
+        ("gain0", C.c_float), ("gain1", C.c_float), ("gain2", C.c_float),
+    ]
+
+
+class FieldDesc(C.Structure):
+    _fields_ = [("out", _f32p), ("n", C.c_int64), ("seed", C.c_uint64), ("draw", C.c_int32)]
+
+
+class WarpDesc(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("table", C.c_void_p), ("field", C.c_void_p), ("out", _f32p), ("in_f64", C.c_int32), ("field_f64", C.c_int32),
+        ("volumes", C.c_int32), ("vols_per_field", C.c_int32), ("id", C.c_int32), ("ih", C.c_int32), ("iw", C.c_int32), ("od", C.c_int32),
+        ("oh", C.c_int32), ("ow", C.c_int32), ("order", C.c_int32), ("cval", C.c_float),
+    ]
+
+
+GUIDE_PARTIAL_BLOCKS = 256        # DM3D_GUIDE_PARTIAL_BLOCKS: GuideDesc.partials holds [batch][256][4] doubles
 LOSS_PARTIAL_BLOCKS = 64            # DM3D_LOSS_PARTIAL_BLOCKS: LossDesc.partials holds [batch][64] doubles
 GRADNORM_PARTIAL_BLOCKS = 1024      # DM3D_GRADNORM_PARTIAL_BLOCKS: GradScaleDesc.partials holds [1024] doubles
 PAIR_PARTIAL_BLOCKS = 64            # DM3D_PAIR_PARTIAL_BLOCKS: dm3d_pair_stats runs min(ceil(h*w / 4096), 64) blocks a slice
@@ -281,7 +301,10 @@ RESAMPLE_F32, RESAMPLE_F64 = 0, 1   # DM3D_RESAMPLE_F32 / DM3D_RESAMPLE_F64: Res
 NORM_PARTIAL_BLOCKS = 256           # DM3D_NORM_PARTIAL_BLOCKS: NormalizeDesc.partials holds [volumes][256][2] floats
 AUG_PARTIAL_BLOCKS = 256            # DM3D_AUG_PARTIAL_BLOCKS: AugmentDesc.partials holds [batch][256] doubles
 STREAM_AUGMENT = 0xA063             # DM3D_STREAM_AUGMENT: word 3 of the Philox counter of dm3d_augment's draws
-MSSSIM_TILE = (32, 16, 32)          # DM3D_MSSSIM_TD / TH / TW: dm3d_ms_ssim leaves one partial pair per tile of 32 x 16 x 32 (d, h, w) outputs
+GAUSS_MAX_RADIUS = 64               # DM3D_GAUSS_MAX_RADIUS: the longest half-kernel of dm3d_gaussian_filter; GaussDesc.weights is [3][65] doubles
+GAUSS_MODES = {"reflect": 0, "mirror": 1, "nearest": 2, "constant": 3}   # DM3D_GAUSS_*: GaussDesc.mode
+STREAM_ELASTIC = 0xE1A5             # DM3D_STREAM_ELASTIC: word 3 of the Philox counter of dm3d_uniform_field's draws
+MSSSIM_TILE = (32, 16, 32)         # DM3D_MSSSIM_TD / TH / TW: dm3d_ms_ssim leaves one partial pair per tile of 32 x 16 x 32 (d, h, w) outputs
 
 # name -> (restype, argtypes): every symbol include/dm3d.h declares
 SIGNATURES = {
@@ -368,6 +391,9 @@ SIGNATURES = {
     "dm3d_affine_resample": (C.c_int, [C.POINTER(ResampleDesc), C.c_void_p]),
     "dm3d_volume_normalize": (C.c_int, [C.POINTER(NormalizeDesc), C.c_void_p]),
     "dm3d_augment": (C.c_int, [C.POINTER(AugmentDesc), C.c_void_p]),
+    "dm3d_gaussian_filter": (C.c_int, [C.POINTER(GaussDesc), C.c_void_p]),
+    "dm3d_uniform_field": (C.c_int, [C.POINTER(FieldDesc), C.c_void_p]),
+    "dm3d_warp": (C.c_int, [C.POINTER(WarpDesc), C.c_void_p]),
     "dm3d_range_check": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "dm3d_add_i32": (C.c_int, [_i32p, C.c_int32, C.c_int32, C.c_void_p]),
     "dm3d_randn": (C.c_int, [_f32p, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p]),

@@ -2,8 +2,9 @@
 // resample at orders 0, 1 and 3 by scipy.ndimage's rules, fold-and-min-max normalisation and the flip / brightness / contrast
 // augmentation.  Coordinates, weights, coefficients and every sum are float64 in one fixed order, the stores float32 (float64 for the
 // coefficients); no kernel here uses an atomic, so runs repeat bitwise.  Plain HIP: no MFMA, no inline assembly.
-// The tiling of the three prefilter passes and the block min / max are dm3d_volume.h's.
+// The tiling of the three prefilter passes and the block min / max are dm3d_volume.h's, the taps and the tap sum dm3d_interp.h's.
 #include "dm3d_volume.h"
+#include "dm3d_interp.h"
 #include "dm3d_philox.h"
 #include <math.h>
 
@@ -11,7 +12,7 @@ namespace {
 
 constexpr int MAXE = DM3D_SPLINE_MAX_EXTENT;       // longest line staged in LDS
 constexpr int LDT = DM3D_LINE_LDT;                 // LDS row of one line position
-constexpr int BX = 16, BY = 4, BZ = 4;             // the output brick of a resample block (x, y, z): 256 lanes
+constexpr int BX = DM3D_BRICK_X, BY = DM3D_BRICK_Y, BZ = DM3D_BRICK_Z;
 constexpr int NORM_BLOCKS = DM3D_NORM_PARTIAL_BLOCKS;
 constexpr int AUG_BLOCKS = DM3D_AUG_PARTIAL_BLOCKS;
 constexpr uint32_t STREAM_AUGMENT = DM3D_STREAM_AUGMENT;
@@ -77,39 +78,6 @@ struct ResArgs {
     float cval;
 };
 
-// scipy's mirror of a tap index: period 2n - 2, no repeated edge
-__device__ __forceinline__ int mirror_tap(int i, int n) {
-    if (n == 1) return 0;
-    const int period = 2 * n - 2;
-    i %= period;
-    if (i < 0) i += period;
-    return i < n ? i : period - i;
-}
-
-// The taps of one axis for an inside coordinate c: their (mirrored) indices and weights, as scipy forms them.
-template <int ORDER>
-__device__ __forceinline__ void axis_taps(double c, int n, int (&idx)[ORDER + 1], double (&w)[ORDER + 1]) {
-    if (ORDER == 0) {
-        idx[0] = (int)floor(c + 0.5);
-        w[0] = 1.0;
-        return;
-    }
-    const double fl = floor(c), x = c - fl;
-    const int start = (int)fl - ORDER / 2;
-#pragma unroll
-    for (int k = 0; k <= ORDER; ++k) idx[k] = mirror_tap(start + k, n);
-    if (ORDER == 1) {
-        w[0] = 1.0 - x;
-        w[1] = 1.0 - w[0];
-    } else {
-        const double y = 1.0 - x;
-        w[1] = (x * x * (x - 2.0) * 3.0 + 4.0) / 6.0;
-        w[2] = (y * y * (y - 2.0) * 3.0 + 4.0) / 6.0;
-        w[0] = y * y * y / 6.0;
-        w[ORDER] = ((1.0 - w[0]) - w[1]) - w[2];
-    }
-}
-
 // Grid (bricks, volumes); a block owns a brick of BZ x BY x BX outputs, a wave one z-slice of it: BX = 16 neighbours along x read 16
 // (times the x scale) neighbouring input elements per tap row, one 128-byte line of float64 at unit scale, and the BY rows and BZ
 // slices share three of their four tap rows and planes with their neighbours.  out = sum over the taps, axis 0 outermost, of
@@ -117,39 +85,14 @@ __device__ __forceinline__ void axis_taps(double c, int n, int (&idx)[ORDER + 1]
 template <int ORDER, typename T>
 __global__ __launch_bounds__(256) void resample_kernel(const ResArgs p) {
     const int v = blockIdx.y;
-    const int bx = blockIdx.x % p.tx, by = (blockIdx.x / p.tx) % p.ty, bz = blockIdx.x / (p.tx * p.ty);
-    const int ox = bx * BX + (threadIdx.x & (BX - 1)), oy = by * BY + ((threadIdx.x / BX) & (BY - 1)), oz = bz * BZ + threadIdx.x / (BX * BY);
-    if (ox >= p.ow || oy >= p.oh || oz >= p.od) return;
+    int oz, oy, ox;
+    if (!dm3d_brick_voxel(p.tx, p.ty, p.od, p.oh, p.ow, oz, oy, ox)) return;
     const double* m = p.table + (long)v * 12;
-    const int n[3] = {p.id, p.ih, p.iw};
     double c[3];
-    bool inside = true;
 #pragma unroll
-    for (int h = 0; h < 3; ++h) {
-        c[h] = (((double)oz * m[3 * h] + (double)oy * m[3 * h + 1]) + (double)ox * m[3 * h + 2]) + m[9 + h];
-        inside = inside && c[h] >= 0.0 && c[h] <= (double)(n[h] - 1);
-    }
-    float* out = p.out + (((long)v * p.od + oz) * p.oh + oy) * p.ow + ox;
-    if (!inside) {
-        *out = p.cval;
-        return;
-    }
-    int iz[ORDER + 1], iy[ORDER + 1], ix[ORDER + 1];
-    double wz[ORDER + 1], wy[ORDER + 1], wx[ORDER + 1];
-    axis_taps<ORDER>(c[0], n[0], iz, wz);
-    axis_taps<ORDER>(c[1], n[1], iy, wy);
-    axis_taps<ORDER>(c[2], n[2], ix, wx);
-    const T* in = static_cast<const T*>(p.in) + (long)v * p.id * p.ih * p.iw;
-    double t = 0.0;
-#pragma unroll
-    for (int i = 0; i <= ORDER; ++i)
-#pragma unroll
-        for (int j = 0; j <= ORDER; ++j) {
-            const T* row = in + ((long)iz[i] * p.ih + iy[j]) * p.iw;
-#pragma unroll
-            for (int k = 0; k <= ORDER; ++k) t += (((double)row[ix[k]] * wz[i]) * wy[j]) * wx[k];
-        }
-    *out = (float)t;
+    for (int h = 0; h < 3; ++h) c[h] = (((double)oz * m[3 * h] + (double)oy * m[3 * h + 1]) + (double)ox * m[3 * h + 2]) + m[9 + h];
+    dm3d_interp_store<ORDER, T>(static_cast<const T*>(p.in) + (long)v * p.id * p.ih * p.iw, p.id, p.ih, p.iw, c, p.cval,
+                                p.out + (((long)v * p.od + oz) * p.oh + oy) * p.ow + ox);
 }
 
 // ---- fold and min-max normalise --------------------------------------------------------------------------------------------------------

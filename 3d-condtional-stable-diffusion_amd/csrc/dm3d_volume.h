@@ -1,4 +1,4 @@
-// dm3d_volume.h — what the volume kernels share (dm3d_metrics, dm3d_msssim, dm3d_mask, dm3d_ccl, dm3d_resample): the host checks of an
+// dm3d_volume.h — what the volume kernels share (dm3d_metrics, dm3d_msssim, dm3d_mask, dm3d_ccl, dm3d_resample, dm3d_deform): the host checks of an
 // NDHWC channel window and of a mask volume, the line-pass tiler of the separable passes (the distance transform's and the spline
 // prefilter's), and the block min / max.  A new volume kernel starts here.
 #pragma once

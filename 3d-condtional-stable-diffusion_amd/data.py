@@ -6,14 +6,14 @@ single [D,H,W] volume is taken as a batch of one and returned as one).  NIfTI re
 voxel sizes.  Between two resamples a volume is rounded to float32, where the reference carries float64."""
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import ops
 
-__all__ = ["reslice", "transform_image", "normalize", "augment", "preprocess"]    # the preprocessing set, pinned by its host test; clean_mask is public beside it
+__all__ = ["reslice", "transform_image", "normalize", "augment", "preprocess"]    # the preprocessing set, pinned by its host test; clean_mask and the spatial augmentations are public beside it
 
 
 def _batched(x):
@@ -136,6 +136,122 @@ def preprocess(x: torch.Tensor, affine, voxsize, mask: Optional[torch.Tensor] = 
     image = normalize(vol).unsqueeze(-1)
     context = torch.zeros(image.shape[0], 1, 1, dtype=torch.int64, device=image.device)
     return image, torch.zeros_like(image), context
+
+
+class SpatialAugmented(NamedTuple):
+    """What the spatial augmentations return: the warped ``images`` and ``masks`` (None without masks), the host ``matrices`` float64
+    [B,4,4] that map an output voxel to its input coordinate (None where no affine was drawn) and the device displacement ``field``
+    float32 [B,3,D,H,W] (None where none was drawn)."""
+    images: torch.Tensor
+    masks: Optional[torch.Tensor]
+    matrices: Optional[np.ndarray]
+    field: Optional[torch.Tensor]
+
+
+def _image_mask_check(images, masks, host=None):
+    """Dtype, rank and shape rules of both tensors, then ``host()`` (the caller's host arguments, whose value is returned), the devices last."""
+    def masks_match():
+        if masks.shape[:4] != images.shape[:4]:
+            raise ValueError(f"masks must be [B,D,H,W,C] with the batch and spatial shape of images, got {tuple(masks.shape)} and {tuple(images.shape)}")
+
+    def rest():
+        checked = host() if host is not None else None
+        if masks is not None:
+            ops._volume_check(masks, "masks", ndhwc=True, host=masks_match)
+        return checked
+
+    return ops._volume_check(images, "images", ndhwc=True, host=rest)
+
+
+def _range3(v, name):
+    a = np.asarray(v, np.float64)
+    if a.shape not in ((), (3,)) or not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError(f"{name} must be a non-negative finite scalar or 3-vector, got {v!r}")
+    return np.broadcast_to(a, (3,))
+
+
+def affine_matrices(shape, batch: int, seed: int, rotate_range=0.0, scale_range=0.0, translate_range=0.0) -> np.ndarray:
+    """The float64 [batch,4,4] matrices of ``random_affine`` for volumes of the spatial ``shape`` (its docstring states the draw order
+    and the composition).  Host work only."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"shape must be three positive extents, got {shape!r}")
+    if not isinstance(seed, int) or seed < 0:
+        raise ValueError(f"seed must be a non-negative integer, got {seed!r}")
+    rot, sc, tr = _range3(rotate_range, "rotate_range"), _range3(scale_range, "scale_range"), _range3(translate_range, "translate_range")
+    if (sc >= 1).any():
+        raise ValueError(f"scale_range must stay below 1 (scales are drawn from U(1 - s, 1 + s)), got {scale_range!r}")
+    rng = np.random.Generator(np.random.Philox(seed))
+    angles = rng.uniform(-rot, rot, (batch, 3))
+    scales = rng.uniform(1.0 - sc, 1.0 + sc, (batch, 3))
+    shifts = rng.uniform(-tr, tr, (batch, 3))
+    centre = (np.array(shape, np.float64) - 1.0) / 2.0
+    out = np.zeros((batch, 4, 4))
+    for b in range(batch):
+        (cx, cy, cz), (sx, sy, sz) = np.cos(angles[b]), np.sin(angles[b])
+        R = (np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]]) @ np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]]) @
+             np.array([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]]))
+        M = R @ np.diag(scales[b])
+        out[b, :3, :3], out[b, :3, 3], out[b, 3, 3] = M, (centre - M @ centre) + shifts[b], 1.0
+    return out
+
+
+def _spatial(images, masks, matrices, field, order, mask_order, cval):
+    """One ``ops.warp`` launch per tensor under the same table and field; without a field it is ``ops.affine_transform``."""
+    def one(t, o):
+        if field is None:
+            return ops.affine_transform(t, matrices, order=o, cval=cval)
+        return ops.warp(t, field, matrices, order=o, cval=cval)
+    return SpatialAugmented(one(images, order), None if masks is None else one(masks, mask_order), matrices, field)
+
+
+def random_affine(images: torch.Tensor, masks: Optional[torch.Tensor] = None, *, seed: int, rotate_range=0.0, scale_range=0.0, translate_range=0.0,
+                  order: int = 1, mask_order: int = 0, cval: float = 0.0) -> SpatialAugmented:
+    """A random rotation, scale and translation per item of an NDHWC batch, the masks under the same matrix (``mask_order`` 0 keeps a
+    binary mask binary), zeros (``cval``) outside.  Each range is a scalar or a 3-vector over the axes (d, h, w).
+
+    The draw, on the host: ``rng = numpy.random.Generator(numpy.random.Philox(seed))``, then in this order
+    ``angles = rng.uniform(-rotate_range, rotate_range, (B, 3))`` (radians, about the d, h and w axis),
+    ``scales = rng.uniform(1 - scale_range, 1 + scale_range, (B, 3))`` and
+    ``shifts = rng.uniform(-translate_range, translate_range, (B, 3))`` (voxels); all three are drawn whatever the ranges.
+
+    The composition, in float64: ``R = Rd(a0) @ Rh(a1) @ Rw(a2)`` with Rd = [[1,0,0],[0,c,-s],[0,s,c]], Rh = [[c,0,s],[0,1,0],[-s,0,c]],
+    Rw = [[c,-s,0],[s,c,0],[0,0,1]]; ``M = R @ diag(scales)``; the input coordinate of output voxel o is
+    ``c = M (o - centre) + centre + shifts`` with centre = (n - 1) / 2 per axis, uploaded as the table (M, (centre - M centre) + shifts)
+    of ``dm3d_affine_resample``.  Nothing is read back.  Returns ``SpatialAugmented(images, masks, matrices, None)``; all ranges 0 give
+    identity matrices.  Per-item probabilities and anisotropic voxel spacing are not offered."""
+    matrices = _image_mask_check(images, masks, lambda: affine_matrices(images.shape[1:4], images.shape[0], seed, rotate_range, scale_range, translate_range))
+    return _spatial(images, masks, matrices, None, order, mask_order, cval)
+
+
+def elastic_deform(images: torch.Tensor, masks: Optional[torch.Tensor] = None, *, alpha, sigma, seed: int, order: int = 1, mask_order: int = 0,
+                   cval: float = 0.0) -> SpatialAugmented:
+    """A random elastic deformation (Simard et al. 2003) per item of an NDHWC batch: one displacement field
+    ``gaussian_filter(U(-1, 1), sigma, mode="constant") * alpha`` per item (``ops.elastic_field`` documents the Philox stream), images and
+    masks resampled at ``o + field[:, o]`` by one ``ops.warp`` each.  ``alpha`` (voxels) and ``sigma`` are scalars or 3-vectors.  Returns
+    ``SpatialAugmented(images, masks, None, field)``.  The field is drawn at full resolution: MONAI's coarse-grid-then-upsample field is
+    not offered, nor are the other boundary modes of the warp."""
+    _image_mask_check(images, masks, lambda: ops._field_arguments(alpha, sigma, seed))
+    field = ops.elastic_field(images.shape[1:4], images.shape[0], alpha, sigma, seed, device=images.device)
+    return _spatial(images, masks, None, field, order, mask_order, cval)
+
+
+def spatial_augment(images: torch.Tensor, masks: Optional[torch.Tensor] = None, *, seed: int, rotate_range=0.0, scale_range=0.0, translate_range=0.0,
+                    elastic_alpha=None, elastic_sigma=None, order: int = 1, mask_order: int = 0, cval: float = 0.0) -> SpatialAugmented:
+    """``random_affine`` and ``elastic_deform`` composed: the input coordinate of output voxel o is ``(M o + offset) + field[:, o]``, the
+    table of the one and the field of the other under the same ``seed``, in **one** ``dm3d_warp`` launch per tensor, so an image is
+    interpolated once.  With ``elastic_alpha=None`` it is ``random_affine``; with all ranges 0 it is ``elastic_deform`` (the identity
+    table adds nothing to a coordinate).  Returns ``SpatialAugmented(images, masks, matrices, field)``."""
+    def host_arguments():
+        if (elastic_alpha is None) != (elastic_sigma is None):
+            raise ValueError("elastic_alpha and elastic_sigma must be given together or both left None")
+        if elastic_alpha is not None:
+            ops._field_arguments(elastic_alpha, elastic_sigma, seed)
+        return affine_matrices(images.shape[1:4], images.shape[0], seed, rotate_range, scale_range, translate_range)
+
+    matrices = _image_mask_check(images, masks, host_arguments)
+    field = None if elastic_alpha is None else ops.elastic_field(images.shape[1:4], images.shape[0], elastic_alpha, elastic_sigma, seed, device=images.device)
+    return _spatial(images, masks, matrices, field, order, mask_order, cval)
 
 
 def clean_mask(mask: torch.Tensor, *, keep_largest: bool = True, fill_holes: bool = True, min_size: Optional[int] = None, connectivity: int = 6,

@@ -978,6 +978,176 @@ def augment(images: torch.Tensor, masks: Optional[torch.Tensor] = None, *, seed:
     return Augmented(out, mask_out, *tables)
 
 
+# ---- spatial augmentation (include/dm3d.h, "Spatial augmentation"): Gaussian filter, elastic field, warp ---------------------------------
+def _vec3(v, name, low=None):
+    """A scalar or a 3-vector as three finite floats (at least ``low`` when given)."""
+    import numpy as np
+    try:
+        a = np.broadcast_to(np.asarray(v, np.float64), (3,))
+    except (TypeError, ValueError):
+        a = None
+    if a is None or not np.isfinite(a).all() or (low is not None and (a < low).any()):
+        raise ValueError(f"{name} must be a finite scalar or 3-vector" + (f" of at least {low:g}" if low is not None else "") + f", got {v!r}")
+    return [float(s) for s in a]
+
+
+def _gauss_table(sigma, truncate):
+    """The radii (-1 where scipy skips the axis: sigma <= 1e-15) and the host table [3, GAUSS_MAX_RADIUS + 1] of the float64 weights w[0 .. r]
+    per axis d, h, w, formed as scipy.ndimage forms them: exp(-0.5 / sigma^2 * k^2) over k = -r .. r, divided by their sum."""
+    import numpy as np
+    sig = _vec3(sigma, "sigma", 0.0)
+    if not (isinstance(truncate, (int, float)) and math.isfinite(truncate) and truncate > 0):
+        raise ValueError(f"truncate must be a positive finite number, got {truncate!r}")
+    radii, table = [], np.zeros((3, _lib.GAUSS_MAX_RADIUS + 1), np.float64)
+    for a, s in enumerate(sig):
+        if s <= 1e-15:
+            radii.append(-1)
+            continue
+        r = int(float(truncate) * s + 0.5)
+        if r > _lib.GAUSS_MAX_RADIUS:
+            raise ValueError(f"sigma={s:g} with truncate={truncate:g} has radius {r}, above DM3D_GAUSS_MAX_RADIUS={_lib.GAUSS_MAX_RADIUS}")
+        k = np.arange(-r, r + 1)
+        phi = np.exp(-0.5 / (s * s) * k ** 2)
+        phi = phi / phi.sum()
+        table[a, :r + 1] = phi[r:]
+        radii.append(r)
+    return radii, table
+
+
+def _gaussian(planar, out, radii, table, mode, cval, gain=None):
+    d = _lib.GaussDesc()
+    d.x, d.out, d.weights = planar.data_ptr(), out.data_ptr(), table.ctypes.data
+    d.volumes, d.d, d.h, d.w = planar.shape
+    d.rd, d.rh, d.rw = radii
+    d.mode, d.cval = _lib.GAUSS_MODES[mode], float(cval)
+    if gain is not None:
+        d.gains, (d.gain0, d.gain1, d.gain2) = 3, gain
+    check(lib().dm3d_gaussian_filter(C.byref(d), _st()), "gaussian_filter")      # the weights are copied into the launches during the call
+    return out
+
+
+def gaussian_filter(x: torch.Tensor, sigma, mode: str = "reflect", cval: float = 0.0, truncate: float = 4.0, *, order: int = 0) -> torch.Tensor:
+    """``scipy.ndimage.gaussian_filter(volume, sigma, order=0, mode=mode, cval=cval, truncate=truncate)`` of every volume of ``x``
+    ([B,D,H,W], or NDHWC with each channel a volume), float32 in x's layout.  ``sigma`` is a scalar or a 3-vector (d, h, w); an axis with
+    sigma 0 is left out, an axis of length 1 is filtered (scipy sums its extended taps).  The float64 weights are formed on the host as
+    scipy forms them (radius int(truncate sigma + 0.5), at most 64); each axis pass sums x[l] w0 + sum_{k=r..1} (x[l-k] + x[l+k]) w_k in
+    float64 and stores float32, in the order d, h, w, so the result is scipy's bit for bit.  ``mode`` is "reflect", "mirror", "nearest" or
+    "constant" (``cval``); "wrap" and Gaussian derivatives (``order`` != 0) are not offered.  No axis may exceed 512 voxels."""
+    if order != 0:
+        raise ValueError(f"order must be 0, got {order!r}: Gaussian derivatives are not offered")
+    if mode not in _lib.GAUSS_MODES:
+        raise ValueError(f'mode must be "reflect", "mirror", "nearest" or "constant", got {mode!r}: "wrap" is not offered')
+    if not (isinstance(cval, (int, float)) and math.isfinite(cval)):
+        raise ValueError(f"cval must be finite, got {cval!r}")
+    radii, table = _volume_check(x, spline=True, host=lambda: _gauss_table(sigma, truncate))
+    planar, back = _planar(x)
+    return back(_gaussian(planar, torch.empty_like(planar), radii, table, mode, cval))
+
+
+def _field_arguments(alpha, sigma, seed, truncate=4.0):
+    """The host arguments of an elastic field, checked: (gain per component, radii, weight table)."""
+    gain = _vec3(alpha, "alpha")
+    radii, table = _gauss_table(sigma, truncate)
+    if not isinstance(seed, int):
+        raise ValueError(f"seed must be an integer, got {seed!r}")
+    return gain, radii, table
+
+
+def elastic_field(shape, batch: int, alpha, sigma, seed: int, draw: int = 0, device="cuda", truncate: float = 4.0) -> torch.Tensor:
+    """The displacement field of a random elastic deformation (Simard et al. 2003), float32 [batch, 3, D, H, W] in voxels:
+    ``gaussian_filter(U(-1, 1), sigma, mode="constant", cval=0) * alpha``; ``alpha`` and ``sigma`` are scalars or 3-vectors (alpha per
+    displacement component d, h, w; sigma per spatial axis).  Element e of the flat field takes word e & 3 of the Philox4x32-10 block of
+    counter (lo32(e >> 2), hi32(e >> 2), draw, 0xE1A5) under the 64-bit key ``seed``: v = float32(word) * 2^-32, then 2 v - 1 in float32.
+    The draw is a launch of its own, the filter runs in place on it, the scaling is one float32 multiply.  Nothing is read back."""
+    shape = tuple(int(s) for s in shape) if hasattr(shape, "__len__") else ()
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"shape must be three positive extents, got {shape!r}")
+    if max(shape) > _lib.SPLINE_MAX_EXTENT:
+        raise ValueError(f"shape {shape} exceeds {_lib.SPLINE_MAX_EXTENT} voxels per axis, the longest line the Gaussian filter stages")
+    if not isinstance(batch, int) or batch < 1:
+        raise ValueError(f"batch must be a positive integer, got {batch!r}")
+    gain, radii, table = _field_arguments(alpha, sigma, seed, truncate)
+    if not isinstance(draw, int) or not 0 <= draw < 2 ** 31:
+        raise ValueError(f"draw must be an integer in [0, 2^31), got {draw!r}")
+    field = torch.empty(batch, 3, *shape, dtype=torch.float32, device=device)
+    _f32c(field, "the field (device=)")
+    d = _lib.FieldDesc()
+    d.out, d.n, d.seed, d.draw = field.data_ptr(), field.numel(), seed & (2 ** 64 - 1), draw
+    check(lib().dm3d_uniform_field(C.byref(d), _st()), "uniform_field")
+    planar = field.view(batch * 3, *shape)
+    _gaussian(planar, planar, radii, table, "constant", 0.0, gain)
+    return field
+
+
+def warp(x: torch.Tensor, displacement: Optional[torch.Tensor] = None, matrix=None, offset=0.0, output_shape=None, order: int = 1, cval: float = 0.0,
+         prefilter: bool = True, *, coordinates: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Every volume of ``x`` ([B,D,H,W], or NDHWC with each channel a volume) resampled at per-voxel coordinates, in one interpolation:
+    ``out[o] = interp(volume, (matrix @ o + offset) + displacement[:, o])``, float32 in x's layout with the spatial shape ``output_shape``
+    (default: the field's, else x's).  ``matrix`` / ``offset`` are what ``affine_transform`` accepts (None: the identity);
+    ``displacement`` is a contiguous device tensor [B,3,od,oh,ow] (or [1,3,od,oh,ow], shared by the batch), float32 or float64, in voxels
+    along d, h, w; the channels of one NDHWC item share its field.  Orders, ``cval``, ``prefilter``, the taps and the sums are
+    ``affine_transform``'s; the coordinate is (((o0 m0 + o1 m1) + o2 m2) + offset) + u in float64.  ``coordinates`` instead of
+    ``displacement`` gives absolute float64 coordinates (``map_coordinates``); then ``matrix`` stays None.  The other boundary modes of
+    ``scipy.ndimage.map_coordinates`` are not offered."""
+    if order not in SPLINE_ORDERS:
+        raise ValueError(f"order must be 0, 1 or 3, got {order!r}: orders 2, 4 and 5 are not offered")
+    if not (isinstance(cval, (int, float)) and math.isfinite(cval)):
+        raise ValueError(f"cval must be finite, got {cval!r}")
+    if displacement is not None and coordinates is not None:
+        raise ValueError("displacement and coordinates must not both be given: coordinates are absolute, a displacement is added to the grid")
+    if coordinates is not None and matrix is not None:
+        raise ValueError("matrix must stay None with coordinates: they are absolute")
+    field, fname = (displacement, "displacement") if coordinates is None else (coordinates, "coordinates")
+    filtered = order == 3 and prefilter
+
+    def host_arguments():
+        import numpy as np
+        B, per = x.shape[0], (1 if x.dim() == 4 else x.shape[4])
+        default = x.shape[1:4] if field is None or not isinstance(field, torch.Tensor) or field.dim() != 5 else field.shape[2:]
+        shape = tuple(int(s) for s in (default if output_shape is None else output_shape))
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError(f"output_shape must be three positive extents, got {output_shape!r}")
+        if field is not None:
+            if not isinstance(field, torch.Tensor) or field.dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"{fname} must be a float32 or float64 tensor, got {getattr(field, 'dtype', type(field).__name__)}")
+            if field.dim() != 5 or field.shape[0] not in (1, B) or tuple(field.shape[1:]) != (3,) + shape:
+                raise ValueError(f"{fname} must be [B,3,od,oh,ow] or [1,3,od,oh,ow] with B={B} and the output shape {shape}, got {tuple(field.shape)}")
+            if not field.is_cuda or not field.is_contiguous() or field.device != x.device:
+                raise ValueError(f"{fname} must be a contiguous device tensor on x's device")
+        if coordinates is not None:
+            table = np.zeros((B * per, 12), np.float64)
+        else:
+            table = _affine_table(np.eye(3) if matrix is None else matrix, offset, B, per)
+        return table, shape, (per if field is None or field.shape[0] == B else B * per)
+
+    table, shape, per_field = _volume_check(x, spline=filtered, host=host_arguments)
+    planar, back = _planar(x)
+    src = _spline_coefficients(planar) if filtered else planar
+    V = planar.shape[0]
+    dev_table = torch.from_numpy(table).to(x.device)
+    out = torch.empty(V, *shape, dtype=torch.float32, device=x.device)
+    d = _lib.WarpDesc()
+    d.src, d.table, d.field, d.out = src.data_ptr(), dev_table.data_ptr(), _p(field), out.data_ptr()
+    d.in_f64 = _lib.RESAMPLE_F64 if filtered else _lib.RESAMPLE_F32
+    d.field_f64 = _lib.RESAMPLE_F64 if field is not None and field.dtype == torch.float64 else _lib.RESAMPLE_F32
+    d.volumes, d.id, d.ih, d.iw = planar.shape
+    d.vols_per_field = per_field
+    d.od, d.oh, d.ow = shape
+    d.order, d.cval = order, float(cval)
+    check(lib().dm3d_warp(C.byref(d), _st()), "warp")
+    del src, dev_table                                                          # alive until the launch is enqueued (same stream)
+    return back(out)
+
+
+def map_coordinates(x: torch.Tensor, coordinates: torch.Tensor, order: int = 1, cval: float = 0.0, prefilter: bool = True) -> torch.Tensor:
+    """``scipy.ndimage.map_coordinates(volume, coordinates[b], order=order, mode="constant", cval=cval, prefilter=prefilter)`` of every
+    volume of ``x``: ``coordinates`` is a contiguous float64 (or float32) device tensor [B,3,od,oh,ow] (or [1,3,...], shared).  It is
+    ``warp`` with a zero matrix and offset: (0 + 0 + 0 + 0) + c is c exactly."""
+    if coordinates is None:
+        raise ValueError("coordinates must be given")
+    return warp(x, None, None, 0.0, None, order, cval, prefilter, coordinates=coordinates)
+
+
 # ---- distribution metrics on feature vectors (include/dm3d.h, dm3d_dist_desc): moments, k-NN radii, PRDC counts, cubic-kernel sums -----
 class FeatureMoments(NamedTuple):
     """What dm3d_feature_moments leaves: ``mean`` float64 [D] and the unbiased ``cov`` float64 [D, D], symmetric bit for bit."""

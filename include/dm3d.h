@@ -1173,6 +1173,72 @@ typedef struct dm3d_augment_desc {
 } dm3d_augment_desc;
 int dm3d_augment(const dm3d_augment_desc* d, void* stream);
 
+/* ---- Spatial augmentation (random affine plus random elastic deformation, Simard et al. 2003): the Gaussian filter, the uniform draw of
+ * a displacement field and the resample at per-voxel coordinates, on channel-planar volumes [volumes, d, h, w].  Sums and coordinates
+ * are float64 in one fixed order (the library builds with -ffp-contract=off), stores are float32; no kernel uses an atomic: runs
+ * repeat bitwise.
+ *
+ * dm3d_gaussian_filter   scipy.ndimage.gaussian_filter(order=0) per volume: one pass per axis in scipy's order d, h, w, each
+ *         t = x[l] w[0];   t += (x[l - k] + x[l + k]) w[k]   for k = r .. 1          in float64, multiply and add rounded separately,
+ *     stored as float32 after every axis (scipy's intermediate is its float32 output array).  weights is a HOST table
+ *     [3][DM3D_GAUSS_MAX_RADIUS + 1] of float64, row a (d, h, w) holding w[0 .. r_a] as scipy forms them (r = int(truncate sigma + 0.5),
+ *     exp(-0.5 / sigma^2 k^2) divided by the sum over -r .. r); it is read during the call.  A radius of -1 leaves that axis out (scipy's
+ *     sigma = 0); an axis of length 1 is filtered like any other.  A tap outside the line maps into it: DM3D_GAUSS_REFLECT has period 2n
+ *     with the edge repeated, _MIRROR period 2n - 2, _NEAREST clamps, _CONSTANT reads cval; no halo is staged, so r may exceed n.  A
+ *     workgroup stages DM3D_SPLINE_LANES neighbouring lines in LDS ([n][DM3D_SPLINE_LANES + 1] float32, the line-pass tiler of
+ *     csrc/dm3d_volume.h) and all its lanes form the outputs.  out may be x itself.  gains = 1 or 3 multiplies volume v by
+ *     gain[v % gains] in float32 after the last pass (the alpha of an elastic field [fields, 3, d, h, w]); gains = 0 is scipy's result.
+ * dm3d_uniform_field   out[e] = 2 v - 1 in float32, v = (float)word * 2^-32 (dm3d_augment's rule), word = word e & 3 of the
+ *     Philox4x32-10 block of counter (lo32(e >> 2), hi32(e >> 2), draw, DM3D_STREAM_ELASTIC) under the key seed, for e < n.
+ * dm3d_warp   out[v][o] = interp(src[v], c(o)),   c[h] = ((((o0 M[h][0] + o1 M[h][1]) + o2 M[h][2]) + offset[h]) + (double)u[h][o]
+ *     with table[v] = {M row by row, offset} as in dm3d_affine_resample and u = field[v / vols_per_field] ([fields, 3, od, oh, ow],
+ *     float32 or float64 by field_f64; NULL: no last term).  The inside test, the taps, the order of the tap sum, cval and the float32
+ *     store are dm3d_affine_resample's, as is the brick of 4 x 4 x 16 outputs.  With a zero table and float64 coordinates as the field
+ *     this is scipy.ndimage.map_coordinates(mode="constant").  Nothing bounds the field's values: no read leaves the volume.
+ *
+ * Checked before any launch (DM3D_EINVAL; the message starts "gaussian_filter:", "uniform_field:" or "warp:"): the descriptor and every
+ * pointer but warp's field non-NULL and aligned to its element; volumes >= 1 (warp: at most 65535, a multiple of vols_per_field >= 1);
+ * every extent >= 1; gaussian_filter: d, h, w <= DM3D_SPLINE_MAX_EXTENT, each radius in [-1, DM3D_GAUSS_MAX_RADIUS], mode one of the four
+ * constants, cval, the weights in use and the gains finite, gains 0, 1 or 3, out either x or sharing no byte with it; uniform_field:
+ * n >= 1, draw >= 0; warp: order 0, 1 or 3, in_f64 and field_f64 one of the two constants, cval finite, an input volume below 2^31
+ * voxels, out sharing no byte with src. */
+#define DM3D_GAUSS_MAX_RADIUS 64
+#define DM3D_GAUSS_REFLECT 0
+#define DM3D_GAUSS_MIRROR 1
+#define DM3D_GAUSS_NEAREST 2
+#define DM3D_GAUSS_CONSTANT 3
+#define DM3D_STREAM_ELASTIC 0xE1A5u
+typedef struct dm3d_gauss_desc {
+    const float* x;             /* [volumes, d, h, w] */
+    float* out;                 /* [volumes, d, h, w]; may be x itself */
+    const double* weights;      /* host table [3, DM3D_GAUSS_MAX_RADIUS + 1]; may be NULL when every radius is -1 */
+    int32_t volumes, d, h, w;
+    int32_t rd, rh, rw;         /* radius per axis, -1: the axis is left out */
+    int32_t mode;               /* DM3D_GAUSS_* */
+    double cval;
+    int32_t gains;              /* 0, 1 or 3 */
+    float gain0, gain1, gain2;
+} dm3d_gauss_desc;
+int dm3d_gaussian_filter(const dm3d_gauss_desc* d, void* stream);
+typedef struct dm3d_field_desc {
+    float* out;                 /* [n] */
+    int64_t n;
+    uint64_t seed;
+    int32_t draw;
+} dm3d_field_desc;
+int dm3d_uniform_field(const dm3d_field_desc* d, void* stream);
+typedef struct dm3d_warp_desc {
+    const void* src;            /* [volumes, id, ih, iw] float32 or float64 */
+    const double* table;        /* [volumes, 12] */
+    const void* field;          /* [volumes / vols_per_field, 3, od, oh, ow] float32 or float64, or NULL */
+    float* out;                 /* [volumes, od, oh, ow] */
+    int32_t in_f64, field_f64;  /* DM3D_RESAMPLE_F32 or DM3D_RESAMPLE_F64 */
+    int32_t volumes, vols_per_field, id, ih, iw, od, oh, ow;
+    int32_t order;              /* 0, 1 or 3 */
+    float cval;
+} dm3d_warp_desc;
+int dm3d_warp(const dm3d_warp_desc* d, void* stream);
+
 /* p[i] = max(p[i] + delta, 0) (the loop counter of generate kept on the device so a captured step replays unchanged; it
  * saturates at 0, so a step issued past the end of a chain never indexes row -1 of a table). */
 int dm3d_add_i32(int32_t* p, int32_t n, int32_t delta, void* stream);
